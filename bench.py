@@ -13,7 +13,15 @@ device-resident scene: path-trace kernels + in-order sample resolve + RGB8, and
 for N > 1 the RCCL gather of every rank's packed RGB8 tiles to rank 0.
 Mrays = Scene.traceRay segments (primary + bounce + pass-through).
 
-Beside the timed loop (rank 0, N = 1, after it):
+A plain run sets up, warms up, times the K steps and prints the line: value,
+ms_per_step, the workload and the sha1 of the last timed frame (img_sha1).
+--dump-outputs DIR also writes what that last step returned (dump_outputs
+below); the scene, camera and RNG keys are fixed, so two builds can be compared
+array for array.  Everything else is behind --full: the untimed counting frame
+(exact work counts, asserted against the timed frames), the oracle's frame
+hash, the roofline frame, and
+
+beside the timed loop (rank 0, N = 1, after it):
   * wall_clock_ms: the `zrt` CLI end to end on the same scene written as glTF
     with the repo's config.json (its num_samples), i.e. the reference's "Done
     in" (main.zig:78 -> :142: load, grid build, render, PNG save), and the CPU
@@ -21,7 +29,8 @@ Beside the timed loop (rank 0, N = 1, after it):
   * cpu_baseline: the oracle's REF mode (the reference's schedule) on the
     host's CPUs over a bounded sample of the timed frame.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--no-wall-clock]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py --full [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--no-wall-clock]
   N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
          or plain `python bench.py --gpus N`: with no WORLD_SIZE in the
          environment the process (which has made no HIP call) starts the N
@@ -31,11 +40,12 @@ Beside the timed loop (rank 0, N = 1, after it):
          fewer GPUs than asked (the reference's partition, stage3.zig:228-229).
 
 Rank 0 prints ONE JSON line, with the sha1 of the whole frame (img_sha1: the
-same for any N, asserted equal to the untimed counting frame's and to the CPU
-oracle's whole-frame hash in tests/golden/frames.json: oracle_frame_match).
+same for any N; with --full asserted equal to the untimed counting frame's and
+to the CPU oracle's whole-frame hash in tests/golden/frames.json:
+oracle_frame_match).
 Image tiles (32x32 over several ranks, interleaved t % N) shard the frame: total work is fixed as N grows
-("scaling": "strong").  The roofline block is the dominant kernel's, from one
-extra frame on one HIP stream (exclusive kernel durations).
+("scaling": "strong").  The roofline block (--full) is the dominant kernel's, from
+one extra frame on one HIP stream (exclusive kernel durations).
 """
 from __future__ import annotations
 
@@ -79,7 +89,34 @@ def parse():
                          "profile of the roofline, NOT the headline schedule)")
     ap.add_argument("--backend", default="nccl", choices=("nccl", "gloo"),
                     help="N > 1 process group; gloo (tests only) gathers host copies, ranks may share a GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps: the counting frame and its checks, the oracle's frame "
+                         "hash, the roofline frame, the CLI wall clock and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (rank 0)")
     return ap.parse_args()
+
+
+DUMP_MAX_PIXELS = 2 << 20      # above it a fixed, seeded sample of the pixels is written
+
+
+def dump_outputs(d, img, segments):
+    """What the last timed step handed back, as float arrays under d:
+      rgb8.npy      f32 [pixels, 3]: the RGB8 image as the step returned it
+                    (N = 1: the packed tiles in tile order, zrt_tile_pixels;
+                    N > 1: the gathered row-major frame)
+      segments.npy  f64 [1]: this rank's Scene.traceRay segments of that step
+    An image of more than DUMP_MAX_PIXELS pixels is sampled: DUMP_MAX_PIXELS
+    rows drawn once with seed 0 (the same rows for the same frame size), their
+    indices beside them in rgb8_rows.npy (f64), 40 MB in all."""
+    os.makedirs(d, exist_ok=True)
+    rgb = np.asarray(img.cpu().numpy() if hasattr(img, "cpu") else img).reshape(-1, 3)
+    if rgb.shape[0] > DUMP_MAX_PIXELS:
+        rows = np.sort(np.random.default_rng(0).choice(rgb.shape[0], DUMP_MAX_PIXELS, replace=False))
+        np.save(os.path.join(d, "rgb8_rows.npy"), rows.astype(np.float64))
+        rgb = rgb[rows]
+    np.save(os.path.join(d, "rgb8.npy"), np.ascontiguousarray(rgb, dtype=np.float32))
+    np.save(os.path.join(d, "segments.npy"), np.array([segments], dtype=np.float64))
 
 
 def cpu_model():
@@ -407,9 +444,10 @@ def main():
 
     # untimed counting run: exact algorithmic work of one step (same RNG ->
     # same paths as the timed kernels), and the frame every timed frame must equal
-    cst, cimg = step(stats=True)
-    cprof = rs.context.profile()
-    count_sha1 = frame_sha1(cimg) if rank == 0 else None
+    if a.full:
+        cst, cimg = step(stats=True)
+        cprof = rs.context.profile()
+        count_sha1 = frame_sha1(cimg) if rank == 0 else None
     for _ in range(a.warmup):
         step()
 
@@ -441,8 +479,36 @@ def main():
         total_segs = float(segs)
 
     if rank == 0:
-        assert cst["segments"] * a.steps == segs, "counting and timed kernels disagree"
         img_sha1 = frame_sha1(img)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, img, st["segments"])
+        out = {
+            "metric": "Mrays/sec + wall-clock to output.png on contest config.json scene",
+            "value": round(total_segs / elapsed / 1e6, 3),
+            "unit": "Mrays/s",
+            "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": round(elapsed / a.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{a.config}: {cfgd['scene']} stand-in "
+                                   f"({soup.num_triangles} tris, {rs.geometry.num_refs} refs), "
+                                   f"{cam.w}x{cam.h}, {spp} spp, max_bounce "
+                                   f"{cfgd['max_bounce']}, grid 128^3",
+                       "global_batch": cam.w * cam.h * spp, "parallelism": f"tiles{world}",
+                       "segments_per_step": int(total_segs / a.steps),
+                       "schedule": "one pass set (profiling)" if a.one_set else "timed: default pass sets"},
+            "img_sha1": img_sha1,
+            # SURVEY.md d1's companion rate: w*h*spp per second of the timed frames
+            "msamples_per_s": round(cam.w * cam.h * spp * a.steps / elapsed / 1e6, 3),
+        }
+        if world > 1:
+            out["backend"] = a.backend
+        if not a.full:
+            print(json.dumps(out), flush=True)
+    # ---- --full only, after the line's own figures: the checks against the
+    # counting frame and the oracle, the roofline frame, wall clock, CPU baseline
+    if rank == 0 and a.full:
+        assert cst["segments"] * a.steps == segs, "counting and timed kernels disagree"
         assert img_sha1 == count_sha1, "the timed frame differs from the counting frame"
         # the whole frame against the CPU oracle's (tools/make_frame_golden.py:
         # every pixel of the frame through oracle/zrt_oracle.c, the
@@ -532,23 +598,9 @@ def main():
             "GBps": round(frame_alg * a.steps / (gpu_ms / 1e3) / 1e9, 1),
             "gpu_ms_per_step": round(gpu_ms / a.steps, 3),
             "avg_launch_ms_overlapped": round(kern_ms / max(launches, 1), 3)}
-        out = {
-            "metric": "Mrays/sec + wall-clock to output.png on contest config.json scene",
-            "value": round(total_segs / elapsed / 1e6, 3),
-            "unit": "Mrays/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": round(elapsed / a.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{a.config}: {cfgd['scene']} stand-in "
-                                   f"({soup.num_triangles} tris, {rs.geometry.num_refs} refs), "
-                                   f"{cam.w}x{cam.h}, {spp} spp, max_bounce "
-                                   f"{cfgd['max_bounce']}, grid 128^3",
-                       "global_batch": cam.w * cam.h * spp, "parallelism": f"tiles{world}",
-                       "segments_per_step": int(total_segs / a.steps),
-                       "schedule": "one pass set (profiling)" if a.one_set else
-                                   f"{cprof['passes']} counting passes; timed: default pass sets"},
-            "img_sha1": img_sha1,
+        if not a.one_set:
+            out["config"]["schedule"] = f"{cprof['passes']} counting passes; timed: default pass sets"
+        out.update({
             "oracle_frame_match": oracle_match,
             "oracle_frame": None if golden is None else {
                 "rgb8_sha1": golden["rgb8_sha1"], "segments": golden["segments"],
@@ -558,11 +610,7 @@ def main():
             "work": {k: int(cst[k]) for k in ("segments", "cells_visited", "triangle_tests",
                                                "hits", "samples")},
             "work_primary": pc,
-            # SURVEY.md d1's companion rate: w*h*spp per second of the timed frames
-            "msamples_per_s": round(cam.w * cam.h * spp * a.steps / elapsed / 1e6, 3),
-        }
-        if world > 1:
-            out["backend"] = a.backend
+        })
         if world == 1 and not a.no_wall_clock:
             out.update(wall_clock(soup, cfgd, cpu=not a.no_cpu_baseline))
         if not a.no_cpu_baseline and world == 1:

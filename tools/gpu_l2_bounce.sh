@@ -9,7 +9,7 @@ cfg=${2:-cfg5}
 out=gpurun_out/$tag/l2_$cfg
 mkdir -p $out
 export TMPDIR=/tmp
-cmd="python3 bench.py --config $cfg --one-set --steps 1 --warmup 0 --no-cpu-baseline --no-wall-clock"
+cmd="python3 bench.py --full --config $cfg --one-set --steps 1 --warmup 0 --no-cpu-baseline --no-wall-clock"
 timeout -s KILL 400 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --kernel-trace --output-format csv -d $out/pmc_l2 -o run -- \
     $cmd > $out/pmc_l2.json 2> $out/pmc_l2.err
 rc=$?; echo "l2 $cfg rc=$rc"; [ $rc -eq 0 ] || exit $rc

@@ -11,7 +11,7 @@ i=0
 for grp in "$@"; do
   i=$((i+1))
   timeout -k 10 300 rocprofv3 --pmc $grp --kernel-trace --stats --output-format csv -d $out/p$i -o run -- \
-      python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline > $out/p${i}_bench.log 2>&1
+      python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline > $out/p${i}_bench.log 2>&1
   rc=$?; echo "pass $i ($grp) rc=$rc"
   [ $rc -eq 0 ] || exit $rc
 done

@@ -12,16 +12,16 @@ timeout -k 10 900 python3 -u -m pytest tests -m gpu -x -q --timeout 300 --timeou
 rc=$?; echo "pytest rc=$rc"; tail -3 $out/pytest_gpu.log
 [ $rc -eq 0 ] || exit $rc
 fi
-timeout -k 10 900 python3 bench.py > $out/bench.json 2> $out/bench.err
+timeout -k 10 900 python3 bench.py --full > $out/bench.json 2> $out/bench.err
 rc=$?; echo "bench rc=$rc"; cat $out/bench.json
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o run -- \
-    python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-wall-clock > $out/prof_bench.json 2> $out/prof_bench.err
+    python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-wall-clock > $out/prof_bench.json 2> $out/prof_bench.err
 rc=$?; echo "rocprof rc=$rc"; cat $out/prof_bench.json
 [ $rc -eq 0 ] || exit $rc
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/pmc_$c -o run -- \
-      python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-wall-clock > $out/pmc_$c.json 2> $out/pmc_$c.err
+      python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-wall-clock > $out/pmc_$c.json 2> $out/pmc_$c.err
   rc=$?; echo "pmc $c rc=$rc"
   [ $rc -eq 0 ] || exit $rc
 done

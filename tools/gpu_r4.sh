@@ -14,7 +14,7 @@ rc=$?; echo "pytest rc=$rc"; tail -3 $out/pytest_gpu.log
 [ $rc -eq 0 ] || exit $rc
 fi
 if [ "${SKIP_BENCH:-0}" != 1 ]; then
-timeout -k 10 900 python3 bench.py > $out/bench.json 2> $out/bench.err
+timeout -k 10 900 python3 bench.py --full > $out/bench.json 2> $out/bench.err
 rc=$?; echo "bench rc=$rc"; cat $out/bench.json
 [ $rc -eq 0 ] || exit $rc
 fi

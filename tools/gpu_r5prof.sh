@@ -16,7 +16,7 @@ export TMPDIR=/tmp
 for s in $steps; do
 case $s in
 two)
-  cmd="python3 bench.py --steps 2 --warmup 0 --no-cpu-baseline --no-wall-clock"
+  cmd="python3 bench.py --full --steps 2 --warmup 0 --no-cpu-baseline --no-wall-clock"
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/two -o run -- \
       $cmd > $out/two_bench.json 2> $out/two_bench.err
   rc=$?; echo "two-stream trace rc=$rc"; [ $rc -eq 0 ] || exit $rc

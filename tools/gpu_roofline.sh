@@ -10,7 +10,7 @@ cfg=${2:-cfg3}
 out=gpurun_out/$tag/roof_$cfg
 mkdir -p $out
 export TMPDIR=/tmp
-cmd="python3 bench.py --config $cfg --one-set --steps 1 --warmup 0 --no-cpu-baseline --no-wall-clock"
+cmd="python3 bench.py --full --config $cfg --one-set --steps 1 --warmup 0 --no-cpu-baseline --no-wall-clock"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o run -- \
     $cmd > $out/prof_bench.json 2> $out/prof_bench.err
 rc=$?; echo "roof $cfg trace rc=$rc"; [ $rc -eq 0 ] || exit $rc
