@@ -238,6 +238,52 @@ int zrt_context_render(zrt_context* ctx, const zrt_camera* camera, const zrt_ren
                        const zrt_outputs* outputs, zrt_stats* stats);
 void zrt_context_destroy(zrt_context* ctx);
 
+/* ---- batch ray queries (ABI 2, added) ----------------------------------- */
+
+/* Scene.traceRay (stage3.zig:152-186) for a batch of rays against the
+ * context's scene: the grid DDA (linalg.zig:443-496), Moller-Trumbore over the
+ * refs of every visited cell in cell order begin -> end, a hit kept when
+ * `nearest > t and t > 0` (strict: the first ref among equal t wins), the walk
+ * stopped once nearest <= the next crossing -- the function the render kernels
+ * implement, bit for bit, without a camera or shading around it. */
+typedef struct zrt_hit {
+    float t;                         /* nearest t > 0 among the refs the walk tests; +inf: miss */
+    float u, v;                      /* barycentrics of that ref (0 on a miss) */
+    uint32_t triangle;               /* baked ref: indexes zrt_scene.triangles_pos / triangles_data
+                                        (the reference's Hit.triangle_idx); 0xFFFFFFFF on a miss */
+} zrt_hit;                           /* 16 B */
+
+#define ZRT_TRACE_PARK 0x10000u      /* zrt_ray_batch.flags only: take the park kernel whatever the batch
+                                        size, where the context can run it (else the lane walk, silently).
+                                        Unasked, batches of 2^19 rays or more take it and smaller ones the
+                                        lane walk (ZRT_FLAG_LANE_WALK: always); incoherent rays are faster
+                                        through the park kernel at any size */
+
+typedef struct zrt_ray_batch {
+    uint64_t num_rays;
+    const float* rays;               /* num_rays * 6: origin xyz, direction xyz.  Any finite direction
+                                        with a non-zero component (need not be unit length); for others
+                                        (NaN, infinite, all zero) the result is unspecified, the call
+                                        still returns */
+    zrt_hit* hits;                   /* num_rays */
+    uint32_t on_device;              /* 0: host pointers; 1: both are device pointers on the context's
+                                        device (4-byte aligned), complete once the call returns */
+    uint32_t flags;                  /* ZRT_FLAG_COUNT_STATS | ZRT_FLAG_LANE_WALK | ZRT_FLAG_MT_EXACT |
+                                        ZRT_FLAG_ESCAPE / NO_ESCAPE / RELEASE / NO_RELEASE as in a render
+                                        (same hits either way) | ZRT_TRACE_PARK; any other bit is
+                                        ZRT_ERR_INVALID_ARG */
+} zrt_ray_batch;
+
+/* Synchronous; one thread at a time per context, like a render (the two share
+ * the context's stream and work buffers, so they may alternate freely).
+ * num_rays == 0 returns ZRT_OK and touches nothing; null rays or hits with
+ * num_rays > 0 is ZRT_ERR_INVALID_ARG.  Batches of any size: the rays run in
+ * chunks of at most 2^20, so no index wraps and the staging memory is bounded.
+ * stats (may be null): segments = num_rays, samples = 0, render_ms the device
+ * time of the call; cells_visited, triangle_tests and hits with
+ * ZRT_FLAG_COUNT_STATS, counted as a counting render counts them. */
+int zrt_context_trace(zrt_context* ctx, const zrt_ray_batch* batch, zrt_stats* stats_or_null);
+
 /* A device group: one context per entry of `devices` (HIP ordinals, repeats
  * allowed), the scene resident on each, rendered by one call -- Scene.render's
  * spawn + join of its workers (stage3.zig:247-256) across GPUs in one

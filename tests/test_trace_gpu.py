@@ -1,0 +1,323 @@
+"""Batch ray queries on the GPU (zrt_context_trace, Context.trace) against
+Scene.traceRay composed from the CPU oracle's unit entry points
+(trace_ref.py), bit for bit: t, u, v as uint32 patterns and the baked ref; a
+miss is exactly (+inf, 0, 0, 0xFFFFFFFF).
+
+Every case runs through the lane walk, the park path (ZRT_TRACE_PARK) and the
+IEEE-division kernel (ZRT_FLAG_MT_EXACT), on both ways of making a context.
+A case's 256 rays (seeded) are: origins outside the bbox pointing in, origins
+inside it, origins outside pointing away, directions with one and two exact
+zero components (+0 and -0), rays lying in a cell-boundary plane, rays through
+mesh vertices and edge midpoints, and directions scaled by 2^-10 .. 2^10.  Its
+reference is computed once and shared by every test that needs it.
+"""
+import dataclasses
+
+import numpy as np
+import pytest
+
+try:
+    import torch  # noqa: F401  (first: libzrt then binds to torch's HIP runtime, as in bench.py)
+except ImportError:
+    torch = None
+
+from zig_raytracing_contest_amd import RenderScene, camera_for, native, scenes
+
+import trace_ref
+
+pytestmark = pytest.mark.gpu
+
+
+def _degenerate_sphere():
+    """test_gpu_edges._degenerate_sphere: the sphere plus a point, a collinear
+    triple, two equal vertices and a proper triangle."""
+    s = scenes.get_scene("sphere")
+    v = np.array([[0.2, 0.1, 0.9], [0.2, 0.1, 0.9], [0.2, 0.1, 0.9],
+                  [-0.5, 0.0, 1.1], [0.0, 0.0, 1.1], [0.5, 0.0, 1.1],
+                  [0.3, -0.4, 1.05], [0.3, -0.4, 1.05], [0.6, 0.2, 1.05],
+                  [-0.2, 0.3, 1.2], [0.1, 0.3, 1.2], [-0.2, 0.6, 1.2]], np.float32).reshape(4, 9)
+    n = np.tile(np.array([0, 0, 1], np.float32), (4, 3))
+    return dataclasses.replace(s, name="sphere_degenerate", pos=np.concatenate([s.pos, v]),
+                               nrm=np.concatenate([s.nrm, n]), uv=np.concatenate([s.uv, np.zeros((4, 6), np.float32)]),
+                               mat=np.concatenate([s.mat, np.zeros(4, s.mat.dtype)]))
+
+
+def _one_triangle():
+    s = scenes.get_scene("sphere")
+    return dataclasses.replace(s, name="one_triangle", pos=np.array([[-1, -1, 0, 1, -1, 0, 0, 1, 0]], np.float32),
+                               nrm=np.tile(np.array([0, 0, 1], np.float32), (1, 3)),
+                               uv=np.zeros((1, 6), np.float32), mat=np.zeros(1, s.mat.dtype))
+
+
+# case -> (scene, grid).  PARK_RUNS: the cases whose context runs the park kernel when asked
+# (packed walk, OccX in LDS); on the others ZRT_TRACE_PARK may fall back to the lane walk.
+CASES = {"cornell_bm": (lambda: scenes.get_scene("cornell"), (16, 16, 16)),       # brick-major words
+         "cornell_fields": (lambda: scenes.get_scene("cornell"), (12, 20, 9)),    # field words
+         "degenerate": (_degenerate_sphere, (16, 16, 16)),
+         "tri_1": (_one_triangle, (1, 1, 1)),
+         "tri_wide": (_one_triangle, (1100, 2, 2))}                              # the unpacked walk
+PARK_RUNS = ("cornell_bm", "cornell_fields", "degenerate")
+MODES = {"lane": 0, "park": native.TRACE_PARK, "mt_exact": native.FLAG_MT_EXACT}
+N_RAYS = 256
+
+
+def _case_rays(ref, soup, seed):
+    """The case's N_RAYS rays, (origins, dirs) float32."""
+    rng = np.random.default_rng(seed)
+    lo, hi = ref.bmin.astype(np.float64), ref.bmax.astype(np.float64)
+    c, ext = (lo + hi) / 2, hi - lo
+    R = 1.5 * max(float(np.linalg.norm(ext)), 1e-3)
+
+    def unit(n):
+        v = rng.normal(size=(n, 3))
+        return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+    def inside(n):
+        return lo + rng.random((n, 3)) * ext
+
+    def through(p, d, k):
+        """Origins for rays along d through the points p: p itself for even k, a point behind it else."""
+        back = (np.arange(len(p)) + k) % 2
+        return p - back[:, None] * R * d.astype(np.float64)
+
+    O, D = [], []
+    o = c + R * unit(87)                                   # outside, pointing in
+    d = inside(87) - o
+    O.append(o)
+    D.append(d / np.linalg.norm(d, axis=1, keepdims=True))
+    O.append(inside(40))                                   # inside the bbox
+    D.append(unit(40))
+    u = unit(20)                                           # outside, pointing away
+    O.append(c + R * u)
+    D.append(u)
+    z = []                                                 # exact zero components, both signs of zero
+    for a in range(3):
+        for zero in (0.0, -0.0):
+            for s1 in (1.0, -1.0):
+                for s2 in (1.0, -1.0):
+                    v = np.array([0.6 * s1, 0.8 * s2, 0.0], np.float32)
+                    v[2] = zero
+                    z.append(np.roll(v, a + 1))            # the zero on each axis in turn
+        for s in (1.0, -1.0):
+            for z1 in (0.0, -0.0):
+                for z2 in (0.0, -0.0):
+                    z.append(np.roll(np.array([s, z1, z2], np.float32), a))
+    z = np.array(z, np.float32)                            # 24 + 24
+    O.append(through(inside(len(z)), z, 0))
+    D.append(z)
+    pl_o, pl_d = [], []                                    # in a cell-boundary plane of axis a
+    for i in range(16):
+        a = i % 3
+        k = int(rng.integers(0, ref.res[a] + 1))
+        ang = rng.random() * 2 * np.pi
+        v = np.array([np.cos(ang), np.sin(ang), -0.0 if i & 1 else 0.0], np.float32)
+        d = np.roll(v, a + 1)
+        p = inside(1)[0].astype(np.float32)
+        p[a] = np.float32(ref.bmin[a]) + np.float32(k) * np.float32(ref.cs[a])   # the grid's own f32 plane
+        pl_o.append(p if i & 2 else (p.astype(np.float64) - R * d).astype(np.float32))
+        pl_o[-1][a] = p[a]
+        pl_d.append(d)
+    O.append(np.array(pl_o))
+    D.append(np.array(pl_d, np.float32))
+    tri = soup.pos.reshape(-1, 3, 3)[rng.integers(0, soup.num_triangles, 24)].astype(np.float64)
+    tgt = np.where(np.arange(24)[:, None] < 12, tri[np.arange(24), np.arange(24) % 3],      # a vertex
+                   (tri[np.arange(24), np.arange(24) % 3] + tri[np.arange(24), (np.arange(24) + 1) % 3]) / 2)
+    o = (c + R * unit(24)).astype(np.float32)
+    d = tgt.astype(np.float32) - o                         # f32 throughout: as close to the vertex as a ray gets
+    O.append(o)
+    D.append(d / np.sqrt((d * d).sum(1, dtype=np.float32), dtype=np.float32)[:, None])
+    O.append(O[0][:21])                                    # directions scaled by 2^-10 .. 2^10 (exact in f32)
+    D.append(D[0][:21].astype(np.float32) * np.exp2(np.arange(-10, 11, dtype=np.float32))[:, None])
+    o = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32) for x in O]))
+    d = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32) for x in D]))
+    assert o.shape == d.shape == (N_RAYS, 3) and np.isfinite(o).all() and np.isfinite(d).all()
+    assert (np.abs(d).max(1) > 0).all()
+    return o, d
+
+
+@dataclasses.dataclass
+class Case:
+    soup: object
+    res: tuple
+    ref: trace_ref.RayRef
+    o: np.ndarray
+    d: np.ndarray
+    bits: np.ndarray           # (N_RAYS, 4) uint32: the reference's (t, u, v, ref)
+    counts: tuple              # the reference's (cells visited, refs tested, hits) for the batch
+
+
+_CASES = {}
+
+
+@pytest.fixture(scope="module")
+def case(oracle_mod):
+    def get(name):
+        if name not in _CASES:
+            mk, res = CASES[name]
+            soup = mk()
+            ref = trace_ref.RayRef(oracle_mod, soup, res)
+            o, d = _case_rays(ref, soup, sorted(CASES).index(name) + 1)
+            bits, counts = ref.trace_batch(o, d)
+            bits.setflags(write=False)
+            _CASES[name] = Case(soup, res, ref, o, d, bits, counts)
+        return _CASES[name]
+    return get
+
+
+@pytest.fixture(scope="module")
+def scene(case):
+    """The context of (case, build), made once."""
+    made = {}
+
+    def get(name, build="host"):
+        if (name, build) not in made:
+            cs = case(name)
+            made[(name, build)] = RenderScene(cs.soup, cs.res, device=0, device_build=build == "device")
+        return made[(name, build)]
+    yield get
+    for rs in made.values():
+        rs.close()
+
+
+def _check(got, want, what):
+    bad = np.nonzero((got != want).any(axis=1))[0]
+    assert bad.size == 0, (f"{what}: {bad.size} rays differ, first {bad[0]}: got "
+                           f"{[hex(int(x)) for x in got[bad[0]]]}, reference {[hex(int(x)) for x in want[bad[0]]]}")
+
+
+@pytest.mark.parametrize("build", ["host", "device"])
+@pytest.mark.parametrize("mode", list(MODES))
+@pytest.mark.parametrize("name", list(CASES))
+def test_hits_match_the_reference(name, mode, build, case, scene):
+    cs, rs = case(name), scene(name, build)
+    res = rs.trace(cs.o, cs.d, flags=MODES[mode])
+    got = trace_ref.hit_bits(res)
+    _check(got, cs.bits, f"{name} {mode} {build}")
+    miss = np.isinf(res["t"])
+    assert (got[miss] == np.array([0x7F800000, 0, 0, 0xFFFFFFFF], np.uint32)).all()
+    assert miss.any() and (~miss).any(), "the case covers hits and misses"
+    assert res["stats"]["segments"] == N_RAYS and res["stats"]["samples"] == 0
+    if build == "host":
+        src = res["source_triangle"]
+        assert (src[miss] == native.MISS).all()
+        assert np.array_equal(src[~miss], cs.ref.indices[res["triangle"][~miss]])
+    # the launches of one chunk: pack + park + out + the rest, fast walk + the rest, or the exact walk alone
+    want = 4 if mode == "park" and name in PARK_RUNS else 1 if mode == "mt_exact" else 2 if mode == "lane" else None
+    if want is not None:
+        assert res["stats"]["trace_launches"] == want
+
+
+@pytest.mark.parametrize("mode", ["lane", "park"])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 200])
+def test_batch_sizes(n, mode, case, scene):
+    cs, rs = case("cornell_bm"), scene("cornell_bm")
+    pick = np.random.default_rng(7).permutation(N_RAYS)[:n]
+    res = rs.trace(cs.o[pick], cs.d[pick], flags=MODES[mode])
+    _check(trace_ref.hit_bits(res), cs.bits[pick], f"n = {n} {mode}")
+
+
+def _random_batch(cs, n, seed):
+    rng = np.random.default_rng(seed)
+    lo, ext = cs.ref.bmin, cs.ref.bmax - cs.ref.bmin
+    o = (lo + (rng.random((n, 3), dtype=np.float32) * 1.6 - 0.3) * ext).astype(np.float32)
+    d = rng.normal(size=(n, 3)).astype(np.float32)
+    d /= np.sqrt((d * d).sum(1))[:, None]
+    return np.ascontiguousarray(o), np.ascontiguousarray(d, np.float32)
+
+
+# (rays, where the case's 256 rays sit, the mode a call takes unasked); a chunk of the lane walk is two
+# launches (fast + the rest), one of the park path four (pack, park, out, the rest)
+@pytest.mark.parametrize("n,at,unasked", [
+    (5000, None, "lane"),                      # several waves and queue chunks, eight unequal regions
+    ((1 << 19) - 1, None, "lane"),             # the last size that takes the lane walk unasked ...
+    (1 << 19, None, "park"),                   # ... and the first that takes the park path
+    ((1 << 20) + 200, (1 << 20) - 128, "park")])   # two host-side chunks, the case's rays across the cut
+def test_large_batches_park_equals_lane(n, at, unasked, case, scene):
+    cs, rs = case("cornell_bm"), scene("cornell_bm")
+    o, d = _random_batch(cs, n, 11)
+    pos = (np.sort(np.random.default_rng(12).choice(n, N_RAYS, replace=False)) if at is None
+           else np.arange(at, at + N_RAYS))
+    o[pos], d[pos] = cs.o, cs.d
+    chunks = -(-n // (1 << 20))
+    res = {m: rs.trace(o, d, flags=f) for m, f in (("lane", native.FLAG_LANE_WALK), ("park", native.TRACE_PARK),
+                                                   ("unasked", 0))}
+    launches = {m: r["stats"]["trace_launches"] for m, r in res.items()}
+    assert launches == {"lane": 2 * chunks, "park": 4 * chunks, "unasked": launches[unasked]}
+    lane = trace_ref.hit_bits(res["lane"])
+    assert np.array_equal(lane, trace_ref.hit_bits(res["park"]))
+    assert np.array_equal(lane, trace_ref.hit_bits(res["unasked"]))
+    _check(lane[pos], cs.bits, f"n = {n}, the 256 reference rays")
+    assert np.isinf(lane[:, 0].view(np.float32)).any() and (lane[:, 3] != native.MISS).any()
+
+
+def test_empty_batch_touches_nothing(scene):
+    rs = scene("cornell_bm")
+    hits = np.full(8, 0xABABABAB, np.uint32)
+    rays = np.zeros(6, np.float32)
+    st = rs.context.trace_raw(0, rays.ctypes.data, hits.ctypes.data, False)
+    assert (hits == 0xABABABAB).all() and st["segments"] == 0
+    rs.context.trace_raw(0, None, None, False, native.TRACE_PARK)
+    res = rs.trace(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32))
+    assert res["t"].shape == (0,) and res["triangle"].shape == (0,)
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_counters_match_the_reference(name, case, scene):
+    cs = case(name)
+    res = scene(name).trace(cs.o, cs.d, stats=True)
+    _check(trace_ref.hit_bits(res), cs.bits, f"{name} counting")
+    st = res["stats"]
+    assert (st["segments"], st["cells_visited"], st["triangle_tests"], st["hits"]) == (N_RAYS,) + cs.counts
+
+
+def test_queries_and_renders_share_a_context_cleanly(case, scene):
+    cs = case("cornell_bm")
+    cam = camera_for(cs.soup, None, 24, 24)
+    fresh = RenderScene(cs.soup, cs.res, device=0)
+    want, _ = fresh.render(cam, num_samples=2, max_bounce=4)
+    fresh.close()
+    rs = scene("cornell_bm")
+    o, d = _random_batch(cs, 3000, 21)
+    first = {m: trace_ref.hit_bits(rs.trace(o, d, flags=f)) for m, f in MODES.items()}
+    for m, f in MODES.items():                                 # the same bytes twice, a render in between
+        img, _ = rs.render(cam, num_samples=2, max_bounce=4)
+        assert np.array_equal(img, want), f"render after a {m} query"
+        assert np.array_equal(trace_ref.hit_bits(rs.trace(o, d, flags=f)), first[m]), m
+    img, _ = rs.render(cam, num_samples=2, max_bounce=4, stats=True)
+    assert np.array_equal(img, want)
+    assert np.array_equal(first["lane"], first["park"]) and np.array_equal(first["lane"], first["mt_exact"])
+
+
+def test_bad_batches_raise(scene):
+    ctx = scene("cornell_bm").context
+    rays = np.zeros(6, np.float32)
+    hits = np.zeros(4, np.uint32)
+    for rp, hp, flags in ((None, hits.ctypes.data, 0), (rays.ctypes.data, None, 0),
+                          (rays.ctypes.data, hits.ctypes.data, 0x4),             # a reserved render bit
+                          (rays.ctypes.data, hits.ctypes.data, native.FLAG_ONE_SET),   # a render-only flag
+                          (rays.ctypes.data, hits.ctypes.data, 0x20000)):
+        with pytest.raises(native.ZrtError) as e:
+            ctx.trace_raw(1, rp, hp, False, flags)
+        assert e.value.status == -1
+
+
+def test_torch_tensors_are_traced_in_place(case, scene):
+    if torch is None or not torch.cuda.is_available():
+        pytest.skip("torch sees no device")
+    cs, rs = case("cornell_bm"), scene("cornell_bm")
+    pick = np.random.default_rng(7).permutation(N_RAYS)[:200]
+    dev = torch.device("cuda", 0)
+    before = torch.arange(4096, dtype=torch.int32, device=dev)
+    o, d = torch.from_numpy(cs.o[pick]).to(dev), torch.from_numpy(cs.d[pick]).to(dev)
+    for mode, flags in MODES.items():
+        res = rs.trace(o, d, flags=flags)
+        after = torch.full((4096,), 5, dtype=torch.int32, device=dev)
+        hits = res["hits"]
+        assert hits.shape == (200, 4) and hits.dtype == torch.float32 and hits.device == dev
+        got = hits.cpu().numpy().view(np.uint32)
+        _check(got, trace_ref.hit_bits(rs.trace(cs.o[pick], cs.d[pick], flags=flags)), f"torch {mode}")
+        _check(got, cs.bits[pick], f"torch {mode} vs the reference")
+        ref_i32 = hits[:, 3].view(torch.int32).cpu().numpy()      # as Context.trace documents
+        assert np.array_equal(ref_i32.view(np.uint32), cs.bits[pick, 3])
+        assert torch.equal(before.cpu(), torch.arange(4096, dtype=torch.int32)) and bool((after == 5).all())
+        assert res["stats"]["segments"] == 200

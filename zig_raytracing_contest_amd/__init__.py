@@ -102,3 +102,17 @@ class RenderScene:
                                   num_ranks=num_ranks, stats=stats, image=img, linear=linear,
                                   packed=packed, samples_per_pass=samples_per_pass, flags=flags)
         return img, res
+
+    def trace(self, origins, dirs, flags: int = 0, stats: bool = False):
+        """Scene.traceRay (stage3.zig:152-186) for a batch of rays: see
+        native.Context.trace.  With numpy inputs and a host-built scene the
+        result also holds "source_triangle": each hit's ref mapped through
+        stage 2's Geometry.indices to the soup's triangle (native.MISS kept)."""
+        res = self.context.trace(origins, dirs, flags=flags, stats=stats)
+        if self.geometry is not None and "triangle" in res:
+            ref = res["triangle"]
+            hit = ref != native.MISS
+            src = np.full(ref.shape, native.MISS, np.uint32)
+            src[hit] = self.geometry.indices()[ref[hit]]
+            res["source_triangle"] = src
+        return res

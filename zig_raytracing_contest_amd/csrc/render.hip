@@ -2022,6 +2022,180 @@ const WfFn kWfBounceWide = (WfFn)wf_kernel<kWfMinWaves, false, false>;
 const WfFn kWfPrimaryExact = (WfFn)wf_kernel<kWfMinWaves, true, false, false, true>;
 const WfFn kWfBounceExact = (WfFn)wf_kernel<kWfMinWaves, false, false, false, true>;
 
+// ---------------------------------------------------------------------------
+// Batch ray queries (zrt_context_trace): Scene.traceRay (stage3.zig:152-186)
+// for caller-given rays through the render's own walks -- trace_ray per lane,
+// or wf_park_kernel over an identity queue (ray i = queue entry i).
+//
+// Directions need not be unit length, which the render's are.  Its kernels
+// lean on that in three places:
+//  * Moller-Trumbore's short reciprocal (mt_inv_det) is the division for
+//    |det| < 2^126, and |det| <= |e1| |e2| |d| stays below that for edge
+//    components below 2^62 (the contexts' mt_exact threshold) when |d| < 4/3;
+//  * dda_init_fq's quotients are the divisions for divisors |d_a| <= 2^32
+//    (quot_rn; its own guards cover small components and the numerators);
+//  * the escape table bins a direction by its slopes over the reciprocal of
+//    its dominant component (esc_dir_bin), which has to be a normal float
+//    with a normal reciprocal.
+// A ray with 0.5 <= d.d <= 1.5 (ray_fast; the f32 dot product's rounding is
+// far inside that slack, and an overflow, an underflow to zero or a NaN fails
+// it) meets all three: every |d_a| <= |d| < 1.23 and the dominant |d_a| >=
+// 0.4.  Such rays take the fast kernels; the others (and every ray of an
+// mt_exact context, of ZRT_FLAG_MT_EXACT or of a counting call) take the
+// unpacked lane walk with dda_init and the IEEE division, which is the
+// reference's arithmetic for any direction.  The frustum bounds do not apply
+// to a query: tau = -inf (no fast-forward, not even over crossings at
+// negative t, which tau = 0 would skip) and tfar = +inf.
+struct RayParams {
+    WfParams w;               // w.t: grid and scene; the park path's queue, hit records and counters
+    const float* rays;        // this chunk: 6 floats per ray (origin, direction)
+    uint32_t* hits;           // this chunk: a zrt_hit per ray as 4 u32 (4-byte aligned)
+    float4* q;                // rays_pack_kernel: the queue (w.q_in)
+    uint32_t* n_in8;          // rays_pack_kernel: the queue's region counts (w.n_in8)
+    uint32_t n;               // rays of this chunk (the host cuts a batch into chunks of <= kTraceChunk)
+    uint32_t which;           // kRaysAll, kRaysFast or kRaysRest
+    uint32_t* ctr;            // [0], [1]: work counters of the chunk's two walk launches;
+                              // [2]: its rays outside the fast domain
+};
+constexpr uint32_t kRaysAll = 0, kRaysFast = 1, kRaysRest = 2;
+
+__device__ __forceinline__ bool ray_fast(v3 d) {
+    const float n2 = dot(d, d);
+    return n2 >= 0.5f && n2 <= 1.5f;
+}
+__device__ __forceinline__ void ray_load(const float* rays, uint32_t i, v3& o, v3& d) {
+    const float* q = rays + 6ull * i;
+    o = mk(q[0], q[1], q[2]);
+    d = mk(q[3], q[4], q[5]);
+}
+// The zrt_hit of a ray; a miss (nearest stayed +inf: a kept t is below it) is
+// (+inf, 0, 0, 0xFFFFFFFF), which the reference leaves undefined.
+__device__ __forceinline__ void ray_store_hit(uint32_t* hits, uint32_t i, float t, float u, float v, uint32_t ref) {
+    const bool miss = t == kInf;
+    uint32_t* h = hits + 4ull * i;
+    h[0] = __float_as_uint(t);
+    h[1] = miss ? 0u : __float_as_uint(u);
+    h[2] = miss ? 0u : __float_as_uint(v);
+    h[3] = miss ? 0xFFFFFFFFu : ref;
+}
+
+// One lane = one ray, walked and tested by the lane itself (trace_ray), on a
+// persistent grid: a wave takes 64 * kWfChunk consecutive rays per work atomic.
+// `which`: kRaysFast leaves (and counts) the rays outside the fast domain,
+// kRaysRest traces only those -- the chunk's second launch, which ends at once
+// when the first counted none -- and kRaysAll every ray.
+// The walk ends for any input, NaN and infinite components included: a step
+// moves one axis's cell by one towards that axis's exit cell (0 or res - 1,
+// fixed by the direction's sign at the start; the start cell is clamped into
+// the grid), whatever the crossing values compare like, and the step out of
+// an exit cell ends the walk (T_EXIT = +inf, `exited`), so a ray takes at
+// most res0 + res1 + res2 steps; a cell's tests are bounded by its range.
+// STATS: per-lane work counters, the counting render's conventions
+// (trace_kernel): a cell per loop trip, a test per ref tried.
+template <bool STATS, bool PACKED, bool PK_BM, bool MTX>
+__global__ __launch_bounds__(kTraceBlock, STATS ? 1 : kWfMinWaves) void rays_walk_kernel(const RayParams r) {
+    const TraceParams& p = r.w.t;
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_occ[];
+    __shared__ uint32_t s_wcnt[2 * (kTraceBlock / 64)];
+    if (r.which == kRaysRest && r.ctr[2] == 0u) return;            // (the whole grid: nothing left)
+    for (uint32_t i = threadIdx.x; i < p.occ_words; i += blockDim.x) s_occ[i] = p.occ[i];
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t* const work = r.ctr + (r.which == kRaysRest ? 1u : 0u);
+    uint64_t prof[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t n_seg = 0, n_cells = 0, n_tests = 0, n_hits = 0, n_rest = 0;
+    for (;;) {
+        uint32_t base = 0;
+        if (lane == 0) base = atomicAdd(work, 64u * kWfChunk);
+        base = __builtin_amdgcn_readfirstlane(base);
+        if (base >= r.n) break;
+        for (uint32_t sub = 0; sub < kWfChunk; ++sub) {
+            const uint32_t i = base + 64u * sub + lane;
+            if (i >= r.n) continue;
+            v3 o, d;
+            ray_load(r.rays, i, o, d);
+            const bool fast = ray_fast(d);
+            if (r.which == kRaysFast && !fast) { ++n_rest; continue; }
+            if (r.which == kRaysRest && fast) continue;
+            float hu = 0.0f, hv = 0.0f;
+            uint32_t hidx = 0;
+            const float t = trace_ray<STATS, kTriBatch, PACKED, PK_BM, MTX>(p, s_occ, o, d, hu, hv, hidx, n_cells,
+                                                                            n_tests, prof, s_wcnt, -kInf, kInf);
+            ++n_seg;
+            if (t != kInf) ++n_hits;
+            ray_store_hit(r.hits, i, t, hu, hv, hidx);
+        }
+    }
+    if (r.which == kRaysFast) {
+        const unsigned long long s = wave_sum(n_rest);
+        if (lane == 0 && s != 0ull) atomicAdd(&r.ctr[2], (uint32_t)s);
+    }
+    if (STATS) {
+        const unsigned long long s0 = wave_sum(n_seg), s1 = wave_sum(n_cells), s2 = wave_sum(n_tests),
+                                 s3 = wave_sum(n_hits);
+        if (lane == 0) {
+            atomicAdd(&p.stats[0], s0);
+            atomicAdd(&p.stats[1], s1);
+            atomicAdd(&p.stats[2], s2);
+            atomicAdd(&p.stats[3], s3);
+        }
+    }
+}
+
+// The park path's queue for a chunk of n rays: ray i is queue entry i.  With
+// S = 1 and P = n, region g of the queue (region_base) is entries
+// [xcd_q0(n, g), xcd_q0(n, g + 1)), so eight full regions are the identity
+// layout and their counts the differences.  A record's (o, item) and
+// (d, depth) words are all wf_park_kernel reads; the hit record of entry i is
+// w.hit[i].  Rays outside the fast domain are counted for the launch that
+// retraces them (rays_walk_kernel, kRaysRest); the park kernel walks them
+// like any ray (it ends for any input, as above: its exit test compares cell
+// fields) and their records are overwritten.
+__global__ __launch_bounds__(kBlock) void rays_pack_kernel(const RayParams r) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < 8u) r.n_in8[i * kCtr] = xcd_q0(r.n, i + 1u) - xcd_q0(r.n, i);
+    bool rest = false;
+    if (i < r.n) {
+        v3 o, d;
+        ray_load(r.rays, i, o, d);
+        r.q[3ull * i] = make_float4(o.x, o.y, o.z, __uint_as_float(i));
+        r.q[3ull * i + 1] = make_float4(d.x, d.y, d.z, __uint_as_float(1u));
+        rest = !ray_fast(d);
+    }
+    const uint64_t m = __ballot(rest);
+    if (m != 0ull && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(m)) atomicAdd(&r.ctr[2], (uint32_t)__popcll(m));
+}
+
+// The park kernel's hit records (t, u, v, ref) as zrt_hit: the same refs as
+// the lane walk's, the miss fields set.
+__global__ __launch_bounds__(kBlock) void rays_out_kernel(const RayParams r) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= r.n) return;
+    const float4 h = r.w.hit[i];
+    ray_store_hit(r.hits, i, h.x, h.y, h.z, __float_as_uint(h.w));
+}
+
+using RayFn = void (*)(const RayParams);
+const RayFn kRaysWalkBM = (RayFn)rays_walk_kernel<false, true, true, false>;
+const RayFn kRaysWalk = (RayFn)rays_walk_kernel<false, true, false, false>;
+const RayFn kRaysWalkWide = (RayFn)rays_walk_kernel<false, false, false, false>;
+const RayFn kRaysWalkExact = (RayFn)rays_walk_kernel<false, false, false, true>;
+const RayFn kRaysWalkCount = (RayFn)rays_walk_kernel<true, false, false, true>;
+// rays per chunk of a batch: queue indices and work counters stay far below
+// 2^32, and the staging and queue memory of a call is bounded (104 B per ray)
+constexpr uint64_t kTraceChunk = 1ull << 20;
+// batch size from which a call takes the park path unasked (ZRT_TRACE_PARK
+// forces it, ZRT_FLAG_LANE_WALK forbids it): 2^19, the smallest size at which
+// the park path won in both repeats on BOTH ray sets of tools/trace_bench.py
+// (cfg3 scene, profiles/trace_bench_cfg3.json: camera rays 0.100 vs 0.137 ms,
+// incoherent rays 0.48 vs 1.12 ms per call).  Below it the winner depends on
+// the rays, which the call cannot know: incoherent rays are 2-3.6x faster
+// through the park path at every size from 2^10 up, coherent rays that all
+// miss 1.2-5x faster through the lane walk
+constexpr uint64_t kTraceParkMin = 1ull << 19;
+constexpr uint32_t kTraceFlags = ZRT_FLAG_COUNT_STATS | ZRT_FLAG_LANE_WALK | ZRT_FLAG_MT_EXACT | ZRT_FLAG_ESCAPE |
+                                 ZRT_FLAG_NO_ESCAPE | ZRT_FLAG_RELEASE | ZRT_FLAG_NO_RELEASE | ZRT_TRACE_PARK;
+
 // max_bounce picks the stack depth the counting kernel is compiled for.
 TraceFn count_fn(uint32_t max_bounce) {
     if (max_bounce <= 4) return (TraceFn)trace_kernel<4>;
@@ -2136,6 +2310,9 @@ struct zrt_context {
     float4* d_acc = nullptr; size_t acc_cap = 0;
     uint8_t* d_rgb = nullptr; size_t rgb_cap = 0;
     float* d_lin = nullptr; size_t lin_cap = 0;
+    // zrt_context_trace: a host batch's chunk on the device (6 floats, 4 u32 per ray)
+    float* d_rays = nullptr; size_t rays_cap = 0;
+    uint32_t* d_hits = nullptr; size_t hits_cap = 0;
     std::vector<hipEvent_t> ev_pass;   // per pass: its resolve done
     hipEvent_t ev_fork = nullptr;
     uint32_t* d_counter = nullptr;
@@ -2291,7 +2468,7 @@ extern "C" void zrt_context_destroy(zrt_context* c) {
     if (c->d_cell32) (void)hipFree(c->d_cell32);
     void* bufs[] = {c->d_cells, c->d_pos, c->d_data, c->d_mats, c->d_texels, c->d_zig, c->d_occ, c->d_occx, c->d_esc,
                     c->d_bmask, c->d_sat, c->d_tlo,
-                    c->d_pix, c->d_out, c->d_acc, c->d_rgb, c->d_lin, c->d_counter, c->d_stats};
+                    c->d_pix, c->d_out, c->d_acc, c->d_rgb, c->d_lin, c->d_rays, c->d_hits, c->d_counter, c->d_stats};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (zrt_context::PassSet& ps : c->set) {
@@ -3061,6 +3238,53 @@ extern "C" int zrt_context_grid_info(zrt_context* c, zrt_grid* grid, uint32_t in
     return ZRT_OK;
 }
 
+// The grid and scene part of a launch's TraceParams (everything but the
+// camera, the pass and the output fields, which are left zero).
+static void scene_params(const zrt_context* c, TraceParams& tp) {
+    memset(&tp, 0, sizeof tp);
+    for (int i = 0; i < 3; ++i) {
+        tp.bmin[i] = c->grid.bbox_min[i];
+        tp.bmax[i] = c->grid.bbox_max[i];
+        tp.res[i] = c->grid.resolution[i];
+        tp.cs[i] = c->grid.cell_size[i];
+        tp.ics[i] = 1.0f / c->grid.cell_size[i];          // IEEE: RN(1 / cs)
+    }
+    tp.cs_ok = 1u;
+    for (int i = 0; i < 3; ++i)
+        if (!(fabsf(tp.cs[i]) >= 0x1p-32f && fabsf(tp.cs[i]) <= 0x1p32f)) tp.cs_ok = 0u;
+    tp.cells = c->d_cells;
+    tp.pk = c->pk;
+    tp.cell32 = c->d_cell32;
+    {
+        const uint32_t sh = c->occ_shift, b[3] = {c->pk.b0, c->pk.b1, c->pk.b2};
+        tp.occ_w0 = b[0] > sh ? b[0] - sh : 0u;
+        tp.occ_w1 = b[1] > sh ? b[1] - sh : 0u;
+        tp.occ_w2 = b[2] > sh ? b[2] - sh : 0u;
+        auto lowbits = [&](int a) { return (1u << std::min(sh, b[a])) - 1u; };
+        tp.occ_o1 = c->pk.o1 + sh;
+        tp.occ_o2 = c->pk.o2 + sh;
+        // (brick-major words: occupancy bricks of 4^3, the word's low six bits)
+        tp.occ_lowm = c->pk.bm ? 63u : lowbits(0) | (lowbits(1) << c->pk.o1) | (lowbits(2) << c->pk.o2);
+        tp.ox1 = c->pk.o1 + 2u;
+        tp.ox2 = c->pk.o2 + 2u;
+        tp.ow0 = b[0] - 2u;
+        tp.ow1 = b[1] - 2u;
+        tp.ow2 = b[2] - 2u;
+    }
+    tp.tri_pos = c->d_pos;
+    tp.tri_data = c->d_data;
+    tp.mats = c->d_mats;
+    tp.nmat = c->nmat;
+    tp.texels = c->d_texels;
+    tp.zig = c->d_zig;
+    tp.occ = c->d_occ;
+    tp.bmask = c->d_bmask;
+    tp.occ_shift = c->occ_shift;
+    tp.occ_nb0 = c->occ_nb[0];
+    tp.occ_nb01 = c->occ_nb[0] * c->occ_nb[1];
+    tp.occ_words = c->occ_words;
+}
+
 // Samples per pass: the caller's cfg->samples_per_pass, else as few passes
 // as the queue budget allows but at least one per pass set (the sets' kernels
 // overlap on their streams), split evenly: cfg3 256 spp = 2 x 128 (r02bq, two
@@ -3345,52 +3569,13 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
     }
 
     TraceParams tp;
-    memset(&tp, 0, sizeof tp);
+    scene_params(c, tp);
     for (int i = 0; i < 3; ++i) {
-        tp.bmin[i] = c->grid.bbox_min[i];
-        tp.bmax[i] = c->grid.bbox_max[i];
-        tp.res[i] = c->grid.resolution[i];
-        tp.cs[i] = c->grid.cell_size[i];
-        tp.ics[i] = 1.0f / c->grid.cell_size[i];          // IEEE: RN(1 / cs)
         tp.org[i] = cam->origin[i];
         tp.llc[i] = cam->lower_left_corner[i];
         tp.right[i] = cam->right[i];
         tp.up[i] = cam->up[i];
     }
-    tp.cs_ok = 1u;
-    for (int i = 0; i < 3; ++i)
-        if (!(fabsf(tp.cs[i]) >= 0x1p-32f && fabsf(tp.cs[i]) <= 0x1p32f)) tp.cs_ok = 0u;
-    tp.cells = c->d_cells;
-    tp.pk = c->pk;
-    tp.cell32 = c->d_cell32;
-    {
-        const uint32_t sh = c->occ_shift, b[3] = {c->pk.b0, c->pk.b1, c->pk.b2};
-        tp.occ_w0 = b[0] > sh ? b[0] - sh : 0u;
-        tp.occ_w1 = b[1] > sh ? b[1] - sh : 0u;
-        tp.occ_w2 = b[2] > sh ? b[2] - sh : 0u;
-        auto lowbits = [&](int a) { return (1u << std::min(sh, b[a])) - 1u; };
-        tp.occ_o1 = c->pk.o1 + sh;
-        tp.occ_o2 = c->pk.o2 + sh;
-        // (brick-major words: occupancy bricks of 4^3, the word's low six bits)
-        tp.occ_lowm = c->pk.bm ? 63u : lowbits(0) | (lowbits(1) << c->pk.o1) | (lowbits(2) << c->pk.o2);
-        tp.ox1 = c->pk.o1 + 2u;
-        tp.ox2 = c->pk.o2 + 2u;
-        tp.ow0 = b[0] - 2u;
-        tp.ow1 = b[1] - 2u;
-        tp.ow2 = b[2] - 2u;
-    }
-    tp.tri_pos = c->d_pos;
-    tp.tri_data = c->d_data;
-    tp.mats = c->d_mats;
-    tp.nmat = c->nmat;
-    tp.texels = c->d_texels;
-    tp.zig = c->d_zig;
-    tp.occ = c->d_occ;
-    tp.bmask = c->d_bmask;
-    tp.occ_shift = c->occ_shift;
-    tp.occ_nb0 = c->occ_nb[0];
-    tp.occ_nb01 = c->occ_nb[0] * c->occ_nb[1];
-    tp.occ_words = c->occ_words;
     tp.w = cam->w;
     tp.pixlist = c->d_pix;
     tp.P = P;
@@ -3653,6 +3838,193 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
 extern "C" int zrt_context_profile(const zrt_context* c, zrt_kernel_profile* out) {
     if (!c || !out) return ZRT_ERR_INVALID_ARG;
     *out = c->prof;
+    return ZRT_OK;
+}
+
+// Blocks of a persistent launch of `f`: what the device holds at once.
+static int resident_blocks(const zrt_context* c, const void* f, int threads, size_t lds, uint32_t* blocks) {
+    int bpc = 0;
+    HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, f, threads, lds));
+    bpc = std::max(1, std::min(bpc, 2048 / threads));
+    *blocks = (uint32_t)(c->num_cus * bpc);
+    return ZRT_OK;
+}
+
+// Scene.traceRay (stage3.zig:152-186) for a batch of rays: see include/zrt.h
+// and the kernels' comment (rays_walk_kernel).  Per chunk of at most
+// kTraceChunk rays, all on the context's stream:
+//   lane walk:  rays_walk_kernel (fast kernel of the context, kRaysFast), then
+//               the IEEE-division kernel over the rays it left (kRaysRest);
+//               an mt_exact context, ZRT_FLAG_MT_EXACT or a counting call:
+//               that kernel alone over every ray (kRaysAll);
+//   park path:  rays_pack_kernel -> wf_park_kernel (the render's, unchanged)
+//               -> rays_out_kernel, then the kRaysRest launch as above.
+// The park path shares pass set 0's queue, hit records and counters with the
+// renders; each use writes what it reads first, so nothing carries over.
+extern "C" int zrt_context_trace(zrt_context* c, const zrt_ray_batch* b, zrt_stats* stats) {
+    if (!c || !b) return ZRT_ERR_INVALID_ARG;
+    if ((b->flags & ~kTraceFlags) != 0u || b->on_device > 1u) return ZRT_ERR_INVALID_ARG;
+    zrt_stats st{};
+    if (b->num_rays == 0) { if (stats) *stats = st; return ZRT_OK; }
+    if (!b->rays || !b->hits) return ZRT_ERR_INVALID_ARG;
+    DeviceGuard g(c->device);
+
+    // the same choices as a render's bounce launches (zrt_context_render)
+    const bool counting = (b->flags & ZRT_FLAG_COUNT_STATS) != 0;
+    const bool mtx = c->mt_exact || (b->flags & ZRT_FLAG_MT_EXACT);
+    const bool park_ok = c->occx_ok && !counting && !(b->flags & ZRT_FLAG_LANE_WALK) && c->packed && !mtx;
+    const bool park = park_ok && ((b->flags & ZRT_TRACE_PARK) || b->num_rays >= kTraceParkMin);
+    const bool packed = c->packed && !mtx;
+    const bool pbm = packed && c->pk.bm;
+    const bool rel = !(b->flags & ZRT_FLAG_NO_RELEASE) && (c->rel_on || (b->flags & ZRT_FLAG_RELEASE));
+    int rc;
+    if (!c->esc_tried && park && !(b->flags & ZRT_FLAG_NO_ESCAPE) &&
+        (b->num_rays >= kSetsMinSamples || (b->flags & ZRT_FLAG_ESCAPE))) {
+        c->esc_tried = true;
+        if ((rc = context_escape(c)) != ZRT_OK) return rc;
+    }
+    const bool esc = c->d_esc && !(b->flags & ZRT_FLAG_NO_ESCAPE) && (c->esc_on || (b->flags & ZRT_FLAG_ESCAPE));
+    // the fast kernel (null: every ray takes f_exact) and the IEEE-division one
+    const RayFn f_fast = (counting || mtx) ? nullptr : packed ? (pbm ? kRaysWalkBM : kRaysWalk) : kRaysWalkWide;
+    const RayFn f_exact = counting ? kRaysWalkCount : kRaysWalkExact;
+    const WfFn f_park = pbm ? (esc ? (WfFn)wf_park_kernel<true, true> : (WfFn)wf_park_kernel<false, true>)
+                            : (esc ? (WfFn)wf_park_kernel<true, false> : (WfFn)wf_park_kernel<false, false>);
+
+    // chunk size: at most kTraceChunk rays, fewer if the device is short of
+    // memory (the budget of pass_samples: 60% of what is free, counting what
+    // the context already holds, shared between a group's contexts)
+    zrt_context::PassSet& ps = c->set[0];
+    const uint64_t per_ray = (b->on_device ? 0ull : 40ull) + (park ? 64ull : 0ull);
+    const size_t held = 4ull * (c->rays_cap + c->hits_cap) + 16ull * (ps.q0_cap + ps.hit_cap);
+    size_t budget = (size_t)144 << 30;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b) budget = std::min(budget, (free_b + held) / 10 * 6);
+    budget /= std::max<uint32_t>(c->mem_share, 1u);
+    uint64_t chunk = std::min<uint64_t>(kTraceChunk, b->num_rays);
+    if (per_ray) chunk = std::max<uint64_t>(64, std::min<uint64_t>(chunk, budget / per_ray));
+    if (!b->on_device) {
+        if ((rc = grow(&c->d_rays, &c->rays_cap, 6 * chunk)) != ZRT_OK) return rc;
+        if ((rc = grow(&c->d_hits, &c->hits_cap, 4 * chunk)) != ZRT_OK) return rc;
+    }
+    const size_t wfc_words = 32ull * kCtr * 2;     // (a render's smallest; this call uses 16 counters)
+    if (park) {
+        if ((rc = grow(&ps.q0, &ps.q0_cap, 3 * chunk)) != ZRT_OK) return rc;
+        if ((rc = grow(&ps.hit, &ps.hit_cap, chunk)) != ZRT_OK) return rc;
+        if ((rc = grow(&ps.wfc, &ps.wfc_cap, wfc_words)) != ZRT_OK) return rc;
+    }
+    // capacity guard (as zrt_context_render's): every buffer a launch below
+    // writes holds a chunk
+    if ((!b->on_device && (!c->d_rays || c->rays_cap < 6 * chunk || !c->d_hits || c->hits_cap < 4 * chunk)) ||
+        (park && (!ps.q0 || ps.q0_cap < 3 * chunk || !ps.hit || ps.hit_cap < chunk || !ps.wfc ||
+                  ps.wfc_cap < wfc_words)))
+        return ZRT_ERR_INVALID_ARG;
+    while (c->ev_trace.size() < 2) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreate(&e));
+        c->ev_trace.push_back(e);
+    }
+
+    // occupancy-sized persistent grids (no more blocks than a chunk has work for)
+    const size_t lds_wf = 4ull * c->occ_words;
+    const uint32_t occx_ldsw = (uint32_t)occx_lds_words(c->occx_nbw, c->occx_moff, c->occx_words);
+    const size_t lds_park = 4ull * occx_ldsw + (size_t)(kParkBlock / 64) * sizeof(ParkSlot);
+    uint32_t grid_fast = 0, grid_exact = 0, grid_park = 0;
+    if (f_fast && !park && (rc = resident_blocks(c, (const void*)f_fast, kTraceThreads, lds_wf, &grid_fast)) != ZRT_OK)
+        return rc;
+    if ((rc = resident_blocks(c, (const void*)f_exact, kTraceThreads, lds_wf, &grid_exact)) != ZRT_OK) return rc;
+    if (park && (rc = resident_blocks(c, (const void*)f_park, kParkBlock, lds_park, &grid_park)) != ZRT_OK) return rc;
+
+    RayParams R;
+    memset(&R, 0, sizeof R);
+    scene_params(c, R.w.t);
+    R.w.t.max_bounce = 1;
+    R.w.t.counter = c->d_counter;
+    R.w.t.stats = c->d_stats;
+    R.ctr = c->d_counter;
+    if (park) {
+        R.w.q_in = ps.q0;
+        R.w.hit = ps.hit;
+        R.w.fetch8 = ps.wfc;
+        R.w.n_in8 = ps.wfc + 8 * kCtr;
+        R.w.occx = c->d_occx;
+        R.w.occx_words = c->occx_words;
+        R.w.occx_ldsw = occx_ldsw;
+        R.w.occx_nbw = c->occx_nbw;
+        R.w.occx_moff = c->occx_moff;
+        R.w.occx_nb0 = c->occx_nb[0];
+        R.w.occx_nb01 = c->occx_nb[0] * c->occx_nb[1];
+        R.w.test_min = rel ? kParkTestMinRel : kParkTestMin;
+        R.w.refill_min = kParkRefillMin;
+        R.w.rel_min = rel ? R.w.test_min : 0u;
+        R.w.rel_emin = 1;
+        R.w.esc = c->d_esc;
+        R.q = ps.q0;
+        R.n_in8 = ps.wfc + 8 * kCtr;
+    }
+
+    HIP_TRY(hipMemsetAsync(c->d_stats, 0, 512, c->stream));
+    HIP_TRY(hipEventRecord(c->ev_begin, c->stream));
+    uint32_t launches = 0;
+    for (uint64_t off = 0; off < b->num_rays; off += chunk) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, b->num_rays - off);
+        if (b->on_device) {
+            R.rays = b->rays + 6 * off;
+            R.hits = reinterpret_cast<uint32_t*>(b->hits + off);
+        } else {
+            HIP_TRY(hipMemcpyAsync(c->d_rays, b->rays + 6 * off, 24ull * n, hipMemcpyHostToDevice, c->stream));
+            R.rays = c->d_rays;
+            R.hits = c->d_hits;
+            HIP_TRY(hipEventRecord(c->ev_trace[0], c->stream));
+        }
+        R.n = n;
+        HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
+        const uint32_t nblk = (n + kBlock - 1) / kBlock;         // one thread per ray; also all a walk launch needs
+        if (park) {
+            // the work counters; rays_pack_kernel writes the region counts
+            HIP_TRY(hipMemsetAsync(ps.wfc, 0, 4ull * 16 * kCtr, c->stream));
+            R.w.t.P = n;
+            R.w.t.S = 1;
+            R.w.t.total = n;
+            R.w.t.sdiv = div_magic(1);
+            R.which = kRaysAll;
+            hipLaunchKernelGGL(rays_pack_kernel, dim3(nblk), dim3(kBlock), 0, c->stream, R);
+            hipLaunchKernelGGL(f_park, dim3(grid_park), dim3(kParkBlock), lds_park, c->stream, R.w);
+            hipLaunchKernelGGL(rays_out_kernel, dim3(nblk), dim3(kBlock), 0, c->stream, R);
+            launches += 3;
+        } else if (f_fast) {
+            R.which = kRaysFast;
+            hipLaunchKernelGGL(f_fast, dim3(std::min(grid_fast, nblk)), dim3(kTraceThreads), lds_wf, c->stream, R);
+            ++launches;
+        }
+        R.which = park || f_fast ? kRaysRest : kRaysAll;
+        hipLaunchKernelGGL(f_exact, dim3(std::min(grid_exact, nblk)), dim3(kTraceThreads), lds_wf, c->stream, R);
+        ++launches;
+        HIP_TRY(hipGetLastError());
+        if (!b->on_device) {
+            HIP_TRY(hipEventRecord(c->ev_trace[1], c->stream));
+            HIP_TRY(copy_sync(b->hits + off, c->d_hits, 16ull * n, hipMemcpyDeviceToHost, c->stream));
+            float t = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&t, c->ev_trace[0], c->ev_trace[1]));
+            st.trace_kernel_ms += t;
+        }
+    }
+    HIP_TRY(hipEventRecord(c->ev_end, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev_begin, c->ev_end));
+    st.render_ms = ms;
+    if (b->on_device) st.trace_kernel_ms = ms;
+    st.trace_launches = launches;
+    st.segments = b->num_rays;
+    if (counting) {
+        unsigned long long hs[4];
+        HIP_TRY(copy_sync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+        st.cells_visited = hs[1];
+        st.triangle_tests = hs[2];
+        st.hits = hs[3];
+    }
+    if (stats) *stats = st;
     return ZRT_OK;
 }
 

@@ -25,6 +25,8 @@ FLAG_FRUSTUM, FLAG_NO_FRUSTUM = 0x100, 0x200
 FLAG_ONE_SET, FLAG_KERNEL_TIMES = 0x10, 0x20
 FLAG_MT_EXACT = 0x400
 FLAG_RELEASE, FLAG_NO_RELEASE = 0x800, 0x1000
+TRACE_PARK = 0x10000       # ZRT_TRACE_PARK (zrt_ray_batch.flags only)
+MISS = 0xFFFFFFFF          # zrt_hit.triangle of a ray that hit nothing
 # zrt_kernel_profile classes (include/zrt.h)
 KERNEL_CLASSES = ("primary", "park", "shade", "bounce", "resolve", "count")
 
@@ -111,13 +113,25 @@ class Outputs(C.Structure):
                 ("linear_packed", C.c_void_p), ("device_rgb_packed", C.c_void_p)]
 
 
+class Hit(C.Structure):
+    _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("triangle", C.c_uint32)]
+
+
+HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("triangle", "<u4")])
+
+
+class RayBatch(C.Structure):
+    _fields_ = [("num_rays", C.c_uint64), ("rays", C.c_void_p), ("hits", C.c_void_p),
+                ("on_device", C.c_uint32), ("flags", C.c_uint32)]
+
+
 EXPORTS = [
     "zrt_error_string", "zrt_abi_version", "zrt_device_count", "zrt_device_warmup", "zrt_geometry_build",
     "zrt_geometry_build_device",
     "zrt_geometry_scene", "zrt_geometry_indices", "zrt_geometry_free", "zrt_render",
     "zrt_context_create", "zrt_context_create_built", "zrt_context_grid_info", "zrt_context_render", "zrt_context_destroy", "zrt_tile_pixels",
     "zrt_gltf_load", "zrt_gltf_soup", "zrt_gltf_materials", "zrt_gltf_camera", "zrt_gltf_free",
-    "zrt_camera_from_matrix", "zrt_probe", "zrt_timed_kernels", "zrt_context_profile",
+    "zrt_camera_from_matrix", "zrt_probe", "zrt_timed_kernels", "zrt_context_profile", "zrt_context_trace",
     "zrt_group_create", "zrt_group_create_built", "zrt_group_render", "zrt_group_context", "zrt_group_destroy",
 ]
 
@@ -153,6 +167,7 @@ def lib():
     L.zrt_context_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderConfig),
                                      C.POINTER(Outputs), C.POINTER(Stats)]
     L.zrt_context_profile.argtypes = [C.c_void_p, C.POINTER(KernelProfile)]
+    L.zrt_context_trace.argtypes = [C.c_void_p, C.POINTER(RayBatch), C.POINTER(Stats)]
     L.zrt_context_destroy.argtypes = [C.c_void_p]
     L.zrt_context_destroy.restype = None
     if hasattr(L, "zrt_group_create"):      # ABI 2 (an ABI-1 build: tools/ A/B baselines only)
@@ -361,6 +376,52 @@ class Context:
                                        C.byref(st)), "zrt_context_render")
         res["stats"] = st.as_dict()
         return res
+
+    def trace_raw(self, num_rays: int, rays_ptr, hits_ptr, on_device: bool, flags: int = 0):
+        """zrt_context_trace on raw pointers; returns the stats dict."""
+        batch = RayBatch(int(num_rays), rays_ptr, hits_ptr, 1 if on_device else 0, int(flags))
+        st = Stats()
+        check(lib().zrt_context_trace(self._h, C.byref(batch), C.byref(st)), "zrt_context_trace")
+        return st.as_dict()
+
+    def trace(self, origins, dirs, flags: int = 0, stats: bool = False):
+        """Scene.traceRay (stage3.zig:152-186) for n rays: where each one first
+        hits the context's scene.  `dirs` need not be unit length.
+
+        Two (n, 3) float32 numpy arrays give {"t", "u", "v", "triangle"} as
+        (n,) numpy arrays -- a miss is (+inf, 0, 0, MISS); "triangle" is the
+        baked ref -- and "stats" (the work counters filled with stats=True).
+
+        Two (n, 3) float32 CUDA tensors (torch-ROCm) on the context's device
+        are traced in place, after a sync of torch's current stream; the
+        result is {"hits": an (n, 4) float32 CUDA tensor of (t, u, v, ref bit
+        pattern), "stats"}; `hits[:, 3].view(torch.int32)` is the ref (-1: a
+        miss).  The call returns with the tensor complete."""
+        flags = int(flags) | (FLAG_COUNT_STATS if stats else 0)
+        if type(origins).__module__.split(".")[0] == "torch":
+            import torch
+            if not (origins.is_cuda and dirs.is_cuda and origins.device == dirs.device):
+                raise ValueError("trace: torch inputs must be CUDA tensors on the context's device")
+            if origins.dtype != torch.float32 or dirs.dtype != torch.float32:
+                raise ValueError("trace: float32 tensors expected")
+            if origins.dim() != 2 or origins.shape[1] != 3 or origins.shape != dirs.shape:
+                raise ValueError("trace: two (n, 3) tensors expected")
+            n = int(origins.shape[0])
+            rays = torch.cat([origins, dirs], dim=1).contiguous()
+            hits = torch.empty((n, 4), dtype=torch.float32, device=origins.device)
+            torch.cuda.current_stream(origins.device).synchronize()
+            st = self.trace_raw(n, rays.data_ptr() if n else None, hits.data_ptr() if n else None, True, flags)
+            return {"hits": hits, "stats": st}
+        o = np.asarray(origins, np.float32)
+        d = np.asarray(dirs, np.float32)
+        if o.ndim != 2 or o.shape[1] != 3 or o.shape != d.shape:
+            raise ValueError("trace: two (n, 3) arrays expected")
+        n = o.shape[0]
+        rays = np.ascontiguousarray(np.concatenate([o, d], axis=1))
+        hits = np.empty(n, HIT_DTYPE)
+        st = self.trace_raw(n, rays.ctypes.data if n else None, hits.ctypes.data if n else None, False, flags)
+        return {"t": hits["t"].copy(), "u": hits["u"].copy(), "v": hits["v"].copy(),
+                "triangle": hits["triangle"].copy(), "stats": st}
 
 
 def render_oneshot(scene: Scene, cam: Camera, spp: int, max_bounce: int, seed: int = 0,
