@@ -144,6 +144,12 @@ typedef struct zrt_render_config {
                                         entry faces of the occupied cells have nothing left to test); same
                                         image */
 #define ZRT_FLAG_NO_RELEASE   0x1000u /* never (wins over ZRT_FLAG_RELEASE); same image */
+#define ZRT_FLAG_BFCULL       0x2000u /* the park kernel skips, in a segment's first cell, the refs whose
+                                        determinant test fails for every direction of the ray's direction
+                                        bin (back-face cull masks, built at the first such call if they fit
+                                        the memory budget; by default only on scenes whose statistic says
+                                        they pay); same image */
+#define ZRT_FLAG_NO_BFCULL    0x4000u /* never (wins over ZRT_FLAG_BFCULL); same image */
 
 /* Per-call statistics.  segments = Scene.traceRay calls (primary + bounce +
  * transparency pass-through); Mrays/s = segments / render time. */
@@ -269,7 +275,7 @@ typedef struct zrt_ray_batch {
     uint32_t on_device;              /* 0: host pointers; 1: both are device pointers on the context's
                                         device (4-byte aligned), complete once the call returns */
     uint32_t flags;                  /* ZRT_FLAG_COUNT_STATS | ZRT_FLAG_LANE_WALK | ZRT_FLAG_MT_EXACT |
-                                        ZRT_FLAG_ESCAPE / NO_ESCAPE / RELEASE / NO_RELEASE as in a render
+                                        ZRT_FLAG_ESCAPE / NO_ESCAPE / RELEASE / NO_RELEASE / BFCULL / NO_BFCULL as in a render
                                         (same hits either way) | ZRT_TRACE_PARK; any other bit is
                                         ZRT_ERR_INVALID_ARG */
 } zrt_ray_batch;

@@ -277,4 +277,89 @@ ZHD FrustumBound frustum_bound(const EscSat& S, const uint32_t res[3], const flo
     return fb;
 }
 
+// ---------------------------------------------------------------------------
+// Back-face cull masks (render.hip bfc_build_kernel, the park kernel's first
+// cell; tests/cpp/bfcull_check.cpp).
+//
+// tri_ray rejects a ref as soon as det = dot(e1, cross(d, e2)) < 1e-8.  Per
+// (cell, direction bin) the table holds one u32: bit r stays set when ref r of
+// the cell must still be tested for some direction of the bin; a cleared bit
+// means det < 1e-8 for EVERY direction the device can assign to the bin, so
+// the test could only have been rejected.  Cells of more than 32 refs keep
+// all ones (as the entry-face masks do).
+//
+// Bins: esc_dir_bin's, merged kEscBins / kBfcBins to a side (a coarse bin's
+// cone is the union of its fine bins' cones, widened by kEscEps like them).
+// esc_dir_bin computes the slopes u = d_b * rcp(|d_a|) and the cell index
+// floor((u + 1) * 0.5 * K) in f32: a reciprocal within 2 ulp and four
+// roundings of values <= K move the index boundary by less than 3e-6 in u,
+// far inside kEscEps = 1e-3; that needs a normal dominant component with a
+// normal reciprocal, which bfc_dir_ok guarantees (and the caller checks).
+//
+// The bound.  With D = d / |d_a| = (+-1, u, v) (dominant axis first) and
+// s = |d_a| > 0, the exact determinant is s * det(D), and det(D) =
+// -(e1 x e2) . D is linear in (u, v).  tri_ray evaluates it in f32 without
+// contraction: each of the six products e1_i * (d_j * e2_k) passes through at
+// most five roundings (d_j e2_k, the subtraction, the product with e1_i, two
+// additions), so
+//     |det_f32 - s det(D)| <= ((1 + 2^-24)^5 - 1) s S(D) + 9 * 2^-126,
+//     S(D) = sum_i |e1_i| (|D_j| |e2_k| + |D_k| |e2_j|)
+// (the last term: every operation that underflows adds at most 2^-126,
+// flushed or not).  S scales with |e1| |e2| |D|, not with |e1 x e2|: a
+// sliver's normal is tiny, its rounding error is not.  g(D) = det(D) +
+// kBfcMargin S(D), kBfcMargin = 2^-21 = 8 * 2^-24, is convex in (u, v)
+// (linear plus a sum of absolute values of linear forms), so its maximum over
+// the bin's square is at a corner.  The four corners are evaluated in double
+// (relative error 2^-50 of S, inside the 3 * 2^-24 of slack over the five
+// roundings); if g < 0 at all four, det_f32 <= s g(D) + 9 * 2^-126 < 1e-8 for
+// every d of the cone.  No intermediate may overflow either: with the
+// caller's |d_x| + |d_y| + |d_z| <= 4 (bfc_dir_ok) every partial sum is below
+// 4 S (1 + 2^-20), so S <= 2^120 at the corners keeps them finite.  A ref
+// with a non-finite edge component is never culled.
+#ifndef ZRT_BFC_BINS
+#define ZRT_BFC_BINS 4
+#endif
+constexpr uint32_t kBfcBins = ZRT_BFC_BINS;                    // per face axis
+static_assert(kBfcBins >= 1 && kEscBins % kBfcBins == 0, "a cull bin is a union of escape bins");
+constexpr uint32_t kBfcNBin = 6 * kBfcBins * kBfcBins;         // u32 words per cell
+constexpr double kBfcMargin = 0x1p-21;
+
+// The cull bin of esc_dir_bin's bin.
+ZHD uint32_t bfc_bin_of(uint32_t esc_bin) {
+    constexpr uint32_t q = kEscBins / kBfcBins;
+    const uint32_t f = esc_bin / (kEscBins * kEscBins), iu = (esc_bin / kEscBins) % kEscBins, iv = esc_bin % kEscBins;
+    return (f * kBfcBins + iu / q) * kBfcBins + iv / q;
+}
+// Directions the masks hold for: finite, dominant component normal with a
+// normal reciprocal (>= 3.3e-31), components within the overflow bound above.
+ZHD bool bfc_dir_ok(v3 d) {
+    const float s = (fabsf(d.x) + fabsf(d.y)) + fabsf(d.z);
+    return s >= 1e-30f && s <= 4.0f;                           // (a NaN fails both)
+}
+// Whether the ref with edges e1, e2 can be skipped for every direction of
+// cull bin `bin`.  margin and eps are kBfcMargin and kEscEps everywhere but in
+// the host check's controls (0: the check must then find violations).
+ZHD bool bfc_cull(const float e1[3], const float e2[3], uint32_t bin, double margin = kBfcMargin,
+                  double eps = kEscEps) {
+    for (int k = 0; k < 3; ++k)
+        if (!(fabsf(e1[k]) < kInf) || !(fabsf(e2[k]) < kInf)) return false;
+    const uint32_t fc = bin / (kBfcBins * kBfcBins), iu = (bin / kBfcBins) % kBfcBins, iv = bin % kBfcBins;
+    const int a = (int)(fc / 2u), b = a == 0 ? 1 : 0, c = a == 2 ? 1 : 2;
+    const double nb = (double)kBfcBins;
+    const double uu[2] = {-1.0 + 2.0 * iu / nb - eps, -1.0 + 2.0 * (iu + 1) / nb + eps};
+    const double vv[2] = {-1.0 + 2.0 * iv / nb - eps, -1.0 + 2.0 * (iv + 1) / nb + eps};
+    const double ax = e1[0], ay = e1[1], az = e1[2], bx = e2[0], by = e2[1], bz = e2[2];
+    for (int k = 0; k < 4; ++k) {
+        double D[3];
+        D[a] = (fc & 1u) ? -1.0 : 1.0;
+        D[b] = uu[k & 1];
+        D[c] = vv[k >> 1];
+        const double det = ax * (D[1] * bz - D[2] * by) + ay * (D[2] * bx - D[0] * bz) + az * (D[0] * by - D[1] * bx);
+        const double S = fabs(ax) * (fabs(D[1] * bz) + fabs(D[2] * by)) + fabs(ay) * (fabs(D[2] * bx) + fabs(D[0] * bz)) +
+                         fabs(az) * (fabs(D[0] * by) + fabs(D[1] * bx));
+        if (!(S <= 0x1p120) || !(det + margin * S < 0.0)) return false;
+    }
+    return true;
+}
+
 }  // namespace zrt

@@ -735,6 +735,10 @@ struct WfParams {
     // escape table (escape.h): kEscWords u32 per 4^3 brick, bit b of word
     // w = direction bin 32 w + b; null: not built (the walk never stops early)
     const uint32_t* esc;
+    // back-face cull masks (escape.h): kBfcNBin u32 per packed cell word, then
+    // one all-ones word; null: the first cell of a segment tests every ref
+    const uint32_t* bfc;
+    uint64_t bfc_ones;        // index of the all-ones word (cells x kBfcNBin)
 };
 
 // Work / append counters: one per 128-byte line (32 u32), so the waves'
@@ -1196,7 +1200,9 @@ __device__ __forceinline__ void park_load_range(const TraceParams& p, uint32_t p
 }
 // Range and the mask of the refs to test for a ray that entered the cell
 // across `face` (cell32_kernel) into rng[lane], rng[64 + lane], rng[128 + lane].
-__device__ __forceinline__ void park_load_cell(const TraceParams& p, uint32_t pc, uint32_t face, uint32_t* rng) {
+// Range and one mask word (`mask`: any u32 in global memory) into the same slots.
+__device__ __forceinline__ void park_load_masked(const TraceParams& p, uint32_t pc, const uint32_t* mask,
+                                                 uint32_t* rng) {
     const uint32_t* c = p.cell32 + 8ull * pc;
     const uint32_t m0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)rng);
     asm volatile("s_mov_b32 m0, %3\n\t"
@@ -1206,8 +1212,11 @@ __device__ __forceinline__ void park_load_cell(const TraceParams& p, uint32_t pc
                  "s_add_u32 m0, m0, 0x100\n\t"
                  "global_load_lds_dword %2, off"
                  :
-                 : "v"(c), "v"(c + 1), "v"(c + 2 + face), "s"(m0)
+                 : "v"(c), "v"(c + 1), "v"(mask), "s"(m0)
                  : "memory");
+}
+__device__ __forceinline__ void park_load_cell(const TraceParams& p, uint32_t pc, uint32_t face, uint32_t* rng) {
+    park_load_masked(p, pc, p.cell32 + 8ull * pc + 2 + face, rng);
 }
 
 // The escape-table word of a walking lane's current brick into its wave's
@@ -1289,7 +1298,7 @@ template <bool ESC, bool PK_BM>
 __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const WfParams w) {
     const TraceParams& p = w.t;
     extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[];
-    __shared__ uint32_t s_rng[kParkWaves * 192];            // LDS-DMA range + face-mask slots
+    __shared__ uint32_t s_rng[kParkWaves * 192];            // LDS-DMA range + mask slots
     uint32_t* const rng_slot = s_rng + 192u * (threadIdx.x >> 6);
     __shared__ uint32_t s_esc[kParkWaves * 64];             // escape-table words (park_load_esc)
     uint32_t* const esc_slot = s_esc + 64u * (threadIdx.x >> 6);
@@ -1404,6 +1413,7 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
                             if (ZRT_FAST_QUOT ? dda_init_fq(p.bmin, p.bmax, p.res, p.cs, p.ics, p.cs_ok != 0u, o, d, s0)
                                               : dda_init(p.bmin, p.bmax, p.res, p.cs, o, d, s0)) {   // stage3.zig:153-156
                                 ddav_from_t<PK_BM>(s0, gk, pk, s);
+                                const uint32_t bin = (ESC || w.bfc) ? esc_dir_bin(d) : 0u;
                                 if (ESC) {
                                     // (every DMA into this slot from the lane's last
                                     // ray has landed before this store: that ray's
@@ -1415,15 +1425,27 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
                                     // ZRT_PARK_LATE_DRAIN the kDone drain no longer
                                     // sits between them; the parity suite renders
                                     // every scene with the table forced on)
-                                    const uint32_t bin = esc_dir_bin(d);
                                     eoff = (bin >> 5) * 4u;
                                     emask = w.esc && s0.neg < 8u ? 1u << (bin & 31u) : 0u;
                                     eb = ~0u;
                                     esc_slot[lane] = 0u;
                                 }
                                 if (occx_cell<PK_BM>(occx_mask(L, occx_brick<PK_BM>(w, s)), s, pk)) {
-                                    park_load_range(p, s.pc, rng_slot);
-                                    rng_slot[128 + lane] = ~0u;    // first cell: every ref
+                                    if (w.bfc) {
+                                        // first cell: no cell was left, so no entry-face
+                                        // mask; the refs that the ray's direction bin
+                                        // cannot reject by their determinant alone
+                                        // (escape.h bfc_cull; every ref for a direction
+                                        // outside the proof's domain).  The lane's last
+                                        // DMA into this slot was drained by the test
+                                        // round that let its last ray leave its last cell
+                                        const uint64_t wi = bfc_dir_ok(d) ? (uint64_t)s.pc * kBfcNBin + bfc_bin_of(bin)
+                                                                          : w.bfc_ones;
+                                        park_load_masked(p, s.pc, w.bfc + wi, rng_slot);
+                                    } else {
+                                        park_load_range(p, s.pc, rng_slot);
+                                        rng_slot[128 + lane] = ~0u;    // first cell: every ref
+                                    }
                                     st = kPark;
                                 } else {
                                     st = kWalk;
@@ -2194,7 +2216,8 @@ constexpr uint64_t kTraceChunk = 1ull << 20;
 // miss 1.2-5x faster through the lane walk
 constexpr uint64_t kTraceParkMin = 1ull << 19;
 constexpr uint32_t kTraceFlags = ZRT_FLAG_COUNT_STATS | ZRT_FLAG_LANE_WALK | ZRT_FLAG_MT_EXACT | ZRT_FLAG_ESCAPE |
-                                 ZRT_FLAG_NO_ESCAPE | ZRT_FLAG_RELEASE | ZRT_FLAG_NO_RELEASE | ZRT_TRACE_PARK;
+                                 ZRT_FLAG_NO_ESCAPE | ZRT_FLAG_RELEASE | ZRT_FLAG_NO_RELEASE | ZRT_FLAG_BFCULL |
+                                 ZRT_FLAG_NO_BFCULL | ZRT_TRACE_PARK;
 
 // max_bounce picks the stack depth the counting kernel is compiled for.
 TraceFn count_fn(uint32_t max_bounce) {
@@ -2283,6 +2306,15 @@ struct zrt_context {
     bool rel_on = false;
     bool esc_tried = false;         // context_escape ran (at the first render that can use it)
     double esc_density = 0.0;       // fraction of its (brick, bin) bits set
+    // back-face cull masks (escape.h, context_bfcull): built at the first
+    // render that can use them, if they fit kBfcBudget / mem_share
+    uint32_t* d_bfc = nullptr;
+    size_t bfc_bytes = 0;
+    bool bfc_tried = false, bfc_tried_forced = false;
+    bool bfc_stat = false;          // the statistic below is known
+    bool bfc_on = false;            // the park launches use them unasked
+    double bfc_frac = 0.0;          // cleared bits / ref bits of the cells of 1..32 refs
+    double bfc_cleared = 0.0;       // cleared bits per (cell, bin) word of those cells
     uint32_t occx_words = 0, occx_nbw = 0, occx_moff = 0, occx_nb[3] = {0, 0, 0};
     bool occx_ok = false;
     // an edge component of 2^62 or more, or infinite: every launch takes the
@@ -2467,7 +2499,7 @@ extern "C" void zrt_context_destroy(zrt_context* c) {
     DeviceGuard g(c->device);
     if (c->d_cell32) (void)hipFree(c->d_cell32);
     void* bufs[] = {c->d_cells, c->d_pos, c->d_data, c->d_mats, c->d_texels, c->d_zig, c->d_occ, c->d_occx, c->d_esc,
-                    c->d_bmask, c->d_sat, c->d_tlo,
+                    c->d_bfc, c->d_bmask, c->d_sat, c->d_tlo,
                     c->d_pix, c->d_out, c->d_acc, c->d_rgb, c->d_lin, c->d_rays, c->d_hits, c->d_counter, c->d_stats};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
@@ -2691,6 +2723,123 @@ static int context_packed(zrt_context* c) {
         c->rel_on = c->rel_frac >= kRelMinFrac;
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return ZRT_OK;
+}
+
+// Back-face cull masks (escape.h bfc_cull): word pc * kBfcNBin + bin for
+// every packed cell word pc and cull bin, then one all-ones word.  Bit r of
+// a cell of 1..32 refs is cleared when ref begin + r cannot pass tri_ray's
+// determinant test for any direction of the bin; every other cell keeps all
+// ones.  stat[0]: ref bits of the cells of 1..32 refs over all bins, stat[1]:
+// those cleared, stat[2]: (such cell, bin) words, stat[3]: those left empty.
+__global__ __launch_bounds__(kBlock) void bfc_build_kernel(const uint32_t* __restrict__ rec, uint64_t ncell,
+                                                           const float* __restrict__ pos, uint32_t* __restrict__ out,
+                                                           unsigned long long* __restrict__ stat) {
+    const uint64_t total = ncell * kBfcNBin;
+    unsigned long long bits = 0, cleared = 0, words = 0, empty = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (uint64_t)gridDim.x * kBlock) {
+        const uint64_t pc = i / kBfcNBin;
+        const uint32_t bin = (uint32_t)(i - pc * kBfcNBin);
+        const uint32_t b = rec[8 * pc], n = rec[8 * pc + 1] - b;
+        uint32_t m = ~0u;
+        if (n >= 1u && n <= 32u) {
+            for (uint32_t r = 0; r < n; ++r) {
+                float e1[3], e2[3];
+                for (uint32_t k = 0; k < 3; ++k) {
+                    e1[k] = __uint_as_float(tri_word(pos, b + r, 3 + k));
+                    e2[k] = __uint_as_float(tri_word(pos, b + r, 6 + k));
+                }
+                if (bfc_cull(e1, e2, bin)) m &= ~(1u << r);
+            }
+            const uint32_t all = n == 32u ? ~0u : (1u << n) - 1u;
+            bits += n;
+            cleared += n - (uint32_t)__popc(m & all);
+            words += 1;
+            empty += (m & all) == 0u ? 1 : 0;
+        }
+        if (out) out[i] = m;                       // (null: the statistic only)
+    }
+    if (out && blockIdx.x == 0 && threadIdx.x == 0) out[total] = ~0u;
+    bits = wave_sum(bits);
+    cleared = wave_sum(cleared);
+    words = wave_sum(words);
+    empty = wave_sum(empty);
+    if ((threadIdx.x & 63u) == 0) {
+        atomicAdd(&stat[0], bits);
+        atomicAdd(&stat[1], cleared);
+        atomicAdd(&stat[2], words);
+        atomicAdd(&stat[3], empty);
+    }
+}
+
+// The table is packed cells x kBfcNBin x 4 B (the contest stand-in at 128^3:
+// 0.8 GB at 4 x 4 bins per face, 3.2 GB at 8 x 8): built only if it fits
+// kBfcBudget over the contexts sharing the device, else the park kernel
+// renders without it.
+#ifndef ZRT_BFC_BUDGET_MB
+#define ZRT_BFC_BUDGET_MB 2048
+#endif
+constexpr uint64_t kBfcBudget = (uint64_t)ZRT_BFC_BUDGET_MB << 20;
+// Unasked, the park launches use the masks when they remove at least this
+// many triangle tests from a first-cell park on average (cleared bits per
+// (cell, bin) word over the cells of 1..32 refs): the park pays one more
+// gather for them.  Measured (r07b): Cornell box 0.36, -2.6%;
+// contest stand-in 1.78, +1.1%; Sponza-scale stand-in 2.39, +3.8%.
+#ifndef ZRT_BFC_MIN_CLEARED
+#define ZRT_BFC_MIN_CLEARED 1.0
+#endif
+constexpr double kBfcMinCleared = ZRT_BFC_MIN_CLEARED;
+// forced: build the table whatever the statistic says (ZRT_FLAG_BFCULL).
+static int context_bfcull(zrt_context* c, bool forced) {
+    if (c->d_bfc || !c->packed || !c->d_cell32) return ZRT_OK;
+    const uint64_t n = 1ull << (c->pk.b0 + c->pk.b1 + c->pk.b2);
+    const uint64_t bytes = 4ull * (n * kBfcNBin + 1);
+    if (bytes > kBfcBudget / std::max<uint32_t>(c->mem_share, 1u)) return ZRT_OK;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b / 4 < bytes) return ZRT_OK;
+    // one pass for the statistic alone (no table), one that writes the table
+    // if the scene uses it
+    unsigned long long* d = nullptr;
+    HIP_TRY(hipMalloc((void**)&d, 4 * sizeof(unsigned long long)));
+    const uint64_t blocks = (n * kBfcNBin + kBlock - 1) / kBlock;
+    auto pass = [&](uint32_t* out, unsigned long long* h) -> hipError_t {
+        hipError_t e = hipMemsetAsync(d, 0, 4 * sizeof(unsigned long long), c->stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(bfc_build_kernel, dim3((uint32_t)std::min<uint64_t>(blocks, 1u << 16)), dim3(kBlock), 0,
+                           c->stream, (const uint32_t*)c->d_cell32, n, (const float*)c->d_pos, out, d);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(h, d, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
+            return e;
+        return hipStreamSynchronize(c->stream);
+    };
+    unsigned long long h[4] = {0, 0, 0, 0};
+    hipError_t e = hipSuccess;
+    if (!c->bfc_stat) {
+        e = pass(nullptr, h);
+        if (e == hipSuccess) {
+            c->bfc_stat = true;
+            c->bfc_frac = h[0] ? (double)h[1] / (double)h[0] : 0.0;
+            c->bfc_cleared = h[2] ? (double)h[1] / (double)h[2] : 0.0;
+            c->bfc_on = c->bfc_cleared >= kBfcMinCleared;
+            if (getenv("ZRT_WF_DEBUG"))
+                fprintf(stderr, "{\"zrt_bfcull\": {\"bytes\": %llu, \"bins\": %u, \"cleared_frac\": %.4f, "
+                        "\"cleared_per_word\": %.4f, \"empty_word_frac\": %.4f, \"on\": %d}}\n",
+                        (unsigned long long)bytes, kBfcNBin, c->bfc_frac, c->bfc_cleared,
+                        h[2] ? (double)h[3] / (double)h[2] : 0.0, c->bfc_on ? 1 : 0);
+        }
+    }
+    uint32_t* tab = nullptr;
+    if (e == hipSuccess && (c->bfc_on || forced)) {
+        e = hipMalloc((void**)&tab, bytes);
+        if (e == hipSuccess) e = pass(tab, h);
+        if (e != hipSuccess && tab) (void)hipFree(tab);
+    }
+    (void)hipFree(d);
+    HIP_TRY(e);
+    if (tab) {
+        c->d_bfc = tab;
+        c->bfc_bytes = bytes;
+    }
     return ZRT_OK;
 }
 
@@ -3364,7 +3513,7 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
     if (const char* e = getenv("ZRT_SETS")) want_sets = (uint32_t)std::max(1, std::min((int)kMaxPassSets, atoi(e)));
 #endif
     const bool ktimes = (cfg->flags & ZRT_FLAG_KERNEL_TIMES) != 0;
-    size_t held = 16ull * c->out_cap;
+    size_t held = 16ull * c->out_cap + c->bfc_bytes;   // (the cull masks: the split must not depend on them)
     for (const zrt_context::PassSet& ps : c->set)
         held += 16ull * (ps.q0_cap + ps.q1_cap + ps.term_cap + ps.stk4_cap + ps.hit_cap) + 8ull * ps.stk2_cap +
                 4ull * ps.wfc_cap;
@@ -3490,6 +3639,18 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
     }
     const bool esc = c->d_esc && !(cfg->flags & ZRT_FLAG_NO_ESCAPE) &&
                      (c->esc_on || (cfg->flags & ZRT_FLAG_ESCAPE));
+    // the back-face cull masks: built like the escape table, at the first big
+    // frame or the first the flag forces; used where the scene's statistic
+    // says they pay (context_bfcull) or as the flags force (same image)
+    if (park_next && !(cfg->flags & ZRT_FLAG_NO_BFCULL)) {
+        const bool forced = (cfg->flags & ZRT_FLAG_BFCULL) != 0;
+        if (forced ? !c->bfc_tried_forced : (big && !c->bfc_tried)) {
+            c->bfc_tried = true;
+            c->bfc_tried_forced = c->bfc_tried_forced || forced;
+            if ((rc = context_bfcull(c, forced)) != ZRT_OK) return rc;
+        }
+    }
+    const bool bfc = c->d_bfc && !(cfg->flags & ZRT_FLAG_NO_BFCULL) && (c->bfc_on || (cfg->flags & ZRT_FLAG_BFCULL));
     const WfFn f_next = park_next ? (pbm ? (esc ? (WfFn)wf_park_kernel<true, true> : (WfFn)wf_park_kernel<false, true>)
                                          : (esc ? (WfFn)wf_park_kernel<true, false> : (WfFn)wf_park_kernel<false, false>))
                                   : mtx ? kWfBounceExact : (packed ? (pbm ? kWfBounceBM : kWfBounce) : kWfBounceWide);
@@ -3690,6 +3851,8 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
             W.rel_min = rel ? rel_min : 0u;
             W.rel_emin = rel_emin;
             W.esc = c->d_esc;
+            W.bfc = bfc ? c->d_bfc : nullptr;
+            W.bfc_ones = c->bfc_bytes ? c->bfc_bytes / 4 - 1 : 0;
             for (uint32_t k = 0; k < nb; ++k) {
                 W.q_in = (k & 1) ? q0 : q1;
                 W.q_out = (k & 1) ? q1 : q0;
@@ -3885,6 +4048,15 @@ extern "C" int zrt_context_trace(zrt_context* c, const zrt_ray_batch* b, zrt_sta
         if ((rc = context_escape(c)) != ZRT_OK) return rc;
     }
     const bool esc = c->d_esc && !(b->flags & ZRT_FLAG_NO_ESCAPE) && (c->esc_on || (b->flags & ZRT_FLAG_ESCAPE));
+    if (park && !(b->flags & ZRT_FLAG_NO_BFCULL)) {
+        const bool forced = (b->flags & ZRT_FLAG_BFCULL) != 0;
+        if (forced ? !c->bfc_tried_forced : (b->num_rays >= kSetsMinSamples && !c->bfc_tried)) {
+            c->bfc_tried = true;
+            c->bfc_tried_forced = c->bfc_tried_forced || forced;
+            if ((rc = context_bfcull(c, forced)) != ZRT_OK) return rc;
+        }
+    }
+    const bool bfc = c->d_bfc && !(b->flags & ZRT_FLAG_NO_BFCULL) && (c->bfc_on || (b->flags & ZRT_FLAG_BFCULL));
     // the fast kernel (null: every ray takes f_exact) and the IEEE-division one
     const RayFn f_fast = (counting || mtx) ? nullptr : packed ? (pbm ? kRaysWalkBM : kRaysWalk) : kRaysWalkWide;
     const RayFn f_exact = counting ? kRaysWalkCount : kRaysWalkExact;
@@ -3896,7 +4068,7 @@ extern "C" int zrt_context_trace(zrt_context* c, const zrt_ray_batch* b, zrt_sta
     // the context already holds, shared between a group's contexts)
     zrt_context::PassSet& ps = c->set[0];
     const uint64_t per_ray = (b->on_device ? 0ull : 40ull) + (park ? 64ull : 0ull);
-    const size_t held = 4ull * (c->rays_cap + c->hits_cap) + 16ull * (ps.q0_cap + ps.hit_cap);
+    const size_t held = 4ull * (c->rays_cap + c->hits_cap) + 16ull * (ps.q0_cap + ps.hit_cap) + c->bfc_bytes;
     size_t budget = (size_t)144 << 30;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b) budget = std::min(budget, (free_b + held) / 10 * 6);
@@ -3959,6 +4131,8 @@ extern "C" int zrt_context_trace(zrt_context* c, const zrt_ray_batch* b, zrt_sta
         R.w.rel_min = rel ? R.w.test_min : 0u;
         R.w.rel_emin = 1;
         R.w.esc = c->d_esc;
+        R.w.bfc = bfc ? c->d_bfc : nullptr;
+        R.w.bfc_ones = c->bfc_bytes ? c->bfc_bytes / 4 - 1 : 0;
         R.q = ps.q0;
         R.n_in8 = ps.wfc + 8 * kCtr;
     }
@@ -4232,11 +4406,13 @@ __global__ void probe_kernel(int which, const void* in, void* out, uint32_t n, c
 // short reciprocal against the IEEE division, bit for bit (NaN == NaN).
 __global__ __launch_bounds__(kBlock) void recip_sweep_kernel(uint32_t lo, uint32_t count, uint32_t* out) {
     uint32_t bad = 0, first = 0xFFFFFFFFu;
-    for (uint32_t k = blockIdx.x * kBlock + threadIdx.x; k < count; k += gridDim.x * kBlock) {
-        const float x = __uint_as_float(lo + k);
+    // (a 64-bit index: count + the grid's stride can pass 2^32, and a wrapped
+    // 32-bit k would stay below count for ever)
+    for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < count; k += (uint64_t)gridDim.x * kBlock) {
+        const float x = __uint_as_float(lo + (uint32_t)k);
         const float a = mt_inv_det<false>(x), b = mt_inv_det<true>(x);
         const bool same = __float_as_uint(a) == __float_as_uint(b) || (a != a && b != b);
-        if (!same) { ++bad; first = min(first, lo + k); }
+        if (!same) { ++bad; first = min(first, lo + (uint32_t)k); }
     }
     for (int o = 32; o > 0; o >>= 1) {
         bad += __shfl_xor(bad, o);

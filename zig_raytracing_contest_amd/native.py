@@ -25,6 +25,7 @@ FLAG_FRUSTUM, FLAG_NO_FRUSTUM = 0x100, 0x200
 FLAG_ONE_SET, FLAG_KERNEL_TIMES = 0x10, 0x20
 FLAG_MT_EXACT = 0x400
 FLAG_RELEASE, FLAG_NO_RELEASE = 0x800, 0x1000
+FLAG_BFCULL, FLAG_NO_BFCULL = 0x2000, 0x4000
 TRACE_PARK = 0x10000       # ZRT_TRACE_PARK (zrt_ray_batch.flags only)
 MISS = 0xFFFFFFFF          # zrt_hit.triangle of a ray that hit nothing
 # zrt_kernel_profile classes (include/zrt.h)
