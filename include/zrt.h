@@ -290,6 +290,63 @@ typedef struct zrt_ray_batch {
  * ZRT_FLAG_COUNT_STATS, counted as a counting render counts them. */
 int zrt_context_trace(zrt_context* ctx, const zrt_ray_batch* batch, zrt_stats* stats_or_null);
 
+/* ---- radiance queries (ABI 2, added) ------------------------------------ */
+
+/* Scene.traceRayRecursive (stage3.zig:188-220) -- the path tracer itself --
+ * for rays the caller chooses: light and irradiance probes, lightmap texels,
+ * cameras of the caller's own (panoramic, fisheye, orthographic, thin lens), a
+ * handful of pixels again.  For ray i (o_i, d_i) of the batch and sample s in
+ * [0, num_samples):
+ *   direction  what Camera.getRay (stage3.zig:27-35) computes for the camera
+ *              origin = o_i, lower_left_corner = d_i, right = up = 0: +0 added
+ *              to every component of d_i twice (so -0 becomes +0), then the
+ *              camera's normalisation; the origin is o_i;
+ *   RNG        the stream of (seed, pixel (uint32_t)(index_base + i), sample s)
+ *              with its first two floats drawn and dropped (the jitter draws);
+ *   path       traceRayRecursive(ray, max_bounce) as a render traces a sample;
+ *   result     radiance[i] = (the samples' radiances summed in sample order)
+ *              * (1 / num_samples), a render's linear_packed value, and
+ *              rgb[i] = toRGB(radiance[i]).
+ * So radiance[i] is, bit for bit, pixel 0 of a 1x1 zrt_context_render with
+ * that camera and seed if that pixel's index were index_base + i.  The first
+ * segment of a ray's num_samples paths is one Scene.traceRay call: it is
+ * traced once per ray and shaded once per sample. */
+#define ZRT_RADIANCE_PER_SAMPLE 0x20000u  /* zrt_radiance_batch.flags only: trace the first segment once per
+                                             sample instead of once per ray (same result; the A/B baseline) */
+typedef struct zrt_radiance_batch {
+    uint64_t num_rays;
+    const float* rays;               /* num_rays * 6: origin xyz, direction xyz.  Any finite direction whose
+                                        squared length neither overflows nor vanishes; for others (NaN,
+                                        infinite, all zero) the result is unspecified, the call still returns */
+    float* radiance;                 /* num_rays * 3, linear */
+    uint8_t* rgb;                    /* num_rays * 3, or null */
+    uint32_t on_device;              /* 0: host pointers; 1: device pointers on the context's device (rays and
+                                        radiance 4-byte aligned), complete once the call returns */
+    uint32_t flags;                  /* ZRT_FLAG_LANE_WALK | ZRT_FLAG_MT_EXACT | ZRT_FLAG_ESCAPE / NO_ESCAPE /
+                                        RELEASE / NO_RELEASE / BFCULL / NO_BFCULL as in a render |
+                                        ZRT_TRACE_PARK (the first segment's kernel, as in zrt_context_trace) |
+                                        ZRT_RADIANCE_PER_SAMPLE; any other bit is ZRT_ERR_INVALID_ARG */
+    uint32_t num_samples;            /* 1..65535 */
+    uint32_t max_bounce;             /* 0..32 (0: every radiance is +0); above: ZRT_ERR_UNSUPPORTED, as a render */
+    uint64_t seed;
+    uint64_t index_base;             /* stream key of ray 0; keys wrap at 2^32 */
+} zrt_radiance_batch;                /* 64 B */
+
+/* Synchronous; one thread at a time per context.  It shares the context's
+ * stream and work buffers with renders and zrt_context_trace and may
+ * alternate freely with them (every use writes what it reads first).
+ * num_rays == 0 returns ZRT_OK and touches nothing; null rays or radiance with
+ * num_rays > 0, a bad flag (ZRT_FLAG_COUNT_STATS included) or num_samples
+ * outside 1..65535 is ZRT_ERR_INVALID_ARG before any device work.  Batches of
+ * any size: the rays run in chunks of at most 2^20, fewer where num_samples
+ * paths per ray would not fit the memory budget of a render's pass.
+ * stats (may be null): segments = the Scene.traceRay calls of these paths as
+ * the reference makes them (a shared first segment counts num_samples times;
+ * the same number in both modes), samples = num_rays * num_samples, render_ms
+ * the device time of the call, trace_kernel_ms and trace_launches as in
+ * zrt_context_trace. */
+int zrt_context_radiance(zrt_context* ctx, const zrt_radiance_batch* batch, zrt_stats* stats_or_null);
+
 /* A device group: one context per entry of `devices` (HIP ordinals, repeats
  * allowed), the scene resident on each, rendered by one call -- Scene.render's
  * spawn + join of its workers (stage3.zig:247-256) across GPUs in one

@@ -1,0 +1,307 @@
+"""Radiance queries on the GPU (zrt_context_radiance, Context.radiance)
+against Scene.traceRayRecursive from the CPU oracle (radiance_ref.py), bit for
+bit: the linear radiance as uint32 patterns, the RGB8 and the segment count.
+
+Every (spp, max_bounce) of CONFIGS runs through the shared first segment (by
+the lane walk, the park kernel and the IEEE-division kernel), through
+ZRT_RADIANCE_PER_SAMPLE with and without the park kernel, on both ways of
+making a context.  A case's 256 rays (seeded) are: origins outside the bbox
+pointing in, origins inside it with uniform directions, origins outside
+pointing away, directions with one and two exact zero components (+0 and -0),
+directions scaled by 2^-10 .. 2^10 and by 3.  No NaN, infinite or all-zero
+direction; no ray is left out of any comparison.  A (case, spp, max_bounce)
+reference is computed once and shared by every test that needs it.
+"""
+import dataclasses
+
+import numpy as np
+import pytest
+
+try:
+    import torch  # noqa: F401  (first: libzrt then binds to torch's HIP runtime, as in bench.py)
+except ImportError:
+    torch = None
+
+from zig_raytracing_contest_amd import RenderScene, camera_for, native, scenes
+
+import radiance_ref
+
+pytestmark = pytest.mark.gpu
+
+
+def _one_triangle():
+    s = scenes.get_scene("sphere")
+    return dataclasses.replace(s, name="one_triangle", pos=np.array([[-1, -1, 0, 1, -1, 0, 0, 1, 0]], np.float32),
+                               nrm=np.tile(np.array([0, 0, 1], np.float32), (1, 3)),
+                               uv=np.zeros((1, 6), np.float32), mat=np.zeros(1, s.mat.dtype))
+
+
+# case -> (scene, grid)
+CASES = {"cornell_bm": (lambda: scenes.get_scene("cornell"), (16, 16, 16)),       # brick-major words
+         "cornell_fields": (lambda: scenes.get_scene("cornell"), (12, 20, 9)),    # field words
+         "contest": (lambda: scenes.get_scene("contest"), (32, 32, 32)),          # textures, pass-through segments
+         "tri_wide": (_one_triangle, (1100, 2, 2))}                              # the unpacked walk, no park path
+CONFIGS = [(1, 1), (3, 4), (64, 4), (65, 5), (2, 32), (4, 0)]                     # (spp, max_bounce)
+MODES = {"default": 0, "park": native.TRACE_PARK, "lane": native.FLAG_LANE_WALK, "mt_exact": native.FLAG_MT_EXACT,
+         "per_sample": native.RADIANCE_PER_SAMPLE, "per_sample_park": native.RADIANCE_PER_SAMPLE | native.TRACE_PARK}
+N_RAYS = 256
+SEED = 5
+
+
+def _case_rays(soup, seed):
+    """The case's N_RAYS rays, (origins, dirs) float32."""
+    rng = np.random.default_rng(seed)
+    xyz = soup.pos.reshape(-1, 3).astype(np.float64)
+    lo, hi = xyz.min(0), xyz.max(0)
+    c, ext = (lo + hi) / 2, hi - lo
+    R = 1.5 * max(float(np.linalg.norm(ext)), 1e-3)
+
+    def unit(n):
+        v = rng.normal(size=(n, 3))
+        return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+    def inside(n):
+        return lo + rng.random((n, 3)) * ext
+
+    O, D = [], []
+    o = c + R * unit(87)                                   # outside, pointing in
+    d = inside(87) - o
+    O.append(o)
+    D.append(d / np.linalg.norm(d, axis=1, keepdims=True))
+    O.append(inside(60))                                   # inside the bbox, uniform directions
+    D.append(unit(60))
+    u = unit(20)                                           # outside, pointing away
+    O.append(c + R * u)
+    D.append(u)
+    z = []                                                 # exact zero components, both signs of zero
+    for a in range(3):
+        for zero in (0.0, -0.0):
+            for s1 in (1.0, -1.0):
+                for s2 in (1.0, -1.0):
+                    v = np.array([0.6 * s1, 0.8 * s2, 0.0], np.float32)
+                    v[2] = zero
+                    z.append(np.roll(v, a + 1))            # the zero on each axis in turn
+        for s in (1.0, -1.0):
+            for z1 in (0.0, -0.0):
+                for z2 in (0.0, -0.0):
+                    z.append(np.roll(np.array([s, z1, z2], np.float32), a))
+    z = np.array(z, np.float32)                            # 24 + 24
+    p = inside(len(z))
+    back = (np.arange(len(z)) % 2)[:, None]                # from the point itself, or from behind it
+    O.append(p - back * R * z.astype(np.float64))
+    D.append(z)
+    O.append(O[0][:21])                                    # scaled by 2^-10 .. 2^10 (exact in f32)
+    D.append(D[0][:21].astype(np.float32) * np.exp2(np.arange(-10, 11, dtype=np.float32))[:, None])
+    O.append(O[1][:20])                                    # scaled by 3
+    D.append(D[1][:20].astype(np.float32) * np.float32(3.0))
+    o = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32) for x in O]))
+    d = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32) for x in D]))
+    assert o.shape == d.shape == (N_RAYS, 3) and np.isfinite(o).all() and np.isfinite(d).all()
+    assert (np.abs(d).max(1) > 0).all()
+    return o, d
+
+
+class Case:
+    def __init__(self, orc, name):
+        mk, self.res = CASES[name]
+        self.soup = mk()
+        self.ref = radiance_ref.RadianceRef(orc, self.soup, self.res)
+        self.o, self.d = _case_rays(self.soup, sorted(CASES).index(name) + 1)
+        self._want = {}
+
+    def want(self, spp, mb, seed=SEED):
+        """The reference's (linear bits (N_RAYS, 3) uint32, rgb, segments) at index_base 0."""
+        key = (spp, mb, seed)
+        if key not in self._want:
+            lin, rgb, ctr = self.ref.radiance(self.o, self.d, spp, mb, seed=seed)
+            bits = lin.view(np.uint32).copy()
+            bits.setflags(write=False)
+            rgb.setflags(write=False)
+            self._want[key] = (bits, rgb, int(ctr[0]))
+        return self._want[key]
+
+
+_CASES = {}
+
+
+@pytest.fixture(scope="module")
+def case(oracle_mod):
+    def get(name):
+        if name not in _CASES:
+            _CASES[name] = Case(oracle_mod, name)
+        return _CASES[name]
+    return get
+
+
+@pytest.fixture(scope="module")
+def scene(case):
+    """The context of (case, build), made once."""
+    made = {}
+
+    def get(name, build="host"):
+        if (name, build) not in made:
+            cs = case(name)
+            made[(name, build)] = RenderScene(cs.soup, cs.res, device=0, device_build=build == "device")
+        return made[(name, build)]
+    yield get
+    for rs in made.values():
+        rs.close()
+
+
+def _check(got, want, what):
+    got = np.asarray(got)
+    bad = np.nonzero((got != want).any(axis=1))[0]
+    assert bad.size == 0, (f"{what}: {bad.size} rays differ, first {bad[0]}: got "
+                           f"{[hex(int(x)) for x in got[bad[0]]]}, reference {[hex(int(x)) for x in want[bad[0]]]}")
+
+
+def _bits(res):
+    return res["radiance"].view(np.uint32)
+
+
+@pytest.mark.parametrize("build", ["host", "device"])
+@pytest.mark.parametrize("cfg", CONFIGS, ids=lambda c: f"spp{c[0]}_mb{c[1]}")
+@pytest.mark.parametrize("name", list(CASES))
+def test_radiance_matches_the_reference(name, cfg, build, case, scene):
+    spp, mb = cfg
+    cs, rs = case(name), scene(name, build)
+    bits, rgb, segments = cs.want(spp, mb)
+    for mode, flags in MODES.items():
+        res = rs.radiance(cs.o, cs.d, spp, mb, seed=SEED, flags=flags, rgb=True)
+        what = f"{name} spp {spp} max_bounce {mb} {mode} {build}"
+        _check(_bits(res), bits, what)
+        _check(res["rgb"], rgb, what + " rgb")
+        assert res["stats"]["segments"] == segments, what
+        assert res["stats"]["samples"] == N_RAYS * spp
+    if mb == 0:
+        assert not bits.any() and not rgb.any() and segments == 0       # +0, RGB 0, nothing traced
+    else:
+        assert bits.any() and len({r.tobytes() for r in bits}) > 1, "the case is not degenerate"
+
+
+@pytest.mark.parametrize("mode", ["default", "park", "per_sample"])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 200])
+def test_batch_sizes_and_index_base(n, mode, case, scene):
+    """Rays [k, k + n) with index_base = k are rows k .. of the whole batch."""
+    cs, rs = case("cornell_bm"), scene("cornell_bm")
+    bits, rgb, _ = cs.want(3, 4)
+    k = 17
+    res = rs.radiance(cs.o[k:k + n], cs.d[k:k + n], 3, 4, seed=SEED, index_base=k, flags=MODES[mode], rgb=True)
+    _check(_bits(res), bits[k:k + n], f"n = {n} {mode}")
+    _check(res["rgb"], rgb[k:k + n], f"n = {n} {mode} rgb")
+    assert res["stats"]["samples"] == 3 * n
+
+
+def test_two_chunks_and_wrapping_keys(case, scene):
+    """2^20 + 200 rays: two chunks.  The case's 256 rays repeat along the batch
+    and sit as rays 0 .. 255 across the cut, with index_base = 2^32 - (2^20 -
+    128): the keys wrap there, and those rows take keys 0 .. 255."""
+    cs, rs = case("cornell_bm"), scene("cornell_bm")
+    n, at = (1 << 20) + 200, (1 << 20) - 128
+    idx = (np.arange(n) - at) % N_RAYS
+    o, d = np.ascontiguousarray(cs.o[idx]), np.ascontiguousarray(cs.d[idx])
+    base = (1 << 32) - at
+    shared = rs.radiance(o, d, 1, 2, seed=SEED, index_base=base, rgb=True)
+    per = rs.radiance(o, d, 1, 2, seed=SEED, index_base=base, flags=native.RADIANCE_PER_SAMPLE, rgb=True)
+    assert np.array_equal(_bits(shared), _bits(per)) and np.array_equal(shared["rgb"], per["rgb"])
+    assert shared["stats"]["segments"] == per["stats"]["segments"]
+    assert shared["stats"]["samples"] == n
+    bits, rgb, _ = cs.want(1, 2)
+    _check(_bits(shared)[at:at + N_RAYS], bits, "the 256 reference rows across the cut")
+    _check(shared["rgb"][at:at + N_RAYS], rgb, "their rgb")
+    # equal rays under other keys: the stream differs
+    assert not np.array_equal(_bits(shared)[at - N_RAYS:at], _bits(shared)[at:at + N_RAYS])
+
+
+def test_seed_and_index_change_the_result(case, scene):
+    cs, rs = case("cornell_bm"), scene("cornell_bm")
+    a = _bits(rs.radiance(cs.o, cs.d, 3, 4, seed=SEED))
+    _check(a, cs.want(3, 4)[0], "seed 5")
+    b = _bits(rs.radiance(cs.o, cs.d, 3, 4, seed=SEED + 1))
+    _check(b, cs.want(3, 4, seed=SEED + 1)[0], "seed 6")
+    assert not np.array_equal(a, b)
+    c = _bits(rs.radiance(cs.o, cs.d, 3, 4, seed=SEED, index_base=1000))
+    assert not np.array_equal(a, c)
+
+
+def test_a_degenerate_camera_renders_the_same_bits(case, scene):
+    """radiance[i] is pixel 0 of a 1x1 render with origin = o, lower_left_corner = d, right = up = 0."""
+    cs, rs = case("cornell_bm"), scene("cornell_bm")
+    hits = 0
+    for i in list(range(87, 93)) + [3, 150]:
+        cam = native.Camera(1, 1, tuple(cs.o[i]), tuple(cs.d[i]), (0.0, 0.0, 0.0), (0.0, 0.0, 0.0))
+        img = rs.context.render(cam, 3, 4, seed=SEED, linear=True, packed=True)
+        res = rs.radiance(cs.o[i:i + 1], cs.d[i:i + 1], 3, 4, seed=SEED, index_base=0, rgb=True)
+        assert np.array_equal(img["linear"].view(np.uint32), _bits(res)), i
+        assert np.array_equal(img["packed"], res["rgb"]), i
+        assert res["stats"]["segments"] == img["stats"]["segments"]
+        hits += res["stats"]["segments"] > 3
+    assert hits, "some of the rays hit the scene"
+
+
+def test_queries_and_renders_share_a_context_cleanly(case, scene):
+    cs = case("cornell_bm")
+    cam = camera_for(cs.soup, None, 24, 24)
+    rs = scene("cornell_bm")
+    first, _ = rs.render(cam, num_samples=2, max_bounce=4)
+    hits = rs.trace(cs.o, cs.d)
+    rad = {m: _bits(rs.radiance(cs.o, cs.d, 3, 4, seed=SEED, flags=f)) for m, f in MODES.items()}
+    for m, f in MODES.items():
+        img, _ = rs.render(cam, num_samples=2, max_bounce=4)
+        assert np.array_equal(img, first), f"render after a {m} radiance query"
+        again = rs.trace(cs.o, cs.d, flags=native.TRACE_PARK)
+        assert np.array_equal(again["t"].view(np.uint32), hits["t"].view(np.uint32))
+        assert np.array_equal(_bits(rs.radiance(cs.o, cs.d, 3, 4, seed=SEED, flags=f)), rad[m]), m
+        _check(rad[m], cs.want(3, 4)[0], m)
+    img, _ = rs.render(cam, num_samples=2, max_bounce=4)
+    assert np.array_equal(img, first)
+
+
+def test_empty_batch_touches_nothing(scene):
+    ctx = scene("cornell_bm").context
+    out = np.full(6, 7.0, np.float32)
+    rays = np.zeros(6, np.float32)
+    st = ctx.radiance_raw(0, rays.ctypes.data, out.ctypes.data, None, False, 3, 4)
+    assert (out == 7.0).all() and st["segments"] == 0 and st["samples"] == 0
+    ctx.radiance_raw(0, None, None, None, False, 3, 4, flags=native.RADIANCE_PER_SAMPLE)
+    res = scene("cornell_bm").radiance(np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), 3, 4, rgb=True)
+    assert res["radiance"].shape == (0, 3) and res["rgb"].shape == (0, 3)
+
+
+def test_bad_flags_and_sizes_raise(scene):
+    ctx = scene("cornell_bm").context
+    rays = np.zeros(6, np.float32)
+    rays[5] = 1.0
+    out = np.zeros(3, np.float32)
+    rp, op = rays.ctypes.data, out.ctypes.data
+    for kw, status in ((dict(flags=native.FLAG_COUNT_STATS), -1), (dict(flags=native.FLAG_ONE_SET), -1),
+                       (dict(flags=0x4), -1), (dict(flags=0x40000), -1), (dict(spp=0), -1), (dict(spp=65536), -1),
+                       (dict(max_bounce=33), -5), (dict(rays=None), -1), (dict(out=None), -1)):
+        a = dict(rays=rp, out=op, spp=1, max_bounce=1, flags=0)
+        a.update(kw)
+        with pytest.raises(native.ZrtError) as e:
+            ctx.radiance_raw(1, a["rays"], a["out"], None, False, a["spp"], a["max_bounce"], flags=a["flags"])
+        assert e.value.status == status, kw
+    assert ctx.radiance_raw(1, rp, op, None, False, 1, 32)["samples"] == 1      # the largest depth runs
+
+
+def test_torch_tensors_are_used_in_place(case, scene):
+    if torch is None or not torch.cuda.is_available():
+        pytest.skip("torch sees no device")
+    cs, rs = case("cornell_bm"), scene("cornell_bm")
+    bits, rgb, segments = cs.want(3, 4)
+    dev = torch.device("cuda", 0)
+    before = torch.arange(4096, dtype=torch.int32, device=dev)
+    o, d = torch.from_numpy(cs.o).to(dev), torch.from_numpy(cs.d).to(dev)
+    for mode, flags in MODES.items():
+        res = rs.radiance(o, d, 3, 4, seed=SEED, flags=flags, rgb=True)
+        after = torch.full((4096,), 5, dtype=torch.int32, device=dev)
+        rad = res["radiance"]
+        assert rad.shape == (N_RAYS, 3) and rad.dtype == torch.float32 and rad.device == dev
+        assert res["rgb"].shape == (N_RAYS, 3) and res["rgb"].dtype == torch.uint8
+        _check(rad.cpu().numpy().view(np.uint32), bits, f"torch {mode}")
+        _check(res["rgb"].cpu().numpy(), rgb, f"torch {mode} rgb")
+        assert res["stats"]["segments"] == segments
+        assert torch.equal(before.cpu(), torch.arange(4096, dtype=torch.int32)) and bool((after == 5).all())
+    zero = rs.radiance(o, d, 4, 0, rgb=True)
+    assert not bool(zero["radiance"].view(torch.int32).any()) and not bool(zero["rgb"].any())

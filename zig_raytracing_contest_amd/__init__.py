@@ -116,3 +116,10 @@ class RenderScene:
             src[hit] = self.geometry.indices()[ref[hit]]
             res["source_triangle"] = src
         return res
+
+    def radiance(self, origins, dirs, spp: int, max_bounce: int, seed: int = 0, index_base: int = 0,
+                 flags: int = 0, rgb: bool = False, stats: bool = False):
+        """Scene.traceRayRecursive (stage3.zig:188-220) for a batch of rays,
+        `spp` path samples each: see native.Context.radiance."""
+        return self.context.radiance(origins, dirs, spp, max_bounce, seed=seed, index_base=index_base,
+                                     flags=flags, rgb=rgb, stats=stats)

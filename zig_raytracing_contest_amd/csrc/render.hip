@@ -2219,6 +2219,159 @@ constexpr uint32_t kTraceFlags = ZRT_FLAG_COUNT_STATS | ZRT_FLAG_LANE_WALK | ZRT
                                  ZRT_FLAG_NO_ESCAPE | ZRT_FLAG_RELEASE | ZRT_FLAG_NO_RELEASE | ZRT_FLAG_BFCULL |
                                  ZRT_FLAG_NO_BFCULL | ZRT_TRACE_PARK;
 
+// ---------------------------------------------------------------------------
+// Radiance queries (zrt_context_radiance): Scene.traceRayRecursive
+// (stage3.zig:188-220) for caller-given rays, S samples each, through the
+// render's own queues, park, shade and resolve kernels.  A chunk
+// of n rays is a "frame" of P = n pixels in one pass of S samples: item =
+// ray * S + s, pixel-major, so the XCD regions, the bounce planes and the
+// resolve are a render's.  What a render does not have is S paths that start
+// with the SAME ray (its samples are jittered): their first segment is one
+// Scene.traceRay call, traced once per ray -- as zrt_context_trace traces a
+// chunk -- and fanned out into S shaded continuations (rad_fanout_kernel).
+struct RadParams {
+    WfParams w;               // w.t: P = n rays, S samples per ray; queues, planes, counters of the launch
+    const float* rays;        // this chunk: 6 floats per ray (origin, direction as given)
+    float* nrays;             // rad_pack_kernel: the rays with their directions normalised, 6 floats each
+                              // (rays_walk_kernel's input)
+    float4* q;                // the pack kernels: the queue they fill (launch 0's q_in)
+    uint32_t* n_in8;          //   and its region counts
+    uint32_t* ctr;            // [2]: rays outside the fast domain (rays_walk_kernel, kRaysRest)
+    uint32_t n;               // rays of this chunk
+    uint32_t key0;            // RNG stream key ("pixel") of the chunk's ray 0; keys wrap at 2^32
+};
+
+// Camera.getRay (stage3.zig:27-35) for the camera lower_left_corner = d,
+// right = up = 0: d + right * x + up * y adds +0 twice (x, y >= 0: the
+// products are +0; a -0 component becomes +0), then camera_ray's normalize.
+__device__ __forceinline__ v3 rad_direction(v3 d) {
+    const v3 z = mk(0.0f, 0.0f, 0.0f);
+    return ZRT_NORM_RN(add(add(d, z), z));
+}
+// What camera_rng leaves for (pixel key, sample s): the stream after the two
+// jitter draws.
+__device__ __forceinline__ Rng rad_rng(uint64_t seed, uint32_t key, uint32_t s) {
+    Rng rng;
+    rng.s = path_key(seed, key, s);
+    (void)rng_float(rng);
+    (void)rng_float(rng);
+    return rng;
+}
+
+// One thread per ray: ray i, its direction normalised, as queue entry i of the
+// identity layout (rays_pack_kernel: P = n, S = 1) for the park kernel, and as
+// six floats for the lane walk.  A normalised direction is in the fast domain
+// (ray_fast) unless the given one was NaN, infinite, zero or of a squared
+// length that overflows or vanishes; those are counted for the kRaysRest launch.
+__global__ __launch_bounds__(kBlock) void rad_pack_kernel(const RadParams r) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < 8u) r.n_in8[i * kCtr] = xcd_q0(r.n, i + 1u) - xcd_q0(r.n, i);
+    bool rest = false;
+    if (i < r.n) {
+        v3 o, d;
+        ray_load(r.rays, i, o, d);
+        d = rad_direction(d);
+        r.q[3ull * i] = make_float4(o.x, o.y, o.z, __uint_as_float(i));
+        r.q[3ull * i + 1] = make_float4(d.x, d.y, d.z, __uint_as_float(1u));
+        float* q = r.nrays + 6ull * i;
+        q[0] = o.x; q[1] = o.y; q[2] = o.z;
+        q[3] = d.x; q[4] = d.y; q[5] = d.z;
+        rest = !ray_fast(d);
+    }
+    const uint64_t m = __ballot(rest);
+    if (m != 0ull && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(m)) atomicAdd(&r.ctr[2], (uint32_t)__popcll(m));
+}
+
+// ZRT_RADIANCE_PER_SAMPLE: one thread per item = ray * S + s, its path record
+// as queue entry `item` (region g of the identity layout with P = n, S = S is
+// full: S paths per ray of pixel range g): depth max_bounce, slot 0, no scatter
+// yet, the stream after its two jitter draws.  Launch 0 then runs over them as
+// a bounce launch does.
+__global__ __launch_bounds__(kBlock) void rad_pack_samples_kernel(const RadParams r) {
+    const TraceParams& p = r.w.t;
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;          // (items of a chunk stay below 2^31)
+    if (i < 8u) r.n_in8[i * kCtr] = p.S * (xcd_q0(r.n, i + 1u) - xcd_q0(r.n, i));
+    if (i >= p.total) return;
+    const uint32_t ray = div_by(i, p.sdiv);
+    const uint32_t s = i - ray * p.S;
+    v3 o, d;
+    ray_load(r.rays, ray, o, d);
+    d = rad_direction(d);
+    const Rng rng = rad_rng(p.seed, r.key0 + ray, s);
+    r.q[3ull * i] = make_float4(o.x, o.y, o.z, __uint_as_float(i));
+    r.q[3ull * i + 1] = make_float4(d.x, d.y, d.z, __uint_as_float(p.max_bounce));
+    r.q[3ull * i + 2] = make_float4(__uint_as_float((uint32_t)rng.s), __uint_as_float((uint32_t)(rng.s >> 32)),
+                                    __uint_as_float(0u), 0.0f);
+}
+
+// The fan-out: traceRayRecursive's body after the first traceRay
+// (stage3.zig:195-219) for the S paths of every ray, from the ONE hit record
+// (t, u, v, ref) its first segment left in w.hit[ray] and its normalised ray
+// in queue entry `ray` of w.q_in.  Items ray * S + s are fetched per XCD group
+// like a primary launch's (wf_fetch<PRIMARY>, P = n), so a wave of 64 samples
+// of one ray reads one hit record, one ray and one triangle record (every
+// lane the same address: one request), and its terminal and bounce-plane
+// stores are contiguous.  Each lane builds the stream of (ray, s) and shades:
+// a path that ends writes term[item], one that goes on writes its bounce plane
+// (shade_segment) and joins region g of the bounce-1 queue.  LMATS, LAST: as
+// wf_shade_kernel (LAST: max_bounce == 1, the terminal radiance only).
+// n_seg counts the segment traced, once per ray.
+template <bool LMATS, bool LAST>
+__global__ __launch_bounds__(kTraceBlock, 1) void rad_fanout_kernel(const RadParams r) {
+    const WfParams& w = r.w;
+    const TraceParams& p = w.t;
+    __shared__ double s_zig[514];
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_dynm[];    // LMATS: p.nmat DevMat
+    DevMat* const s_mats = reinterpret_cast<DevMat*>(s_dynm);
+    for (uint32_t i = threadIdx.x; i < 514; i += blockDim.x) s_zig[i] = p.zig[i];
+    if (LMATS)
+        for (uint32_t i = threadIdx.x; i < p.nmat * (uint32_t)(sizeof(DevMat) / 4); i += blockDim.x)
+            reinterpret_cast<uint32_t*>(s_mats)[i] = reinterpret_cast<const uint32_t*>(p.mats)[i];
+    __syncthreads();
+    const DevMat* const mats = LMATS ? s_mats : p.mats;
+    const double* zx = s_zig;
+    const double* zf = s_zig + 257;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t below = lane ? (~0ull >> (64u - lane)) : 0ull;
+    uint32_t n_seg = 0;
+    uint32_t grp = blockIdx.x & 7u, tried = 0;
+    for (;;) {
+        uint32_t base = 0, lim = 0;
+        if (!wf_fetch<true>(w, 64u * kWfChunk, grp, tried, base, lim)) break;
+        for (uint32_t sub = 0; sub < kWfChunk && base + 64u * sub < lim; ++sub) {
+            const uint32_t j = base + 64u * sub + lane;
+            bool cont = false;
+            uint32_t item = 0, depth = 0, slot = 0, mask = 0;
+            v3 o = mk(0, 0, 0), d = mk(0, 0, 0);
+            Rng rng;
+            rng.s = 0;
+            if (j < lim) {
+                item = ent_index<true>(w, grp, j);
+                const uint32_t ray = div_by(item, p.sdiv);
+                const uint32_t s = item - ray * p.S;
+                const float4 a = w.q_in[3ull * ray], b = w.q_in[3ull * ray + 1], h = w.hit[ray];
+                o = mk(a.x, a.y, a.z);
+                d = mk(b.x, b.y, b.z);
+                rng = rad_rng(p.seed, r.key0 + ray, s);
+                depth = p.max_bounce;                              // >= 1 (the host never launches this at 0)
+                n_seg += s == 0u ? 1u : 0u;
+                v3 L = mk(0, 0, 0);
+                cont = shade_segment<LAST>(w, zx, zf, mats, item, h.x, h.y, h.z, tri_rec(p, h.x, __float_as_uint(h.w)),
+                                           o, d, depth, slot, rng, mask, L);
+                if (!cont) w.term[item] = make_float4(L.x, L.y, L.z, __uint_as_float(mask));
+            }
+            if (!LAST) wf_append(w, cont, below, o, d, item, depth, slot, rng, mask, grp);
+        }
+    }
+    const unsigned long long s0 = wave_sum(n_seg);
+    if (lane == 0) atomicAdd(&p.stats[0], s0);
+}
+
+using RadFn = void (*)(const RadParams);
+constexpr uint32_t kRadianceFlags = ZRT_FLAG_LANE_WALK | ZRT_FLAG_MT_EXACT | ZRT_FLAG_ESCAPE | ZRT_FLAG_NO_ESCAPE |
+                                    ZRT_FLAG_RELEASE | ZRT_FLAG_NO_RELEASE | ZRT_FLAG_BFCULL | ZRT_FLAG_NO_BFCULL |
+                                    ZRT_TRACE_PARK | ZRT_RADIANCE_PER_SAMPLE;
+
 // max_bounce picks the stack depth the counting kernel is compiled for.
 TraceFn count_fn(uint32_t max_bounce) {
     if (max_bounce <= 4) return (TraceFn)trace_kernel<4>;
@@ -2345,6 +2498,8 @@ struct zrt_context {
     // zrt_context_trace: a host batch's chunk on the device (6 floats, 4 u32 per ray)
     float* d_rays = nullptr; size_t rays_cap = 0;
     uint32_t* d_hits = nullptr; size_t hits_cap = 0;
+    // zrt_context_radiance: a chunk's rays with normalised directions (6 floats per ray)
+    float* d_nrays = nullptr; size_t nrays_cap = 0;
     std::vector<hipEvent_t> ev_pass;   // per pass: its resolve done
     hipEvent_t ev_fork = nullptr;
     uint32_t* d_counter = nullptr;
@@ -2500,7 +2655,8 @@ extern "C" void zrt_context_destroy(zrt_context* c) {
     if (c->d_cell32) (void)hipFree(c->d_cell32);
     void* bufs[] = {c->d_cells, c->d_pos, c->d_data, c->d_mats, c->d_texels, c->d_zig, c->d_occ, c->d_occx, c->d_esc,
                     c->d_bfc, c->d_bmask, c->d_sat, c->d_tlo,
-                    c->d_pix, c->d_out, c->d_acc, c->d_rgb, c->d_lin, c->d_rays, c->d_hits, c->d_counter, c->d_stats};
+                    c->d_pix, c->d_out, c->d_acc, c->d_rgb, c->d_lin, c->d_rays, c->d_hits, c->d_nrays, c->d_counter,
+                    c->d_stats};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (zrt_context::PassSet& ps : c->set) {
@@ -4198,6 +4354,319 @@ extern "C" int zrt_context_trace(zrt_context* c, const zrt_ray_batch* b, zrt_sta
         st.triangle_tests = hs[2];
         st.hits = hs[3];
     }
+    if (stats) *stats = st;
+    return ZRT_OK;
+}
+
+// Scene.traceRayRecursive (stage3.zig:188-220) for a batch of rays: see
+// include/zrt.h, the kernels' comment (RadParams) and DESIGN 5.12.  Per chunk
+// of n rays, S samples each, all on the context's stream and pass set 0:
+//   shared first segment (default):
+//     rad_pack_kernel -> the chunk's first segments as zrt_context_trace traces
+//     them (wf_park_kernel over the identity queue, or rays_walk_kernel; then
+//     the kRaysRest launch) -> rad_fanout_kernel: n * S shaded continuations;
+//   ZRT_RADIANCE_PER_SAMPLE:
+//     rad_pack_samples_kernel -> launch 0 as a bounce launch over n * S records;
+//   then bounces 1 .. max_bounce - 1 as a render launches them and
+//   wf_resolve_kernel (P = n, one pass), d_lin / d_rgb copied to the outputs.
+extern "C" int zrt_context_radiance(zrt_context* c, const zrt_radiance_batch* b, zrt_stats* stats) {
+    if (!c || !b) return ZRT_ERR_INVALID_ARG;
+    if ((b->flags & ~kRadianceFlags) != 0u || b->on_device > 1u) return ZRT_ERR_INVALID_ARG;
+    if (b->num_samples == 0 || b->num_samples > 65535) return ZRT_ERR_INVALID_ARG;
+    // the scatter mask holds one bit per bounce slot, the queue 16 bits of depth
+    if (b->max_bounce > 32) return ZRT_ERR_UNSUPPORTED;
+    zrt_stats st{};
+    if (b->num_rays == 0) { if (stats) *stats = st; return ZRT_OK; }
+    if (!b->rays || !b->radiance) return ZRT_ERR_INVALID_ARG;
+    DeviceGuard g(c->device);
+
+    const uint32_t S = b->num_samples, mb = b->max_bounce, nb = std::max<uint32_t>(mb, 1);
+    st.samples = b->num_rays * S;
+    if (mb == 0) {
+        // traceRayRecursive at depth 0 returns 0: the sum of S zeros times 1 / S, and toRGB(0) = 0
+        if (b->on_device) {
+            HIP_TRY(hipMemsetAsync(b->radiance, 0, 12ull * b->num_rays, c->stream));
+            if (b->rgb) HIP_TRY(hipMemsetAsync(b->rgb, 0, 3ull * b->num_rays, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        } else {
+            memset(b->radiance, 0, 12ull * b->num_rays);
+            if (b->rgb) memset(b->rgb, 0, 3ull * b->num_rays);
+        }
+        if (stats) *stats = st;
+        return ZRT_OK;
+    }
+
+    // the same choices as a render's bounce launches (zrt_context_render); the
+    // first segment takes the park kernel by zrt_context_trace's rule, on the
+    // segments launch 0 traces (n rays, or n * S with ZRT_RADIANCE_PER_SAMPLE)
+    const bool per_sample = (b->flags & ZRT_RADIANCE_PER_SAMPLE) != 0;
+    const bool mtx = c->mt_exact || (b->flags & ZRT_FLAG_MT_EXACT);
+    const bool park_next = c->occx_ok && !(b->flags & ZRT_FLAG_LANE_WALK) && c->packed && !mtx;
+    const uint64_t first_n = per_sample ? b->num_rays * S : b->num_rays;
+    const bool park_first = park_next && ((b->flags & ZRT_TRACE_PARK) || first_n >= kTraceParkMin);
+    const bool park_any = park_first || (park_next && nb > 1);
+    const bool packed = c->packed && !mtx;
+    const bool pbm = packed && c->pk.bm;
+    const bool rel = !(b->flags & ZRT_FLAG_NO_RELEASE) && (c->rel_on || (b->flags & ZRT_FLAG_RELEASE));
+    const bool big = b->num_rays * S >= kSetsMinSamples;
+    int rc;
+    if (!c->esc_tried && park_any && !(b->flags & ZRT_FLAG_NO_ESCAPE) && (big || (b->flags & ZRT_FLAG_ESCAPE))) {
+        c->esc_tried = true;
+        if ((rc = context_escape(c)) != ZRT_OK) return rc;
+    }
+    const bool esc = c->d_esc && !(b->flags & ZRT_FLAG_NO_ESCAPE) && (c->esc_on || (b->flags & ZRT_FLAG_ESCAPE));
+    if (park_any && !(b->flags & ZRT_FLAG_NO_BFCULL)) {
+        const bool forced = (b->flags & ZRT_FLAG_BFCULL) != 0;
+        if (forced ? !c->bfc_tried_forced : (big && !c->bfc_tried)) {
+            c->bfc_tried = true;
+            c->bfc_tried_forced = c->bfc_tried_forced || forced;
+            if ((rc = context_bfcull(c, forced)) != ZRT_OK) return rc;
+        }
+    }
+    const bool bfc = c->d_bfc && !(b->flags & ZRT_FLAG_NO_BFCULL) && (c->bfc_on || (b->flags & ZRT_FLAG_BFCULL));
+    const RayFn f_fast = mtx ? nullptr : packed ? (pbm ? kRaysWalkBM : kRaysWalk) : kRaysWalkWide;
+    const RayFn f_exact = kRaysWalkExact;
+    const WfFn f_park = pbm ? (esc ? (WfFn)wf_park_kernel<true, true> : (WfFn)wf_park_kernel<false, true>)
+                            : (esc ? (WfFn)wf_park_kernel<true, false> : (WfFn)wf_park_kernel<false, false>);
+    const WfFn f_walk = mtx ? kWfBounceExact : (packed ? (pbm ? kWfBounceBM : kWfBounce) : kWfBounceWide);
+    const bool lmats = c->nmat <= kLdsMats;
+    const WfFn s_next = lmats ? (WfFn)wf_shade_kernel<true> : (WfFn)wf_shade_kernel<false>;
+    const WfFn s_last = !ZRT_SHADE_LAST ? s_next : lmats ? (WfFn)wf_shade_kernel<true, true> : (WfFn)wf_shade_kernel<false, true>;
+    const RadFn f_fan = nb == 1 ? (lmats ? (RadFn)rad_fanout_kernel<true, true> : (RadFn)rad_fanout_kernel<false, true>)
+                                : (lmats ? (RadFn)rad_fanout_kernel<true, false> : (RadFn)rad_fanout_kernel<false, false>);
+    const size_t lds_shade = lmats ? c->nmat * sizeof(DevMat) : 0;
+
+    // chunk size: at most kTraceChunk rays, its n * S items below 2^31 and
+    // within the memory budget of a render's pass (pass_samples: its per-item
+    // bytes, 60% of what is free counting what the context holds, shared
+    // between a group's contexts); S <= 65535 always fits at 64 rays
+    zrt_context::PassSet& ps = c->set[0];
+    const uint64_t per_item = 96ull + 16ull + 16ull + (ZRT_PLANES16 ? 32ull : 24ull) * nb;
+    const uint64_t per_ray = per_item * S + 24ull + 15ull + (b->on_device ? 0ull : 24ull);
+    const size_t held = 4ull * (c->rays_cap + c->nrays_cap + c->lin_cap) + c->rgb_cap + c->bfc_bytes +
+                        16ull * (ps.q0_cap + ps.q1_cap + ps.term_cap + ps.stk4_cap + ps.hit_cap) + 8ull * ps.stk2_cap +
+                        4ull * ps.wfc_cap;
+    size_t budget = (size_t)144 << 30;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b) budget = std::min(budget, (free_b + held) / 10 * 6);
+    budget /= std::max<uint32_t>(c->mem_share, 1u);
+    uint64_t chunk = std::min<uint64_t>(kTraceChunk, 0x7FFFFF00ull / S);
+    chunk = std::max<uint64_t>(64, std::min<uint64_t>(chunk, budget / per_ray));
+    chunk = std::min<uint64_t>(chunk, b->num_rays);
+    const uint64_t T = chunk * S;                  // items of the largest chunk
+    const size_t wfc_words = 32ull * kCtr * (mb + 2);
+    const uint64_t hit_need = std::max<uint64_t>(park_any ? T : 0, per_sample ? 0 : chunk);
+    if (!b->on_device && (rc = grow(&c->d_rays, &c->rays_cap, 6 * chunk)) != ZRT_OK) return rc;
+    if (!per_sample && (rc = grow(&c->d_nrays, &c->nrays_cap, 6 * chunk)) != ZRT_OK) return rc;
+    if ((rc = grow(&c->d_lin, &c->lin_cap, 3 * chunk)) != ZRT_OK) return rc;
+    if ((rc = grow(&c->d_rgb, &c->rgb_cap, 3 * chunk)) != ZRT_OK) return rc;
+    if ((rc = grow(&ps.q0, &ps.q0_cap, 3 * T)) != ZRT_OK) return rc;
+    if ((rc = grow(&ps.q1, &ps.q1_cap, 3 * T)) != ZRT_OK) return rc;
+    if ((rc = grow(&ps.term, &ps.term_cap, T)) != ZRT_OK) return rc;
+    if ((rc = grow(&ps.stk4, &ps.stk4_cap, T * nb)) != ZRT_OK) return rc;
+    if ((rc = grow(&ps.stk2, &ps.stk2_cap, T * nb * (ZRT_PLANES16 ? 2 : 1))) != ZRT_OK) return rc;
+    if ((rc = grow(&ps.wfc, &ps.wfc_cap, wfc_words)) != ZRT_OK) return rc;
+    if (hit_need && (rc = grow(&ps.hit, &ps.hit_cap, hit_need)) != ZRT_OK) return rc;
+    // capacity guard (as zrt_context_render's): every buffer a launch below
+    // writes holds what a chunk's launches write; a chunk's items fit 31 bits
+    {
+        auto shortfall = [&](const void* ptr, size_t cap, uint64_t need) { return !ptr || cap < need; };
+        if ((!b->on_device && shortfall(c->d_rays, c->rays_cap, 6 * chunk)) ||
+            (!per_sample && shortfall(c->d_nrays, c->nrays_cap, 6 * chunk)) ||
+            shortfall(c->d_lin, c->lin_cap, 3 * chunk) || shortfall(c->d_rgb, c->rgb_cap, 3 * chunk) ||
+            shortfall(ps.q0, ps.q0_cap, 3 * T) || shortfall(ps.q1, ps.q1_cap, 3 * T) ||
+            shortfall(ps.term, ps.term_cap, T) || shortfall(ps.stk4, ps.stk4_cap, T * nb) ||
+            shortfall(ps.stk2, ps.stk2_cap, T * nb * (ZRT_PLANES16 ? 2 : 1)) ||
+            shortfall(ps.wfc, ps.wfc_cap, wfc_words) || (hit_need && shortfall(ps.hit, ps.hit_cap, hit_need)) ||
+            chunk == 0 || chunk > kTraceChunk || T > 0x7FFFFF00ull)
+            return ZRT_ERR_INVALID_ARG;
+    }
+    while (c->ev_trace.size() < 2) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreate(&e));
+        c->ev_trace.push_back(e);
+    }
+
+    // occupancy-sized persistent grids
+    const size_t lds_wf = 4ull * c->occ_words;
+    const uint32_t occx_ldsw = (uint32_t)occx_lds_words(c->occx_nbw, c->occx_moff, c->occx_words);
+    const size_t lds_park = 4ull * occx_ldsw + (size_t)(kParkBlock / 64) * sizeof(ParkSlot);
+    uint32_t grid_fast = 0, grid_exact = 0, grid_park = 0, grid_walk = 0, grid_shade = 0, grid_shade_last = 0,
+             grid_fan = 0;
+    if (!per_sample) {
+        if (f_fast && !park_first &&
+            (rc = resident_blocks(c, (const void*)f_fast, kTraceThreads, lds_wf, &grid_fast)) != ZRT_OK)
+            return rc;
+        if ((rc = resident_blocks(c, (const void*)f_exact, kTraceThreads, lds_wf, &grid_exact)) != ZRT_OK) return rc;
+        if ((rc = resident_blocks(c, (const void*)f_fan, kTraceThreads, lds_shade, &grid_fan)) != ZRT_OK) return rc;
+    }
+    if (park_any) {
+        if ((rc = resident_blocks(c, (const void*)f_park, kParkBlock, lds_park, &grid_park)) != ZRT_OK) return rc;
+        if ((rc = resident_blocks(c, (const void*)s_next, kTraceThreads, lds_shade, &grid_shade)) != ZRT_OK) return rc;
+        if ((rc = resident_blocks(c, (const void*)s_last, kTraceThreads, lds_shade, &grid_shade_last)) != ZRT_OK)
+            return rc;
+    }
+    if ((!park_next && nb > 1) || (per_sample && !park_first)) {
+        if ((rc = resident_blocks(c, (const void*)f_walk, kTraceThreads, lds_wf, &grid_walk)) != ZRT_OK) return rc;
+    }
+
+    RadParams R;
+    memset(&R, 0, sizeof R);
+    WfParams& W = R.w;
+    scene_params(c, W.t);
+    W.t.max_bounce = mb;
+    W.t.seed = b->seed;
+    W.t.counter = c->d_counter;
+    W.t.stats = c->d_stats;
+    W.stk4 = ps.stk4;
+    W.stk2 = ps.stk2;
+    W.term = ps.term;
+    W.hit = ps.hit;
+    W.occx = c->d_occx;
+    W.occx_words = c->occx_words;
+    W.occx_ldsw = occx_ldsw;
+    W.occx_nbw = c->occx_nbw;
+    W.occx_moff = c->occx_moff;
+    W.occx_nb0 = c->occx_nb[0];
+    W.occx_nb01 = c->occx_nb[0] * c->occx_nb[1];
+    W.test_min = rel ? kParkTestMinRel : kParkTestMin;
+    W.refill_min = kParkRefillMin;
+    W.rel_min = rel ? W.test_min : 0u;
+    W.rel_emin = 1;
+    W.esc = c->d_esc;
+    W.bfc = bfc ? c->d_bfc : nullptr;
+    W.bfc_ones = c->bfc_bytes ? c->bfc_bytes / 4 - 1 : 0;
+    R.ctr = c->d_counter;
+    R.nrays = c->d_nrays;
+    R.q = ps.q1;                                   // launch 0 reads q1 (a render's k = 0)
+    R.n_in8 = ps.wfc + kCtr * 8;
+    uint32_t* const wfc = ps.wfc;
+    // stage3.zig:223 inv_num_samples = ones / splat(spp)  (f32 division)
+    const float inv_spp = 1.0f / (float)S;
+
+    HIP_TRY(hipMemsetAsync(c->d_stats, 0, 512, c->stream));
+    HIP_TRY(hipEventRecord(c->ev_begin, c->stream));
+    uint32_t launches = 0;
+    // launch k of a chunk as a render runs a bounce launch: the park kernel +
+    // the shading half, or the lane walk
+    auto bounce = [&](uint32_t k, bool park) -> int {
+        W.q_in = (k & 1) ? ps.q0 : ps.q1;
+        W.q_out = (k & 1) ? ps.q1 : ps.q0;
+        W.fetch8 = wfc + kCtr * (16 * k);
+        W.n_in8 = wfc + kCtr * (16 * k + 8);
+        W.n_out8 = wfc + kCtr * (16 * (k + 1) + 8);
+        W.fetch8s = wfc + kCtr * (16 * (mb + 2) + 8 * k);
+        if (park) {
+            hipLaunchKernelGGL(f_park, dim3(grid_park), dim3(kParkBlock), lds_park, c->stream, W);
+            if (k + 1 == nb)
+                hipLaunchKernelGGL(s_last, dim3(grid_shade_last), dim3(kTraceThreads), lds_shade, c->stream, W);
+            else
+                hipLaunchKernelGGL(s_next, dim3(grid_shade), dim3(kTraceThreads), lds_shade, c->stream, W);
+            launches += 2;
+        } else {
+            hipLaunchKernelGGL(f_walk, dim3(grid_walk), dim3(kTraceThreads), lds_wf, c->stream, W);
+            ++launches;
+        }
+        HIP_TRY(hipGetLastError());
+        return ZRT_OK;
+    };
+    for (uint64_t off = 0; off < b->num_rays; off += chunk) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, b->num_rays - off);
+        const uint32_t items = n * S;              // <= T < 2^31
+        if (b->on_device) {
+            R.rays = b->rays + 6 * off;
+        } else {
+            HIP_TRY(hipMemcpyAsync(c->d_rays, b->rays + 6 * off, 24ull * n, hipMemcpyHostToDevice, c->stream));
+            R.rays = c->d_rays;
+            HIP_TRY(hipEventRecord(c->ev_trace[0], c->stream));
+        }
+        R.n = n;
+        R.key0 = (uint32_t)(b->index_base + off);
+        // per launch k: 8 work counters, then 8 region counts of the paths
+        // entering launch k (a render's layout); the pack kernels write launch 0's
+        HIP_TRY(hipMemsetAsync(wfc, 0, 4ull * wfc_words, c->stream));
+        HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
+        W.t.P = n;
+        W.t.S = S;
+        W.t.total = items;
+        W.t.sdiv = div_magic(S);
+        W.T = items;
+        const uint32_t nblk = (n + kBlock - 1) / kBlock;
+        if (per_sample) {
+            hipLaunchKernelGGL(rad_pack_samples_kernel, dim3((items + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, R);
+            ++launches;
+            HIP_TRY(hipGetLastError());
+            if ((rc = bounce(0, park_first)) != ZRT_OK) return rc;
+        } else {
+            hipLaunchKernelGGL(rad_pack_kernel, dim3(nblk), dim3(kBlock), 0, c->stream, R);
+            ++launches;
+            // the first segments: one per ray, the identity queue (P = n, S = 1)
+            RayParams Q;
+            memset(&Q, 0, sizeof Q);
+            Q.w = W;
+            Q.w.t.P = n;
+            Q.w.t.S = 1;
+            Q.w.t.total = n;
+            Q.w.t.sdiv = div_magic(1);
+            Q.w.t.max_bounce = 1;
+            Q.w.q_in = ps.q1;
+            Q.w.fetch8 = wfc;
+            Q.w.n_in8 = wfc + kCtr * 8;
+            Q.rays = c->d_nrays;
+            Q.hits = reinterpret_cast<uint32_t*>(ps.hit);
+            Q.n = n;
+            Q.ctr = c->d_counter;
+            if (park_first) {
+                hipLaunchKernelGGL(f_park, dim3(grid_park), dim3(kParkBlock), lds_park, c->stream, Q.w);
+                ++launches;
+            } else if (f_fast) {
+                Q.which = kRaysFast;
+                hipLaunchKernelGGL(f_fast, dim3(std::min(grid_fast, nblk)), dim3(kTraceThreads), lds_wf, c->stream, Q);
+                ++launches;
+            }
+            Q.which = park_first || f_fast ? kRaysRest : kRaysAll;
+            hipLaunchKernelGGL(f_exact, dim3(std::min(grid_exact, nblk)), dim3(kTraceThreads), lds_wf, c->stream, Q);
+            ++launches;
+            // the fan-out: items fetched like a primary launch's, appended to launch 1's queue
+            W.q_in = ps.q1;
+            W.q_out = ps.q0;
+            W.fetch8 = wfc + kCtr * (16 * (mb + 2));
+            W.n_in8 = wfc + kCtr * 8;
+            W.n_out8 = wfc + kCtr * (16 + 8);
+            hipLaunchKernelGGL(f_fan, dim3(grid_fan), dim3(kTraceThreads), lds_shade, c->stream, R);
+            ++launches;
+            HIP_TRY(hipGetLastError());
+        }
+        for (uint32_t k = 1; k < nb; ++k)
+            if ((rc = bounce(k, park_next)) != ZRT_OK) return rc;
+        hipLaunchKernelGGL(wf_resolve_kernel, dim3((n + kResPix - 1) / kResPix), dim3(kBlock), 0, c->stream, ps.term,
+                           ps.stk4, ps.stk2, items, n, S, mb, c->d_acc, 1, 1, inv_spp, c->d_rgb, c->d_lin);
+        ++launches;
+        HIP_TRY(hipGetLastError());
+        if (b->on_device) {
+            HIP_TRY(hipMemcpyAsync(b->radiance + 3 * off, c->d_lin, 12ull * n, hipMemcpyDeviceToDevice, c->stream));
+            if (b->rgb)
+                HIP_TRY(hipMemcpyAsync(b->rgb + 3 * off, c->d_rgb, 3ull * n, hipMemcpyDeviceToDevice, c->stream));
+        } else {
+            HIP_TRY(hipEventRecord(c->ev_trace[1], c->stream));
+            HIP_TRY(copy_sync(b->radiance + 3 * off, c->d_lin, 12ull * n, hipMemcpyDeviceToHost, c->stream));
+            if (b->rgb) HIP_TRY(copy_sync(b->rgb + 3 * off, c->d_rgb, 3ull * n, hipMemcpyDeviceToHost, c->stream));
+            float t = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&t, c->ev_trace[0], c->ev_trace[1]));
+            st.trace_kernel_ms += t;
+        }
+    }
+    HIP_TRY(hipEventRecord(c->ev_end, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev_begin, c->ev_end));
+    st.render_ms = ms;
+    if (b->on_device) st.trace_kernel_ms = ms;
+    st.trace_launches = launches;
+    unsigned long long hs[1];
+    HIP_TRY(copy_sync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+    // the reference traces a shared first segment once per sample
+    st.segments = hs[0] + (per_sample ? 0ull : b->num_rays * (uint64_t)(S - 1));
     if (stats) *stats = st;
     return ZRT_OK;
 }

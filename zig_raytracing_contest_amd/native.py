@@ -26,7 +26,8 @@ FLAG_ONE_SET, FLAG_KERNEL_TIMES = 0x10, 0x20
 FLAG_MT_EXACT = 0x400
 FLAG_RELEASE, FLAG_NO_RELEASE = 0x800, 0x1000
 FLAG_BFCULL, FLAG_NO_BFCULL = 0x2000, 0x4000
-TRACE_PARK = 0x10000       # ZRT_TRACE_PARK (zrt_ray_batch.flags only)
+TRACE_PARK = 0x10000       # ZRT_TRACE_PARK (zrt_ray_batch / zrt_radiance_batch flags only)
+RADIANCE_PER_SAMPLE = 0x20000   # ZRT_RADIANCE_PER_SAMPLE (zrt_radiance_batch.flags only)
 MISS = 0xFFFFFFFF          # zrt_hit.triangle of a ray that hit nothing
 # zrt_kernel_profile classes (include/zrt.h)
 KERNEL_CLASSES = ("primary", "park", "shade", "bounce", "resolve", "count")
@@ -126,6 +127,12 @@ class RayBatch(C.Structure):
                 ("on_device", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class RadianceBatch(C.Structure):
+    _fields_ = [("num_rays", C.c_uint64), ("rays", C.c_void_p), ("radiance", C.c_void_p), ("rgb", C.c_void_p),
+                ("on_device", C.c_uint32), ("flags", C.c_uint32), ("num_samples", C.c_uint32),
+                ("max_bounce", C.c_uint32), ("seed", C.c_uint64), ("index_base", C.c_uint64)]
+
+
 EXPORTS = [
     "zrt_error_string", "zrt_abi_version", "zrt_device_count", "zrt_device_warmup", "zrt_geometry_build",
     "zrt_geometry_build_device",
@@ -134,6 +141,7 @@ EXPORTS = [
     "zrt_gltf_load", "zrt_gltf_soup", "zrt_gltf_materials", "zrt_gltf_camera", "zrt_gltf_free",
     "zrt_camera_from_matrix", "zrt_probe", "zrt_timed_kernels", "zrt_context_profile", "zrt_context_trace",
     "zrt_group_create", "zrt_group_create_built", "zrt_group_render", "zrt_group_context", "zrt_group_destroy",
+    "zrt_context_radiance",
 ]
 
 
@@ -171,7 +179,8 @@ def lib():
     L.zrt_context_trace.argtypes = [C.c_void_p, C.POINTER(RayBatch), C.POINTER(Stats)]
     L.zrt_context_destroy.argtypes = [C.c_void_p]
     L.zrt_context_destroy.restype = None
-    if hasattr(L, "zrt_group_create"):      # ABI 2 (an ABI-1 build: tools/ A/B baselines only)
+    L.zrt_context_radiance.argtypes = [C.c_void_p, C.POINTER(RadianceBatch), C.POINTER(Stats)]
+    if hasattr(L, "zrt_group_create"):     # ABI 2 (an ABI-1 build: tools/ A/B baselines only)
         L.zrt_group_create.argtypes = [C.POINTER(Scene), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
         L.zrt_group_create_built.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                              C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Material),
@@ -423,6 +432,67 @@ class Context:
         st = self.trace_raw(n, rays.ctypes.data if n else None, hits.ctypes.data if n else None, False, flags)
         return {"t": hits["t"].copy(), "u": hits["u"].copy(), "v": hits["v"].copy(),
                 "triangle": hits["triangle"].copy(), "stats": st}
+
+    def radiance_raw(self, num_rays: int, rays_ptr, radiance_ptr, rgb_ptr, on_device: bool, spp: int,
+                     max_bounce: int, seed: int = 0, index_base: int = 0, flags: int = 0):
+        """zrt_context_radiance on raw pointers; returns the stats dict."""
+        batch = RadianceBatch(int(num_rays), rays_ptr, radiance_ptr, rgb_ptr, 1 if on_device else 0, int(flags),
+                              int(spp), int(max_bounce), int(seed), int(index_base))
+        st = Stats()
+        check(lib().zrt_context_radiance(self._h, C.byref(batch), C.byref(st)), "zrt_context_radiance")
+        return st.as_dict()
+
+    def radiance(self, origins, dirs, spp: int, max_bounce: int, seed: int = 0, index_base: int = 0,
+                 flags: int = 0, rgb: bool = False, stats: bool = False):
+        """Scene.traceRayRecursive (stage3.zig:188-220) along n rays of the
+        caller's: the mean of `spp` path samples per ray, each traced as a
+        render traces a pixel's sample (include/zrt.h, zrt_context_radiance).
+        `dirs` need not be unit length.  Ray i draws from the RNG stream of
+        "pixel" index_base + i, so a batch cut in two gives the same rows.
+
+        Two (n, 3) float32 numpy arrays give {"radiance": (n, 3) float32
+        linear, "rgb": (n, 3) uint8 (with rgb=True), "stats"}.  Two (n, 3)
+        float32 CUDA tensors (torch-ROCm) on the context's device are used in
+        place, after a sync of torch's current stream, and the results are
+        CUDA tensors, complete when the call returns.  `stats` is always
+        filled (no counting variant exists); the argument is kept for symmetry
+        with trace()."""
+        del stats
+        if type(origins).__module__.split(".")[0] == "torch":
+            import torch
+            if not (origins.is_cuda and dirs.is_cuda and origins.device == dirs.device):
+                raise ValueError("radiance: torch inputs must be CUDA tensors on the context's device")
+            if origins.dtype != torch.float32 or dirs.dtype != torch.float32:
+                raise ValueError("radiance: float32 tensors expected")
+            if origins.dim() != 2 or origins.shape[1] != 3 or origins.shape != dirs.shape:
+                raise ValueError("radiance: two (n, 3) tensors expected")
+            n = int(origins.shape[0])
+            rays = torch.cat([origins, dirs], dim=1).contiguous()
+            out = torch.empty((n, 3), dtype=torch.float32, device=origins.device)
+            out8 = torch.empty((n, 3), dtype=torch.uint8, device=origins.device) if rgb else None
+            torch.cuda.current_stream(origins.device).synchronize()
+            st = self.radiance_raw(n, rays.data_ptr() if n else None, out.data_ptr() if n else None,
+                                   out8.data_ptr() if rgb and n else None, True, spp, max_bounce, seed,
+                                   index_base, flags)
+            res = {"radiance": out, "stats": st}
+            if rgb:
+                res["rgb"] = out8
+            return res
+        o = np.asarray(origins, np.float32)
+        d = np.asarray(dirs, np.float32)
+        if o.ndim != 2 or o.shape[1] != 3 or o.shape != d.shape:
+            raise ValueError("radiance: two (n, 3) arrays expected")
+        n = o.shape[0]
+        rays = np.ascontiguousarray(np.concatenate([o, d], axis=1))
+        out = np.empty((n, 3), np.float32)
+        out8 = np.empty((n, 3), np.uint8) if rgb else None
+        st = self.radiance_raw(n, rays.ctypes.data if n else None, out.ctypes.data if n else None,
+                               out8.ctypes.data if rgb and n else None, False, spp, max_bounce, seed, index_base,
+                               flags)
+        res = {"radiance": out, "stats": st}
+        if rgb:
+            res["rgb"] = out8
+        return res
 
 
 def render_oneshot(scene: Scene, cam: Camera, spp: int, max_bounce: int, seed: int = 0,
