@@ -6,9 +6,7 @@ and contest golden fixtures at their golden sizes and on a hand-made scene
 opposite-facing triangles, a zero-area triangle, walls whose normals are
 exactly an axis); and batch ray queries through the park kernel, where every
 ray is a segment's first cell, axis-parallel rays included."""
-import dataclasses
 import itertools
-import math
 import os
 
 import numpy as np
@@ -16,47 +14,9 @@ import pytest
 
 from zig_raytracing_contest_amd import RenderScene, camera_for, native, scenes
 
+from edge_scenes import HAND_RES, hand_scene
+
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-HAND_RES = (8, 8, 8)
-
-
-def hand_scene():
-    """An 8^3-cell box [0, 8]^3: axis-aligned floor (y = 0) and back wall
-    (z = 0), a corner triangle pinning the bbox, 32 small triangles inside
-    cell (2, 3, 2) and 33 inside cell (5, 3, 5) (one of them zero-area), and a
-    coincident pair of opposite-facing triangles."""
-    s = scenes.get_scene("cornell")
-    tris = []
-    quad = lambda a, b, c, d: [a + b + c, a + c + d]
-    tris += quad([0, 0, 0], [0, 0, 8], [8, 0, 8], [8, 0, 0])            # floor, normal +y
-    tris += quad([0, 0, 0], [8, 0, 0], [8, 8, 0], [0, 8, 0])            # back wall, normal +z
-    tris += [[8, 8, 8, 7.5, 8, 8, 8, 8, 7.5]]                            # bbox corner
-    rng = np.random.default_rng(5)
-
-    def cluster(cell, n):
-        out = []
-        c = np.array(cell, np.float64) + 0.5
-        for _ in range(n):
-            p = c + rng.uniform(-0.25, 0.25, 3)
-            out.append(list(np.concatenate([p, p + rng.uniform(-0.15, 0.15, 3), p + rng.uniform(-0.15, 0.15, 3)])))
-        return out
-    tris += cluster((2, 3, 2), 32)
-    c33 = cluster((5, 3, 5), 33)
-    c33[7][3:6] = c33[7][0:3]                                           # zero area: v1 = v0
-    tris += c33
-    pair = [3.2, 2.2, 6.3, 4.7, 2.4, 6.4, 3.9, 3.6, 6.2]
-    tris += [pair, pair[0:3] + pair[6:9] + pair[3:6]]                   # the same triangle, both windings
-    pos = np.array(tris, np.float32).reshape(-1, 9)
-    n = len(pos)
-    e1, e2 = pos[:, 3:6] - pos[:, 0:3], pos[:, 6:9] - pos[:, 0:3]
-    nr = np.cross(e1, e2)
-    ln = np.linalg.norm(nr, axis=1, keepdims=True)
-    nr = np.where(ln > 0, nr / np.maximum(ln, 1e-30), np.array([0, 1, 0])).astype(np.float32)
-    cam = scenes.CameraDef("Hand", scenes.look_at((4.0, 4.0, 14.0), (4.0, 4.0, 0.0)), math.radians(45.0), None)
-    return dataclasses.replace(s, name="bfcull_hand", pos=pos, nrm=np.tile(nr, (1, 3)).astype(np.float32),
-                               uv=np.zeros((n, 6), np.float32),
-                               mat=(np.arange(n) % s.num_materials).astype(s.mat.dtype), cameras=[cam])
-
 
 def test_hand_scene_has_the_cells_it_is_about():
     soup = hand_scene()

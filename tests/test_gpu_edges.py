@@ -16,51 +16,16 @@ upload, and the device build straight into the context):
 - the capacity guard's premise: counting, timed and counting renders on one
   context at growing sizes (every buffer regrown before its launch).
 """
-import dataclasses
-import math
-
 import numpy as np
 import pytest
 
 from zig_raytracing_contest_amd import RenderScene, camera_for, native, scenes
 
+from edge_scenes import (FAR, FAR_IDS, cornell_inside as _cornell_inside, degenerate_sphere as _degenerate_sphere,
+                         far_floor as _far_floor, far_vertex as _far_vertex, one_triangle as _one_triangle,
+                         with_camera as _with_camera)
+
 pytestmark = pytest.mark.gpu
-
-
-def _with_camera(soup, eye, target, yfov_deg=50.0):
-    cam = scenes.CameraDef("Edge", scenes.look_at(eye, target), math.radians(yfov_deg), None)
-    return dataclasses.replace(soup, cameras=[cam])
-
-
-def _degenerate_sphere():
-    s = scenes.get_scene("sphere")
-    v = np.array([[0.2, 0.1, 0.9], [0.2, 0.1, 0.9], [0.2, 0.1, 0.9],      # one point
-                  [-0.5, 0.0, 1.1], [0.0, 0.0, 1.1], [0.5, 0.0, 1.1],    # collinear
-                  [0.3, -0.4, 1.05], [0.3, -0.4, 1.05], [0.6, 0.2, 1.05],  # two equal vertices
-                  [-0.2, 0.3, 1.2], [0.1, 0.3, 1.2], [-0.2, 0.6, 1.2]],  # a proper one on top
-                 np.float32).reshape(4, 9)
-    n = np.tile(np.array([0, 0, 1], np.float32), (4, 3))
-    uv = np.zeros((4, 6), np.float32)
-    return dataclasses.replace(s, name="sphere_degenerate", pos=np.concatenate([s.pos, v]),
-                               nrm=np.concatenate([s.nrm, n]), uv=np.concatenate([s.uv, uv]),
-                               mat=np.concatenate([s.mat, np.zeros(4, s.mat.dtype)]))
-
-
-def _one_triangle():
-    s = scenes.get_scene("sphere")
-    pos = np.array([[-1, -1, 0, 1, -1, 0, 0, 1, 0]], np.float32)
-    nrm = np.tile(np.array([0, 0, 1], np.float32), (1, 3))
-    return dataclasses.replace(s, name="one_triangle", pos=pos, nrm=nrm,
-                               uv=np.zeros((1, 6), np.float32), mat=np.zeros(1, s.mat.dtype))
-
-
-def _cornell_inside():
-    s = scenes.get_scene("cornell")
-    lo = s.pos.reshape(-1, 3).min(0)
-    hi = s.pos.reshape(-1, 3).max(0)
-    mid = (lo + hi) / 2
-    eye = mid + (hi - lo) * np.array([0.1, 0.15, 0.2])
-    return _with_camera(s, tuple(float(x) for x in eye), tuple(float(x) for x in lo), 70.0)
 
 
 def _sky_only():
@@ -113,9 +78,13 @@ _ORACLE = {}
 # ... and (round 6) the IEEE-division lane walk that scenes with edges of
 # 2^62 or more take (ZRT_FLAG_MT_EXACT forces it on any scene), and the park
 # release forced on / off
+# ... and the park kernel's back-face cull masks forced on / off (by default a
+# per-scene statistic decides, and leaves them off on scenes this small), and
+# the lane walk for every bounce
 MODES = {"default": 0, "escape": native.FLAG_ESCAPE, "no_escape": native.FLAG_NO_ESCAPE,
          "frustum": native.FLAG_FRUSTUM, "mt_exact": native.FLAG_MT_EXACT,
-         "release": native.FLAG_RELEASE, "no_release": native.FLAG_NO_RELEASE}
+         "release": native.FLAG_RELEASE, "no_release": native.FLAG_NO_RELEASE,
+         "bfcull": native.FLAG_BFCULL, "no_bfcull": native.FLAG_NO_BFCULL, "lane_walk": native.FLAG_LANE_WALK}
 
 
 @pytest.mark.parametrize("mode", list(MODES))
@@ -171,41 +140,9 @@ def test_growing_frames_counting_timed_counting(oracle_mod):
         rs.close()
 
 
-def _far_vertex(scale):
-    """The sphere with one vertex moved to (scale, scale, scale): the
-    triangles around it get edge components near `scale` (Moller-Trumbore
-    dets up to ~scale^2, past the short reciprocal's 2^126 from 2^62 on)."""
-    s = scenes.get_scene("sphere")
-    pos = s.pos.astype(np.float32).copy()
-    pos[0, 0:3] = np.float32(scale)
-    return dataclasses.replace(s, name=f"far_vertex_{scale}", pos=pos)
-
-
-def _far_floor(scale):
-    """The sphere over a floor triangle with edges of 2 * scale, facing up
-    (y = -1.5): Moller-Trumbore's det for a ray down onto it is
-    4 scale^2 |d.y|, so from scale 2^62 on the bounce rays that hit it have
-    dets of 2^124 .. 2^128 and past (the short reciprocal's 2^126 limit, the
-    subnormal reciprocals, the overflow to inf)."""
-    s = scenes.get_scene("sphere")
-    S = np.float32(scale)
-    tri = np.array([[-S, -1.5, -S, 0, -1.5, S, S, -1.5, -S]], np.float32)
-    n = np.tile(np.array([0, 1, 0], np.float32), (1, 3))
-    return dataclasses.replace(s, name=f"far_floor_{scale}", pos=np.concatenate([s.pos, tri]),
-                               nrm=np.concatenate([s.nrm, n]), uv=np.concatenate([s.uv, np.zeros((1, 6), np.float32)]),
-                               mat=np.concatenate([s.mat, np.zeros(1, s.mat.dtype)]))
-
-
-# (scene, scale, needs the IEEE-division kernels)
-FAR = [("vertex", 2.0 ** 40, False), ("vertex", 2.0 ** 62, True), ("vertex", 2.0 ** 64, True),
-       ("vertex", 2.0 ** 100, True), ("vertex", float("inf"), True), ("vertex", float("nan"), False),
-       ("floor", 2.0 ** 40, False), ("floor", 2.0 ** 62, True), ("floor", 2.0 ** 63, True),
-       ("floor", 2.0 ** 64, True)]
-
-
+# FAR (edge_scenes.py): (scene, scale, needs the IEEE-division kernels)
 @pytest.mark.parametrize("device_build", [False, True], ids=["host-build", "device-build"])
-@pytest.mark.parametrize("kind,scale,exact", FAR, ids=[f"{k}-2^{int(np.log2(s))}" if np.isfinite(s) else f"{k}-{s}"
-                                                        for k, s, _ in FAR])
+@pytest.mark.parametrize("kind,scale,exact", FAR, ids=FAR_IDS)
 def test_far_vertex_scene_renders_bitexact_vs_oracle(oracle_mod, kind, scale, exact, device_build):
     """the contexts no longer refuse scenes the reference
     renders (linalg.zig:696-722 takes any f32).  A scene with an edge

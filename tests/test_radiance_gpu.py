@@ -12,8 +12,6 @@ directions scaled by 2^-10 .. 2^10 and by 3.  No NaN, infinite or all-zero
 direction; no ray is left out of any comparison.  A (case, spp, max_bounce)
 reference is computed once and shared by every test that needs it.
 """
-import dataclasses
-
 import numpy as np
 import pytest
 
@@ -25,15 +23,9 @@ except ImportError:
 from zig_raytracing_contest_amd import RenderScene, camera_for, native, scenes
 
 import radiance_ref
+from edge_scenes import one_triangle as _one_triangle
 
 pytestmark = pytest.mark.gpu
-
-
-def _one_triangle():
-    s = scenes.get_scene("sphere")
-    return dataclasses.replace(s, name="one_triangle", pos=np.array([[-1, -1, 0, 1, -1, 0, 0, 1, 0]], np.float32),
-                               nrm=np.tile(np.array([0, 0, 1], np.float32), (1, 3)),
-                               uv=np.zeros((1, 6), np.float32), mat=np.zeros(1, s.mat.dtype))
 
 
 # case -> (scene, grid)

@@ -48,13 +48,17 @@ class RayRef:
         rx, ry, _ = self.res
         n_cells = n_tests = 0
         cell = first
+        asked = {}       # source triangle -> the oracle's answer for this ray (a triangle sits in many cells)
         for k in range(len(ts)):
             b, e = self.cells[(int(cell[2]) * ry + int(cell[1])) * rx + int(cell[0])]
             n_cells += 1
             for r in range(int(b), int(e)):
                 n_tests += 1
-                tri = self.pos[self.indices[r]]
-                hit, tuv = self.orc.tri_intersect(tri[0:3], tri[3:6], tri[6:9], o, d)
+                src = int(self.indices[r])
+                if src not in asked:
+                    tri = self.pos[src]
+                    asked[src] = self.orc.tri_intersect(tri[0:3], tri[3:6], tri[6:9], o, d)
+                hit, tuv = asked[src]
                 if hit and tuv[0] < best[0] and tuv[0] > 0:    # stage3.zig:172: strict, the first ref wins a tie
                     best = (tuv[0], tuv[1], tuv[2])
                     ref = r
