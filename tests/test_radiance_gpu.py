@@ -35,7 +35,11 @@ CASES = {"cornell_bm": (lambda: scenes.get_scene("cornell"), (16, 16, 16)),     
          "tri_wide": (_one_triangle, (1100, 2, 2))}                              # the unpacked walk, no park path
 CONFIGS = [(1, 1), (3, 4), (64, 4), (65, 5), (2, 32), (4, 0)]                     # (spp, max_bounce)
 MODES = {"default": 0, "park": native.TRACE_PARK, "lane": native.FLAG_LANE_WALK, "mt_exact": native.FLAG_MT_EXACT,
-         "per_sample": native.RADIANCE_PER_SAMPLE, "per_sample_park": native.RADIANCE_PER_SAMPLE | native.TRACE_PARK}
+         "per_sample": native.RADIANCE_PER_SAMPLE, "per_sample_park": native.RADIANCE_PER_SAMPLE | native.TRACE_PARK,
+         # the escape-table park kernel and the release path, forced on and off
+         "park_escape": native.TRACE_PARK | native.FLAG_ESCAPE,
+         "park_release": native.TRACE_PARK | native.FLAG_RELEASE,
+         "park_no_release": native.TRACE_PARK | native.FLAG_NO_RELEASE}
 N_RAYS = 256
 SEED = 5
 

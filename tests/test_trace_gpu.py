@@ -41,7 +41,11 @@ PARK_RUNS = ("cornell_bm", "cornell_fields", "degenerate")
 MODES = {"lane": 0, "park": native.TRACE_PARK, "mt_exact": native.FLAG_MT_EXACT,
          # every ray parks in its first cell: the back-face cull masks forced on and off there
          "park_bfcull": native.TRACE_PARK | native.FLAG_BFCULL,
-         "park_no_bfcull": native.TRACE_PARK | native.FLAG_NO_BFCULL}
+         "park_no_bfcull": native.TRACE_PARK | native.FLAG_NO_BFCULL,
+         # the escape-table park kernel and the release path, forced on and off
+         "park_escape": native.TRACE_PARK | native.FLAG_ESCAPE,
+         "park_release": native.TRACE_PARK | native.FLAG_RELEASE,
+         "park_no_release": native.TRACE_PARK | native.FLAG_NO_RELEASE}
 N_RAYS = 256
 
 

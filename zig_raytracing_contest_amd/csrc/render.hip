@@ -3590,27 +3590,353 @@ static void scene_params(const zrt_context* c, TraceParams& tp) {
     tp.occ_words = c->occ_words;
 }
 
+// ---------------------------------------------------------------------------
+// The launch plan.  zrt_context_render, zrt_context_trace and
+// zrt_context_radiance launch the same park, shade and lane-walk kernels over
+// the same pass-set buffers.  What they decide alike before a launch, and the
+// layout the kernels expect of a set's queues and counters, is written once
+// here; an entry point keeps only what is its own.
+
+// `v` grown to n events.
+static int event_pool(std::vector<hipEvent_t>& v, size_t n, unsigned flags = hipEventDefault) {
+    while (v.size() < n) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreateWithFlags(&e, flags));
+        v.push_back(e);
+    }
+    return ZRT_OK;
+}
+
+// Blocks of a persistent launch of `f`: what the device holds at once.
+static int resident_blocks(const zrt_context* c, const void* f, int threads, size_t lds, uint32_t* blocks) {
+    int bpc = 0;
+    HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, f, threads, lds));
+    if (getenv("ZRT_WF_DEBUG"))
+        fprintf(stderr, "{\"zrt_grid\": {\"threads\": %d, \"lds\": %zu, \"blocks_per_cu\": %d}}\n", threads, lds, bpc);
+    bpc = std::max(1, std::min(bpc, 2048 / threads));
+    *blocks = (uint32_t)(c->num_cus * bpc);
+    return ZRT_OK;
+}
+
+// The device memory a call may spend on its work buffers: 144 GiB (HBM is
+// 288 GB), at most 60% of the free device memory, shared between the contexts
+// of a group on this device.  `held`: the bytes of grow-only buffers the
+// context already holds and this call reuses, counted as free: otherwise a
+// split would depend on the calls before (a warm context saw less free memory
+// and rendered 3 passes on 2 sets, the last one alone).  A call reads it
+// before it grows any buffer.
+static size_t device_budget(const zrt_context* c, size_t held) {
+    size_t budget = (size_t)144 << 30;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b) budget = std::min(budget, (free_b + held) / 10 * 6);
+    return budget / std::max<uint32_t>(c->mem_share, 1u);
+}
+
+// The bytes of a pass set's wavefront buffers.
+static size_t held_bytes(const zrt_context::PassSet& ps) {
+    return 16ull * (ps.q0_cap + ps.q1_cap + ps.term_cap + ps.stk4_cap + ps.hit_cap) + 8ull * ps.stk2_cap +
+           4ull * ps.wfc_cap;
+}
+
+// Capacity guard: every buffer a launch writes holds what that launch writes
+// (round 2's counting render once wrote through an unallocated d_out after a
+// refactor of the pass logic; a stale, smaller buffer must not pass silently
+// either).  True if `ptr` does not hold `need` elements.
+static bool shortfall(const char* what, const void* ptr, size_t cap, uint64_t need) {
+    if (ptr && cap >= need) return false;
+    if (getenv("ZRT_DEBUG"))
+        fprintf(stderr, "zrt: capacity guard: %s holds %zu, the launch writes %llu\n", what, ptr ? cap : 0,
+                (unsigned long long)need);
+    return true;
+}
+
+// A pass set's counters, kCtr words each (a contract with the kernels): per
+// launch k = 0 .. max_bounce + 1, 8 work counters, then 8 region counts of the
+// paths entering launch k (written by launch k - 1); after those, 8 work
+// counters of launch k's shade kernel.
+static size_t wfc_words(uint32_t mb) { return kCtr * 2ull * (16 * (mb + 2)); }
+static uint32_t* region_counts(const zrt_context::PassSet& ps, uint32_t k) { return ps.wfc + kCtr * (16 * k + 8); }
+
+// Launch k of a pass: the queue it reads and the one it appends to (ping-pong;
+// launch 0 reads q1), and its counters.
+static void bounce_params(WfParams& W, const zrt_context::PassSet& ps, uint32_t k, uint32_t mb) {
+    W.q_in = (k & 1) ? ps.q0 : ps.q1;
+    W.q_out = (k & 1) ? ps.q1 : ps.q0;
+    W.fetch8 = ps.wfc + kCtr * (16 * k);
+    W.n_in8 = region_counts(ps, k);
+    W.n_out8 = region_counts(ps, k + 1);
+    W.fetch8s = ps.wfc + wfc_words(mb) / 2 + kCtr * (8 * k);
+}
+
+// A pass set's wavefront buffers grown to T items of nb bounce slots each and
+// the counters of max_bounce mb, then the capacity guard over them.  Queues 3
+// float4 per item, bounce planes a float4 + a float2 per (slot, item), terminal
+// radiance 1 per item; `hit_items` hit records (the park kernel hands one per
+// item to the shade kernel; a query's first segments leave one per ray), 0: none.
+static int grow_pass_set(zrt_context::PassSet& ps, uint64_t T, uint32_t nb, uint32_t mb, uint64_t hit_items) {
+    const uint64_t planes2 = T * nb * (ZRT_PLANES16 ? 2 : 1);
+    int rc;
+    if ((rc = grow(&ps.q0, &ps.q0_cap, 3 * T)) != ZRT_OK) return rc;
+    if ((rc = grow(&ps.q1, &ps.q1_cap, 3 * T)) != ZRT_OK) return rc;
+    if ((rc = grow(&ps.term, &ps.term_cap, T)) != ZRT_OK) return rc;
+    if ((rc = grow(&ps.stk4, &ps.stk4_cap, T * nb)) != ZRT_OK) return rc;
+    if ((rc = grow(&ps.stk2, &ps.stk2_cap, planes2)) != ZRT_OK) return rc;
+    if ((rc = grow(&ps.wfc, &ps.wfc_cap, wfc_words(mb))) != ZRT_OK) return rc;
+    if (hit_items && (rc = grow(&ps.hit, &ps.hit_cap, hit_items)) != ZRT_OK) return rc;
+    const bool bad = shortfall("q0", ps.q0, ps.q0_cap, 3 * T) || shortfall("q1", ps.q1, ps.q1_cap, 3 * T) ||
+                     shortfall("term", ps.term, ps.term_cap, T) || shortfall("planes4", ps.stk4, ps.stk4_cap, T * nb) ||
+                     shortfall("planes2", ps.stk2, ps.stk2_cap, planes2) ||
+                     shortfall("counters", ps.wfc, ps.wfc_cap, wfc_words(mb)) ||
+                     (hit_items && shortfall("hit records", ps.hit, ps.hit_cap, hit_items));
+    return bad ? ZRT_ERR_INVALID_ARG : ZRT_OK;
+}
+
+// What a call's flags and the context settle for its bounce launches.
+struct LaunchPlan {
+    bool mtx;                 // Moller-Trumbore with the IEEE division in every launch (kWf*Exact)
+    bool packed, pbm;         // packed walk state; brick-major packed words (dda.h)
+    bool park_ok;             // the context and the flags allow the park kernel
+    bool park;                //   ... and this call launches it
+    bool rel, esc, bfc;       // the park launches use the release, the escape table, the cull masks
+    WfFn f_park, f_walk;      // a bounce launch: the park kernel (+ the shading half), or the lane walk
+    WfFn s_next, s_last;      // the shading half; of a pass's last bounce (terminal radiance only, LAST)
+    int park_block;           // threads of a park workgroup
+    uint32_t occx_ldsw;       // u32 words OccX takes in LDS
+    size_t lds_wf, lds_park, lds_shade;
+    // the park schedule (WfParams): parked lanes before a test round, finished
+    // lanes before a shade + refill round, the release's two thresholds
+    uint32_t test_min, refill_min, rel_min, rel_emin;
+};
+
+static void plan_park_block(LaunchPlan& pl, int block) {
+    pl.park_block = block;
+    pl.lds_park = 4ull * pl.occx_ldsw + (size_t)(block / 64) * sizeof(ParkSlot);
+}
+
+// Kernel per bounce launch: the park kernel (traces, writes hit records) +
+// wf_shade_kernel (incoherent rays) when the scene's OccX fits the LDS budget
+// (the park walk packs a cell into one word: at most 1024 cells per axis);
+// else, and with ZRT_FLAG_LANE_WALK, wf_kernel (round 1's path, and the
+// fallback).  mtx: scenes whose edges leave the short reciprocal's domain, or
+// as the flag forces: the unpacked lane walk.
+// `want_park`: what the entry point asks besides (a small query takes the lane
+// walk unasked); `big`: a call of kSetsMinSamples samples or more.
+// The escape table and the back-face cull masks are built here, at the first
+// big call that parks or the first a flag forces: 2.1 ms on cfg3 at 384 bins
+// (r04eb2), more than the table saves a 3-spp 1080p frame.  Each is used where
+// the scene's statistic says it pays (context_escape, context_bfcull) or as
+// the flags force it; the image is the same either way.
+static int resolve_plan(zrt_context* c, uint32_t flags, bool counting, bool want_park, bool big, LaunchPlan& pl) {
+    int rc;
+    pl.mtx = c->mt_exact || (flags & ZRT_FLAG_MT_EXACT);
+    pl.packed = c->packed && !pl.mtx;
+    pl.pbm = pl.packed && c->pk.bm;
+    pl.park_ok = c->occx_ok && !counting && !(flags & ZRT_FLAG_LANE_WALK) && pl.packed;
+    pl.park = pl.park_ok && want_park;
+    // the park release (wf_park_kernel): where enough entry faces are empty
+    // (context_packed), or as the flags force it (same image either way);
+    // with it the test rounds start at 12 parked lanes instead of 14 (r06u,
+    // in one process, images identical: cfg3 7004 vs 6979, cfg2 4795 vs
+    // 4632 Mrays/s; 10: 6987 / 4815, 8: 6927 / 4748;
+    // profiles/r06/r06u_knobs_release_trigger.log)
+    pl.rel = !(flags & ZRT_FLAG_NO_RELEASE) && (c->rel_on || (flags & ZRT_FLAG_RELEASE));
+    if (!c->esc_tried && pl.park && !(flags & ZRT_FLAG_NO_ESCAPE) && (big || (flags & ZRT_FLAG_ESCAPE))) {
+        c->esc_tried = true;
+        if ((rc = context_escape(c)) != ZRT_OK) return rc;
+    }
+    pl.esc = c->d_esc && !(flags & ZRT_FLAG_NO_ESCAPE) && (c->esc_on || (flags & ZRT_FLAG_ESCAPE));
+    if (pl.park && !(flags & ZRT_FLAG_NO_BFCULL)) {
+        const bool forced = (flags & ZRT_FLAG_BFCULL) != 0;
+        if (forced ? !c->bfc_tried_forced : (big && !c->bfc_tried)) {
+            c->bfc_tried = true;
+            c->bfc_tried_forced = c->bfc_tried_forced || forced;
+            if ((rc = context_bfcull(c, forced)) != ZRT_OK) return rc;
+        }
+    }
+    pl.bfc = c->d_bfc && !(flags & ZRT_FLAG_NO_BFCULL) && (c->bfc_on || (flags & ZRT_FLAG_BFCULL));
+    pl.f_park = pl.pbm ? (pl.esc ? (WfFn)wf_park_kernel<true, true> : (WfFn)wf_park_kernel<false, true>)
+                       : (pl.esc ? (WfFn)wf_park_kernel<true, false> : (WfFn)wf_park_kernel<false, false>);
+    pl.f_walk = pl.mtx ? kWfBounceExact : (pl.packed ? (pl.pbm ? kWfBounceBM : kWfBounce) : kWfBounceWide);
+    const bool lmats = c->nmat <= kLdsMats;
+    pl.s_next = lmats ? (WfFn)wf_shade_kernel<true> : (WfFn)wf_shade_kernel<false>;
+    pl.s_last = !ZRT_SHADE_LAST ? pl.s_next : lmats ? (WfFn)wf_shade_kernel<true, true> : (WfFn)wf_shade_kernel<false, true>;
+    pl.lds_wf = 4ull * c->occ_words;
+    pl.lds_shade = lmats ? c->nmat * sizeof(DevMat) : 0;
+    pl.occx_ldsw = (uint32_t)occx_lds_words(c->occx_nbw, c->occx_moff, c->occx_words);
+    plan_park_block(pl, kParkBlock);
+    pl.test_min = pl.rel ? kParkTestMinRel : kParkTestMin;
+    pl.refill_min = kParkRefillMin;
+    pl.rel_min = pl.test_min;              // park release: the parked lanes with refs a round needs
+    pl.rel_emin = 1;                       //   and the empty ones that make skipping it worth it
+    return ZRT_OK;
+}
+
+// The park kernel's fields of a launch's WfParams: OccX, the schedule, the
+// escape table and the cull masks.
+static void park_params(const zrt_context* c, const LaunchPlan& pl, WfParams& W) {
+    W.occx = c->d_occx;
+    W.occx_words = c->occx_words;
+    W.occx_ldsw = pl.occx_ldsw;
+    W.occx_nbw = c->occx_nbw;
+    W.occx_moff = c->occx_moff;
+    W.occx_nb0 = c->occx_nb[0];
+    W.occx_nb01 = c->occx_nb[0] * c->occx_nb[1];
+    W.test_min = pl.test_min;
+    W.refill_min = pl.refill_min;
+    W.rel_min = pl.rel ? pl.rel_min : 0u;
+    W.rel_emin = pl.rel_emin;
+    W.esc = c->d_esc;
+    W.bfc = pl.bfc ? c->d_bfc : nullptr;
+    W.bfc_ones = c->bfc_bytes ? c->bfc_bytes / 4 - 1 : 0;
+}
+
+// The occupancy-sized persistent grids of a call's bounce launches.
+struct BounceGrids {
+    uint32_t park, shade, shade_last, walk;
+};
+static int bounce_grids(const zrt_context* c, const LaunchPlan& pl, bool park, bool walk, BounceGrids& g) {
+    int rc;
+    g = BounceGrids{};
+    if (park) {
+        if ((rc = resident_blocks(c, (const void*)pl.f_park, pl.park_block, pl.lds_park, &g.park)) != ZRT_OK) return rc;
+        if ((rc = resident_blocks(c, (const void*)pl.s_next, kTraceThreads, pl.lds_shade, &g.shade)) != ZRT_OK) return rc;
+        if ((rc = resident_blocks(c, (const void*)pl.s_last, kTraceThreads, pl.lds_shade, &g.shade_last)) != ZRT_OK)
+            return rc;
+    }
+    if (walk && (rc = resident_blocks(c, (const void*)pl.f_walk, kTraceThreads, pl.lds_wf, &g.walk)) != ZRT_OK) return rc;
+    return ZRT_OK;
+}
+
+// ZRT_FLAG_KERNEL_TIMES: an event pair of the context's pool around every
+// kernel launch of a render, and the launch's class; the launches per class
+// are counted either way.
+struct KernelTimes {
+    zrt_context* c;
+    bool on;
+    size_t n = 0;                              // kernels timed
+    zrt_kernel_profile kp{};
+    int begin(int cls, hipStream_t sm) {
+        ++kp.launches[cls];
+        if (!on) return ZRT_OK;
+        c->ev_k_cls[n] = (uint8_t)cls;
+        HIP_TRY(hipEventRecord(c->ev_k[2 * n], sm));
+        return ZRT_OK;
+    }
+    int end(hipStream_t sm) {
+        if (!on) return ZRT_OK;
+        HIP_TRY(hipEventRecord(c->ev_k[2 * n + 1], sm));
+        ++n;
+        return ZRT_OK;
+    }
+};
+
+// A bounce launch on stream sm: the park kernel and the shading half of the
+// same bounce (`last`: a pass's last), or the lane walk.  `kt`: a render's
+// per-kernel events, or null.
+static int launch_bounce(const LaunchPlan& pl, const BounceGrids& g, const WfParams& W, hipStream_t sm, bool park,
+                         bool last, KernelTimes* kt) {
+    int rc;
+    if (kt && (rc = kt->begin(park ? ZRT_KERNEL_PARK : ZRT_KERNEL_BOUNCE, sm)) != ZRT_OK) return rc;
+    if (park)
+        hipLaunchKernelGGL(pl.f_park, dim3(g.park), dim3(pl.park_block), pl.lds_park, sm, W);
+    else
+        hipLaunchKernelGGL(pl.f_walk, dim3(g.walk), dim3(kTraceThreads), pl.lds_wf, sm, W);
+    HIP_TRY(hipGetLastError());
+    if (kt && (rc = kt->end(sm)) != ZRT_OK) return rc;
+    if (!park) return ZRT_OK;
+    if (kt && (rc = kt->begin(ZRT_KERNEL_SHADE, sm)) != ZRT_OK) return rc;
+    if (last)
+        hipLaunchKernelGGL(pl.s_last, dim3(g.shade_last), dim3(kTraceThreads), pl.lds_shade, sm, W);
+    else
+        hipLaunchKernelGGL(pl.s_next, dim3(g.shade), dim3(kTraceThreads), pl.lds_shade, sm, W);
+    HIP_TRY(hipGetLastError());
+    return kt ? kt->end(sm) : ZRT_OK;
+}
+
+// The launches that trace a query chunk's first segments, Scene.traceRay per
+// ray: rays in the fast domain (ray_fast) through the park kernel or the
+// context's fast lane walk, the others through the IEEE-division walk.
+struct RayLaunch {
+    RayFn f_fast;             // null (mtx, a counting call): every ray takes f_exact
+    RayFn f_exact;
+    bool park;
+    uint32_t grid_fast, grid_exact, grid_park;
+};
+static int ray_launch(const zrt_context* c, const LaunchPlan& pl, bool counting, bool park, uint32_t grid_park,
+                      RayLaunch& rl) {
+    int rc;
+    rl = RayLaunch{};
+    rl.f_fast = (counting || pl.mtx) ? nullptr : pl.packed ? (pl.pbm ? kRaysWalkBM : kRaysWalk) : kRaysWalkWide;
+    rl.f_exact = counting ? kRaysWalkCount : kRaysWalkExact;
+    rl.park = park;
+    rl.grid_park = grid_park;
+    if (rl.f_fast && !park &&
+        (rc = resident_blocks(c, (const void*)rl.f_fast, kTraceThreads, pl.lds_wf, &rl.grid_fast)) != ZRT_OK)
+        return rc;
+    return resident_blocks(c, (const void*)rl.f_exact, kTraceThreads, pl.lds_wf, &rl.grid_exact);
+}
+
+// A chunk's n first segments on the context's stream, over the identity queue
+// (ray i = entry i: P = n, S = 1) and the rays of Q: wf_park_kernel, or the
+// fast lane walk, then the kRaysRest launch over the rays those left (it ends
+// at once when they counted none); without a fast kernel the kRaysAll launch
+// alone.  `pack_out`: Q.rays are the caller's rays as given, so
+// rays_pack_kernel fills the queue before the park kernel and rays_out_kernel
+// writes its hit records to Q.hits after it.
+static int trace_first_segments(const zrt_context* c, const LaunchPlan& pl, const RayLaunch& rl, RayParams& Q, uint32_t n,
+                                bool pack_out, uint32_t* launches) {
+    const uint32_t nblk = (n + kBlock - 1) / kBlock;             // one thread per ray; also all a walk launch needs
+    Q.n = n;
+    Q.w.t.P = n;
+    Q.w.t.S = 1;
+    Q.w.t.total = n;
+    Q.w.t.sdiv = div_magic(1);
+    if (rl.park) {
+        Q.which = kRaysAll;
+        if (pack_out) hipLaunchKernelGGL(rays_pack_kernel, dim3(nblk), dim3(kBlock), 0, c->stream, Q);
+        hipLaunchKernelGGL(pl.f_park, dim3(rl.grid_park), dim3(pl.park_block), pl.lds_park, c->stream, Q.w);
+        if (pack_out) hipLaunchKernelGGL(rays_out_kernel, dim3(nblk), dim3(kBlock), 0, c->stream, Q);
+        *launches += pack_out ? 3 : 1;
+    } else if (rl.f_fast) {
+        Q.which = kRaysFast;
+        hipLaunchKernelGGL(rl.f_fast, dim3(std::min(rl.grid_fast, nblk)), dim3(kTraceThreads), pl.lds_wf, c->stream, Q);
+        ++*launches;
+    }
+    Q.which = rl.park || rl.f_fast ? kRaysRest : kRaysAll;
+    hipLaunchKernelGGL(rl.f_exact, dim3(std::min(rl.grid_exact, nblk)), dim3(kTraceThreads), pl.lds_wf, c->stream, Q);
+    ++*launches;
+    HIP_TRY(hipGetLastError());
+    return ZRT_OK;
+}
+
+// The end of a query call: the call's time, and the kernel time of a batch
+// that stayed on the device (a host batch sums its chunks' between the copies).
+static int finish_query(zrt_context* c, bool on_device, uint32_t launches, zrt_stats& st) {
+    HIP_TRY(hipEventRecord(c->ev_end, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev_begin, c->ev_end));
+    st.render_ms = ms;
+    if (on_device) st.trace_kernel_ms = ms;
+    st.trace_launches = launches;
+    return ZRT_OK;
+}
+
 // Samples per pass: the caller's cfg->samples_per_pass, else as few passes
 // as the queue budget allows but at least one per pass set (the sets' kernels
 // overlap on their streams), split evenly: cfg3 256 spp = 2 x 128 (r02bq, two
 // streams: 2 x 128 265.5 ms, 4 x 64 269.2, 8 x 32 273.1; cfg2 64 spp: 2 x 32
-// 18.1 ms vs one pass 20.1).  The budget covers every set: 144 GiB (HBM is
-// 288 GB), at most 60% of the free device memory.
-// `held`: the bytes of pass buffers this context already holds (grow-only,
-// reused by this render), counted as free: otherwise the split would depend
-// on the renders before (a warm context saw less free memory and ran 3 passes
-// on 2 sets, the last one alone).  The pass count is a multiple of the sets
-// (when spp allows), so the streams stay balanced to the end of the frame.
-static uint64_t pass_samples(const zrt_render_config* cfg, uint64_t per_item, uint32_t P, uint32_t sets,
-                             size_t held, uint32_t share) {
+// 18.1 ms vs one pass 20.1).  The budget (device_budget) covers every set.
+// `held`: the bytes of pass buffers this context already holds.  The pass
+// count is a multiple of the sets (when spp allows), so the streams stay
+// balanced to the end of the frame.
+static uint64_t pass_samples(const zrt_context* c, const zrt_render_config* cfg, uint64_t per_item, uint32_t P,
+                             uint32_t sets, size_t held) {
     const uint64_t spp = cfg->num_samples;
     const uint64_t cap = std::max<uint64_t>(1, 0x7FFFFF00ull / P);     // items of a pass < 2^31
     if (cfg->samples_per_pass) return std::min<uint64_t>(std::min<uint64_t>(cfg->samples_per_pass, spp), cap);
-    size_t budget = (size_t)144 << 30;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b)
-        budget = std::min(budget, (free_b + held) / 10 * 6);
-    budget /= std::max<uint32_t>(share, 1u);      // contexts of a group sharing this device
+    const size_t budget = device_budget(c, held);
     const uint64_t fit = std::min<uint64_t>(cap, std::max<uint64_t>(1, budget / sets / (per_item * P)));
     uint64_t npass = std::max<uint64_t>(std::min<uint64_t>(sets, spp), (spp + fit - 1) / fit);
     npass = std::min<uint64_t>(spp, (npass + sets - 1) / sets * sets);
@@ -3670,10 +3996,8 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
 #endif
     const bool ktimes = (cfg->flags & ZRT_FLAG_KERNEL_TIMES) != 0;
     size_t held = 16ull * c->out_cap + c->bfc_bytes;   // (the cull masks: the split must not depend on them)
-    for (const zrt_context::PassSet& ps : c->set)
-        held += 16ull * (ps.q0_cap + ps.q1_cap + ps.term_cap + ps.stk4_cap + ps.hit_cap) + 8ull * ps.stk2_cap +
-                4ull * ps.wfc_cap;
-    const uint64_t s_pass = pass_samples(cfg, per_item, P, counting ? 1u : want_sets, held, c->mem_share);
+    for (const zrt_context::PassSet& ps : c->set) held += held_bytes(ps);
+    const uint64_t s_pass = pass_samples(c, cfg, per_item, P, counting ? 1u : want_sets, held);
     const uint32_t npasses = (uint32_t)((spp + s_pass - 1) / s_pass);
     // pass sets: pass p runs on set p % nsets, each set with its own stream
     // and buffers, so one pass's launches fill the machine while another's
@@ -3705,15 +4029,33 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
     };
     const uint64_t T = (s_pass + lead) * P;      // the first pass is the largest
     int rc;
+    // the bounce launches (resolve_plan), after the budget was read: a first
+    // big frame builds the escape table and the cull masks here
+    LaunchPlan pl;
+    if ((rc = resolve_plan(c, cfg->flags, counting, true, big, pl)) != ZRT_OK) return rc;
+    const bool park_next = pl.park;
+    // the tuning builds' schedule, for renders only
+#if defined(ZRT_SWEEP) || defined(ZRT_SETS_ENV)
+    if (const char* e = getenv("ZRT_PARK_T")) pl.test_min = pl.rel_min = (uint32_t)std::max(1, std::min(64, atoi(e)));
+    if (const char* e = getenv("ZRT_PARK_R")) pl.refill_min = (uint32_t)std::max(1, std::min(64, atoi(e)));
+    if (const char* e = getenv("ZRT_PARK_REL")) pl.rel_min = (uint32_t)std::max(1, std::min(64, atoi(e)));
+    if (const char* e = getenv("ZRT_PARK_REL_E")) pl.rel_emin = (uint32_t)std::max(1, std::min(64, atoi(e)));
+#endif
+#ifdef ZRT_SWEEP
+    if (const char* e = getenv("ZRT_PARK_BLOCK")) plan_park_block(pl, std::max(64, std::min(kParkBlock, atoi(e) / 64 * 64)));
+#endif
+    if (getenv("ZRT_WF_DEBUG"))
+        fprintf(stderr, "{\"zrt_park_lds\": {\"occx_bytes\": %u, \"block\": %d, \"lds_per_block\": %zu, "
+                "\"release_frac\": %.4f, \"release\": %d}}\n",
+                4u * pl.occx_ldsw, pl.park_block, pl.lds_park, c->rel_frac, pl.rel ? 1 : 0);
+    // the primary launch: wf_kernel (coherent 8x8-pixel waves: 22 vs 42 ms
+    // for the park kernel at cfg3 64 spp, r02d)
+    const WfFn f_first = pl.mtx ? kWfPrimaryExact : pl.packed ? (pl.pbm ? kWfPrimaryBM : kWfPrimary) : kWfPrimaryWide;
+
     if (counting && (rc = grow(&c->d_out, &c->out_cap, (size_t)T)) != ZRT_OK) return rc;
     for (uint32_t k = 0; k < nsets && !counting; ++k) {
         zrt_context::PassSet& ps = c->set[k];
-        if ((rc = grow(&ps.q0, &ps.q0_cap, 3 * T)) != ZRT_OK) return rc;
-        if ((rc = grow(&ps.q1, &ps.q1_cap, 3 * T)) != ZRT_OK) return rc;
-        if ((rc = grow(&ps.term, &ps.term_cap, T)) != ZRT_OK) return rc;
-        if ((rc = grow(&ps.stk4, &ps.stk4_cap, T * nb)) != ZRT_OK) return rc;
-        if ((rc = grow(&ps.stk2, &ps.stk2_cap, T * nb * (ZRT_PLANES16 ? 2 : 1))) != ZRT_OK) return rc;
-        if ((rc = grow(&ps.wfc, &ps.wfc_cap, 32ull * kCtr * (mb + 2))) != ZRT_OK) return rc;
+        if ((rc = grow_pass_set(ps, T, nb, mb, park_next ? T : 0)) != ZRT_OK) return rc;
         if (k == 0) {
             ps.stream = c->stream;
         } else {
@@ -3723,166 +4065,43 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
     }
     if (nsets > 1) {
         if (!c->ev_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-        while (c->ev_pass.size() < npasses) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            c->ev_pass.push_back(e);
-        }
+        if ((rc = event_pool(c->ev_pass, npasses, hipEventDisableTiming)) != ZRT_OK) return rc;
     }
     if (npasses > 1 && (rc = grow(&c->d_acc, &c->acc_cap, P)) != ZRT_OK) return rc;
     if ((rc = grow(&c->d_rgb, &c->rgb_cap, 3ull * P)) != ZRT_OK) return rc;
     const bool want_lin = outs && outs->linear_packed;
     if (want_lin && (rc = grow(&c->d_lin, &c->lin_cap, 3ull * P)) != ZRT_OK) return rc;
     const uint32_t launches_per_pass = counting ? 1 : nb;
-    while (c->ev_trace.size() < 2ull * npasses * launches_per_pass) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        c->ev_trace.push_back(e);
-    }
-
+    if ((rc = event_pool(c->ev_trace, 2ull * npasses * launches_per_pass)) != ZRT_OK) return rc;
     // per-kernel events: per pass the primary, nb - 1 bounces of up to two
     // kernels, the resolve
+    KernelTimes kt{c, ktimes};
     const size_t nk = ktimes ? (size_t)npasses * (2 * nb + 1) : 0;
-    while (c->ev_k.size() < 2 * nk) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        c->ev_k.push_back(e);
-    }
+    if ((rc = event_pool(c->ev_k, 2 * nk)) != ZRT_OK) return rc;
     c->ev_k_cls.assign(nk, 0);
 
-    // Kernel per launch: the park kernel (traces, writes hit records) +
-    // wf_shade_kernel for the bounce launches (incoherent rays) when the
-    // scene's OccX fits the LDS budget, wf_kernel for the primary launch
-    // (coherent 8x8-pixel waves: 22 vs 42 ms for the park kernel at cfg3 64
-    // spp, r02d).  ZRT_FLAG_LANE_WALK: wf_kernel for every launch (round 1's
-    // path, and the fallback).
-    // (the park walk packs a cell into one word: at most 1024 cells per axis)
-    // mtx: Moller-Trumbore with the IEEE division in every launch (scenes
-    // whose edges leave the short reciprocal's domain, or as the flag forces):
-    // the unpacked lane walk, kWf*Exact
-    const bool mtx = c->mt_exact || (cfg->flags & ZRT_FLAG_MT_EXACT);
-    const bool park_next = c->occx_ok && !counting && !(cfg->flags & ZRT_FLAG_LANE_WALK) &&
-                           c->packed && !mtx;
-    // the park release (wf_park_kernel): where enough entry faces are empty
-    // (context_packed), or as the flags force it (same image either way);
-    // with it the test rounds start at 12 parked lanes instead of 14 (r06u,
-    // in one process, images identical: cfg3 7004 vs 6979, cfg2 4795 vs
-    // 4632 Mrays/s; 10: 6987 / 4815, 8: 6927 / 4748;
-    // profiles/r06/r06u_knobs_release_trigger.log)
-    const bool rel = !(cfg->flags & ZRT_FLAG_NO_RELEASE) && (c->rel_on || (cfg->flags & ZRT_FLAG_RELEASE));
-    uint32_t test_min = rel ? kParkTestMinRel : kParkTestMin, refill_min = kParkRefillMin;
-#if defined(ZRT_SWEEP) || defined(ZRT_SETS_ENV)
-    if (const char* e = getenv("ZRT_PARK_T")) test_min = (uint32_t)std::max(1, std::min(64, atoi(e)));
-    if (const char* e = getenv("ZRT_PARK_R")) refill_min = (uint32_t)std::max(1, std::min(64, atoi(e)));
-#endif
-    uint32_t rel_min = test_min;           // park release: the parked lanes with refs a round needs
-    uint32_t rel_emin = 1;                 //   and the empty ones that make skipping it worth it
-#if defined(ZRT_SWEEP) || defined(ZRT_SETS_ENV)
-    if (const char* e = getenv("ZRT_PARK_REL")) rel_min = (uint32_t)std::max(1, std::min(64, atoi(e)));
-    if (const char* e = getenv("ZRT_PARK_REL_E")) rel_emin = (uint32_t)std::max(1, std::min(64, atoi(e)));
-#endif
-    const bool packed = c->packed && !mtx;
-    const bool pbm = packed && c->pk.bm;   // brick-major packed words (dda.h)
-    const WfFn f_first = mtx ? kWfPrimaryExact : packed ? (pbm ? kWfPrimaryBM : kWfPrimary) : kWfPrimaryWide;
-    // the escape table: where dense enough to pay (context_escape), or as
-    // the flags force it (both kernels give the same image)
-    // (built at the first frame of 2^23 samples or more, or the first the flag
-    // forces: 2.1 ms on cfg3 at 384 bins, r04eb2, more than the table saves a
-    // 3-spp 1080p frame)
-    if (!c->esc_tried && park_next && !(cfg->flags & ZRT_FLAG_NO_ESCAPE) && (big || (cfg->flags & ZRT_FLAG_ESCAPE))) {
-        c->esc_tried = true;
-        if ((rc = context_escape(c)) != ZRT_OK) return rc;
-    }
-    const bool esc = c->d_esc && !(cfg->flags & ZRT_FLAG_NO_ESCAPE) &&
-                     (c->esc_on || (cfg->flags & ZRT_FLAG_ESCAPE));
-    // the back-face cull masks: built like the escape table, at the first big
-    // frame or the first the flag forces; used where the scene's statistic
-    // says they pay (context_bfcull) or as the flags force (same image)
-    if (park_next && !(cfg->flags & ZRT_FLAG_NO_BFCULL)) {
-        const bool forced = (cfg->flags & ZRT_FLAG_BFCULL) != 0;
-        if (forced ? !c->bfc_tried_forced : (big && !c->bfc_tried)) {
-            c->bfc_tried = true;
-            c->bfc_tried_forced = c->bfc_tried_forced || forced;
-            if ((rc = context_bfcull(c, forced)) != ZRT_OK) return rc;
-        }
-    }
-    const bool bfc = c->d_bfc && !(cfg->flags & ZRT_FLAG_NO_BFCULL) && (c->bfc_on || (cfg->flags & ZRT_FLAG_BFCULL));
-    const WfFn f_next = park_next ? (pbm ? (esc ? (WfFn)wf_park_kernel<true, true> : (WfFn)wf_park_kernel<false, true>)
-                                         : (esc ? (WfFn)wf_park_kernel<true, false> : (WfFn)wf_park_kernel<false, false>))
-                                  : mtx ? kWfBounceExact : (packed ? (pbm ? kWfBounceBM : kWfBounce) : kWfBounceWide);
-    const WfFn s_next = c->nmat <= kLdsMats ? (WfFn)wf_shade_kernel<true> : (WfFn)wf_shade_kernel<false>;
-    // a pass's last bounce launch: the terminal-radiance-only shade (LAST)
-    const WfFn s_last = !ZRT_SHADE_LAST ? s_next
-                        : c->nmat <= kLdsMats ? (WfFn)wf_shade_kernel<true, true> : (WfFn)wf_shade_kernel<false, true>;
-    const size_t lds_shade = c->nmat <= kLdsMats ? c->nmat * sizeof(DevMat) : 0;
-    for (uint32_t k = 0; k < nsets && park_next; ++k)
-        if ((rc = grow(&c->set[k].hit, &c->set[k].hit_cap, T)) != ZRT_OK) return rc;
-
-    // Capacity guard: every buffer a launch below writes holds what that
-    // launch writes (round 2's counting render once wrote through an
-    // unallocated d_out after a refactor of the pass logic; a stale, smaller
-    // buffer must not pass silently either).  Queues 3 float4 per item, bounce
-    // planes a float4 + a float2 per (slot, item), terminal radiance / hit records / counting
-    // output 1 per item, the pass's items S * P <= T (checked per pass).
+    // capacity guard (shortfall) of what grow_pass_set does not cover: the
+    // frame's buffers, the counting output 1 per item, the other sets'
+    // streams, and every pass's items S * P <= T
     {
-        auto shortfall = [&](const char* what, const void* ptr, size_t cap, uint64_t need) {
-            if (ptr && cap >= need) return false;
-            if (getenv("ZRT_DEBUG"))
-                fprintf(stderr, "zrt: capacity guard: %s holds %zu, the launch writes %llu\n", what, ptr ? cap : 0,
-                        (unsigned long long)need);
-            return true;
-        };
         bool bad = shortfall("pixel list", c->d_pix, c->pix_cap, P) || shortfall("rgb", c->d_rgb, c->rgb_cap, 3ull * P) ||
                    (npasses > 1 && shortfall("accumulator", c->d_acc, c->acc_cap, P)) ||
                    (want_lin && shortfall("linear", c->d_lin, c->lin_cap, 3ull * P)) ||
                    (counting && shortfall("counting output", c->d_out, c->out_cap, T));
-        for (uint32_t k = 0; k < nsets && !counting && !bad; ++k) {
-            const zrt_context::PassSet& ps = c->set[k];
-            bad = shortfall("q0", ps.q0, ps.q0_cap, 3 * T) || shortfall("q1", ps.q1, ps.q1_cap, 3 * T) ||
-                  shortfall("term", ps.term, ps.term_cap, T) || shortfall("planes4", ps.stk4, ps.stk4_cap, T * nb) ||
-                  shortfall("planes2", ps.stk2, ps.stk2_cap, T * nb * (ZRT_PLANES16 ? 2 : 1)) ||
-                  shortfall("counters", ps.wfc, ps.wfc_cap, 32ull * kCtr * (mb + 2)) ||
-                  (park_next && shortfall("hit records", ps.hit, ps.hit_cap, T)) ||
-                  (k > 0 && (!ps.stream || !ps.ev_join));
-        }
+        for (uint32_t k = 1; k < nsets && !counting && !bad; ++k) bad = !c->set[k].stream || !c->set[k].ev_join;
         for (uint32_t pass = 0; pass < npasses && !bad; ++pass)
             bad = (uint64_t)pass_count(pass) * P > T || pass_first(pass) + pass_count(pass) > spp;
         if (bad) return ZRT_ERR_INVALID_ARG;
     }
 
     // occupancy-sized persistent grids
-    const size_t lds_wf = 4ull * c->occ_words;
-    int park_block = kParkBlock;
-#ifdef ZRT_SWEEP
-    if (const char* e = getenv("ZRT_PARK_BLOCK")) park_block = std::max(64, std::min(kParkBlock, atoi(e) / 64 * 64));
-#endif
-    const uint32_t occx_ldsw = (uint32_t)occx_lds_words(c->occx_nbw, c->occx_moff, c->occx_words);
-    const size_t lds_park = 4ull * occx_ldsw + (size_t)(park_block / 64) * sizeof(ParkSlot);
-    if (getenv("ZRT_WF_DEBUG"))
-        fprintf(stderr, "{\"zrt_park_lds\": {\"occx_bytes\": %u, \"block\": %d, \"lds_per_block\": %zu, "
-                "\"release_frac\": %.4f, \"release\": %d}}\n",
-                4u * occx_ldsw, park_block, lds_park, c->rel_frac, rel ? 1 : 0);
-    auto grid_for = [&](const void* f, int threads, size_t lds, uint32_t* blocks) -> int {
-        int bpc = 0;
-        HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, f, threads, lds));
-        if (getenv("ZRT_WF_DEBUG"))
-            fprintf(stderr, "{\"zrt_grid\": {\"threads\": %d, \"lds\": %zu, \"blocks_per_cu\": %d}}\n", threads, lds, bpc);
-        bpc = std::max(1, std::min(bpc, 2048 / threads));
-        *blocks = (uint32_t)(c->num_cus * bpc);
-        return ZRT_OK;
-    };
-    uint32_t grid_first = 0, grid_next = 0, grid_count = 0, grid_shade = 0, grid_shade_last = 0;
-    const int thr_first = kTraceThreads;
-    const int thr_next = park_next ? park_block : kTraceThreads;
-    const size_t lds_first = lds_wf, lds_next = park_next ? lds_park : lds_wf;
+    uint32_t grid_first = 0, grid_count = 0;
+    BounceGrids grids{};
     if (counting) {
-        if ((rc = grid_for((const void*)cfn, kTraceThreads, lds_wf, &grid_count)) != ZRT_OK) return rc;
+        if ((rc = resident_blocks(c, (const void*)cfn, kTraceThreads, pl.lds_wf, &grid_count)) != ZRT_OK) return rc;
     } else {
-        if ((rc = grid_for((const void*)f_first, thr_first, lds_first, &grid_first)) != ZRT_OK) return rc;
-        if ((rc = grid_for((const void*)f_next, thr_next, lds_next, &grid_next)) != ZRT_OK) return rc;
-        if ((rc = grid_for((const void*)s_next, kTraceThreads, lds_shade, &grid_shade)) != ZRT_OK) return rc;
-        if ((rc = grid_for((const void*)s_last, kTraceThreads, lds_shade, &grid_shade_last)) != ZRT_OK) return rc;
+        if ((rc = resident_blocks(c, (const void*)f_first, kTraceThreads, pl.lds_wf, &grid_first)) != ZRT_OK) return rc;
+        if ((rc = bounce_grids(c, pl, park_next, !park_next, grids)) != ZRT_OK) return rc;
     }
 
     TraceParams tp;
@@ -3903,20 +4122,6 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
     tp.stats = c->d_stats;
     // stage3.zig:223 inv_num_samples = ones / splat(spp)  (f32 division)
     const float inv_spp = 1.0f / (float)spp;
-    size_t kn = 0;                             // kernels launched (ZRT_FLAG_KERNEL_TIMES)
-    auto kt_begin = [&](int cls, hipStream_t sm) -> int {
-        if (!ktimes) return ZRT_OK;
-        c->ev_k_cls[kn] = (uint8_t)cls;
-        HIP_TRY(hipEventRecord(c->ev_k[2 * kn], sm));
-        return ZRT_OK;
-    };
-    auto kt_end = [&](hipStream_t sm) -> int {
-        if (!ktimes) return ZRT_OK;
-        HIP_TRY(hipEventRecord(c->ev_k[2 * kn + 1], sm));
-        ++kn;
-        return ZRT_OK;
-    };
-    zrt_kernel_profile kp{};
 
     HIP_TRY(hipMemsetAsync(c->d_stats, 0, 512, c->stream));
     HIP_TRY(hipEventRecord(c->ev_begin, c->stream));
@@ -3924,7 +4129,7 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
     // block, r04fk3; 0.42 ms one thread per block) and save ~18% of the
     // primary launch: frames of 2^23 samples or more (a 3-spp 1080p frame's
     // primary takes ~0.5 ms: break-even)
-    if (ZRT_FRUSTUM && c->d_sat && !counting && packed && !(cfg->flags & ZRT_FLAG_NO_FRUSTUM) &&
+    if (ZRT_FRUSTUM && c->d_sat && !counting && pl.packed && !(cfg->flags & ZRT_FLAG_NO_FRUSTUM) &&
         ((uint64_t)P * cfg->num_samples >= kFrustumMinSamples || (cfg->flags & ZRT_FLAG_FRUSTUM))) {
         // the primary frustum bounds of this camera, every render (inside the
         // timed region: one wave per 4x4 pixel block, 130 K waves at 1080p)
@@ -3970,13 +4175,6 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
         // pass set pass % nsets: its own stream and buffers
         const zrt_context::PassSet& ps = c->set[counting ? 0u : pass % nsets];
         hipStream_t sm = counting ? c->stream : ps.stream;
-        float4* const q0 = ps.q0;
-        float4* const q1 = ps.q1;
-        float4* const term = ps.term;
-        float4* const stk4 = ps.stk4;
-        float2* const stk2 = ps.stk2;
-        uint32_t* const wfc = ps.wfc;
-        float4* const hit = ps.hit;
         const uint32_t s0 = pass_first(pass);
         const uint32_t S = pass_count(pass);
         tp.s0 = s0;
@@ -3985,86 +4183,52 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
         tp.sdiv = div_magic(S);
         const int first = pass == 0 ? 1 : 0, last = pass + 1 == npasses ? 1 : 0;
         if (!counting) {
-            // per launch k: 8 work counters, then 8 region counts of the
-            // paths entering launch k (written by launch k - 1)
-            HIP_TRY(hipMemsetAsync(wfc, 0, 4ull * 32 * kCtr * (mb + 2), sm));
+            HIP_TRY(hipMemsetAsync(ps.wfc, 0, 4ull * wfc_words(mb), sm));
             WfParams W;
             memset(&W, 0, sizeof W);
             W.t = tp;
-            W.stk4 = stk4;
-            W.stk2 = stk2;
-            W.term = term;
+            W.stk4 = ps.stk4;
+            W.stk2 = ps.stk2;
+            W.term = ps.term;
+            W.hit = ps.hit;
             W.T = (uint32_t)T;
-            W.occx = c->d_occx;
-            W.occx_words = c->occx_words;
-            W.occx_ldsw = occx_ldsw;
-            W.occx_nbw = c->occx_nbw;
-            W.occx_moff = c->occx_moff;
-            W.occx_nb0 = c->occx_nb[0];
-            W.occx_nb01 = c->occx_nb[0] * c->occx_nb[1];
-            W.test_min = test_min;
-            W.refill_min = refill_min;
-            W.rel_min = rel ? rel_min : 0u;
-            W.rel_emin = rel_emin;
-            W.esc = c->d_esc;
-            W.bfc = bfc ? c->d_bfc : nullptr;
-            W.bfc_ones = c->bfc_bytes ? c->bfc_bytes / 4 - 1 : 0;
+            park_params(c, pl, W);
             for (uint32_t k = 0; k < nb; ++k) {
-                W.q_in = (k & 1) ? q0 : q1;
-                W.q_out = (k & 1) ? q1 : q0;
-                W.fetch8 = wfc + kCtr * (16 * k);
-                W.n_in8 = wfc + kCtr * (16 * k + 8);
-                W.n_out8 = wfc + kCtr * (16 * (k + 1) + 8);
-                W.hit = hit;
-                W.fetch8s = wfc + kCtr * (16 * (mb + 2) + 8 * k);
+                bounce_params(W, ps, k, mb);
                 HIP_TRY(hipEventRecord(c->ev_trace[ne++], sm));
-                const int cls = k == 0 ? ZRT_KERNEL_PRIMARY : (park_next ? ZRT_KERNEL_PARK : ZRT_KERNEL_BOUNCE);
-                if ((rc = kt_begin(cls, sm)) != ZRT_OK) return rc;
-                if (k == 0)
-                    hipLaunchKernelGGL(f_first, dim3(grid_first), dim3(thr_first), lds_first, sm, W);
-                else
-                    hipLaunchKernelGGL(f_next, dim3(grid_next), dim3(thr_next), lds_next, sm, W);
-                HIP_TRY(hipGetLastError());
-                if ((rc = kt_end(sm)) != ZRT_OK) return rc;
-                ++kp.launches[cls];
-                if (k > 0 && park_next) {                    // same bounce, shading half
-                    if ((rc = kt_begin(ZRT_KERNEL_SHADE, sm)) != ZRT_OK) return rc;
-                    if (k + 1 == nb)
-                        hipLaunchKernelGGL(s_last, dim3(grid_shade_last), dim3(kTraceThreads), lds_shade, sm, W);
-                    else
-                        hipLaunchKernelGGL(s_next, dim3(grid_shade), dim3(kTraceThreads), lds_shade, sm, W);
+                if (k == 0) {
+                    if ((rc = kt.begin(ZRT_KERNEL_PRIMARY, sm)) != ZRT_OK) return rc;
+                    hipLaunchKernelGGL(f_first, dim3(grid_first), dim3(kTraceThreads), pl.lds_wf, sm, W);
                     HIP_TRY(hipGetLastError());
-                    if ((rc = kt_end(sm)) != ZRT_OK) return rc;
-                    ++kp.launches[ZRT_KERNEL_SHADE];
+                    if ((rc = kt.end(sm)) != ZRT_OK) return rc;
+                } else if ((rc = launch_bounce(pl, grids, W, sm, park_next, k + 1 == nb, &kt)) != ZRT_OK) {
+                    return rc;
                 }
                 HIP_TRY(hipEventRecord(c->ev_trace[ne++], sm));
                 ++launches;
             }
             // the passes' sums into acc stay in pass order (stage3.zig:236-242)
             if (nsets > 1 && pass > 0) HIP_TRY(hipStreamWaitEvent(sm, c->ev_pass[pass - 1], 0));
-            if ((rc = kt_begin(ZRT_KERNEL_RESOLVE, sm)) != ZRT_OK) return rc;
+            if ((rc = kt.begin(ZRT_KERNEL_RESOLVE, sm)) != ZRT_OK) return rc;
             hipLaunchKernelGGL(wf_resolve_kernel, dim3((P + kResPix - 1) / kResPix), dim3(kBlock), 0, sm,
-                               term, stk4, stk2, (uint32_t)T, P, S, mb, c->d_acc, first, last, inv_spp,
+                               ps.term, ps.stk4, ps.stk2, (uint32_t)T, P, S, mb, c->d_acc, first, last, inv_spp,
                                c->d_rgb, want_lin ? c->d_lin : nullptr);
-            if ((rc = kt_end(sm)) != ZRT_OK) return rc;
-            ++kp.launches[ZRT_KERNEL_RESOLVE];
+            if ((rc = kt.end(sm)) != ZRT_OK) return rc;
             if (nsets > 1) HIP_TRY(hipEventRecord(c->ev_pass[pass], sm));
         } else {
             HIP_TRY(hipMemsetAsync(c->d_counter, 0, 4, c->stream));
             HIP_TRY(hipEventRecord(c->ev_trace[ne++], c->stream));
-            if ((rc = kt_begin(ZRT_KERNEL_COUNT, c->stream)) != ZRT_OK) return rc;
-            hipLaunchKernelGGL(cfn, dim3(grid_count), dim3(kTraceThreads), lds_wf, c->stream, tp);
+            if ((rc = kt.begin(ZRT_KERNEL_COUNT, c->stream)) != ZRT_OK) return rc;
+            hipLaunchKernelGGL(cfn, dim3(grid_count), dim3(kTraceThreads), pl.lds_wf, c->stream, tp);
             HIP_TRY(hipGetLastError());
-            if ((rc = kt_end(c->stream)) != ZRT_OK) return rc;
-            ++kp.launches[ZRT_KERNEL_COUNT];
+            if ((rc = kt.end(c->stream)) != ZRT_OK) return rc;
             ++launches;
             HIP_TRY(hipEventRecord(c->ev_trace[ne++], c->stream));
-            if ((rc = kt_begin(ZRT_KERNEL_RESOLVE, c->stream)) != ZRT_OK) return rc;
+            if ((rc = kt.begin(ZRT_KERNEL_RESOLVE, c->stream)) != ZRT_OK) return rc;
             hipLaunchKernelGGL(resolve_kernel, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream,
                                c->d_out, P, S, c->d_acc, first, last, inv_spp, c->d_rgb,
                                want_lin ? c->d_lin : nullptr);
-            if ((rc = kt_end(c->stream)) != ZRT_OK) return rc;
-            ++kp.launches[ZRT_KERNEL_RESOLVE];
+            if ((rc = kt.end(c->stream)) != ZRT_OK) return rc;
         }
         HIP_TRY(hipGetLastError());
     }
@@ -4124,16 +4288,16 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
         if (wf_debug) fprintf(stderr, "{\"zrt_launch\": %u, \"ms\": %.3f}\n", e / 2, t);
     }
     st.trace_launches = launches;
-    for (size_t k = 0; k < kn; ++k) {
+    for (size_t k = 0; k < kt.n; ++k) {
         float t = 0.0f;
         HIP_TRY(hipEventElapsedTime(&t, c->ev_k[2 * k], c->ev_k[2 * k + 1]));
-        kp.ms[c->ev_k_cls[k]] += t;
+        kt.kp.ms[c->ev_k_cls[k]] += t;
     }
-    kp.passes = npasses;
-    kp.sets = counting ? 1u : nsets;
+    kt.kp.passes = npasses;
+    kt.kp.sets = counting ? 1u : nsets;
     if (counting)
-        for (int k = 0; k < 4; ++k) kp.primary_counts[k] = hs[8 + k];
-    c->prof = kp;
+        for (int k = 0; k < 4; ++k) kt.kp.primary_counts[k] = hs[8 + k];
+    c->prof = kt.kp;
     st.segments = hs[0];
     st.cells_visited = hs[1];
     st.triangle_tests = hs[2];
@@ -4160,19 +4324,11 @@ extern "C" int zrt_context_profile(const zrt_context* c, zrt_kernel_profile* out
     return ZRT_OK;
 }
 
-// Blocks of a persistent launch of `f`: what the device holds at once.
-static int resident_blocks(const zrt_context* c, const void* f, int threads, size_t lds, uint32_t* blocks) {
-    int bpc = 0;
-    HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, f, threads, lds));
-    bpc = std::max(1, std::min(bpc, 2048 / threads));
-    *blocks = (uint32_t)(c->num_cus * bpc);
-    return ZRT_OK;
-}
-
 // Scene.traceRay (stage3.zig:152-186) for a batch of rays: see include/zrt.h
-// and the kernels' comment (rays_walk_kernel).  Per chunk of at most
-// kTraceChunk rays, all on the context's stream:
+// and the kernels' comment (rays_walk_kernel).  The launch plan is the one a
+// render resolves (resolve_plan); the park path from kTraceParkMin rays, or as
+// ZRT_TRACE_PARK asks.  Per chunk of at most kTraceChunk rays, all on the
+// context's stream (trace_first_segments):
 //   lane walk:  rays_walk_kernel (fast kernel of the context, kRaysFast), then
 //               the IEEE-division kernel over the rays it left (kRaysRest);
 //               an mt_exact context, ZRT_FLAG_MT_EXACT or a counting call:
@@ -4189,79 +4345,47 @@ extern "C" int zrt_context_trace(zrt_context* c, const zrt_ray_batch* b, zrt_sta
     if (!b->rays || !b->hits) return ZRT_ERR_INVALID_ARG;
     DeviceGuard g(c->device);
 
-    // the same choices as a render's bounce launches (zrt_context_render)
     const bool counting = (b->flags & ZRT_FLAG_COUNT_STATS) != 0;
-    const bool mtx = c->mt_exact || (b->flags & ZRT_FLAG_MT_EXACT);
-    const bool park_ok = c->occx_ok && !counting && !(b->flags & ZRT_FLAG_LANE_WALK) && c->packed && !mtx;
-    const bool park = park_ok && ((b->flags & ZRT_TRACE_PARK) || b->num_rays >= kTraceParkMin);
-    const bool packed = c->packed && !mtx;
-    const bool pbm = packed && c->pk.bm;
-    const bool rel = !(b->flags & ZRT_FLAG_NO_RELEASE) && (c->rel_on || (b->flags & ZRT_FLAG_RELEASE));
+    LaunchPlan pl;
     int rc;
-    if (!c->esc_tried && park && !(b->flags & ZRT_FLAG_NO_ESCAPE) &&
-        (b->num_rays >= kSetsMinSamples || (b->flags & ZRT_FLAG_ESCAPE))) {
-        c->esc_tried = true;
-        if ((rc = context_escape(c)) != ZRT_OK) return rc;
-    }
-    const bool esc = c->d_esc && !(b->flags & ZRT_FLAG_NO_ESCAPE) && (c->esc_on || (b->flags & ZRT_FLAG_ESCAPE));
-    if (park && !(b->flags & ZRT_FLAG_NO_BFCULL)) {
-        const bool forced = (b->flags & ZRT_FLAG_BFCULL) != 0;
-        if (forced ? !c->bfc_tried_forced : (b->num_rays >= kSetsMinSamples && !c->bfc_tried)) {
-            c->bfc_tried = true;
-            c->bfc_tried_forced = c->bfc_tried_forced || forced;
-            if ((rc = context_bfcull(c, forced)) != ZRT_OK) return rc;
-        }
-    }
-    const bool bfc = c->d_bfc && !(b->flags & ZRT_FLAG_NO_BFCULL) && (c->bfc_on || (b->flags & ZRT_FLAG_BFCULL));
-    // the fast kernel (null: every ray takes f_exact) and the IEEE-division one
-    const RayFn f_fast = (counting || mtx) ? nullptr : packed ? (pbm ? kRaysWalkBM : kRaysWalk) : kRaysWalkWide;
-    const RayFn f_exact = counting ? kRaysWalkCount : kRaysWalkExact;
-    const WfFn f_park = pbm ? (esc ? (WfFn)wf_park_kernel<true, true> : (WfFn)wf_park_kernel<false, true>)
-                            : (esc ? (WfFn)wf_park_kernel<true, false> : (WfFn)wf_park_kernel<false, false>);
+    if ((rc = resolve_plan(c, b->flags, counting, (b->flags & ZRT_TRACE_PARK) || b->num_rays >= kTraceParkMin,
+                           b->num_rays >= kSetsMinSamples, pl)) != ZRT_OK)
+        return rc;
+    const bool park = pl.park;
 
     // chunk size: at most kTraceChunk rays, fewer if the device is short of
-    // memory (the budget of pass_samples: 60% of what is free, counting what
-    // the context already holds, shared between a group's contexts)
+    // memory (device_budget; of pass set 0 this call reuses the queue and the
+    // hit records only, so only those count as held)
     zrt_context::PassSet& ps = c->set[0];
     const uint64_t per_ray = (b->on_device ? 0ull : 40ull) + (park ? 64ull : 0ull);
     const size_t held = 4ull * (c->rays_cap + c->hits_cap) + 16ull * (ps.q0_cap + ps.hit_cap) + c->bfc_bytes;
-    size_t budget = (size_t)144 << 30;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b) budget = std::min(budget, (free_b + held) / 10 * 6);
-    budget /= std::max<uint32_t>(c->mem_share, 1u);
+    const size_t budget = device_budget(c, held);
     uint64_t chunk = std::min<uint64_t>(kTraceChunk, b->num_rays);
     if (per_ray) chunk = std::max<uint64_t>(64, std::min<uint64_t>(chunk, budget / per_ray));
     if (!b->on_device) {
         if ((rc = grow(&c->d_rays, &c->rays_cap, 6 * chunk)) != ZRT_OK) return rc;
         if ((rc = grow(&c->d_hits, &c->hits_cap, 4 * chunk)) != ZRT_OK) return rc;
     }
-    const size_t wfc_words = 32ull * kCtr * 2;     // (a render's smallest; this call uses 16 counters)
+    const size_t ctr_words = wfc_words(0);         // (a render's smallest; this call uses 16 counters)
     if (park) {
         if ((rc = grow(&ps.q0, &ps.q0_cap, 3 * chunk)) != ZRT_OK) return rc;
         if ((rc = grow(&ps.hit, &ps.hit_cap, chunk)) != ZRT_OK) return rc;
-        if ((rc = grow(&ps.wfc, &ps.wfc_cap, wfc_words)) != ZRT_OK) return rc;
+        if ((rc = grow(&ps.wfc, &ps.wfc_cap, ctr_words)) != ZRT_OK) return rc;
     }
-    // capacity guard (as zrt_context_render's): every buffer a launch below
-    // writes holds a chunk
-    if ((!b->on_device && (!c->d_rays || c->rays_cap < 6 * chunk || !c->d_hits || c->hits_cap < 4 * chunk)) ||
-        (park && (!ps.q0 || ps.q0_cap < 3 * chunk || !ps.hit || ps.hit_cap < chunk || !ps.wfc ||
-                  ps.wfc_cap < wfc_words)))
+    // capacity guard: every buffer a launch below writes holds a chunk
+    if ((!b->on_device && (shortfall("rays", c->d_rays, c->rays_cap, 6 * chunk) ||
+                           shortfall("hits", c->d_hits, c->hits_cap, 4 * chunk))) ||
+        (park && (shortfall("q0", ps.q0, ps.q0_cap, 3 * chunk) || shortfall("hit records", ps.hit, ps.hit_cap, chunk) ||
+                  shortfall("counters", ps.wfc, ps.wfc_cap, ctr_words))))
         return ZRT_ERR_INVALID_ARG;
-    while (c->ev_trace.size() < 2) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        c->ev_trace.push_back(e);
-    }
+    if ((rc = event_pool(c->ev_trace, 2)) != ZRT_OK) return rc;
 
     // occupancy-sized persistent grids (no more blocks than a chunk has work for)
-    const size_t lds_wf = 4ull * c->occ_words;
-    const uint32_t occx_ldsw = (uint32_t)occx_lds_words(c->occx_nbw, c->occx_moff, c->occx_words);
-    const size_t lds_park = 4ull * occx_ldsw + (size_t)(kParkBlock / 64) * sizeof(ParkSlot);
-    uint32_t grid_fast = 0, grid_exact = 0, grid_park = 0;
-    if (f_fast && !park && (rc = resident_blocks(c, (const void*)f_fast, kTraceThreads, lds_wf, &grid_fast)) != ZRT_OK)
+    uint32_t grid_park = 0;
+    if (park && (rc = resident_blocks(c, (const void*)pl.f_park, pl.park_block, pl.lds_park, &grid_park)) != ZRT_OK)
         return rc;
-    if ((rc = resident_blocks(c, (const void*)f_exact, kTraceThreads, lds_wf, &grid_exact)) != ZRT_OK) return rc;
-    if (park && (rc = resident_blocks(c, (const void*)f_park, kParkBlock, lds_park, &grid_park)) != ZRT_OK) return rc;
+    RayLaunch rl;
+    if ((rc = ray_launch(c, pl, counting, park, grid_park, rl)) != ZRT_OK) return rc;
 
     RayParams R;
     memset(&R, 0, sizeof R);
@@ -4274,23 +4398,10 @@ extern "C" int zrt_context_trace(zrt_context* c, const zrt_ray_batch* b, zrt_sta
         R.w.q_in = ps.q0;
         R.w.hit = ps.hit;
         R.w.fetch8 = ps.wfc;
-        R.w.n_in8 = ps.wfc + 8 * kCtr;
-        R.w.occx = c->d_occx;
-        R.w.occx_words = c->occx_words;
-        R.w.occx_ldsw = occx_ldsw;
-        R.w.occx_nbw = c->occx_nbw;
-        R.w.occx_moff = c->occx_moff;
-        R.w.occx_nb0 = c->occx_nb[0];
-        R.w.occx_nb01 = c->occx_nb[0] * c->occx_nb[1];
-        R.w.test_min = rel ? kParkTestMinRel : kParkTestMin;
-        R.w.refill_min = kParkRefillMin;
-        R.w.rel_min = rel ? R.w.test_min : 0u;
-        R.w.rel_emin = 1;
-        R.w.esc = c->d_esc;
-        R.w.bfc = bfc ? c->d_bfc : nullptr;
-        R.w.bfc_ones = c->bfc_bytes ? c->bfc_bytes / 4 - 1 : 0;
+        R.w.n_in8 = region_counts(ps, 0);
+        park_params(c, pl, R.w);
         R.q = ps.q0;
-        R.n_in8 = ps.wfc + 8 * kCtr;
+        R.n_in8 = region_counts(ps, 0);
     }
 
     HIP_TRY(hipMemsetAsync(c->d_stats, 0, 512, c->stream));
@@ -4307,30 +4418,10 @@ extern "C" int zrt_context_trace(zrt_context* c, const zrt_ray_batch* b, zrt_sta
             R.hits = c->d_hits;
             HIP_TRY(hipEventRecord(c->ev_trace[0], c->stream));
         }
-        R.n = n;
         HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
-        const uint32_t nblk = (n + kBlock - 1) / kBlock;         // one thread per ray; also all a walk launch needs
-        if (park) {
-            // the work counters; rays_pack_kernel writes the region counts
-            HIP_TRY(hipMemsetAsync(ps.wfc, 0, 4ull * 16 * kCtr, c->stream));
-            R.w.t.P = n;
-            R.w.t.S = 1;
-            R.w.t.total = n;
-            R.w.t.sdiv = div_magic(1);
-            R.which = kRaysAll;
-            hipLaunchKernelGGL(rays_pack_kernel, dim3(nblk), dim3(kBlock), 0, c->stream, R);
-            hipLaunchKernelGGL(f_park, dim3(grid_park), dim3(kParkBlock), lds_park, c->stream, R.w);
-            hipLaunchKernelGGL(rays_out_kernel, dim3(nblk), dim3(kBlock), 0, c->stream, R);
-            launches += 3;
-        } else if (f_fast) {
-            R.which = kRaysFast;
-            hipLaunchKernelGGL(f_fast, dim3(std::min(grid_fast, nblk)), dim3(kTraceThreads), lds_wf, c->stream, R);
-            ++launches;
-        }
-        R.which = park || f_fast ? kRaysRest : kRaysAll;
-        hipLaunchKernelGGL(f_exact, dim3(std::min(grid_exact, nblk)), dim3(kTraceThreads), lds_wf, c->stream, R);
-        ++launches;
-        HIP_TRY(hipGetLastError());
+        // the work counters; rays_pack_kernel writes the region counts
+        if (park) HIP_TRY(hipMemsetAsync(ps.wfc, 0, 4ull * 16 * kCtr, c->stream));
+        if ((rc = trace_first_segments(c, pl, rl, R, n, true, &launches)) != ZRT_OK) return rc;
         if (!b->on_device) {
             HIP_TRY(hipEventRecord(c->ev_trace[1], c->stream));
             HIP_TRY(copy_sync(b->hits + off, c->d_hits, 16ull * n, hipMemcpyDeviceToHost, c->stream));
@@ -4339,13 +4430,7 @@ extern "C" int zrt_context_trace(zrt_context* c, const zrt_ray_batch* b, zrt_sta
             st.trace_kernel_ms += t;
         }
     }
-    HIP_TRY(hipEventRecord(c->ev_end, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev_begin, c->ev_end));
-    st.render_ms = ms;
-    if (b->on_device) st.trace_kernel_ms = ms;
-    st.trace_launches = launches;
+    if ((rc = finish_query(c, b->on_device != 0, launches, st)) != ZRT_OK) return rc;
     st.segments = b->num_rays;
     if (counting) {
         unsigned long long hs[4];
@@ -4359,16 +4444,20 @@ extern "C" int zrt_context_trace(zrt_context* c, const zrt_ray_batch* b, zrt_sta
 }
 
 // Scene.traceRayRecursive (stage3.zig:188-220) for a batch of rays: see
-// include/zrt.h, the kernels' comment (RadParams) and DESIGN 5.12.  Per chunk
-// of n rays, S samples each, all on the context's stream and pass set 0:
+// include/zrt.h, the kernels' comment (RadParams) and DESIGN 5.12.  The launch
+// plan is the one a render resolves (resolve_plan); the first segment takes
+// the park kernel by zrt_context_trace's rule, on the segments launch 0 traces
+// (n rays, or n * S with ZRT_RADIANCE_PER_SAMPLE).  Per chunk of n rays, S
+// samples each, all on the context's stream and pass set 0:
 //   shared first segment (default):
 //     rad_pack_kernel -> the chunk's first segments as zrt_context_trace traces
-//     them (wf_park_kernel over the identity queue, or rays_walk_kernel; then
-//     the kRaysRest launch) -> rad_fanout_kernel: n * S shaded continuations;
+//     them (trace_first_segments: wf_park_kernel over the identity queue, or
+//     rays_walk_kernel; then the kRaysRest launch) -> rad_fanout_kernel: n * S
+//     shaded continuations;
 //   ZRT_RADIANCE_PER_SAMPLE:
 //     rad_pack_samples_kernel -> launch 0 as a bounce launch over n * S records;
-//   then bounces 1 .. max_bounce - 1 as a render launches them and
-//   wf_resolve_kernel (P = n, one pass), d_lin / d_rgb copied to the outputs.
+//   then bounces 1 .. max_bounce - 1 as a render launches them (launch_bounce)
+//   and wf_resolve_kernel (P = n, one pass), d_lin / d_rgb copied to the outputs.
 extern "C" int zrt_context_radiance(zrt_context* c, const zrt_radiance_batch* b, zrt_stats* stats) {
     if (!c || !b) return ZRT_ERR_INVALID_ARG;
     if ((b->flags & ~kRadianceFlags) != 0u || b->on_device > 1u) return ZRT_ERR_INVALID_ARG;
@@ -4396,118 +4485,54 @@ extern "C" int zrt_context_radiance(zrt_context* c, const zrt_radiance_batch* b,
         return ZRT_OK;
     }
 
-    // the same choices as a render's bounce launches (zrt_context_render); the
-    // first segment takes the park kernel by zrt_context_trace's rule, on the
-    // segments launch 0 traces (n rays, or n * S with ZRT_RADIANCE_PER_SAMPLE)
     const bool per_sample = (b->flags & ZRT_RADIANCE_PER_SAMPLE) != 0;
-    const bool mtx = c->mt_exact || (b->flags & ZRT_FLAG_MT_EXACT);
-    const bool park_next = c->occx_ok && !(b->flags & ZRT_FLAG_LANE_WALK) && c->packed && !mtx;
     const uint64_t first_n = per_sample ? b->num_rays * S : b->num_rays;
-    const bool park_first = park_next && ((b->flags & ZRT_TRACE_PARK) || first_n >= kTraceParkMin);
-    const bool park_any = park_first || (park_next && nb > 1);
-    const bool packed = c->packed && !mtx;
-    const bool pbm = packed && c->pk.bm;
-    const bool rel = !(b->flags & ZRT_FLAG_NO_RELEASE) && (c->rel_on || (b->flags & ZRT_FLAG_RELEASE));
-    const bool big = b->num_rays * S >= kSetsMinSamples;
+    const bool want_first = (b->flags & ZRT_TRACE_PARK) || first_n >= kTraceParkMin;
+    LaunchPlan pl;
     int rc;
-    if (!c->esc_tried && park_any && !(b->flags & ZRT_FLAG_NO_ESCAPE) && (big || (b->flags & ZRT_FLAG_ESCAPE))) {
-        c->esc_tried = true;
-        if ((rc = context_escape(c)) != ZRT_OK) return rc;
-    }
-    const bool esc = c->d_esc && !(b->flags & ZRT_FLAG_NO_ESCAPE) && (c->esc_on || (b->flags & ZRT_FLAG_ESCAPE));
-    if (park_any && !(b->flags & ZRT_FLAG_NO_BFCULL)) {
-        const bool forced = (b->flags & ZRT_FLAG_BFCULL) != 0;
-        if (forced ? !c->bfc_tried_forced : (big && !c->bfc_tried)) {
-            c->bfc_tried = true;
-            c->bfc_tried_forced = c->bfc_tried_forced || forced;
-            if ((rc = context_bfcull(c, forced)) != ZRT_OK) return rc;
-        }
-    }
-    const bool bfc = c->d_bfc && !(b->flags & ZRT_FLAG_NO_BFCULL) && (c->bfc_on || (b->flags & ZRT_FLAG_BFCULL));
-    const RayFn f_fast = mtx ? nullptr : packed ? (pbm ? kRaysWalkBM : kRaysWalk) : kRaysWalkWide;
-    const RayFn f_exact = kRaysWalkExact;
-    const WfFn f_park = pbm ? (esc ? (WfFn)wf_park_kernel<true, true> : (WfFn)wf_park_kernel<false, true>)
-                            : (esc ? (WfFn)wf_park_kernel<true, false> : (WfFn)wf_park_kernel<false, false>);
-    const WfFn f_walk = mtx ? kWfBounceExact : (packed ? (pbm ? kWfBounceBM : kWfBounce) : kWfBounceWide);
+    if ((rc = resolve_plan(c, b->flags, false, want_first || nb > 1, b->num_rays * S >= kSetsMinSamples, pl)) != ZRT_OK)
+        return rc;
+    const bool park_next = pl.park_ok, park_first = pl.park_ok && want_first, park_any = pl.park;
     const bool lmats = c->nmat <= kLdsMats;
-    const WfFn s_next = lmats ? (WfFn)wf_shade_kernel<true> : (WfFn)wf_shade_kernel<false>;
-    const WfFn s_last = !ZRT_SHADE_LAST ? s_next : lmats ? (WfFn)wf_shade_kernel<true, true> : (WfFn)wf_shade_kernel<false, true>;
     const RadFn f_fan = nb == 1 ? (lmats ? (RadFn)rad_fanout_kernel<true, true> : (RadFn)rad_fanout_kernel<false, true>)
                                 : (lmats ? (RadFn)rad_fanout_kernel<true, false> : (RadFn)rad_fanout_kernel<false, false>);
-    const size_t lds_shade = lmats ? c->nmat * sizeof(DevMat) : 0;
 
     // chunk size: at most kTraceChunk rays, its n * S items below 2^31 and
-    // within the memory budget of a render's pass (pass_samples: its per-item
-    // bytes, 60% of what is free counting what the context holds, shared
-    // between a group's contexts); S <= 65535 always fits at 64 rays
+    // within the memory budget of a render's pass (its per-item bytes,
+    // device_budget); S <= 65535 always fits at 64 rays
     zrt_context::PassSet& ps = c->set[0];
     const uint64_t per_item = 96ull + 16ull + 16ull + (ZRT_PLANES16 ? 32ull : 24ull) * nb;
     const uint64_t per_ray = per_item * S + 24ull + 15ull + (b->on_device ? 0ull : 24ull);
-    const size_t held = 4ull * (c->rays_cap + c->nrays_cap + c->lin_cap) + c->rgb_cap + c->bfc_bytes +
-                        16ull * (ps.q0_cap + ps.q1_cap + ps.term_cap + ps.stk4_cap + ps.hit_cap) + 8ull * ps.stk2_cap +
-                        4ull * ps.wfc_cap;
-    size_t budget = (size_t)144 << 30;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b) budget = std::min(budget, (free_b + held) / 10 * 6);
-    budget /= std::max<uint32_t>(c->mem_share, 1u);
+    const size_t held = 4ull * (c->rays_cap + c->nrays_cap + c->lin_cap) + c->rgb_cap + c->bfc_bytes + held_bytes(ps);
+    const size_t budget = device_budget(c, held);
     uint64_t chunk = std::min<uint64_t>(kTraceChunk, 0x7FFFFF00ull / S);
     chunk = std::max<uint64_t>(64, std::min<uint64_t>(chunk, budget / per_ray));
     chunk = std::min<uint64_t>(chunk, b->num_rays);
     const uint64_t T = chunk * S;                  // items of the largest chunk
-    const size_t wfc_words = 32ull * kCtr * (mb + 2);
     const uint64_t hit_need = std::max<uint64_t>(park_any ? T : 0, per_sample ? 0 : chunk);
     if (!b->on_device && (rc = grow(&c->d_rays, &c->rays_cap, 6 * chunk)) != ZRT_OK) return rc;
     if (!per_sample && (rc = grow(&c->d_nrays, &c->nrays_cap, 6 * chunk)) != ZRT_OK) return rc;
     if ((rc = grow(&c->d_lin, &c->lin_cap, 3 * chunk)) != ZRT_OK) return rc;
     if ((rc = grow(&c->d_rgb, &c->rgb_cap, 3 * chunk)) != ZRT_OK) return rc;
-    if ((rc = grow(&ps.q0, &ps.q0_cap, 3 * T)) != ZRT_OK) return rc;
-    if ((rc = grow(&ps.q1, &ps.q1_cap, 3 * T)) != ZRT_OK) return rc;
-    if ((rc = grow(&ps.term, &ps.term_cap, T)) != ZRT_OK) return rc;
-    if ((rc = grow(&ps.stk4, &ps.stk4_cap, T * nb)) != ZRT_OK) return rc;
-    if ((rc = grow(&ps.stk2, &ps.stk2_cap, T * nb * (ZRT_PLANES16 ? 2 : 1))) != ZRT_OK) return rc;
-    if ((rc = grow(&ps.wfc, &ps.wfc_cap, wfc_words)) != ZRT_OK) return rc;
-    if (hit_need && (rc = grow(&ps.hit, &ps.hit_cap, hit_need)) != ZRT_OK) return rc;
-    // capacity guard (as zrt_context_render's): every buffer a launch below
-    // writes holds what a chunk's launches write; a chunk's items fit 31 bits
-    {
-        auto shortfall = [&](const void* ptr, size_t cap, uint64_t need) { return !ptr || cap < need; };
-        if ((!b->on_device && shortfall(c->d_rays, c->rays_cap, 6 * chunk)) ||
-            (!per_sample && shortfall(c->d_nrays, c->nrays_cap, 6 * chunk)) ||
-            shortfall(c->d_lin, c->lin_cap, 3 * chunk) || shortfall(c->d_rgb, c->rgb_cap, 3 * chunk) ||
-            shortfall(ps.q0, ps.q0_cap, 3 * T) || shortfall(ps.q1, ps.q1_cap, 3 * T) ||
-            shortfall(ps.term, ps.term_cap, T) || shortfall(ps.stk4, ps.stk4_cap, T * nb) ||
-            shortfall(ps.stk2, ps.stk2_cap, T * nb * (ZRT_PLANES16 ? 2 : 1)) ||
-            shortfall(ps.wfc, ps.wfc_cap, wfc_words) || (hit_need && shortfall(ps.hit, ps.hit_cap, hit_need)) ||
-            chunk == 0 || chunk > kTraceChunk || T > 0x7FFFFF00ull)
-            return ZRT_ERR_INVALID_ARG;
-    }
-    while (c->ev_trace.size() < 2) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        c->ev_trace.push_back(e);
-    }
+    if ((rc = grow_pass_set(ps, T, nb, mb, hit_need)) != ZRT_OK) return rc;
+    // capacity guard of the rest: every buffer a launch below writes holds
+    // what a chunk's launches write; a chunk's items fit 31 bits
+    if ((!b->on_device && shortfall("rays", c->d_rays, c->rays_cap, 6 * chunk)) ||
+        (!per_sample && shortfall("unit rays", c->d_nrays, c->nrays_cap, 6 * chunk)) ||
+        shortfall("linear", c->d_lin, c->lin_cap, 3 * chunk) || shortfall("rgb", c->d_rgb, c->rgb_cap, 3 * chunk) ||
+        chunk == 0 || chunk > kTraceChunk || T > 0x7FFFFF00ull)
+        return ZRT_ERR_INVALID_ARG;
+    if ((rc = event_pool(c->ev_trace, 2)) != ZRT_OK) return rc;
 
     // occupancy-sized persistent grids
-    const size_t lds_wf = 4ull * c->occ_words;
-    const uint32_t occx_ldsw = (uint32_t)occx_lds_words(c->occx_nbw, c->occx_moff, c->occx_words);
-    const size_t lds_park = 4ull * occx_ldsw + (size_t)(kParkBlock / 64) * sizeof(ParkSlot);
-    uint32_t grid_fast = 0, grid_exact = 0, grid_park = 0, grid_walk = 0, grid_shade = 0, grid_shade_last = 0,
-             grid_fan = 0;
+    BounceGrids grids;
+    if ((rc = bounce_grids(c, pl, park_any, (!park_next && nb > 1) || (per_sample && !park_first), grids)) != ZRT_OK)
+        return rc;
+    RayLaunch rl{};
+    uint32_t grid_fan = 0;
     if (!per_sample) {
-        if (f_fast && !park_first &&
-            (rc = resident_blocks(c, (const void*)f_fast, kTraceThreads, lds_wf, &grid_fast)) != ZRT_OK)
-            return rc;
-        if ((rc = resident_blocks(c, (const void*)f_exact, kTraceThreads, lds_wf, &grid_exact)) != ZRT_OK) return rc;
-        if ((rc = resident_blocks(c, (const void*)f_fan, kTraceThreads, lds_shade, &grid_fan)) != ZRT_OK) return rc;
-    }
-    if (park_any) {
-        if ((rc = resident_blocks(c, (const void*)f_park, kParkBlock, lds_park, &grid_park)) != ZRT_OK) return rc;
-        if ((rc = resident_blocks(c, (const void*)s_next, kTraceThreads, lds_shade, &grid_shade)) != ZRT_OK) return rc;
-        if ((rc = resident_blocks(c, (const void*)s_last, kTraceThreads, lds_shade, &grid_shade_last)) != ZRT_OK)
-            return rc;
-    }
-    if ((!park_next && nb > 1) || (per_sample && !park_first)) {
-        if ((rc = resident_blocks(c, (const void*)f_walk, kTraceThreads, lds_wf, &grid_walk)) != ZRT_OK) return rc;
+        if ((rc = ray_launch(c, pl, false, park_first, grids.park, rl)) != ZRT_OK) return rc;
+        if ((rc = resident_blocks(c, (const void*)f_fan, kTraceThreads, pl.lds_shade, &grid_fan)) != ZRT_OK) return rc;
     }
 
     RadParams R;
@@ -4522,54 +4547,17 @@ extern "C" int zrt_context_radiance(zrt_context* c, const zrt_radiance_batch* b,
     W.stk2 = ps.stk2;
     W.term = ps.term;
     W.hit = ps.hit;
-    W.occx = c->d_occx;
-    W.occx_words = c->occx_words;
-    W.occx_ldsw = occx_ldsw;
-    W.occx_nbw = c->occx_nbw;
-    W.occx_moff = c->occx_moff;
-    W.occx_nb0 = c->occx_nb[0];
-    W.occx_nb01 = c->occx_nb[0] * c->occx_nb[1];
-    W.test_min = rel ? kParkTestMinRel : kParkTestMin;
-    W.refill_min = kParkRefillMin;
-    W.rel_min = rel ? W.test_min : 0u;
-    W.rel_emin = 1;
-    W.esc = c->d_esc;
-    W.bfc = bfc ? c->d_bfc : nullptr;
-    W.bfc_ones = c->bfc_bytes ? c->bfc_bytes / 4 - 1 : 0;
+    park_params(c, pl, W);
     R.ctr = c->d_counter;
     R.nrays = c->d_nrays;
-    R.q = ps.q1;                                   // launch 0 reads q1 (a render's k = 0)
-    R.n_in8 = ps.wfc + kCtr * 8;
-    uint32_t* const wfc = ps.wfc;
+    R.q = ps.q1;                                   // launch 0 reads q1 (bounce_params)
+    R.n_in8 = region_counts(ps, 0);
     // stage3.zig:223 inv_num_samples = ones / splat(spp)  (f32 division)
     const float inv_spp = 1.0f / (float)S;
 
     HIP_TRY(hipMemsetAsync(c->d_stats, 0, 512, c->stream));
     HIP_TRY(hipEventRecord(c->ev_begin, c->stream));
     uint32_t launches = 0;
-    // launch k of a chunk as a render runs a bounce launch: the park kernel +
-    // the shading half, or the lane walk
-    auto bounce = [&](uint32_t k, bool park) -> int {
-        W.q_in = (k & 1) ? ps.q0 : ps.q1;
-        W.q_out = (k & 1) ? ps.q1 : ps.q0;
-        W.fetch8 = wfc + kCtr * (16 * k);
-        W.n_in8 = wfc + kCtr * (16 * k + 8);
-        W.n_out8 = wfc + kCtr * (16 * (k + 1) + 8);
-        W.fetch8s = wfc + kCtr * (16 * (mb + 2) + 8 * k);
-        if (park) {
-            hipLaunchKernelGGL(f_park, dim3(grid_park), dim3(kParkBlock), lds_park, c->stream, W);
-            if (k + 1 == nb)
-                hipLaunchKernelGGL(s_last, dim3(grid_shade_last), dim3(kTraceThreads), lds_shade, c->stream, W);
-            else
-                hipLaunchKernelGGL(s_next, dim3(grid_shade), dim3(kTraceThreads), lds_shade, c->stream, W);
-            launches += 2;
-        } else {
-            hipLaunchKernelGGL(f_walk, dim3(grid_walk), dim3(kTraceThreads), lds_wf, c->stream, W);
-            ++launches;
-        }
-        HIP_TRY(hipGetLastError());
-        return ZRT_OK;
-    };
     for (uint64_t off = 0; off < b->num_rays; off += chunk) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, b->num_rays - off);
         const uint32_t items = n * S;              // <= T < 2^31
@@ -4582,63 +4570,45 @@ extern "C" int zrt_context_radiance(zrt_context* c, const zrt_radiance_batch* b,
         }
         R.n = n;
         R.key0 = (uint32_t)(b->index_base + off);
-        // per launch k: 8 work counters, then 8 region counts of the paths
-        // entering launch k (a render's layout); the pack kernels write launch 0's
-        HIP_TRY(hipMemsetAsync(wfc, 0, 4ull * wfc_words, c->stream));
+        // the counters of every launch (wfc_words); the pack kernels write launch 0's region counts
+        HIP_TRY(hipMemsetAsync(ps.wfc, 0, 4ull * wfc_words(mb), c->stream));
         HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
         W.t.P = n;
         W.t.S = S;
         W.t.total = items;
         W.t.sdiv = div_magic(S);
         W.T = items;
-        const uint32_t nblk = (n + kBlock - 1) / kBlock;
+        bounce_params(W, ps, 0, mb);
         if (per_sample) {
             hipLaunchKernelGGL(rad_pack_samples_kernel, dim3((items + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, R);
             ++launches;
             HIP_TRY(hipGetLastError());
-            if ((rc = bounce(0, park_first)) != ZRT_OK) return rc;
         } else {
-            hipLaunchKernelGGL(rad_pack_kernel, dim3(nblk), dim3(kBlock), 0, c->stream, R);
+            hipLaunchKernelGGL(rad_pack_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, R);
             ++launches;
-            // the first segments: one per ray, the identity queue (P = n, S = 1)
+            // the first segments: one per ray, launch 0's queue as the identity queue
             RayParams Q;
             memset(&Q, 0, sizeof Q);
             Q.w = W;
-            Q.w.t.P = n;
-            Q.w.t.S = 1;
-            Q.w.t.total = n;
-            Q.w.t.sdiv = div_magic(1);
             Q.w.t.max_bounce = 1;
-            Q.w.q_in = ps.q1;
-            Q.w.fetch8 = wfc;
-            Q.w.n_in8 = wfc + kCtr * 8;
             Q.rays = c->d_nrays;
             Q.hits = reinterpret_cast<uint32_t*>(ps.hit);
-            Q.n = n;
             Q.ctr = c->d_counter;
-            if (park_first) {
-                hipLaunchKernelGGL(f_park, dim3(grid_park), dim3(kParkBlock), lds_park, c->stream, Q.w);
-                ++launches;
-            } else if (f_fast) {
-                Q.which = kRaysFast;
-                hipLaunchKernelGGL(f_fast, dim3(std::min(grid_fast, nblk)), dim3(kTraceThreads), lds_wf, c->stream, Q);
-                ++launches;
-            }
-            Q.which = park_first || f_fast ? kRaysRest : kRaysAll;
-            hipLaunchKernelGGL(f_exact, dim3(std::min(grid_exact, nblk)), dim3(kTraceThreads), lds_wf, c->stream, Q);
-            ++launches;
-            // the fan-out: items fetched like a primary launch's, appended to launch 1's queue
-            W.q_in = ps.q1;
-            W.q_out = ps.q0;
-            W.fetch8 = wfc + kCtr * (16 * (mb + 2));
-            W.n_in8 = wfc + kCtr * 8;
-            W.n_out8 = wfc + kCtr * (16 + 8);
-            hipLaunchKernelGGL(f_fan, dim3(grid_fan), dim3(kTraceThreads), lds_shade, c->stream, R);
+            if ((rc = trace_first_segments(c, pl, rl, Q, n, false, &launches)) != ZRT_OK) return rc;
+            // the fan-out: items fetched like a primary launch's, on launch 0's
+            // shade counter, appended to launch 1's queue
+            W.fetch8 = W.fetch8s;
+            hipLaunchKernelGGL(f_fan, dim3(grid_fan), dim3(kTraceThreads), pl.lds_shade, c->stream, R);
             ++launches;
             HIP_TRY(hipGetLastError());
         }
-        for (uint32_t k = 1; k < nb; ++k)
-            if ((rc = bounce(k, park_next)) != ZRT_OK) return rc;
+        // launch k as a render runs a bounce launch; launch 0 of the per-sample records by the first segment's rule
+        for (uint32_t k = per_sample ? 0u : 1u; k < nb; ++k) {
+            const bool park = k == 0 ? park_first : park_next;
+            bounce_params(W, ps, k, mb);
+            if ((rc = launch_bounce(pl, grids, W, c->stream, park, k + 1 == nb, nullptr)) != ZRT_OK) return rc;
+            launches += park ? 2 : 1;
+        }
         hipLaunchKernelGGL(wf_resolve_kernel, dim3((n + kResPix - 1) / kResPix), dim3(kBlock), 0, c->stream, ps.term,
                            ps.stk4, ps.stk2, items, n, S, mb, c->d_acc, 1, 1, inv_spp, c->d_rgb, c->d_lin);
         ++launches;
@@ -4656,13 +4626,7 @@ extern "C" int zrt_context_radiance(zrt_context* c, const zrt_radiance_batch* b,
             st.trace_kernel_ms += t;
         }
     }
-    HIP_TRY(hipEventRecord(c->ev_end, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev_begin, c->ev_end));
-    st.render_ms = ms;
-    if (b->on_device) st.trace_kernel_ms = ms;
-    st.trace_launches = launches;
+    if ((rc = finish_query(c, b->on_device != 0, launches, st)) != ZRT_OK) return rc;
     unsigned long long hs[1];
     HIP_TRY(copy_sync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
     // the reference traces a shared first segment once per sample
