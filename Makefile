@@ -15,7 +15,8 @@ OBJ       := build/obj
 HIPFLAGS  := -O3 -fPIC -std=c++17 --offload-arch=$(ARCH) -ffp-contract=off -fno-fast-math -fno-slp-vectorize \
              -Wall -Wno-unused-function -Iinclude
 CXXFLAGS  := -O2 -fPIC -std=c++17 -ffp-contract=off -fno-fast-math -Wall -Iinclude -pthread
-HDRS      := include/zrt.h $(SRC)/zrt_math.h $(SRC)/zrt_internal.h $(SRC)/dda.h $(SRC)/geometry.h $(SRC)/device_geometry.h
+HDRS      := include/zrt.h $(SRC)/zrt_math.h $(SRC)/zrt_internal.h $(SRC)/dda.h $(SRC)/geometry.h $(SRC)/device_geometry.h \
+             $(SRC)/escape.h $(SRC)/render_context.h
 HOST_SRCS := $(filter-out $(SRC)/cli.cpp,$(wildcard $(SRC)/*.cpp))
 HOST_OBJS := $(patsubst $(SRC)/%.cpp,$(OBJ)/%.o,$(HOST_SRCS))
 LIB       := $(PKG)/libzrt.so
@@ -64,12 +65,14 @@ $(SWEEP_LIB): $(SRC)/render.hip $(HDRS) $(filter-out $(OBJ)/render.o,$(HIP_OBJS)
 	$(HIPCC) $(HIPFLAGS) -DZRT_SWEEP -c $(SRC)/render.hip -o tools/bin/sweep/render.o
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ tools/bin/sweep/render.o $(filter-out $(OBJ)/render.o,$(HIP_OBJS)) $(HOST_OBJS) -lz -pthread
 
-# A/B build of render.hip with extra defines (tools/gpu_ab.sh):
+# A/B build of render.hip and context.hip with extra defines (tools/gpu_ab.sh);
+# both, so that the two never link two opinions of one render_context.h knob:
 #   make variant V=name D="-DZRT_FOO"  ->  tools/bin/name/libzrt.so
-variant: $(filter-out $(OBJ)/render.o,$(HIP_OBJS)) $(HOST_OBJS)
+variant: $(filter-out $(OBJ)/render.o $(OBJ)/context.o,$(HIP_OBJS)) $(HOST_OBJS)
 	@mkdir -p tools/bin/$(V)
 	$(HIPCC) $(HIPFLAGS) $(D) -c $(SRC)/render.hip -o tools/bin/$(V)/render.o
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o tools/bin/$(V)/libzrt.so tools/bin/$(V)/render.o $^ -lz -pthread
+	$(HIPCC) $(HIPFLAGS) $(D) -c $(SRC)/context.hip -o tools/bin/$(V)/context.o
+	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o tools/bin/$(V)/libzrt.so tools/bin/$(V)/render.o tools/bin/$(V)/context.o $^ -lz -pthread
 
 oracle:
 	$(MAKE) -s -C oracle

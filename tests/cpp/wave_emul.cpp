@@ -113,7 +113,7 @@ void trace_wave_emul(const Scn& S, const v3* o, const v3* d, int nl, float* out)
     }
 }
 
-// The park kernel's entry-face skip (render.hip cell32_kernel): refs whose
+// The park kernel's entry-face skip (context.hip cell32_kernel): refs whose
 // (v0, e1, e2) equal a ref of the cell the ray just left are not tested.
 // mask[8 * cell + 2 + f] as the kernel builds it (dense cell index here).
 std::vector<uint32_t> face_masks(const Scn& S, uint32_t ncells) {

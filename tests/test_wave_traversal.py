@@ -59,7 +59,7 @@ def test_wave_shared_tests_match_sequential(emul, name, res):
 @pytest.mark.parametrize("name,res", [("cornell", (32, 32, 32)), ("contest", (128, 128, 128)),
                                       ("sponza", (128, 128, 128)), ("contest", (37, 64, 101))])
 def test_entry_face_skip_is_exact(emul, name, res):
-    """The park kernel's entry-face skip (render.hip cell32_kernel): a ref
+    """The park kernel's entry-face skip (context.hip cell32_kernel): a ref
     whose (v0, e1, e2) bits equal a ref of the cell the ray just left is not
     tested again.  Sequential traceRay with and without the skip, random rays
     from inside and outside the grid: bit-identical nearest t, u, v and ref;

@@ -1,6 +1,6 @@
 // Start-up cost on the GPU box, in the order the zrt CLI pays it: HIP
 // runtime + device context (hipFree(0)), then dlopen(libzrt.so), then
-// zrt_device_warmup (code objects of render.hip and grid_build.hip).
+// zrt_device_warmup (code objects of render.hip, grid_build.hip, context.hip).
 //   hipcc -O2 tools/hip_init_probe.cpp -o tools/bin/hip_init_probe -ldl
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -24,7 +24,7 @@ int main(int argc, char** argv) {
     if (!h) { fprintf(stderr, "%s\n", dlerror()); return 2; }
     const double t3 = now_ms();
     // grid_build.hip's module first (its hipCUB scans and sorts), then the
-    // rest of zrt_device_warmup (render.hip's module)
+    // rest of zrt_device_warmup (render.hip's and context.hip's modules)
     auto gwarm = (int (*)())dlsym(h, "_Z17grid_build_warmupv");
     if (gwarm && gwarm() != 0) return 2;
     const double t3b = now_ms();

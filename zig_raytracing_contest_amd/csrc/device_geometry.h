@@ -1,5 +1,5 @@
 // device_geometry.h -- hand-off from the device grid build (grid_build.hip)
-// to a render context (render.hip zrt_context_create_built): the baked
+// to a render context (context.hip zrt_context_create_built): the baked
 // stage-2 arrays, already in the context's HBM layout, never copied to the
 // host.
 #pragma once

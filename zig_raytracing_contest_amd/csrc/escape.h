@@ -278,7 +278,7 @@ ZHD FrustumBound frustum_bound(const EscSat& S, const uint32_t res[3], const flo
 }
 
 // ---------------------------------------------------------------------------
-// Back-face cull masks (render.hip bfc_build_kernel, the park kernel's first
+// Back-face cull masks (context.hip bfc_build_kernel, the park kernel's first
 // cell; tests/cpp/bfcull_check.cpp).
 //
 // tri_ray rejects a ref as soon as det = dot(e1, cross(d, e2)) < 1e-8.  Per

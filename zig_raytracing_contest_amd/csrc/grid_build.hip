@@ -156,7 +156,7 @@ __global__ __launch_bounds__(kB) void bake_kernel(const float* __restrict__ pos,
     omat[i] = mat[t];
 }
 
-// bakeInto straight into the render context's layout (render.hip
+// bakeInto straight into the render context's layout (context.hip
 // context_init): Pos as 3 float4 (v0 | shape id 0, e1 | 0, e2 | 0), Data as 4
 // float4 (9 normal + 6 texcoord floats, material index bits).
 __global__ __launch_bounds__(kB) void ctx_bake_kernel(const float* __restrict__ pos, const float* __restrict__ nrm,
@@ -566,7 +566,7 @@ extern "C" int zrt_geometry_build_device(const float* positions, const float* no
 }
 
 // Device build into a render context's arrays on the current device and
-// stream (render.hip zrt_context_create_built).  On failure the arrays
+// stream (context.hip zrt_context_create_built).  On failure the arrays
 // allocated so far are freed.
 int grid_build_into_device(const float* positions, const float* normals, const float* texcoords,
                            const uint32_t* material, uint32_t n, const uint32_t resolution[3], hipStream_t st,

@@ -1,5 +1,7 @@
 // render.hip -- the render hot path on CDNA4 (gfx950): wavefront path-trace
-// kernels + in-order sample resolve, behind the C ABI of include/zrt.h.
+// kernels + in-order sample resolve, the launch plan and the render, trace and
+// radiance entry points of include/zrt.h.  Building a context is context.hip's,
+// the parity probes are probe.hip's; render_context.h holds what they share.
 //
 // Reference: Scene.render / renderWorker / traceRayRecursive / traceRay
 // (src/stage3.zig:152-256) over Grid.traceRay + Iterator.next
@@ -19,38 +21,14 @@
 //     SAMPLE ORDER (renderWorker's `pixel = pixel.add(ray_color)`), scales by
 //     the f32 reciprocal of spp and quantizes with toRGB: the image is
 //     bit-identical to the recursion's for any scheduling.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <ctime>
-#include <new>
-#include <vector>
-
-#include "zrt_internal.h"
-#include "dda.h"
+#include "render_context.h"
 #include "escape.h"
-#include "device_geometry.h"
 
 using namespace zrt;
-
-#define HIP_TRY(expr)                                                            \
-    do {                                                                         \
-        hipError_t _e = (expr);                                                  \
-        if (_e != hipSuccess) {                                                  \
-            if (getenv("ZRT_DEBUG"))                                             \
-                fprintf(stderr, "zrt: %s failed: %s (%s:%d)\n", #expr,           \
-                        hipGetErrorString(_e), __FILE__, __LINE__);              \
-            return _e == hipErrorOutOfMemory ? ZRT_ERR_OUT_OF_MEMORY : ZRT_ERR_HIP; \
-        }                                                                        \
-    } while (0)
 
 namespace {
 
 constexpr float kFltEps = 1.1920928955078125e-07f;   // std.math.floatEps(f32)
-constexpr int kBlock = 256;                          // resolve / probes / helpers
 constexpr int kTraceBlock = 512;                     // launch bound of wf_kernel / trace_kernel
 constexpr int kTraceThreads = 256;                   // threads per wf_kernel / trace_kernel block
 // (r03ze, full spp: 1 -1.3 / -0.6 / -1.5%, 3 -0.6 / -0.2 / -0.6% on cfg3 /
@@ -62,10 +40,6 @@ constexpr int kTraceThreads = 256;                   // threads per wf_kernel / 
 #define ZRT_TRI_BATCH 1
 #endif
 constexpr int kTriBatch = ZRT_TRI_BATCH;             // triangle loads in flight per lane
-#ifndef ZRT_PARK_BLOCK_T
-#define ZRT_PARK_BLOCK_T 1024
-#endif
-constexpr int kParkBlock = ZRT_PARK_BLOCK_T;         // wf_park_kernel: one workgroup per CU
 // (3 entries since r05t: 113 VGPRs, which fit beside the park kernel at 96,
 // ZRT_PARK_WPE; one-stream shade 18.9 -> 17.1 ms per cfg3 frame)
 #ifndef ZRT_SHADE_N
@@ -93,11 +67,6 @@ constexpr uint32_t kWfChunk = ZRT_WF_CHUNK;
 // ms per cfg3 frame (profiles/r05/r05j_ab_planes16.log)
 #ifndef ZRT_PLANES16
 #define ZRT_PLANES16 1
-#endif
-// ZRT_ESCAPE: the park walk stops a segment once its escape-table bit
-// (escape.h) says every later cell of its ray is empty
-#ifndef ZRT_ESCAPE
-#define ZRT_ESCAPE 1
 #endif
 // ZRT_FRUSTUM: the primary walk fast-forwards (DDAV_FF) over the crossings
 // below its pixel block's frustum bound (escape.h frustum_bound lo); with
@@ -160,13 +129,6 @@ constexpr uint32_t kWfChunk = ZRT_WF_CHUNK;
 #endif
 constexpr uint32_t kFrustShift = ZRT_FRUSTUM_SHIFT;
 static_assert(kFrustShift <= 3, "a frustum block lies inside one tile (tile edges are multiples of 8)");
-// brick-major packed cell words for the grids that allow them (dda.h): r05ag,
-// 2 rounds, images identical: cfg3 6076 / 6088 vs 6005 / 5999 (+1.3%), cfg2
-// +2.4%, cfg5 +1.2%; the park walk trip 179 -> 165 VALU
-// (profiles/r05/r05ag_ab_brick_major.log)
-#ifndef ZRT_PACK_BM
-#define ZRT_PACK_BM 1
-#endif
 
 constexpr double kFrustB = (double)(1u << ZRT_FRUSTUM_SHIFT);
 // DDA steps per park walk trip, every cell's brick lookup in flight at once
@@ -181,7 +143,6 @@ constexpr double kFrustB = (double)(1u << ZRT_FRUSTUM_SHIFT);
 #ifndef ZRT_WALK_STEPS_NOESC
 #define ZRT_WALK_STEPS_NOESC 5
 #endif
-constexpr uint32_t kTriFloats = 12u;
 
 struct TraceParams {
     float bmin[3], bmax[3];
@@ -507,50 +468,6 @@ __device__ __forceinline__ float trace_ray(const TraceParams& p, const uint32_t*
         if (crossed) occupied = brick_occupied(p, occ, s.c0, s.c1, s.c2);
     }
     return nearest;
-}
-
-// Texture(T).sample (stage3.zig:111-123).  A 1x1 texture -- the dummy of
-// every material slot without an image (stage1.zig:411-425) -- has all four
-// texel indices 0 (any clamp, @mod by 1), so it loads its texel once and
-// runs the same bilinear arithmetic on it (bit-identical: x - x is not
-// folded, NaN/inf weights propagate as before), instead of the index
-// arithmetic and four loads per channel.
-#ifndef ZRT_TEX1
-#define ZRT_TEX1 1
-#endif
-__device__ __forceinline__ v3 sample3(const float* texels, const DevTex& t, float u, float v) {
-    const float* b = texels + t.off;
-    if (ZRT_TEX1 && t.w == 1 && t.h == 1) {
-        const float fu = tex_frac(u), fv = tex_frac(v);
-        // the texel, inlined in the descriptor (dev_tex_inline)
-        const float x = __int_as_float(t.umin), y = __int_as_float(t.umax), z = __int_as_float(t.vmin);
-        return mk(bilerp(x, x, x, x, fu, fv), bilerp(y, y, y, y, fu, fv), bilerp(z, z, z, z, fu, fv));
-    }
-    const TexCoords c = tex_coords(t.w, t.h, t.umin, t.umax, t.vmin, t.vmax, u, v);
-    v3 r;
-    r.x = bilerp(b[3 * c.i11 + 0], b[3 * c.i21 + 0], b[3 * c.i12 + 0], b[3 * c.i22 + 0], c.fu, c.fv);
-    r.y = bilerp(b[3 * c.i11 + 1], b[3 * c.i21 + 1], b[3 * c.i12 + 1], b[3 * c.i22 + 1], c.fu, c.fv);
-    r.z = bilerp(b[3 * c.i11 + 2], b[3 * c.i21 + 2], b[3 * c.i12 + 2], b[3 * c.i22 + 2], c.fu, c.fv);
-    return r;
-}
-__device__ __forceinline__ float sample1(const float* texels, const DevTex& t, float u, float v) {
-    const float* b = texels + t.off;
-    if (ZRT_TEX1 && t.w == 1 && t.h == 1) {               // the 1x1 dummy (see sample3)
-        const float x = __int_as_float(t.umin);
-        return bilerp(x, x, x, x, tex_frac(u), tex_frac(v));
-    }
-    const TexCoords c = tex_coords(t.w, t.h, t.umin, t.umax, t.vmin, t.vmax, u, v);
-    return bilerp(b[c.i11], b[c.i21], b[c.i12], b[c.i22], c.fu, c.fv);
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)x, off);
-        const unsigned hi = __shfl_xor((unsigned)(x >> 32), off);
-        x += ((unsigned long long)hi << 32) | lo;
-    }
-    return x;
 }
 
 // renderWorker: camera.getRay(x + U, y + U) (stage3.zig:238, :27-35) for
@@ -1125,7 +1042,6 @@ __device__ __forceinline__ uint32_t occx_brick(const WfParams& w, const DdaV& s)
 // its address registers doubled as the previous step's load destination,
 // r02k ISA).  Nothing orders an LDS read behind a pending LDS-DMA but the
 // wave's own vmcnt, so the test round drains vmcnt(0) before reading them.
-constexpr int kParkWaves = kParkBlock / 64;
 #ifndef ZRT_PARK_CHUNK
 #define ZRT_PARK_CHUNK 256
 #endif
@@ -1149,10 +1065,7 @@ constexpr uint32_t kParkChunk = ZRT_PARK_CHUNK;
 // images identical: cfg3 6972 vs 6992 (-0.3%), cfg2 -0.4%, cfg5 3845 vs 3892
 // (-1.2%) (profiles/r06/r06ab_ab_queue_prefetch.log): the extra request per
 // lane and refill costs more than the record loads' HBM latency, which the
-// SIMD's other park waves already hide
-#ifndef ZRT_PARK_QPF
-#define ZRT_PARK_QPF 0
-#endif
+// SIMD's other park waves already hide (0; the #define: render_context.h)
 // ZRT_PARK_ADAPT: a launch with few entries per wave (the last bounces, an
 // 8-rank tile set) takes smaller chunks, down to 64, so the waves' last
 // chunks end closer together (the launch tail).  r05e, alternating processes,
@@ -1232,15 +1145,6 @@ __device__ __forceinline__ void park_load_esc(const uint32_t* word, uint32_t* es
                  : "v"(word), "s"(m0)
                  : "memory");
 }
-
-// Per-wave LDS of the test rounds.
-struct ParkSlot {
-    float4 o[64];                    // lane's ray origin; w: nearest entering the round
-    float4 d[64];                    // lane's ray direction; w (bits): ref of its pair slot 0
-    unsigned long long best[64];     // per parked lane: (t bits << 32) | ref of its best pair
-    float2 uv[64];                   // (u, v) of that pair
-    uint32_t mark[64];               // lane + 1 of the parked lane whose pairs start at this slot
-};
 
 // Exclusive prefix sum over the wave (the whole wave must be active: every
 // DPP read below runs under full EXEC).  Row scans by DPP row_shr with
@@ -2381,34 +2285,8 @@ TraceFn count_fn(uint32_t max_bounce) {
     return nullptr;
 }
 
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (dev >= 0) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-template <typename T>
-int grow(T** p, size_t* cap, size_t n) {
-    if (*cap >= n && *p) return ZRT_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    HIP_TRY(hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T)));
-    *cap = n;
-    return ZRT_OK;
-}
-
-// OccX (wf_park_kernel): LDS left for the blob in one 1024-thread workgroup
-// per CU after the per-wave ParkSlots and the static ziggurat tables.
-constexpr size_t kLdsPerCu = 160 * 1024;
 // pass sets in flight (streams) by default, and at most (ZRT_SWEEP: ZRT_SETS)
 constexpr uint32_t kPassSets = 2;
-constexpr uint32_t kMaxPassSets = 4;
 constexpr uint64_t kSetsMinSamples = 1ull << 23;   // samples of a frame that runs kPassSets
 constexpr uint64_t kFrustumMinSamples = 1ull << 23; // samples of a frame that computes the frustum bounds
 // % of a pass moved from the last pass to the first when two sets run (r02d7,
@@ -2418,188 +2296,8 @@ constexpr uint64_t kFrustumMinSamples = 1ull << 23; // samples of a frame that c
 #define ZRT_LEAD_PCT 20
 #endif
 constexpr uint32_t kLeadPct = ZRT_LEAD_PCT;
-constexpr size_t kParkSlotsBytes = (kParkBlock / 64) * sizeof(ParkSlot);
-constexpr size_t kOccxBudget = kLdsPerCu - kParkSlotsBytes - 514 * sizeof(double) - kParkWaves * 192 * 4 - 256 -
-                                256 * 8 -   // the select table
-                                kParkWaves * 64 * 4 -  // the escape slots
-                                (ZRT_PARK_QPF ? kParkWaves * 64 * 4 : 0);   // the prefetch slots
 
 }  // namespace
-
-struct zrt_context {
-    int device = 0;
-    uint32_t mem_share = 1;            // contexts rendering on this device at once (a group's repeats)
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
-    std::vector<hipEvent_t> ev_trace;
-    zrt_grid grid{};
-    uint32_t ncells = 0, nrefs = 0, nmat = 0;
-    uint2* d_cells = nullptr;
-    // packed walks (DdaV): the layout and the cells indexed by the packed word
-    PackK pk{};
-    bool packed = false;
-    uint32_t* d_cell32 = nullptr;      // cell records at the packed index (cell32_kernel)
-    float* d_pos = nullptr;
-    float4* d_data = nullptr;
-    DevMat* d_mats = nullptr;
-    float* d_texels = nullptr;
-    double* d_zig = nullptr;
-    uint32_t* d_occ = nullptr;
-    uint32_t occ_shift = 0, occ_nb[3] = {0, 0, 0}, occ_words = 0;
-    uint32_t* d_occx = nullptr;     // exact per-cell occupancy blob (OccX), if it fits the LDS budget
-    unsigned long long* d_bmask = nullptr;   // every 4^3 brick's cell mask, linear brick order (TraceParams::bmask)
-    uint32_t* d_esc = nullptr;      // escape table (escape.h), with OccX
-    uint32_t* d_sat = nullptr;      // summed-area table of cell occupancy (escape.h EscSat), or null
-    // the primary frustum bounds (frustum_kernel) per 8x8 pixel block
-    float4* d_tlo = nullptr; size_t tlo_cap = 0;
-    bool esc_on = false;            // the park launches use it (dense enough to pay, context_escape)
-    // park release (wf_park_kernel): the fraction of the occupied cells'
-    // entry-face masks that are 0, and whether the launches use it
-    double rel_frac = 0.0;
-    bool rel_on = false;
-    bool esc_tried = false;         // context_escape ran (at the first render that can use it)
-    double esc_density = 0.0;       // fraction of its (brick, bin) bits set
-    // back-face cull masks (escape.h, context_bfcull): built at the first
-    // render that can use them, if they fit kBfcBudget / mem_share
-    uint32_t* d_bfc = nullptr;
-    size_t bfc_bytes = 0;
-    bool bfc_tried = false, bfc_tried_forced = false;
-    bool bfc_stat = false;          // the statistic below is known
-    bool bfc_on = false;            // the park launches use them unasked
-    double bfc_frac = 0.0;          // cleared bits / ref bits of the cells of 1..32 refs
-    double bfc_cleared = 0.0;       // cleared bits per (cell, bin) word of those cells
-    uint32_t occx_words = 0, occx_nbw = 0, occx_moff = 0, occx_nb[3] = {0, 0, 0};
-    bool occx_ok = false;
-    // an edge component of 2^62 or more, or infinite: every launch takes the
-    // lane walk with the IEEE division in Moller-Trumbore (kWf*Exact), since
-    // the park and packed kernels' short reciprocal holds for |det| < 2^126
-    // only (zrt_math.h mt_inv_det)
-    bool mt_exact = false;
-    // grow-only work buffers
-    uint32_t* d_pix = nullptr; size_t pix_cap = 0;
-    float4* d_out = nullptr; size_t out_cap = 0;     // counting build
-    // wavefront buffers of one pass set (queues, terminal radiance, bounce
-    // planes, counters, hit records); set k > 0 runs on its own stream
-    struct PassSet {
-        hipStream_t stream = nullptr;      // set 0: the context stream
-        float4* q0 = nullptr; size_t q0_cap = 0;
-        float4* q1 = nullptr; size_t q1_cap = 0;
-        float4* term = nullptr; size_t term_cap = 0;
-        float4* stk4 = nullptr; size_t stk4_cap = 0;   // bounce planes: (e, a.x) per (slot, item)
-        float2* stk2 = nullptr; size_t stk2_cap = 0;   //   (a.y, a.z) per (slot, item)
-        uint32_t* wfc = nullptr; size_t wfc_cap = 0;
-        float4* hit = nullptr; size_t hit_cap = 0;
-        hipEvent_t ev_join = nullptr;      // set k > 0: its last pass is done
-    };
-    PassSet set[kMaxPassSets];
-    float4* d_acc = nullptr; size_t acc_cap = 0;
-    uint8_t* d_rgb = nullptr; size_t rgb_cap = 0;
-    float* d_lin = nullptr; size_t lin_cap = 0;
-    // zrt_context_trace: a host batch's chunk on the device (6 floats, 4 u32 per ray)
-    float* d_rays = nullptr; size_t rays_cap = 0;
-    uint32_t* d_hits = nullptr; size_t hits_cap = 0;
-    // zrt_context_radiance: a chunk's rays with normalised directions (6 floats per ray)
-    float* d_nrays = nullptr; size_t nrays_cap = 0;
-    std::vector<hipEvent_t> ev_pass;   // per pass: its resolve done
-    hipEvent_t ev_fork = nullptr;
-    uint32_t* d_counter = nullptr;
-    unsigned long long* d_stats = nullptr;
-    int num_cus = 0;
-    // ZRT_FLAG_KERNEL_TIMES: an event pair per kernel launch and its class
-    std::vector<hipEvent_t> ev_k;
-    std::vector<uint8_t> ev_k_cls;
-    zrt_kernel_profile prof{};         // of the last render (zrt_context_profile)
-    // cached pixel list
-    std::vector<uint32_t> pix;
-    uint32_t pix_key[5] = {0, 0, 0, 0, 0};
-    bool pix_valid = false;
-};
-
-static int validate_materials(const zrt_scene* s);
-
-// A copy on the context's stream, waited for: the product path never uses
-// HIP's null stream, whose first use in a process creates its hardware
-// queue (~10 ms of the CLI's start-up, r06d)
-static hipError_t copy_sync(void* dst, const void* src, size_t n, hipMemcpyKind kind, hipStream_t st) {
-    const hipError_t e = hipMemcpyAsync(dst, src, n, kind, st);
-    return e != hipSuccess ? e : hipStreamSynchronize(st);
-}
-
-// ZRT_TIMING=1: context creation's stages on stderr ("timing:" lines), each
-// closed by a stream sync (the start-up split of VERDICT r5 #6)
-struct StageClock {
-    bool on = getenv("ZRT_TIMING") != nullptr;
-    double t = 0.0;
-    static double now_ms() {
-        timespec ts;
-        clock_gettime(CLOCK_MONOTONIC, &ts);
-        return ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6;
-    }
-    StageClock() { t = now_ms(); }
-    void mark(const zrt_context* c, const char* what);
-};
-
-void StageClock::mark(const zrt_context* c, const char* what) {
-    if (!on) return;
-    (void)hipStreamSynchronize(c->stream);
-    const double n = now_ms();
-    fprintf(stderr, "timing: context %s %.3f ms\n", what, n - t);
-    t = n;
-}
-
-static int validate_scene(const zrt_scene* s) {
-    if (!s) return ZRT_ERR_INVALID_ARG;
-    const uint64_t nc = (uint64_t)s->grid.resolution[0] * s->grid.resolution[1] * s->grid.resolution[2];
-    if (nc == 0 || nc != s->num_cells || nc > 0x7FFFFFFFull || !s->cells) return ZRT_ERR_INVALID_ARG;
-    if (s->num_triangles && (!s->triangles_pos || !s->triangles_data || !s->triangles_material))
-        return ZRT_ERR_INVALID_ARG;
-    for (uint64_t c = 0; c < nc; ++c) {
-        const uint32_t b = s->cells[2 * c], e = s->cells[2 * c + 1];
-        if (b > e || e > s->num_triangles) return ZRT_ERR_INVALID_ARG;
-    }
-    for (uint32_t i = 0; i < s->num_triangles; ++i)
-        if (s->triangles_material[i] >= s->num_materials) return ZRT_ERR_INVALID_ARG;
-    return validate_materials(s);
-}
-
-// Whether a scene needs the IEEE-division kernels (zrt_context::mt_exact):
-// `n` floats of which those with k % stride in [first, stride) are checked
-// (baked refs: the e1, e2 components of v0 e1 e2; source triangles: every
-// vertex component, at 2^61, so that their differences stay below 2^62).
-// NaN components need nothing: both forms propagate them.
-static bool needs_mt_exact(const float* v, uint64_t n, uint32_t stride, uint32_t first, float lim) {
-    for (uint64_t k = 0; k < n; ++k)
-        if (k % stride >= first && fabsf(v[k]) >= lim) return true;
-    return false;
-}
-
-// Materials and texels only (textures inside the texel array).
-static int validate_materials(const zrt_scene* s) {
-    if (s->num_materials == 0 || !s->materials || !s->texels) return ZRT_ERR_INVALID_ARG;
-    for (uint32_t m = 0; m < s->num_materials; ++m) {
-        const zrt_texture* t[3] = {&s->materials[m].base_color, &s->materials[m].emissive,
-                                   &s->materials[m].transparency};
-        for (int k = 0; k < 3; ++k) {
-            const uint64_t ch = k < 2 ? 3 : 1;
-            if (t[k]->w <= 0 || t[k]->h <= 0) return ZRT_ERR_INVALID_ARG;
-            if (t[k]->offset + (uint64_t)t[k]->w * t[k]->h * ch > s->num_texel_floats)
-                return ZRT_ERR_INVALID_ARG;
-            if (t[k]->offset > 0xFFFFFFFFull) return ZRT_ERR_UNSUPPORTED;
-        }
-    }
-    return ZRT_OK;
-}
-
-int grid_build_warmup();   // grid_build.hip
-
-extern "C" int zrt_device_count(int* count) {
-    if (!count) return ZRT_ERR_INVALID_ARG;
-    *count = 0;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return ZRT_ERR_NO_DEVICE;
-    *count = n;
-    return ZRT_OK;
-}
 
 // The timed wf_kernel instantiations, as the substrings of their mangled
 // names that tools/spill_check.py / tests/test_codegen.py look for in the
@@ -2622,924 +2320,10 @@ extern "C" const char* zrt_timed_kernels(void) {
 #undef ZRT_STR2
 }
 
-// Start-up work of the first GPU call, done ahead: the device's context and
-// the library's code objects (one fat binary, loaded on first use: ~0.1-0.2 s
-// on MI355X).  Lets a host overlap it with file loading.
-extern "C" int zrt_device_warmup(int device) {
-    // ZRT_TIMING: the split of the HIP start-up (runtime initialisation,
-    // device context, the two code objects) on stderr
-    const bool timing = getenv("ZRT_TIMING") != nullptr;
-    const double t0 = StageClock::now_ms();
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return ZRT_ERR_NO_DEVICE;
-    const double t1 = StageClock::now_ms();
-    if (device < 0) device = 0;
-    if (device >= n) return ZRT_ERR_NO_DEVICE;
-    DeviceGuard g(device);
-    HIP_TRY(hipFree(nullptr));
-    const double t2 = StageClock::now_ms();
+// Load this unit's code object on the current device (zrt_device_warmup).
+int render_warmup() {
     hipFuncAttributes fa;
     HIP_TRY(hipFuncGetAttributes(&fa, (const void*)resolve_kernel));
-    const double t3 = StageClock::now_ms();
-    const int rc = grid_build_warmup();
-    if (timing)
-        fprintf(stderr, "timing: warm-up: runtime init (hipGetDeviceCount) %.3f ms, device context %.3f ms, "
-                "render.hip code object %.3f ms, grid_build.hip code object %.3f ms\n",
-                t1 - t0, t2 - t1, t3 - t2, StageClock::now_ms() - t3);
-    return rc;
-}
-
-extern "C" void zrt_context_destroy(zrt_context* c) {
-    if (!c) return;
-    DeviceGuard g(c->device);
-    if (c->d_cell32) (void)hipFree(c->d_cell32);
-    void* bufs[] = {c->d_cells, c->d_pos, c->d_data, c->d_mats, c->d_texels, c->d_zig, c->d_occ, c->d_occx, c->d_esc,
-                    c->d_bfc, c->d_bmask, c->d_sat, c->d_tlo,
-                    c->d_pix, c->d_out, c->d_acc, c->d_rgb, c->d_lin, c->d_rays, c->d_hits, c->d_nrays, c->d_counter,
-                    c->d_stats};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    for (zrt_context::PassSet& ps : c->set) {
-        void* sb[] = {ps.q0, ps.q1, ps.term, ps.stk4, ps.stk2, ps.wfc, ps.hit};
-        for (void* b : sb)
-            if (b) (void)hipFree(b);
-        if (ps.ev_join) (void)hipEventDestroy(ps.ev_join);
-        if (ps.stream && ps.stream != c->stream) (void)hipStreamDestroy(ps.stream);
-    }
-    for (hipEvent_t e : c->ev_trace) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_pass) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_k) (void)hipEventDestroy(e);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_begin) (void)hipEventDestroy(c->ev_begin);
-    if (c->ev_end) (void)hipEventDestroy(c->ev_end);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
-}
-
-namespace {
-
-// OccX on the device, pass 1: one thread per 4^3 brick -> its 64-bit cell
-// mask (bit (z&3)<<4 | (y&3)<<2 | (x&3) = cell non-empty) and the brick bit.
-__global__ __launch_bounds__(kBlock) void occx_mask_kernel(const uint2* __restrict__ cells, uint32_t r0, uint32_t r1,
-                                                           uint32_t r2, uint32_t nb0, uint32_t nb1, uint32_t nb,
-                                                           unsigned long long* __restrict__ masks,
-                                                           uint32_t* __restrict__ bits) {
-    const uint32_t b = blockIdx.x * kBlock + threadIdx.x;
-    unsigned long long m = 0ull;
-    if (b < nb) {
-        const uint32_t bx = b % nb0, by = (b / nb0) % nb1, bz = b / (nb0 * nb1);
-        for (uint32_t k = 0; k < 64; ++k) {
-            const uint32_t x = bx * 4 + (k & 3u), y = by * 4 + ((k >> 2) & 3u), z = bz * 4 + (k >> 4);
-            if (x < r0 && y < r1 && z < r2) {
-                const uint2 c = cells[((uint64_t)z * r1 + y) * r0 + x];
-                if (c.x < c.y) m |= 1ull << k;
-            }
-        }
-        masks[b] = m;
-    }
-    const uint64_t bal = __ballot(b < nb && m != 0ull);
-    const uint32_t lane = threadIdx.x & 63u;
-    if (b < nb && (lane == 0 || lane == 32)) bits[b >> 5] = (uint32_t)(bal >> lane);
-}
-
-// Pass 2 (one block): 1 + the u16 prefix of occupied bricks per 32-brick
-// word, the zero mask, then the occupied masks compacted in brick order;
-// out[0] = the number of occupied bricks.
-__global__ __launch_bounds__(1024) void occx_pack_kernel(const uint32_t* __restrict__ bits, uint32_t nbw,
-                                                         const unsigned long long* __restrict__ masks,
-                                                         uint16_t* __restrict__ prefix,
-                                                         unsigned long long* __restrict__ packed,
-                                                         uint32_t* __restrict__ out) {
-    __shared__ uint32_t part[1024];
-    const uint32_t per = (nbw + 1023u) / 1024u;
-    const uint32_t w0 = threadIdx.x * per, w1 = min(w0 + per, nbw);
-    uint32_t sum = 0;
-    for (uint32_t wd = w0; wd < w1; ++wd) sum += (uint32_t)__popc(bits[wd]);
-    part[threadIdx.x] = sum;
-    __syncthreads();
-    for (uint32_t off = 1; off < 1024u; off <<= 1) {            // inclusive Hillis-Steele scan
-        const uint32_t v = threadIdx.x >= off ? part[threadIdx.x - off] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[threadIdx.x] - sum;
-    for (uint32_t wd = w0; wd < w1; ++wd) {
-        prefix[wd] = (uint16_t)min(run + 1u, 0xFFFFu);
-        for (uint32_t wb = bits[wd]; wb; wb &= wb - 1u)
-            packed[1u + run++] = masks[32u * wd + (uint32_t)__builtin_ctz(wb)];
-    }
-    if (threadIdx.x == 0) packed[0] = 0ull;
-    if (threadIdx.x == 1023) out[0] = run;
-}
-
-}  // namespace
-
-static int context_base(zrt_context* c) {
-    StageClock sc;
-    HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    sc.mark(c, "stream");
-    HIP_TRY(hipEventCreate(&c->ev_begin));
-    HIP_TRY(hipEventCreate(&c->ev_end));
-    sc.mark(c, "events");
-    // one attribute, not hipGetDeviceProperties (which fills ~100 fields and
-    // took ~10 ms of the CLI's start-up, r06c)
-    HIP_TRY(hipDeviceGetAttribute(&c->num_cus, hipDeviceAttributeMultiprocessorCount, c->device));
-    sc.mark(c, "CU count");
-    return ZRT_OK;
-}
-
-static int context_materials(zrt_context* c, const zrt_scene* s);
-static int context_occupancy(zrt_context* c, const uint32_t* host_cells);
-
-// Word i of ref k's (v0, e1, e2) in the context's triangle layout.
-__device__ __forceinline__ uint32_t tri_word(const float* pos, uint32_t k, uint32_t i) {
-    return __float_as_uint(pos[(uint64_t)kTriFloats * k + i + i / 3]);
-}
-__device__ __forceinline__ bool same_tri(const float* pos, uint32_t a, uint32_t b) {
-    for (uint32_t i = 0; i < 9; ++i)
-        if (tri_word(pos, a, i) != tri_word(pos, b, i)) return false;
-    return true;
-}
-
-// The packed walks' cell records: 8 u32 per cell at its packed-word index
-// (x | y << o1 | z << o2; the padding of a non-power-of-two grid stays empty):
-// begin, end, then for each entry face f = 2 * axis + (the ray steps toward
-// -axis) the mask of the refs (bit k: ref begin + k) that a ray entering the
-// cell across f must still test.
-//
-// A ray enters a cell only from the cell it has just left, across the face
-// they share, and leaves a cell only after testing all of its refs
-// (stage3.zig:164-182).  A ref whose (v0, e1, e2) bits equal those of a ref
-// of that neighbour gives the same (hit, t, u, v) as the one already tested
-// there: if that one was taken, nearest == t and `nearest > t` fails; if not,
-// nearest has only shrunk since.  So skipping it changes no hit, no tie
-// (ties resolve within the cell by ref order, and the kept refs keep their
-// order and index) and no break test.  Refs of cells with more than 32 refs
-// are all kept (mask all ones), and so are those of a face on the grid
-// boundary (no ray steps in across it).  About half of all triangle tests on
-// the contest stand-in repeat the previous cell's (triangles span ~5.6
-// cells), a third on the Sponza-scale one.
-__global__ __launch_bounds__(kBlock) void cell32_kernel(const uint2* __restrict__ cells, uint32_t r0, uint32_t r1,
-                                                        uint32_t r2, uint32_t ncells, const PackK pk,
-                                                        const float* __restrict__ pos, uint32_t* __restrict__ out) {
-    for (uint32_t ci = blockIdx.x * kBlock + threadIdx.x; ci < ncells; ci += gridDim.x * kBlock) {
-        const uint2 c = cells[ci];
-        const uint32_t x = ci % r0, y = (ci / r0) % r1, z = ci / r0 / r1;
-        uint32_t* rec = out + 8ull * pack_cellv(pk, x, y, z);
-        rec[0] = c.x;
-        rec[1] = c.y;
-        const uint32_t n = c.y - c.x;
-        const uint32_t all = n >= 32u ? ~0u : (1u << n) - 1u;
-        for (uint32_t f = 0; f < 6; ++f) {
-            const uint32_t axis = f >> 1, toward_neg = f & 1u;
-            const uint32_t cc = axis == 0 ? x : (axis == 1 ? y : z), rr = axis == 0 ? r0 : (axis == 1 ? r1 : r2);
-            // the cell left: one step back against the ray's direction
-            const bool inside = toward_neg ? cc + 1u < rr : cc > 0u;
-            uint32_t m = all;
-            if (inside && n > 0u && n <= 32u) {
-                const uint32_t step = axis == 0 ? 1u : (axis == 1 ? r0 : r0 * r1);
-                const uint2 pc = cells[toward_neg ? ci + step : ci - step];
-                for (uint32_t k = 0; k < n; ++k)
-                    for (uint32_t q = pc.x; q < pc.y; ++q)
-                        if (same_tri(pos, c.x + k, q)) {
-                            m &= ~(1u << k);
-                            break;
-                        }
-            }
-            rec[2 + f] = m;
-        }
-    }
-}
-
-// Park release statistic (context_release): over the occupied cells of the
-// packed records, how many (cell, entry face) masks are 0 -- out[0] masks
-// of occupied cells, out[1] zero masks among them.
-__global__ __launch_bounds__(kBlock) void release_stat_kernel(const uint32_t* __restrict__ rec, uint64_t n,
-                                                              unsigned long long* __restrict__ out) {
-    unsigned long long faces = 0, zero = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
-        const uint32_t* r = rec + 8 * i;
-        if (r[1] > r[0]) {
-            faces += 6;
-            for (int f = 0; f < 6; ++f) zero += r[2 + f] == 0u ? 1 : 0;
-        }
-    }
-    faces = wave_sum(faces);
-    zero = wave_sum(zero);
-    if ((threadIdx.x & 63u) == 0) {
-        atomicAdd(&out[0], faces);
-        atomicAdd(&out[1], zero);
-    }
-}
-
-// The packed walks' layout (DdaV) and their cell records (cell32_kernel;
-// none beyond 16 GiB, or beyond 1 GiB and 16x the cells' own 8 B -- flat
-// grids whose narrow axis pack_layout widened: such a grid walks unpacked).
-constexpr uint64_t kCell32Max = 16ull << 30;
-constexpr double kRelMinFrac = 0.25;   // park release from this fraction of empty entry-face masks
-static int context_packed(zrt_context* c) {
-    const uint32_t* r = c->grid.resolution;
-    // brick-major words where the grid allows them and the primary's
-    // occupancy bricks are 4^3 (it reads them by pc >> 6); else field words
-    // (and the dense brick masks exist: trace_ray reads them by pc >> 6)
-    c->packed = pack_layout(r, c->pk, ZRT_PACK_BM && c->occ_shift == 2u && c->d_bmask != nullptr);
-    if (!c->packed) return ZRT_OK;
-    const uint64_t n = 1ull << (c->pk.b0 + c->pk.b1 + c->pk.b2);
-    if (32 * n > kCell32Max || (n > 16ull * c->ncells && 32 * n > (1ull << 30))) {
-        c->packed = false;
-        return ZRT_OK;
-    }
-    HIP_TRY(hipMalloc((void**)&c->d_cell32, 32 * n));
-    if (!pack_is_linear(r, c->pk)) HIP_TRY(hipMemsetAsync(c->d_cell32, 0, 32 * n, c->stream));
-    hipLaunchKernelGGL(cell32_kernel, dim3(std::min<uint32_t>((c->ncells + kBlock - 1) / kBlock, 16384)), dim3(kBlock),
-                       0, c->stream, c->d_cells, r[0], r[1], r[2], c->ncells, c->pk, c->d_pos,
-                       c->d_cell32);
-    HIP_TRY(hipGetLastError());
-    // the park release pays on scenes whose rays often park in a cell with
-    // nothing left to test for their entry face: r06q/r06r, alternating
-    // processes, images identical: Cornell box (65% of the occupied cells'
-    // entry faces empty) +7%, contest stand-in (29%) +3%, Sponza-scale
-    // stand-in (18%) -1.5% (profiles/r06/r06q_ab_park_release.log)
-    {
-        unsigned long long h[2] = {0, 0};
-        unsigned long long* d = nullptr;
-        HIP_TRY(hipMalloc((void**)&d, sizeof h));
-        hipError_t e = hipMemsetAsync(d, 0, sizeof h, c->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(release_stat_kernel, dim3(std::min<uint64_t>((n + kBlock - 1) / kBlock, 4096)),
-                               dim3(kBlock), 0, c->stream, (const uint32_t*)c->d_cell32, n, d);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(d);
-        HIP_TRY(e);
-        c->rel_frac = h[0] ? (double)h[1] / (double)h[0] : 0.0;
-        c->rel_on = c->rel_frac >= kRelMinFrac;
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return ZRT_OK;
-}
-
-// Back-face cull masks (escape.h bfc_cull): word pc * kBfcNBin + bin for
-// every packed cell word pc and cull bin, then one all-ones word.  Bit r of
-// a cell of 1..32 refs is cleared when ref begin + r cannot pass tri_ray's
-// determinant test for any direction of the bin; every other cell keeps all
-// ones.  stat[0]: ref bits of the cells of 1..32 refs over all bins, stat[1]:
-// those cleared, stat[2]: (such cell, bin) words, stat[3]: those left empty.
-__global__ __launch_bounds__(kBlock) void bfc_build_kernel(const uint32_t* __restrict__ rec, uint64_t ncell,
-                                                           const float* __restrict__ pos, uint32_t* __restrict__ out,
-                                                           unsigned long long* __restrict__ stat) {
-    const uint64_t total = ncell * kBfcNBin;
-    unsigned long long bits = 0, cleared = 0, words = 0, empty = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (uint64_t)gridDim.x * kBlock) {
-        const uint64_t pc = i / kBfcNBin;
-        const uint32_t bin = (uint32_t)(i - pc * kBfcNBin);
-        const uint32_t b = rec[8 * pc], n = rec[8 * pc + 1] - b;
-        uint32_t m = ~0u;
-        if (n >= 1u && n <= 32u) {
-            for (uint32_t r = 0; r < n; ++r) {
-                float e1[3], e2[3];
-                for (uint32_t k = 0; k < 3; ++k) {
-                    e1[k] = __uint_as_float(tri_word(pos, b + r, 3 + k));
-                    e2[k] = __uint_as_float(tri_word(pos, b + r, 6 + k));
-                }
-                if (bfc_cull(e1, e2, bin)) m &= ~(1u << r);
-            }
-            const uint32_t all = n == 32u ? ~0u : (1u << n) - 1u;
-            bits += n;
-            cleared += n - (uint32_t)__popc(m & all);
-            words += 1;
-            empty += (m & all) == 0u ? 1 : 0;
-        }
-        if (out) out[i] = m;                       // (null: the statistic only)
-    }
-    if (out && blockIdx.x == 0 && threadIdx.x == 0) out[total] = ~0u;
-    bits = wave_sum(bits);
-    cleared = wave_sum(cleared);
-    words = wave_sum(words);
-    empty = wave_sum(empty);
-    if ((threadIdx.x & 63u) == 0) {
-        atomicAdd(&stat[0], bits);
-        atomicAdd(&stat[1], cleared);
-        atomicAdd(&stat[2], words);
-        atomicAdd(&stat[3], empty);
-    }
-}
-
-// The table is packed cells x kBfcNBin x 4 B (the contest stand-in at 128^3:
-// 0.8 GB at 4 x 4 bins per face, 3.2 GB at 8 x 8): built only if it fits
-// kBfcBudget over the contexts sharing the device, else the park kernel
-// renders without it.
-#ifndef ZRT_BFC_BUDGET_MB
-#define ZRT_BFC_BUDGET_MB 2048
-#endif
-constexpr uint64_t kBfcBudget = (uint64_t)ZRT_BFC_BUDGET_MB << 20;
-// Unasked, the park launches use the masks when they remove at least this
-// many triangle tests from a first-cell park on average (cleared bits per
-// (cell, bin) word over the cells of 1..32 refs): the park pays one more
-// gather for them.  Measured (r07b): Cornell box 0.36, -2.6%;
-// contest stand-in 1.78, +1.1%; Sponza-scale stand-in 2.39, +3.8%.
-#ifndef ZRT_BFC_MIN_CLEARED
-#define ZRT_BFC_MIN_CLEARED 1.0
-#endif
-constexpr double kBfcMinCleared = ZRT_BFC_MIN_CLEARED;
-// forced: build the table whatever the statistic says (ZRT_FLAG_BFCULL).
-static int context_bfcull(zrt_context* c, bool forced) {
-    if (c->d_bfc || !c->packed || !c->d_cell32) return ZRT_OK;
-    const uint64_t n = 1ull << (c->pk.b0 + c->pk.b1 + c->pk.b2);
-    const uint64_t bytes = 4ull * (n * kBfcNBin + 1);
-    if (bytes > kBfcBudget / std::max<uint32_t>(c->mem_share, 1u)) return ZRT_OK;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b / 4 < bytes) return ZRT_OK;
-    // one pass for the statistic alone (no table), one that writes the table
-    // if the scene uses it
-    unsigned long long* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, 4 * sizeof(unsigned long long)));
-    const uint64_t blocks = (n * kBfcNBin + kBlock - 1) / kBlock;
-    auto pass = [&](uint32_t* out, unsigned long long* h) -> hipError_t {
-        hipError_t e = hipMemsetAsync(d, 0, 4 * sizeof(unsigned long long), c->stream);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(bfc_build_kernel, dim3((uint32_t)std::min<uint64_t>(blocks, 1u << 16)), dim3(kBlock), 0,
-                           c->stream, (const uint32_t*)c->d_cell32, n, (const float*)c->d_pos, out, d);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(h, d, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
-            return e;
-        return hipStreamSynchronize(c->stream);
-    };
-    unsigned long long h[4] = {0, 0, 0, 0};
-    hipError_t e = hipSuccess;
-    if (!c->bfc_stat) {
-        e = pass(nullptr, h);
-        if (e == hipSuccess) {
-            c->bfc_stat = true;
-            c->bfc_frac = h[0] ? (double)h[1] / (double)h[0] : 0.0;
-            c->bfc_cleared = h[2] ? (double)h[1] / (double)h[2] : 0.0;
-            c->bfc_on = c->bfc_cleared >= kBfcMinCleared;
-            if (getenv("ZRT_WF_DEBUG"))
-                fprintf(stderr, "{\"zrt_bfcull\": {\"bytes\": %llu, \"bins\": %u, \"cleared_frac\": %.4f, "
-                        "\"cleared_per_word\": %.4f, \"empty_word_frac\": %.4f, \"on\": %d}}\n",
-                        (unsigned long long)bytes, kBfcNBin, c->bfc_frac, c->bfc_cleared,
-                        h[2] ? (double)h[3] / (double)h[2] : 0.0, c->bfc_on ? 1 : 0);
-        }
-    }
-    uint32_t* tab = nullptr;
-    if (e == hipSuccess && (c->bfc_on || forced)) {
-        e = hipMalloc((void**)&tab, bytes);
-        if (e == hipSuccess) e = pass(tab, h);
-        if (e != hipSuccess && tab) (void)hipFree(tab);
-    }
-    (void)hipFree(d);
-    HIP_TRY(e);
-    if (tab) {
-        c->d_bfc = tab;
-        c->bfc_bytes = bytes;
-    }
-    return ZRT_OK;
-}
-
-static int context_counters(zrt_context* c) {
-    StageClock sc;
-    int rc = context_packed(c);
-    if (rc != ZRT_OK) return rc;
-    sc.mark(c, "cell records (cell32_kernel)");
-    HIP_TRY(hipMalloc((void**)&c->d_counter, 64));
-    HIP_TRY(hipMalloc((void**)&c->d_stats, 512));
-    return ZRT_OK;
-}
-
-static int context_init(zrt_context* c, const zrt_scene* s) {
-    int rc = context_base(c);
-    if (rc != ZRT_OK) return rc;
-    c->grid = s->grid;
-    c->ncells = s->num_cells;
-    c->nrefs = s->num_triangles;
-    c->nmat = s->num_materials;
-    c->mt_exact = needs_mt_exact(s->triangles_pos, 9ull * s->num_triangles, 9u, 3u, 0x1p62f);
-    HIP_TRY(hipMalloc((void**)&c->d_cells, 8ull * c->ncells));
-    HIP_TRY(copy_sync(c->d_cells, s->cells, 8ull * c->ncells, hipMemcpyHostToDevice, c->stream));
-    const size_t nr = std::max<size_t>(c->nrefs, 1);
-    std::vector<float> pos(kTriFloats * nr, 0.0f);
-    std::vector<float4> dat(4 * nr);
-    for (uint32_t i = 0; i < c->nrefs; ++i) {
-        const float* q = s->triangles_pos + 9ull * i;
-        float* o = pos.data() + (size_t)kTriFloats * i;
-        memcpy(o, q, 12); memcpy(o + 4, q + 3, 12); memcpy(o + 8, q + 6, 12);
-        float tmp[16];
-        memcpy(tmp, s->triangles_data + 15ull * i, 15 * sizeof(float));
-        memcpy(&tmp[15], &s->triangles_material[i], 4);
-        memcpy(&dat[4 * i], tmp, 64);
-    }
-    HIP_TRY(hipMalloc((void**)&c->d_pos, pos.size() * sizeof(float)));
-    HIP_TRY(copy_sync(c->d_pos, pos.data(), pos.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMalloc((void**)&c->d_data, dat.size() * sizeof(float4)));
-    HIP_TRY(copy_sync(c->d_data, dat.data(), dat.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    if ((rc = context_materials(c, s)) != ZRT_OK) return rc;
-    return context_occupancy(c, s->cells);
-}
-
-// Materials, texels, ziggurat tables (stage3.zig:125-129, Zig std ziggurat).
-static int context_materials(zrt_context* c, const zrt_scene* s) {
-    c->nmat = s->num_materials;
-    std::vector<DevMat> mats(c->nmat);
-    for (uint32_t m = 0; m < c->nmat; ++m) {
-        const zrt_texture* t[3] = {&s->materials[m].base_color, &s->materials[m].emissive,
-                                   &s->materials[m].transparency};
-        for (int k = 0; k < 3; ++k) {
-            DevTex& d = mats[m].tex[k];
-            d.off = (uint32_t)t[k]->offset;
-            d.w = t[k]->w; d.h = t[k]->h;
-            d.umin = t[k]->u_min; d.umax = t[k]->u_max;
-            d.vmin = t[k]->v_min; d.vmax = t[k]->v_max;
-            d.pad = 0;
-            dev_tex_inline(d, s->texels, k < 2 ? 3 : 1);
-        }
-    }
-    StageClock sc;
-    HIP_TRY(hipMalloc((void**)&c->d_mats, mats.size() * sizeof(DevMat)));
-    HIP_TRY(copy_sync(c->d_mats, mats.data(), mats.size() * sizeof(DevMat), hipMemcpyHostToDevice, c->stream));
-    sc.mark(c, "materials");
-    HIP_TRY(hipMalloc((void**)&c->d_texels, s->num_texel_floats * sizeof(float)));
-    HIP_TRY(copy_sync(c->d_texels, s->texels, s->num_texel_floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    sc.mark(c, "texels");
-    double zig[514];
-    zig_tables(zig, zig + 257);
-    sc.mark(c, "ziggurat tables (host)");
-    HIP_TRY(hipMalloc((void**)&c->d_zig, sizeof zig));
-    HIP_TRY(copy_sync(c->d_zig, zig, sizeof zig, hipMemcpyHostToDevice, c->stream));
-    sc.mark(c, "ziggurat upload");
-    return ZRT_OK;
-}
-
-// OccX blob layout for nb bricks (nbw 32-brick words) and `occupied` masks:
-// bits | u16 (1 + prefix) per word | (8-byte aligned) the zero mask + masks.
-static void occx_layout(uint64_t nbw, uint64_t occupied, uint64_t* moff, uint64_t* words) {
-    const uint64_t pw = (nbw + 1) / 2;                   // prefix words
-    *moff = (nbw + pw + 1) & ~1ull;
-    *words = *moff + 2 * (occupied + 1);
-}
-// u32 words of the LDS copy: 8-byte (bits, prefix) entries, then the masks
-static uint64_t occx_lds_words(uint64_t nbw, uint64_t moff, uint64_t words) {
-    return (2 * nbw + (words - moff) + 3) & ~3ull;
-}
-
-// Brick occupancy and OccX, from the host cells or (host_cells null) from
-// c->d_cells on the device; then the work counters.
-//  * OccX (the park kernel) is built on 4^3-cell bricks and used when it fits
-//    the LDS budget.
-//  * wf_kernel's brick bits sit in LDS beside 7 waves' worth of workgroups:
-//    4^3-cell bricks (4 KB of bits for a 128^3 grid, round 1's best) while
-//    the bits take at most kOccLdsMax bytes, coarser bricks (8^3, 16^3, ...:
-//    OR of the 4^3 ones) for larger grids -- result-invariant, an empty brick
-//    only lets the walk skip the range loads of its cells.
-#ifndef ZRT_OCC_LDS_KB
-#define ZRT_OCC_LDS_KB 16
-#endif
-#ifndef ZRT_OCC_SH0
-#define ZRT_OCC_SH0 2
-#endif
-constexpr uint64_t kOccLdsMax = (uint64_t)ZRT_OCC_LDS_KB << 10;
-
-__global__ __launch_bounds__(kBlock) void occ_coarsen_kernel(const uint32_t* __restrict__ bits4, uint32_t nb0,
-                                                             uint32_t nb1, uint32_t nb, uint32_t dsh, uint32_t cn0,
-                                                             uint32_t cn01, uint32_t* __restrict__ out) {
-    const uint32_t b = blockIdx.x * kBlock + threadIdx.x;
-    if (b >= nb || !((bits4[b >> 5] >> (b & 31u)) & 1u)) return;
-    const uint32_t bx = b % nb0, by = (b / nb0) % nb1, bz = b / (nb0 * nb1);
-    const uint32_t cb = (bz >> dsh) * cn01 + (by >> dsh) * cn0 + (bx >> dsh);
-    atomicOr(&out[cb >> 5], 1u << (cb & 31u));
-}
-
-// Coarse brick bits straight from the cells (device-built grids whose 4^3
-// bricks are too many for OccX): one thread per cell, atomicOr per non-empty one.
-__global__ __launch_bounds__(kBlock) void occ_cells_kernel(const uint2* __restrict__ cells, uint32_t r0, uint32_t r1,
-                                                           uint32_t ncells, uint32_t sh, uint32_t cn0, uint32_t cn01,
-                                                           uint32_t* __restrict__ out) {
-    for (uint32_t ci = blockIdx.x * kBlock + threadIdx.x; ci < ncells; ci += gridDim.x * kBlock) {
-        const uint2 c = cells[ci];
-        if (c.x >= c.y) continue;
-        const uint32_t x = ci % r0, y = (ci / r0) % r1, z = ci / r0 / r1;
-        const uint32_t cb = (z >> sh) * cn01 + (y >> sh) * cn0 + (x >> sh);
-        atomicOr(&out[cb >> 5], 1u << (cb & 31u));
-    }
-}
-
-// Escape table (escape.h): a summed-area table of cell occupancy, then one
-// thread per (4^3 brick, direction bin).
-__global__ __launch_bounds__(kBlock) void esc_sat_fill_kernel(const uint2* __restrict__ cells, uint32_t r0, uint32_t r1,
-                                                              uint32_t ncells, uint32_t n0, uint32_t n01,
-                                                              uint32_t* __restrict__ sat) {
-    for (uint32_t ci = blockIdx.x * kBlock + threadIdx.x; ci < ncells; ci += gridDim.x * kBlock) {
-        const uint2 c = cells[ci];
-        const uint32_t x = ci % r0, y = (ci / r0) % r1, z = ci / r0 / r1;
-        sat[(uint64_t)(z + 1) * n01 + (uint64_t)(y + 1) * n0 + x + 1] = c.x < c.y ? 1u : 0u;
-    }
-}
-// prefix sums along one axis of the (n0 x n1 x n2) volume: one thread per line
-__global__ __launch_bounds__(kBlock) void esc_sat_scan_kernel(uint32_t* __restrict__ sat, uint32_t n0, uint32_t n1,
-                                                              uint32_t n2, uint32_t axis) {
-    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
-    const uint64_t n01 = (uint64_t)n0 * n1;
-    uint64_t base, stride;
-    uint32_t len;
-    if (axis == 0) {
-        if (t >= n1 * n2) return;
-        base = (uint64_t)(t / n1) * n01 + (uint64_t)(t % n1) * n0; stride = 1; len = n0;
-    } else if (axis == 1) {
-        if (t >= n0 * n2) return;
-        base = (uint64_t)(t / n0) * n01 + t % n0; stride = n0; len = n1;
-    } else {
-        if (t >= n0 * n1) return;
-        base = t; stride = n01; len = n2;
-    }
-    uint32_t acc = 0;
-    for (uint32_t i = 0; i < len; ++i) {
-        acc += sat[base + i * stride];
-        sat[base + i * stride] = acc;
-    }
-}
-__global__ __launch_bounds__(kBlock) void esc_build_kernel(const uint32_t* __restrict__ sat, uint32_t r0, uint32_t r1,
-                                                           uint32_t r2, float cs0, float cs1, float cs2, uint32_t nb0,
-                                                           uint32_t nb1, uint32_t nbr, uint32_t* __restrict__ esc) {
-    const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (t >= (uint64_t)nbr * kEscNBin) return;
-    const uint32_t br = (uint32_t)(t / kEscNBin), bin = (uint32_t)(t % kEscNBin);
-    const uint32_t res[3] = {r0, r1, r2};
-    const float cs[3] = {cs0, cs1, cs2};
-    const EscSat S{sat, r0 + 1u, (r0 + 1u) * (r1 + 1u)};
-    if (esc_compute(S, res, cs, br % nb0, (br / nb0) % nb1, br / (nb0 * nb1), bin))
-        atomicOr(&esc[(uint64_t)br * kEscWords + (bin >> 5)], 1u << (bin & 31u));
-}
-
-// Least fraction of set escape bits for the park launches to use the table.
-constexpr double kEscMinDensity = 0.12;
-// The escape table for a context with OccX (the park walk); none for grids
-// whose summed-area table would pass 2^28 entries (the walk then never stops
-// early, as before).
-// Primary frustum bounds (escape.h frustum_bound): one thread per 8x8 pixel
-// block of the w x h image.
-struct FrustumArgs {
-    uint32_t res[3];
-    float bmin[3], bmax[3], cs[3], org[3], llc[3], right[3], up[3];
-    uint32_t w, h, nbx, nby;
-    // this rank's tiles (capi.cpp tile_pixels: tile t of the tx-wide row-major
-    // grid belongs to rank t % nranks): tile edge in blocks, tiles per row,
-    // the rank and the rank count; the kernel bounds only their blocks.
-    // whole: one wave per block of the image, those of other ranks' tiles
-    // leaving at once (tiles larger than the image: fewer waves that way)
-    uint32_t tb, tx, rank, nranks, whole;
-};
-__global__ __launch_bounds__(kBlock) void frustum_kernel(const uint32_t* __restrict__ sat, const FrustumArgs a,
-                                                         float4* __restrict__ tlo) {
-    const EscSat S{sat, a.res[0] + 1u, (a.res[0] + 1u) * (a.res[1] + 1u)};
-    // one wave per block: lane l tests slices l, l + 64, ... of the same
-    // march (frustum_cone / frustum_slice), the wave takes the first and
-    // last occupied ones (a 1080p frame: 32 K waves of ~4 slices per lane
-    // instead of 32 K threads of ~200 dependent slices, 0.42 ms, r04eb2)
-    const uint32_t lane = threadIdx.x & 63u;
-    // wave i: block i % tb^2 (row-major in the tile) of this rank's tile i / tb^2
-    const uint32_t i = (blockIdx.x * kBlock + threadIdx.x) >> 6, bpt = a.tb * a.tb;
-    uint32_t bx, by;
-    if (a.whole) {                                         // (uniform over the wave)
-        if (i >= a.nbx * a.nby) return;
-        bx = i % a.nbx;
-        by = i / a.nbx;
-        if (((by / a.tb) * a.tx + bx / a.tb) % a.nranks != a.rank) return;
-    } else {
-        const uint32_t t = a.rank + (i / bpt) * a.nranks, k = i % bpt;
-        bx = (t % a.tx) * a.tb + k % a.tb;
-        by = (t / a.tx) * a.tb + k / a.tb;
-        if (bx >= a.nbx || by >= a.nby) return;
-    }
-    const uint32_t b = by * a.nbx + bx;
-    const FrustumCone q = frustum_cone(a.bmin, a.bmax, a.cs, a.org, a.llc, a.right, a.up, kFrustB * bx,
-                                       kFrustB * bx + kFrustB, kFrustB * by, kFrustB * by + kFrustB);
-    int first = 1 << 30, last = -1;
-    if (q.ok)
-        for (int it = (int)lane; it < (1 << 16) && !(it * q.ds > q.s_far); it += 64)
-            if (frustum_slice(S, q, a.res, a.bmin, a.cs, a.org, it)) {
-                first = min(first, it);
-                last = max(last, it);
-            }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        first = min(first, __shfl_xor(first, off));
-        last = max(last, __shfl_xor(last, off));
-    }
-    if (lane == 0) {
-        FrustumBound fb{0.0f, kInf, kInf, kInf};
-        if (q.ok) frustum_finish(q, first == (1 << 30) ? -1 : first, last, fb);
-        tlo[b] = make_float4(fb.lo, fb.hi, kInf, kInf);
-    }
-}
-
-// The summed-area table of cell occupancy (escape.h EscSat): kept in the
-// context for the escape table and the primary frustum bounds; none for grids
-// whose table would pass 2^28 entries (1 GiB).
-static int context_sat(zrt_context* c) {
-    const uint32_t* r = c->grid.resolution;
-    const uint64_t n0 = r[0] + 1ull, n1 = r[1] + 1ull, n2 = r[2] + 1ull;
-    if (n0 * n1 * n2 > (1ull << 28)) return ZRT_OK;
-    HIP_TRY(hipMalloc((void**)&c->d_sat, 4ull * n0 * n1 * n2));
-    HIP_TRY(hipMemsetAsync(c->d_sat, 0, 4ull * n0 * n1 * n2, c->stream));
-    hipLaunchKernelGGL(esc_sat_fill_kernel, dim3(4096), dim3(kBlock), 0, c->stream, c->d_cells, r[0], r[1], c->ncells,
-                       (uint32_t)n0, (uint32_t)(n0 * n1), c->d_sat);
-    const uint64_t lines[3] = {n1 * n2, n0 * n2, n0 * n1};
-    for (uint32_t a = 0; a < 3; ++a)
-        hipLaunchKernelGGL(esc_sat_scan_kernel, dim3((uint32_t)((lines[a] + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                           c->stream, c->d_sat, (uint32_t)n0, (uint32_t)n1, (uint32_t)n2, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return ZRT_OK;
-}
-
-static int context_escape(zrt_context* c) {
-    if (!ZRT_ESCAPE || !c->occx_ok || !c->d_sat) return ZRT_OK;
-    const uint32_t* r = c->grid.resolution;
-    const uint64_t nbr = (uint64_t)c->occx_nb[0] * c->occx_nb[1] * c->occx_nb[2];
-    HIP_TRY(hipMalloc((void**)&c->d_esc, 4ull * kEscWords * nbr));
-    HIP_TRY(hipMemsetAsync(c->d_esc, 0, 4ull * kEscWords * nbr, c->stream));
-    const uint64_t nthr = nbr * kEscNBin;
-    hipLaunchKernelGGL(esc_build_kernel, dim3((uint32_t)((nthr + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
-                       (const uint32_t*)c->d_sat, r[0], r[1], r[2], c->grid.cell_size[0], c->grid.cell_size[1],
-                       c->grid.cell_size[2], c->occx_nb[0], c->occx_nb[1], (uint32_t)nbr, c->d_esc);
-    HIP_TRY(hipGetLastError());
-    // Use it when enough of its bits are set: each walk trip of the park
-    // kernel then issues a table query per brick entered (~4% of a launch on
-    // scenes whose rays never escape, r04g), and the check itself costs ~1.5%.
-    // Measured (r04): contest stand-in 23% of the bits set, +8% frame rate;
-    // Cornell box 6%, -1.5%; Sponza-scale 1.6%, -4%.
-    std::vector<uint32_t> h(kEscWords * nbr);
-    HIP_TRY(hipMemcpyAsync(h.data(), c->d_esc, 4ull * kEscWords * nbr, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    uint64_t set = 0;
-    for (uint32_t x : h) set += (uint64_t)__builtin_popcount(x);
-    c->esc_density = (double)set / ((double)nbr * kEscNBin);
-    c->esc_on = c->esc_density >= kEscMinDensity;
-    return ZRT_OK;
-}
-
-static int context_occupancy(zrt_context* c, const uint32_t* host_cells) {
-    StageClock sc_occ;
-    const uint32_t* r = c->grid.resolution;
-    for (int i = 0; i < 3; ++i) c->occx_nb[i] = (r[i] + 3u) >> 2;
-    const uint64_t nb = (uint64_t)c->occx_nb[0] * c->occx_nb[1] * c->occx_nb[2];
-    // more than 2^24 4^3 bricks (> 2^30 cells): no OccX (24-bit brick
-    // indices), the bounces take the lane walk over the coarse bits below
-    const bool occx_possible = occx_usable(nb, 0, 0, 1);
-    const uint64_t nbw = (nb + 31) / 32;
-    uint32_t sh = ZRT_OCC_SH0;
-    auto words_at = [&](uint32_t k) {
-        const uint64_t n = (uint64_t)((r[0] + (1u << k) - 1) >> k) * ((r[1] + (1u << k) - 1) >> k) *
-                           ((r[2] + (1u << k) - 1) >> k);
-        return (n + 31) / 32;
-    };
-    while (words_at(sh) * 4 > kOccLdsMax) ++sh;
-    c->occ_shift = sh;
-    for (int i = 0; i < 3; ++i) c->occ_nb[i] = (r[i] + (1u << sh) - 1) >> sh;
-    c->occ_words = (uint32_t)words_at(sh);
-    HIP_TRY(hipMalloc((void**)&c->d_occ, 4ull * c->occ_words));
-    if (host_cells) {
-        std::vector<unsigned long long> mask(occx_possible ? nb : 0, 0ull);
-        std::vector<uint32_t> coarse(c->occ_words, 0u);
-        for (uint32_t z = 0; z < r[2]; ++z)
-            for (uint32_t y = 0; y < r[1]; ++y)
-                for (uint32_t x = 0; x < r[0]; ++x) {
-                    const uint64_t ci = ((uint64_t)z * r[1] + y) * r[0] + x;
-                    if (host_cells[2 * ci] < host_cells[2 * ci + 1]) {
-                        const uint64_t b = ((uint64_t)(z >> 2) * c->occx_nb[1] + (y >> 2)) * c->occx_nb[0] + (x >> 2);
-                        if (occx_possible) mask[b] |= 1ull << (((z & 3u) << 4) | ((y & 3u) << 2) | (x & 3u));
-                        const uint64_t cb = ((uint64_t)(z >> sh) * c->occ_nb[1] + (y >> sh)) * c->occ_nb[0] + (x >> sh);
-                        coarse[cb >> 5] |= 1u << (cb & 31);
-                    }
-                }
-        HIP_TRY(copy_sync(c->d_occ, coarse.data(), 4ull * c->occ_words, hipMemcpyHostToDevice, c->stream));
-        if (!occx_possible) {
-            c->occx_ok = false;
-            const int rc = context_sat(c);
-            if (rc != ZRT_OK) return rc;
-            return context_counters(c);
-        }
-        HIP_TRY(hipMalloc((void**)&c->d_bmask, nb * 8));
-        HIP_TRY(copy_sync(c->d_bmask, mask.data(), nb * 8, hipMemcpyHostToDevice, c->stream));
-        std::vector<uint32_t> bits(nbw, 0u);
-        std::vector<uint16_t> prefix(nbw, 0);
-        std::vector<unsigned long long> masks;
-        uint64_t run = 0;
-        for (uint64_t wd = 0; wd < nbw; ++wd) {
-            prefix[wd] = (uint16_t)std::min<uint64_t>(run + 1, 0xFFFF);
-            for (uint64_t b = wd * 32; b < std::min<uint64_t>(nb, wd * 32 + 32); ++b)
-                if (mask[b]) { bits[wd] |= 1u << (b & 31); masks.push_back(mask[b]); ++run; }
-        }
-        masks.insert(masks.begin(), 0ull);
-        uint64_t moff, words;
-        occx_layout(nbw, run, &moff, &words);
-        c->occx_ok = occx_usable(nb, run, occx_lds_words(nbw, moff, words) * 4, kOccxBudget);
-        if (c->occx_ok) {
-            std::vector<uint32_t> blob(words, 0u);
-            memcpy(blob.data(), bits.data(), nbw * 4);
-            memcpy(blob.data() + nbw, prefix.data(), nbw * 2);
-            memcpy(blob.data() + moff, masks.data(), masks.size() * 8);
-            c->occx_words = (uint32_t)words;
-            c->occx_nbw = (uint32_t)nbw;
-            c->occx_moff = (uint32_t)moff;
-            HIP_TRY(hipMalloc((void**)&c->d_occx, words * 4));
-            HIP_TRY(copy_sync(c->d_occx, blob.data(), words * 4, hipMemcpyHostToDevice, c->stream));
-        }
-    } else if (!occx_possible) {
-        HIP_TRY(hipMemsetAsync(c->d_occ, 0, 4ull * c->occ_words, c->stream));
-        hipLaunchKernelGGL(occ_cells_kernel, dim3(4096), dim3(kBlock), 0, c->stream, c->d_cells, r[0], r[1], c->ncells,
-                           sh, c->occ_nb[0], c->occ_nb[0] * c->occ_nb[1], c->d_occ);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        c->occx_ok = false;
-    } else {
-        // the blob for the largest possible occupancy, then the real size
-        uint64_t moff, words;
-        occx_layout(nbw, nb, &moff, &words);
-        // the scratch buffers are freed on every exit path (the blob belongs
-        // to the context as soon as it exists)
-        struct Scratch {
-            uint32_t* n = nullptr;
-            ~Scratch() {
-                if (n) (void)hipFree(n);
-            }
-        } tmp;
-        uint32_t* d_blob = nullptr;
-        HIP_TRY(hipMalloc((void**)&c->d_bmask, nb * 8));   // the dense masks stay (TraceParams::bmask)
-        HIP_TRY(hipMalloc((void**)&tmp.n, 4));
-        HIP_TRY(hipMalloc((void**)&d_blob, words * 4));
-        c->d_occx = d_blob;            // freed with the context from here on
-        unsigned long long* const d_masks = c->d_bmask;
-        uint32_t* const d_n = tmp.n;
-        HIP_TRY(hipMemsetAsync(d_blob, 0, words * 4, c->stream));
-        hipLaunchKernelGGL(occx_mask_kernel, dim3((uint32_t)((nb + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
-                           c->d_cells, r[0], r[1], r[2], c->occx_nb[0], c->occx_nb[1], (uint32_t)nb, d_masks, d_blob);
-        hipLaunchKernelGGL(occx_pack_kernel, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)d_blob,
-                           (uint32_t)nbw, (const unsigned long long*)d_masks,
-                           reinterpret_cast<uint16_t*>(d_blob + nbw),
-                           reinterpret_cast<unsigned long long*>(d_blob + moff), d_n);
-        hipError_t le = hipGetLastError();
-        if (sh == 2) {
-            HIP_TRY(hipMemcpyAsync(c->d_occ, d_blob, nbw * 4, hipMemcpyDeviceToDevice, c->stream));
-        } else if (sh < 2) {                   // (ZRT_OCC_SH0 builds) bricks finer than OccX's
-            HIP_TRY(hipMemsetAsync(c->d_occ, 0, 4ull * c->occ_words, c->stream));
-            hipLaunchKernelGGL(occ_cells_kernel, dim3(4096), dim3(kBlock), 0, c->stream, c->d_cells, r[0], r[1],
-                               c->ncells, sh, c->occ_nb[0], c->occ_nb[0] * c->occ_nb[1], c->d_occ);
-            if (le == hipSuccess) le = hipGetLastError();
-        } else {
-            HIP_TRY(hipMemsetAsync(c->d_occ, 0, 4ull * c->occ_words, c->stream));
-            hipLaunchKernelGGL(occ_coarsen_kernel, dim3((uint32_t)((nb + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                               c->stream, (const uint32_t*)d_blob, c->occx_nb[0], c->occx_nb[1], (uint32_t)nb, sh - 2u,
-                               c->occ_nb[0], c->occ_nb[0] * c->occ_nb[1], c->d_occ);
-            if (le == hipSuccess) le = hipGetLastError();
-        }
-        uint32_t run = 0;
-        HIP_TRY(hipMemcpyAsync(&run, d_n, 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(le);
-        occx_layout(nbw, run, &moff, &words);
-        c->occx_ok = occx_usable(nb, run, occx_lds_words(nbw, moff, words) * 4, kOccxBudget);
-        c->occx_words = (uint32_t)words;
-        c->occx_nbw = (uint32_t)nbw;
-        c->occx_moff = (uint32_t)moff;
-    }
-    // (the escape table itself is built by the first render whose frame is
-    // large enough to pay for it: context_escape)
-    sc_occ.mark(c, "occupancy bits + OccX");
-    const int rc = context_sat(c);
-    sc_occ.mark(c, "summed-area table");
-    if (rc != ZRT_OK) return rc;
-    return context_counters(c);
-}
-
-extern "C" int zrt_context_create(const zrt_scene* s, int device, zrt_context** out) {
-    if (!out) return ZRT_ERR_INVALID_ARG;
-    *out = nullptr;
-    int rc = validate_scene(s);
-    if (rc != ZRT_OK) return rc;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return ZRT_ERR_NO_DEVICE;
-    if (device < 0) {
-        if (hipGetDevice(&device) != hipSuccess) return ZRT_ERR_NO_DEVICE;
-    }
-    if (device >= n) return ZRT_ERR_NO_DEVICE;
-    DeviceGuard g(device);
-    zrt_context* c = new (std::nothrow) zrt_context();
-    if (!c) return ZRT_ERR_OUT_OF_MEMORY;
-    c->device = device;
-    rc = context_init(c, s);
-    if (rc != ZRT_OK) { zrt_context_destroy(c); return rc; }
-    *out = c;
-    return ZRT_OK;
-}
-
-// Device-built context: Geometry.build + bakeInto (stage2.zig:44-164) on the
-// GPU straight into the context's arrays (grid_build.hip), no host copy of the
-// baked scene.  Same render results as zrt_geometry_build + zrt_context_create.
-extern "C" int zrt_context_create_built(const float* positions, const float* normals, const float* texcoords,
-                                        const uint32_t* material, uint32_t num_triangles,
-                                        const uint32_t resolution[3], uint32_t num_materials,
-                                        const zrt_material* materials, const float* texels,
-                                        uint64_t num_texel_floats, int device, zrt_context** out) {
-    if (!out) return ZRT_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (!material) return ZRT_ERR_INVALID_ARG;
-    zrt_scene ms{};
-    ms.num_materials = num_materials;
-    ms.materials = materials;
-    ms.texels = texels;
-    ms.num_texel_floats = num_texel_floats;
-    int rc = validate_materials(&ms);
-    if (rc != ZRT_OK) return rc;
-    for (uint32_t i = 0; i < num_triangles; ++i)
-        if (material[i] >= num_materials) return ZRT_ERR_INVALID_ARG;
-    if (num_triangles && !positions) return ZRT_ERR_INVALID_ARG;
-    // vertex components of 2^61 or more (or infinite) may give edge
-    // components of 2^62 or more: the IEEE-division kernels (mt_exact)
-    const bool mt_exact = needs_mt_exact(positions, 9ull * num_triangles, 1u, 0u, 0x1p61f);
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return ZRT_ERR_NO_DEVICE;
-    if (device < 0) {
-        if (hipGetDevice(&device) != hipSuccess) return ZRT_ERR_NO_DEVICE;
-    }
-    if (device >= n) return ZRT_ERR_NO_DEVICE;
-    DeviceGuard g(device);
-    zrt_context* c = new (std::nothrow) zrt_context();
-    if (!c) return ZRT_ERR_OUT_OF_MEMORY;
-    c->device = device;
-    c->mt_exact = mt_exact;
-    StageClock sc;
-    rc = context_base(c);
-    if (rc == ZRT_OK) {
-        sc.mark(c, "stream + device properties");
-        zrt::Grid grid;
-        DeviceGeometry dg;
-        rc = grid_build_into_device(positions, normals, texcoords, material, num_triangles, resolution, c->stream,
-                                    &grid, &dg);
-        if (rc == ZRT_OK) sc.mark(c, "grid build + bake (grid_build.hip)");
-        if (rc == ZRT_OK) {
-            for (int i = 0; i < 3; ++i) {
-                c->grid.bbox_min[i] = (&grid.bbox.min.x)[i];
-                c->grid.bbox_max[i] = (&grid.bbox.max.x)[i];
-                c->grid.resolution[i] = grid.res[i];
-                c->grid.cell_size[i] = (&grid.cell_size.x)[i];
-            }
-            c->ncells = resolution[0] * resolution[1] * resolution[2];
-            c->nrefs = dg.refs;
-            c->d_cells = dg.cells;
-            c->d_data = dg.data;               // the context owns both from here (freed by destroy)
-            c->d_pos = reinterpret_cast<float*>(dg.pos);   // the device bake's 3 float4 per ref
-            if (rc == ZRT_OK && (rc = context_materials(c, &ms)) == ZRT_OK) {
-                sc.mark(c, "materials + texels");
-                rc = context_occupancy(c, nullptr);
-            }
-        }
-    }
-    if (rc != ZRT_OK) { zrt_context_destroy(c); return rc; }
-    *out = c;
-    return ZRT_OK;
-}
-
-// Empty cells and min/max refs of the non-empty ones (the CLI's grid log,
-// main.zig:117-118 + stage2 logging), reduced on the device.
-__global__ __launch_bounds__(kBlock) void grid_info_kernel(const uint2* __restrict__ cells, uint32_t ncells,
-                                                           uint32_t* __restrict__ out) {
-    uint32_t empty = 0, mn = 0xFFFFFFFFu, mx = 0;
-    for (uint32_t ci = blockIdx.x * kBlock + threadIdx.x; ci < ncells; ci += gridDim.x * kBlock) {
-        const uint2 c = cells[ci];
-        const uint32_t k = c.y - c.x;
-        if (!k) ++empty;
-        else { mn = min(mn, k); mx = max(mx, k); }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        empty += __shfl_xor(empty, o);
-        mn = min(mn, (uint32_t)__shfl_xor(mn, o));
-        mx = max(mx, (uint32_t)__shfl_xor(mx, o));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        atomicAdd(&out[0], empty);
-        atomicMin(&out[1], mn);
-        atomicMax(&out[2], mx);
-    }
-}
-
-extern "C" int zrt_context_grid_info(zrt_context* c, zrt_grid* grid, uint32_t info[4]) {
-    if (!c || !info) return ZRT_ERR_INVALID_ARG;
-    DeviceGuard g(c->device);
-    if (grid) *grid = c->grid;
-    uint32_t h[3] = {0u, 0xFFFFFFFFu, 0u};
-    HIP_TRY(hipMemcpyAsync(c->d_counter, h, sizeof h, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(grid_info_kernel, dim3(std::min<uint32_t>((c->ncells + kBlock - 1) / kBlock, 2048)),
-                       dim3(kBlock), 0, c->stream, c->d_cells, c->ncells, c->d_counter);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h, c->d_counter, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    info[0] = c->nrefs;
-    info[1] = h[0];
-    info[2] = h[1];
-    info[3] = h[2];
     return ZRT_OK;
 }
 
@@ -3944,6 +2728,266 @@ static uint64_t pass_samples(const zrt_context* c, const zrt_render_config* cfg,
     return s_pass;
 }
 
+// The packed pixel order of this rank (tile_pixels) in c->pix and d_pix,
+// cached across calls.
+static int rank_pixels(zrt_context* c, const zrt_camera* cam, const zrt_render_config* cfg, uint32_t nranks) {
+    const uint32_t key[5] = {cam->w, cam->h, cfg->tile_size ? cfg->tile_size : 64, cfg->rank, nranks};
+    if (c->pix_valid && memcmp(key, c->pix_key, sizeof key) == 0) return ZRT_OK;
+    uint32_t n = 0;
+    int rc = tile_pixels(key[0], key[1], key[2], key[3], key[4], nullptr, &n);
+    if (rc != ZRT_OK) return rc;
+    c->pix.resize(std::max<uint32_t>(n, 1));
+    tile_pixels(key[0], key[1], key[2], key[3], key[4], c->pix.data(), &n);
+    c->pix.resize(n);
+    if ((rc = grow(&c->d_pix, &c->pix_cap, std::max<size_t>(n, 1))) != ZRT_OK) return rc;
+    if (n) HIP_TRY(copy_sync(c->d_pix, c->pix.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    memcpy(c->pix_key, key, sizeof key);
+    c->pix_valid = true;
+    return ZRT_OK;
+}
+
+// A render's spp samples as npasses passes of s_pass samples (pass_samples) on
+// nsets pass sets, planned for plan_sets; lead: samples moved from the last pass
+// to the first; T: items of the first pass, the largest.
+struct PassSplit {
+    uint32_t spp, npasses, plan_sets, nsets, lead;
+    uint64_t s_pass, T;
+};
+static uint32_t pass_first(const PassSplit& sp, uint32_t pass) {
+    return pass == 0 ? 0u : (uint32_t)(pass * sp.s_pass + sp.lead);
+}
+static uint32_t pass_count(const PassSplit& sp, uint32_t pass) {
+    return pass == 0 ? (uint32_t)std::min<uint64_t>(sp.spp, sp.s_pass + sp.lead)
+                     : (uint32_t)std::min<uint64_t>(sp.s_pass, sp.spp - pass_first(sp, pass));
+}
+// `big`: a frame of kSetsMinSamples samples or more; per_item: bytes of a
+// pass's buffers per item.  Holds the tuning builds' ZRT_SETS and ZRT_LEAD.
+static PassSplit split_passes(const zrt_context* c, const zrt_render_config* cfg, uint32_t P, bool counting, bool big,
+                              uint64_t per_item) {
+    PassSplit sp{};
+    const uint32_t spp = sp.spp = cfg->num_samples;
+    // small frames run one set: a second stream costs its first launches
+    // (the zrt CLI's 3-spp 1080p frame rendered in 30-39 vs 12.5-13.3 ms on a
+    // fresh process) and does not pay back (cfg3 at 3 spp, warm: 7.1 vs 6.8
+    // ms), while cfg2 (16.8 M samples) gains 10% (r02c4)
+    uint32_t want_sets = big ? kPassSets : 1u;
+#if defined(ZRT_SWEEP) || defined(ZRT_SETS_ENV)
+    if (const char* e = getenv("ZRT_SETS")) want_sets = (uint32_t)std::max(1, std::min((int)kMaxPassSets, atoi(e)));
+#endif
+    size_t held = 16ull * c->out_cap + c->bfc_bytes;   // (the cull masks: the split must not depend on them)
+    for (const zrt_context::PassSet& ps : c->set) held += held_bytes(ps);
+    sp.s_pass = pass_samples(c, cfg, per_item, P, counting ? 1u : want_sets, held);
+    sp.npasses = (uint32_t)((spp + sp.s_pass - 1) / sp.s_pass);
+    // pass sets: pass p runs on set p % nsets, each set with its own stream
+    // and buffers, so one pass's launches fill the machine while another's
+    // drain (tails, the latency-bound shade kernel beside the park kernel):
+    // two sets cfg3 -5%, cfg2 -9%, cfg5 -7% frame time, images identical
+    // (r02c1, profiles/r02/r02c1_ab_two_streams.log)
+    sp.plan_sets = counting ? 1u : std::min<uint32_t>(sp.npasses, want_sets);
+    // ZRT_FLAG_ONE_SET: the same passes (split and lead as planned for the
+    // sets) run one after another on the context's stream, so no kernel
+    // overlaps another: exclusive kernel durations for bench.py's roofline,
+    // the same per-launch work as the frame it stands for
+    sp.nsets = (cfg->flags & ZRT_FLAG_ONE_SET) ? 1u : sp.plan_sets;
+    // lead: samples moved from the last pass to the first.  The second set's
+    // first primary launch waits for the first's (it fills every CU), so the
+    // second set ends behind the first unless the first has more work.
+    uint32_t lead_pct = sp.plan_sets > 1 ? kLeadPct : 0u;
+#if defined(ZRT_SWEEP) || defined(ZRT_SETS_ENV)
+    if (const char* e = getenv("ZRT_LEAD")) lead_pct = sp.plan_sets > 1 ? (uint32_t)std::max(0, std::min(50, atoi(e))) : 0u;
+#endif
+    const uint64_t last_n = spp - (uint64_t)(sp.npasses - 1) * sp.s_pass;     // samples of the last pass
+    const uint64_t cap_items = std::max<uint64_t>(1, 0x7FFFFF00ull / P);
+    sp.lead = sp.npasses > 1 ? (uint32_t)std::min<uint64_t>({sp.s_pass * lead_pct / 100, last_n - 1,
+                                                          cap_items - std::min(cap_items, sp.s_pass)})
+                             : 0u;
+    sp.T = (sp.s_pass + sp.lead) * P;
+    return sp;
+}
+
+// Primary frustum bounds (escape.h frustum_bound): one thread per 8x8 pixel
+// block of the w x h image.
+struct FrustumArgs {
+    uint32_t res[3];
+    float bmin[3], bmax[3], cs[3], org[3], llc[3], right[3], up[3];
+    uint32_t w, h, nbx, nby;
+    // this rank's tiles (capi.cpp tile_pixels: tile t of the tx-wide row-major
+    // grid belongs to rank t % nranks): tile edge in blocks, tiles per row,
+    // the rank and the rank count; the kernel bounds only their blocks.
+    // whole: one wave per block of the image, those of other ranks' tiles
+    // leaving at once (tiles larger than the image: fewer waves that way)
+    uint32_t tb, tx, rank, nranks, whole;
+};
+__global__ __launch_bounds__(kBlock) void frustum_kernel(const uint32_t* __restrict__ sat, const FrustumArgs a,
+                                                         float4* __restrict__ tlo) {
+    const EscSat S{sat, a.res[0] + 1u, (a.res[0] + 1u) * (a.res[1] + 1u)};
+    // one wave per block: lane l tests slices l, l + 64, ... of the same
+    // march (frustum_cone / frustum_slice), the wave takes the first and
+    // last occupied ones (a 1080p frame: 32 K waves of ~4 slices per lane
+    // instead of 32 K threads of ~200 dependent slices, 0.42 ms, r04eb2)
+    const uint32_t lane = threadIdx.x & 63u;
+    // wave i: block i % tb^2 (row-major in the tile) of this rank's tile i / tb^2
+    const uint32_t i = (blockIdx.x * kBlock + threadIdx.x) >> 6, bpt = a.tb * a.tb;
+    uint32_t bx, by;
+    if (a.whole) {                                         // (uniform over the wave)
+        if (i >= a.nbx * a.nby) return;
+        bx = i % a.nbx;
+        by = i / a.nbx;
+        if (((by / a.tb) * a.tx + bx / a.tb) % a.nranks != a.rank) return;
+    } else {
+        const uint32_t t = a.rank + (i / bpt) * a.nranks, k = i % bpt;
+        bx = (t % a.tx) * a.tb + k % a.tb;
+        by = (t / a.tx) * a.tb + k / a.tb;
+        if (bx >= a.nbx || by >= a.nby) return;
+    }
+    const uint32_t b = by * a.nbx + bx;
+    const FrustumCone q = frustum_cone(a.bmin, a.bmax, a.cs, a.org, a.llc, a.right, a.up, kFrustB * bx,
+                                       kFrustB * bx + kFrustB, kFrustB * by, kFrustB * by + kFrustB);
+    int first = 1 << 30, last = -1;
+    if (q.ok)
+        for (int it = (int)lane; it < (1 << 16) && !(it * q.ds > q.s_far); it += 64)
+            if (frustum_slice(S, q, a.res, a.bmin, a.cs, a.org, it)) {
+                first = min(first, it);
+                last = max(last, it);
+            }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        first = min(first, __shfl_xor(first, off));
+        last = max(last, __shfl_xor(last, off));
+    }
+    if (lane == 0) {
+        FrustumBound fb{0.0f, kInf, kInf, kInf};
+        if (q.ok) frustum_finish(q, first == (1 << 30) ? -1 : first, last, fb);
+        tlo[b] = make_float4(fb.lo, fb.hi, kInf, kInf);
+    }
+}
+
+// The primary frustum bounds of this camera into d_tlo, every render (inside
+// the timed region: one wave per 4x4 pixel block, 130 K waves at 1080p), and
+// the primary launch's pointers to them.
+static int launch_frustum(zrt_context* c, const zrt_camera* cam, const zrt_render_config* cfg, uint32_t nranks,
+                          TraceParams& tp) {
+    const uint32_t nbx = (cam->w + (1u << kFrustShift) - 1u) >> kFrustShift;
+    const uint32_t nby = (cam->h + (1u << kFrustShift) - 1u) >> kFrustShift;
+    const int rc = grow(&c->d_tlo, &c->tlo_cap, (size_t)nbx * nby);
+    if (rc != ZRT_OK) return rc;
+    FrustumArgs fa;
+    for (int k = 0; k < 3; ++k) {
+        fa.res[k] = c->grid.resolution[k];
+        fa.bmin[k] = c->grid.bbox_min[k];
+        fa.bmax[k] = c->grid.bbox_max[k];
+        fa.cs[k] = c->grid.cell_size[k];
+        fa.org[k] = cam->origin[k];
+        fa.llc[k] = cam->lower_left_corner[k];
+        fa.right[k] = cam->right[k];
+        fa.up[k] = cam->up[k];
+    }
+    fa.w = cam->w; fa.h = cam->h; fa.nbx = nbx; fa.nby = nby;
+    // only the blocks of this rank's tiles (a tile edge is a multiple of 8
+    // pixels, so of a block edge): an 8-rank frame bounds 1/8 of them
+    const uint32_t tile = cfg->tile_size ? cfg->tile_size : 64u;
+    fa.tb = tile >> kFrustShift;
+    fa.tx = (cam->w + tile - 1u) / tile;
+    fa.rank = cfg->rank;
+    fa.nranks = nranks;
+    const uint64_t ntiles = (uint64_t)fa.tx * ((cam->h + tile - 1u) / tile);
+    // (a rank with pixels owns tile `rank`, so ntiles > rank here)
+    const uint64_t per_tile = (ntiles - cfg->rank + nranks - 1u) / nranks * fa.tb * fa.tb;
+    fa.whole = per_tile > (uint64_t)nbx * nby ? 1u : 0u;
+    const uint64_t fthreads = (fa.whole ? (uint64_t)nbx * nby : per_tile) * 64u;
+    hipLaunchKernelGGL(frustum_kernel, dim3((uint32_t)((fthreads + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
+                       (const uint32_t*)c->d_sat, fa, c->d_tlo);
+    HIP_TRY(hipGetLastError());
+    tp.tlo = c->d_tlo;
+    tp.tlo_nbx = nbx;
+    return ZRT_OK;
+}
+
+// A render's stats words on stderr (debugging only): the counting build's walk
+// and test trip counts; ZRT_SWEEP builds: the kernels' cycle profiles.
+static int report_stats(const unsigned long long* hs, bool counting, bool park) {
+    if (getenv("ZRT_CELL_STATS") && counting)
+        fprintf(stderr, "{\"zrt_profile_cells\": {\"visited\": %llu, \"loaded\": %llu, \"non_empty\": %llu, "
+                "\"tests\": %llu, \"wave_cell_trips\": %llu, \"wave_tri_trips\": %llu, \"trips_with_tests\": %llu, "
+                "\"shared_rounds\": %llu}}\n",
+                hs[1], hs[4], hs[5], hs[2], hs[6], hs[7], hs[14], hs[15]);
+#ifdef ZRT_SWEEP
+    if (hs[60]) {       // the early append's reservation disagreed with shading (shade_entry_keep)
+        fprintf(stderr, "zrt: %llu shade continuations differ from their reservations\n", hs[60]);
+        return ZRT_ERR_HIP;
+    }
+    if (getenv("ZRT_PARK_PROFILE") && park)
+        fprintf(stderr, "{\"zrt_park_profile\": {\"cyc_shade_refill\": %llu, \"cyc_walk\": %llu, \"cyc_test\": %llu, "
+                "\"walk_iters\": %llu, \"walk_lanes\": %llu, \"test_rounds\": %llu, \"sub_rounds\": %llu, "
+                "\"pairs\": %llu, \"refill_rounds\": %llu, \"shaded_lanes\": %llu, \"cyc_drain\": %llu, "
+                "\"cyc_atomic\": %llu, \"cyc_setup\": %llu}}\n",
+                hs[16], hs[17], hs[18], hs[19], hs[20], hs[21], hs[22], hs[23], hs[24], hs[25], hs[26], hs[27], hs[28]);
+    if (getenv("ZRT_PARK_PROFILE") && park)
+        fprintf(stderr, "{\"zrt_walk_steps\": {\"lane_steps\": %llu, \"empty_brick_steps\": %llu, "
+                "\"empty_brick_entries\": %llu, \"escapes\": %llu, \"parked_tested\": %llu, \"parked_no_refs\": %llu, "
+                "\"released_early\": %llu, \"cyc_round_wait\": %llu}}\n",
+                hs[48], hs[49], hs[50], hs[51], hs[52], hs[53], hs[54], hs[55]);
+    if (getenv("ZRT_PARK_PROFILE") && !counting)
+        fprintf(stderr, "{\"zrt_primary_profile\": {\"cyc_walk\": %llu, \"cyc_shade\": %llu, \"cyc_fetch_append\": %llu}}\n",
+                hs[29], hs[30], hs[31]);
+    if (getenv("ZRT_PARK_PROFILE") && park)   // wf_shade_kernel phases: wave cycles, active-lane sums
+        fprintf(stderr, "{\"zrt_shade_profile\": {\"cyc\": [%llu, %llu, %llu, %llu, %llu, %llu, %llu, %llu], "
+                "\"lanes\": [%llu, %llu, %llu, %llu, %llu, %llu, %llu, %llu], \"phases\": [\"fetch\", \"records\", "
+                "\"tri_data\", \"texels\", \"u_draw\", \"pair_ziggurat\", \"tail\", \"append\"]}}\n",
+                hs[32], hs[33], hs[34], hs[35], hs[36], hs[37], hs[38], hs[39], hs[40], hs[41], hs[42], hs[43],
+                hs[44], hs[45], hs[46], hs[47]);
+#endif
+    return ZRT_OK;
+}
+
+// The end of a render, the stream waited for: the stats, the times of its
+// ne / 2 trace launches and of the kernels kt timed, the caller's outputs.
+static int finish_render(zrt_context* c, const zrt_outputs* outs, KernelTimes& kt, const PassSplit& sp, uint32_t P,
+                         bool counting, bool park, uint32_t ne, uint32_t launches, zrt_stats& st) {
+    unsigned long long hs[64];
+    HIP_TRY(copy_sync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+    const int rc = report_stats(hs, counting, park);
+    if (rc != ZRT_OK) return rc;
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev_begin, c->ev_end));
+    st.render_ms = ms;
+    const bool wf_debug = getenv("ZRT_WF_DEBUG") != nullptr;
+    for (uint32_t e = 0; e + 1 < ne; e += 2) {   // trace launches only (not resolve)
+        float t = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&t, c->ev_trace[e], c->ev_trace[e + 1]));
+        st.trace_kernel_ms += t;
+        if (wf_debug) fprintf(stderr, "{\"zrt_launch\": %u, \"ms\": %.3f}\n", e / 2, t);
+    }
+    st.trace_launches = launches;
+    for (size_t k = 0; k < kt.n; ++k) {
+        float t = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&t, c->ev_k[2 * k], c->ev_k[2 * k + 1]));
+        kt.kp.ms[c->ev_k_cls[k]] += t;
+    }
+    kt.kp.passes = sp.npasses;
+    kt.kp.sets = counting ? 1u : sp.nsets;
+    if (counting)
+        for (int k = 0; k < 4; ++k) kt.kp.primary_counts[k] = hs[8 + k];
+    c->prof = kt.kp;
+    st.segments = hs[0];
+    st.cells_visited = hs[1];
+    st.triangle_tests = hs[2];
+    st.hits = hs[3];
+    st.samples = (uint64_t)P * sp.spp;
+
+    if (outs && (outs->rgb_packed || outs->rgb_image)) {
+        std::vector<uint8_t> tmp;
+        uint8_t* dst = outs->rgb_packed;
+        if (!dst) { tmp.resize(3ull * P); dst = tmp.data(); }
+        HIP_TRY(copy_sync(dst, c->d_rgb, 3ull * P, hipMemcpyDeviceToHost, c->stream));
+        if (outs->rgb_image)
+            for (uint32_t q = 0; q < P; ++q) memcpy(outs->rgb_image + 3ull * c->pix[q], dst + 3ull * q, 3);
+    }
+    if (outs && outs->linear_packed)
+        HIP_TRY(copy_sync(outs->linear_packed, c->d_lin, 3ull * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    return ZRT_OK;
+}
+
 extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const zrt_render_config* cfg,
                                   const zrt_outputs* outs, zrt_stats* stats) {
     if (!c || !cam || !cfg) return ZRT_ERR_INVALID_ARG;
@@ -3958,21 +3002,8 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
     if (counting && !cfn) return ZRT_ERR_UNSUPPORTED;
     DeviceGuard g(c->device);
 
-    // packed pixel order of this rank (cached across calls)
-    const uint32_t key[5] = {cam->w, cam->h, cfg->tile_size ? cfg->tile_size : 64, cfg->rank, nranks};
-    if (!c->pix_valid || memcmp(key, c->pix_key, sizeof key) != 0) {
-        uint32_t n = 0;
-        int rc = tile_pixels(key[0], key[1], key[2], key[3], key[4], nullptr, &n);
-        if (rc != ZRT_OK) return rc;
-        c->pix.resize(std::max<uint32_t>(n, 1));
-        tile_pixels(key[0], key[1], key[2], key[3], key[4], c->pix.data(), &n);
-        c->pix.resize(n);
-        int r2 = grow(&c->d_pix, &c->pix_cap, std::max<size_t>(n, 1));
-        if (r2 != ZRT_OK) return r2;
-        if (n) HIP_TRY(copy_sync(c->d_pix, c->pix.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        memcpy(c->pix_key, key, sizeof key);
-        c->pix_valid = true;
-    }
+    int rc;
+    if ((rc = rank_pixels(c, cam, cfg, nranks)) != ZRT_OK) return rc;
     const uint32_t P = (uint32_t)c->pix.size();
     zrt_stats st{};
     if (P == 0) { if (stats) *stats = st; return ZRT_OK; }
@@ -3985,50 +3016,11 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
     // planes per slot ((a, has_e) 16 B + e 16 B with ZRT_PLANES16, else 24 B)
     // (+ the 16 B hit record the park kernel hands the shade kernel)
     const uint64_t per_item = counting ? 16ull : 96ull + 16ull + 16ull + (ZRT_PLANES16 ? 32ull : 24ull) * nb;
-    // small frames run one set: a second stream costs its first launches
-    // (the zrt CLI's 3-spp 1080p frame rendered in 30-39 vs 12.5-13.3 ms on a
-    // fresh process) and does not pay back (cfg3 at 3 spp, warm: 7.1 vs 6.8
-    // ms), while cfg2 (16.8 M samples) gains 10% (r02c4)
     const bool big = (uint64_t)P * cfg->num_samples >= kSetsMinSamples;
-    uint32_t want_sets = big ? kPassSets : 1u;
-#if defined(ZRT_SWEEP) || defined(ZRT_SETS_ENV)
-    if (const char* e = getenv("ZRT_SETS")) want_sets = (uint32_t)std::max(1, std::min((int)kMaxPassSets, atoi(e)));
-#endif
     const bool ktimes = (cfg->flags & ZRT_FLAG_KERNEL_TIMES) != 0;
-    size_t held = 16ull * c->out_cap + c->bfc_bytes;   // (the cull masks: the split must not depend on them)
-    for (const zrt_context::PassSet& ps : c->set) held += held_bytes(ps);
-    const uint64_t s_pass = pass_samples(c, cfg, per_item, P, counting ? 1u : want_sets, held);
-    const uint32_t npasses = (uint32_t)((spp + s_pass - 1) / s_pass);
-    // pass sets: pass p runs on set p % nsets, each set with its own stream
-    // and buffers, so one pass's launches fill the machine while another's
-    // drain (tails, the latency-bound shade kernel beside the park kernel):
-    // two sets cfg3 -5%, cfg2 -9%, cfg5 -7% frame time, images identical
-    // (r02c1, profiles/r02/r02c1_ab_two_streams.log)
-    const uint32_t plan_sets = counting ? 1u : std::min<uint32_t>(npasses, want_sets);
-    // ZRT_FLAG_ONE_SET: the same passes (split and lead as planned for the
-    // sets) run one after another on the context's stream, so no kernel
-    // overlaps another: exclusive kernel durations for bench.py's roofline,
-    // the same per-launch work as the frame it stands for
-    const uint32_t nsets = (cfg->flags & ZRT_FLAG_ONE_SET) ? 1u : plan_sets;
-    // lead: samples moved from the last pass to the first.  The second set's
-    // first primary launch waits for the first's (it fills every CU), so the
-    // second set ends behind the first unless the first has more work.
-    uint32_t lead_pct = plan_sets > 1 ? kLeadPct : 0u;
-#if defined(ZRT_SWEEP) || defined(ZRT_SETS_ENV)
-    if (const char* e = getenv("ZRT_LEAD")) lead_pct = plan_sets > 1 ? (uint32_t)std::max(0, std::min(50, atoi(e))) : 0u;
-#endif
-    const uint64_t last_n = spp - (uint64_t)(npasses - 1) * s_pass;     // samples of the last pass
-    const uint64_t cap_items = std::max<uint64_t>(1, 0x7FFFFF00ull / P);
-    const uint32_t lead = npasses > 1 ? (uint32_t)std::min<uint64_t>(
-                                            {s_pass * lead_pct / 100, last_n - 1, cap_items - std::min(cap_items, s_pass)})
-                                      : 0u;
-    auto pass_first = [&](uint32_t pass) -> uint32_t { return pass == 0 ? 0u : (uint32_t)(pass * s_pass + lead); };
-    auto pass_count = [&](uint32_t pass) -> uint32_t {
-        return pass == 0 ? (uint32_t)std::min<uint64_t>(spp, s_pass + lead)
-                         : (uint32_t)std::min<uint64_t>(s_pass, spp - pass_first(pass));
-    };
-    const uint64_t T = (s_pass + lead) * P;      // the first pass is the largest
-    int rc;
+    const PassSplit sp = split_passes(c, cfg, P, counting, big, per_item);
+    const uint32_t npasses = sp.npasses, nsets = sp.nsets;
+    const uint64_t T = sp.T;
     // the bounce launches (resolve_plan), after the budget was read: a first
     // big frame builds the escape table and the cull masks here
     LaunchPlan pl;
@@ -4090,7 +3082,7 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
                    (counting && shortfall("counting output", c->d_out, c->out_cap, T));
         for (uint32_t k = 1; k < nsets && !counting && !bad; ++k) bad = !c->set[k].stream || !c->set[k].ev_join;
         for (uint32_t pass = 0; pass < npasses && !bad; ++pass)
-            bad = (uint64_t)pass_count(pass) * P > T || pass_first(pass) + pass_count(pass) > spp;
+            bad = (uint64_t)pass_count(sp, pass) * P > T || pass_first(sp, pass) + pass_count(sp, pass) > spp;
         if (bad) return ZRT_ERR_INVALID_ARG;
     }
 
@@ -4130,42 +3122,9 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
     // primary launch: frames of 2^23 samples or more (a 3-spp 1080p frame's
     // primary takes ~0.5 ms: break-even)
     if (ZRT_FRUSTUM && c->d_sat && !counting && pl.packed && !(cfg->flags & ZRT_FLAG_NO_FRUSTUM) &&
-        ((uint64_t)P * cfg->num_samples >= kFrustumMinSamples || (cfg->flags & ZRT_FLAG_FRUSTUM))) {
-        // the primary frustum bounds of this camera, every render (inside the
-        // timed region: one wave per 4x4 pixel block, 130 K waves at 1080p)
-        const uint32_t nbx = (cam->w + (1u << kFrustShift) - 1u) >> kFrustShift;
-        const uint32_t nby = (cam->h + (1u << kFrustShift) - 1u) >> kFrustShift;
-        if ((rc = grow(&c->d_tlo, &c->tlo_cap, (size_t)nbx * nby)) != ZRT_OK) return rc;
-        FrustumArgs fa;
-        for (int k = 0; k < 3; ++k) {
-            fa.res[k] = c->grid.resolution[k];
-            fa.bmin[k] = c->grid.bbox_min[k];
-            fa.bmax[k] = c->grid.bbox_max[k];
-            fa.cs[k] = c->grid.cell_size[k];
-            fa.org[k] = cam->origin[k];
-            fa.llc[k] = cam->lower_left_corner[k];
-            fa.right[k] = cam->right[k];
-            fa.up[k] = cam->up[k];
-        }
-        fa.w = cam->w; fa.h = cam->h; fa.nbx = nbx; fa.nby = nby;
-        // only the blocks of this rank's tiles (a tile edge is a multiple of 8
-        // pixels, so of a block edge): an 8-rank frame bounds 1/8 of them
-        const uint32_t tile = cfg->tile_size ? cfg->tile_size : 64u;
-        fa.tb = tile >> kFrustShift;
-        fa.tx = (cam->w + tile - 1u) / tile;
-        fa.rank = cfg->rank;
-        fa.nranks = nranks;
-        const uint64_t ntiles = (uint64_t)fa.tx * ((cam->h + tile - 1u) / tile);
-        // (a rank with pixels owns tile `rank`, so ntiles > rank here)
-        const uint64_t per_tile = (ntiles - cfg->rank + nranks - 1u) / nranks * fa.tb * fa.tb;
-        fa.whole = per_tile > (uint64_t)nbx * nby ? 1u : 0u;
-        const uint64_t fthreads = (fa.whole ? (uint64_t)nbx * nby : per_tile) * 64u;
-        hipLaunchKernelGGL(frustum_kernel, dim3((uint32_t)((fthreads + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
-                           (const uint32_t*)c->d_sat, fa, c->d_tlo);
-        HIP_TRY(hipGetLastError());
-        tp.tlo = c->d_tlo;
-        tp.tlo_nbx = nbx;
-    }
+        ((uint64_t)P * cfg->num_samples >= kFrustumMinSamples || (cfg->flags & ZRT_FLAG_FRUSTUM)) &&
+        (rc = launch_frustum(c, cam, cfg, nranks, tp)) != ZRT_OK)
+        return rc;
     if (nsets > 1) {                           // the other sets start after the stats reset
         HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
         for (uint32_t k = 1; k < nsets; ++k) HIP_TRY(hipStreamWaitEvent(c->set[k].stream, c->ev_fork, 0));
@@ -4175,8 +3134,8 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
         // pass set pass % nsets: its own stream and buffers
         const zrt_context::PassSet& ps = c->set[counting ? 0u : pass % nsets];
         hipStream_t sm = counting ? c->stream : ps.stream;
-        const uint32_t s0 = pass_first(pass);
-        const uint32_t S = pass_count(pass);
+        const uint32_t s0 = pass_first(sp, pass);
+        const uint32_t S = pass_count(sp, pass);
         tp.s0 = s0;
         tp.total = S * P;
         tp.S = S;
@@ -4242,78 +3201,7 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
                                c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
 
-    unsigned long long hs[64];
-    HIP_TRY(copy_sync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
-    // diagnostics (debugging only): counting-build walk/test trip counts,
-    // per-launch device times
-    if (getenv("ZRT_CELL_STATS") && counting)
-        fprintf(stderr, "{\"zrt_profile_cells\": {\"visited\": %llu, \"loaded\": %llu, \"non_empty\": %llu, "
-                "\"tests\": %llu, \"wave_cell_trips\": %llu, \"wave_tri_trips\": %llu, \"trips_with_tests\": %llu, "
-                "\"shared_rounds\": %llu}}\n",
-                hs[1], hs[4], hs[5], hs[2], hs[6], hs[7], hs[14], hs[15]);
-#ifdef ZRT_SWEEP
-    if (hs[60]) {       // the early append's reservation disagreed with shading (shade_entry_keep)
-        fprintf(stderr, "zrt: %llu shade continuations differ from their reservations\n", hs[60]);
-        return ZRT_ERR_HIP;
-    }
-    if (getenv("ZRT_PARK_PROFILE") && park_next)
-        fprintf(stderr, "{\"zrt_park_profile\": {\"cyc_shade_refill\": %llu, \"cyc_walk\": %llu, \"cyc_test\": %llu, "
-                "\"walk_iters\": %llu, \"walk_lanes\": %llu, \"test_rounds\": %llu, \"sub_rounds\": %llu, "
-                "\"pairs\": %llu, \"refill_rounds\": %llu, \"shaded_lanes\": %llu, \"cyc_drain\": %llu, "
-                "\"cyc_atomic\": %llu, \"cyc_setup\": %llu}}\n",
-                hs[16], hs[17], hs[18], hs[19], hs[20], hs[21], hs[22], hs[23], hs[24], hs[25], hs[26], hs[27], hs[28]);
-    if (getenv("ZRT_PARK_PROFILE") && park_next)
-        fprintf(stderr, "{\"zrt_walk_steps\": {\"lane_steps\": %llu, \"empty_brick_steps\": %llu, "
-                "\"empty_brick_entries\": %llu, \"escapes\": %llu, \"parked_tested\": %llu, \"parked_no_refs\": %llu, "
-                "\"released_early\": %llu, \"cyc_round_wait\": %llu}}\n",
-                hs[48], hs[49], hs[50], hs[51], hs[52], hs[53], hs[54], hs[55]);
-    if (getenv("ZRT_PARK_PROFILE") && !counting)
-        fprintf(stderr, "{\"zrt_primary_profile\": {\"cyc_walk\": %llu, \"cyc_shade\": %llu, \"cyc_fetch_append\": %llu}}\n",
-                hs[29], hs[30], hs[31]);
-    if (getenv("ZRT_PARK_PROFILE") && park_next)   // wf_shade_kernel phases: wave cycles, active-lane sums
-        fprintf(stderr, "{\"zrt_shade_profile\": {\"cyc\": [%llu, %llu, %llu, %llu, %llu, %llu, %llu, %llu], "
-                "\"lanes\": [%llu, %llu, %llu, %llu, %llu, %llu, %llu, %llu], \"phases\": [\"fetch\", \"records\", "
-                "\"tri_data\", \"texels\", \"u_draw\", \"pair_ziggurat\", \"tail\", \"append\"]}}\n",
-                hs[32], hs[33], hs[34], hs[35], hs[36], hs[37], hs[38], hs[39], hs[40], hs[41], hs[42], hs[43],
-                hs[44], hs[45], hs[46], hs[47]);
-#endif
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev_begin, c->ev_end));
-    st.render_ms = ms;
-    const bool wf_debug = getenv("ZRT_WF_DEBUG") != nullptr;
-    for (uint32_t e = 0; e + 1 < ne; e += 2) {   // trace launches only (not resolve)
-        float t = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&t, c->ev_trace[e], c->ev_trace[e + 1]));
-        st.trace_kernel_ms += t;
-        if (wf_debug) fprintf(stderr, "{\"zrt_launch\": %u, \"ms\": %.3f}\n", e / 2, t);
-    }
-    st.trace_launches = launches;
-    for (size_t k = 0; k < kt.n; ++k) {
-        float t = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&t, c->ev_k[2 * k], c->ev_k[2 * k + 1]));
-        kt.kp.ms[c->ev_k_cls[k]] += t;
-    }
-    kt.kp.passes = npasses;
-    kt.kp.sets = counting ? 1u : nsets;
-    if (counting)
-        for (int k = 0; k < 4; ++k) kt.kp.primary_counts[k] = hs[8 + k];
-    c->prof = kt.kp;
-    st.segments = hs[0];
-    st.cells_visited = hs[1];
-    st.triangle_tests = hs[2];
-    st.hits = hs[3];
-    st.samples = (uint64_t)P * spp;
-
-    if (outs && (outs->rgb_packed || outs->rgb_image)) {
-        std::vector<uint8_t> tmp;
-        uint8_t* dst = outs->rgb_packed;
-        if (!dst) { tmp.resize(3ull * P); dst = tmp.data(); }
-        HIP_TRY(copy_sync(dst, c->d_rgb, 3ull * P, hipMemcpyDeviceToHost, c->stream));
-        if (outs->rgb_image)
-            for (uint32_t q = 0; q < P; ++q) memcpy(outs->rgb_image + 3ull * c->pix[q], dst + 3ull * q, 3);
-    }
-    if (want_lin)
-        HIP_TRY(copy_sync(outs->linear_packed, c->d_lin, 3ull * P * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = finish_render(c, outs, kt, sp, P, counting, park_next, ne, launches, st)) != ZRT_OK) return rc;
     if (stats) *stats = st;
     return ZRT_OK;
 }
@@ -4635,20 +3523,6 @@ extern "C" int zrt_context_radiance(zrt_context* c, const zrt_radiance_batch* b,
     return ZRT_OK;
 }
 
-void* zrt::context_stream(const zrt_context* c) { return c ? (void*)c->stream : nullptr; }
-
-void zrt::context_set_mem_share(zrt_context* c, uint32_t share) {
-    if (c) c->mem_share = std::max<uint32_t>(share, 1u);
-}
-
-int zrt::context_device_rgb(const zrt_context* c, const uint8_t** d_rgb, uint32_t* pixels, int* device) {
-    if (!c || !d_rgb || !pixels || !device) return ZRT_ERR_INVALID_ARG;
-    *d_rgb = c->d_rgb;
-    *pixels = c->pix_valid ? (uint32_t)c->pix.size() : 0u;
-    *device = c->device;
-    return ZRT_OK;
-}
-
 extern "C" int zrt_render(const zrt_scene* scene, const zrt_camera* cam, const zrt_render_config* cfg,
                           uint8_t* rgb_out, zrt_stats* stats) {
     if (!scene || !cam || !cfg || !rgb_out) return ZRT_ERR_INVALID_ARG;
@@ -4678,302 +3552,5 @@ extern "C" int zrt_render(const zrt_scene* scene, const zrt_camera* cam, const z
     o.rgb_image = rgb_out;
     rc = zrt_context_render(c, cam, &one, &o, stats);
     zrt_context_destroy(c);
-    return rc;
-}
-
-// ---------------------------------------------------------------------------
-// Device-function parity probes: the exact __device__ code paths of the
-// kernel, evaluated on the GPU for the Tier-1 tests.
-namespace {
-
-__global__ void probe_kernel(int which, const void* in, void* out, uint32_t n, const void* aux,
-                             const double* zig) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    switch (which) {
-        case ZRT_PROBE_TRIANGLE: {
-            const float* a = (const float*)in + 15ull * i;
-            float* o = (float*)out + 4ull * i;
-            const v3 v0 = ld3(a), v1 = ld3(a + 3), v2 = ld3(a + 6);
-            float t = 0, u = 0, v = 0;
-            const bool h = tri_ray(v0, sub(v1, v0), sub(v2, v0), ld3(a + 9), ld3(a + 12), &t, &u, &v);
-            o[0] = h ? 1.0f : 0.0f; o[1] = t; o[2] = u; o[3] = v;
-            break;
-        }
-        case ZRT_PROBE_TRIANGLE_EXACT: {  // the IEEE-division test of the mt_exact kernels
-            const float* a = (const float*)in + 15ull * i;
-            float* o = (float*)out + 4ull * i;
-            const v3 v0 = ld3(a), v1 = ld3(a + 3), v2 = ld3(a + 6);
-            float t = 0, u = 0, v = 0;
-            const bool h = tri_ray<true>(v0, sub(v1, v0), sub(v2, v0), ld3(a + 9), ld3(a + 12), &t, &u, &v);
-            o[0] = h ? 1.0f : 0.0f; o[1] = t; o[2] = u; o[3] = v;
-            break;
-        }
-        case ZRT_PROBE_TRIANGLE_FLAT: {   // wf_park_kernel's branch-free test
-            const float* a = (const float*)in + 15ull * i;
-            float* o = (float*)out + 4ull * i;
-            const v3 v0 = ld3(a), v1 = ld3(a + 3), v2 = ld3(a + 6);
-            float t = 0, u = 0, v = 0;
-            const bool h = tri_ray_flat(v0, sub(v1, v0), sub(v2, v0), ld3(a + 9), ld3(a + 12), &t, &u, &v);
-            o[0] = h ? 1.0f : 0.0f; o[1] = h ? t : 0.0f; o[2] = h ? u : 0.0f; o[3] = h ? v : 0.0f;
-            break;
-        }
-        case ZRT_PROBE_BBOX: {
-            const float* a = (const float*)in + 12ull * i;
-            float* o = (float*)out + 2ull * i;
-            Bbox b; b.min = ld3(a); b.max = ld3(a + 3);
-            float t = 0;
-            const bool h = bbox_ray(b, ld3(a + 6), ld3(a + 9), &t);
-            o[0] = h ? 1.0f : 0.0f; o[1] = h ? t : 0.0f;
-            break;
-        }
-        case ZRT_PROBE_DDA: {
-            // the kernels' own DDA: dda_init (Grid.traceRay) + DDA_STEP
-            // (Iterator.next).  out: [0] steps (-1: misses the bbox, -2: the
-            // incremental linear index disagreed with linearlizeCellIdx),
-            // [1..3] first cell, then per step (cell after next(), t): the
-            // reference's it.cell / it.next() pairs (linalg.zig:583-681)
-            const float* a = (const float*)in + 12ull * i;
-            const uint32_t* res = (const uint32_t*)aux;
-            float* o = (float*)out + (4ull + 4ull * 64) * i;
-            Bbox bb; bb.min = ld3(a); bb.max = ld3(a + 3);
-            const uint32_t r3[3] = {res[0], res[1], res[2]};
-            const Grid g = grid_init(bb, r3);
-            const float bmin[3] = {bb.min.x, bb.min.y, bb.min.z}, bmax[3] = {bb.max.x, bb.max.y, bb.max.z};
-            const float cs[3] = {g.cell_size.x, g.cell_size.y, g.cell_size.z};
-            Dda s;
-            // the park kernel's dda_init (dda_init_fq: the quotients from one
-            // reciprocal per axis where exact, else dda_init)
-            const float ics[3] = {1.0f / cs[0], 1.0f / cs[1], 1.0f / cs[2]};
-            bool cs_ok = true;
-            for (int k = 0; k < 3; ++k) cs_ok = cs_ok && fabsf(cs[k]) >= 0x1p-32f && fabsf(cs[k]) <= 0x1p32f;
-            const bool in = ZRT_FAST_QUOT ? dda_init_fq(bmin, bmax, r3, cs, ics, cs_ok, ld3(a + 6), ld3(a + 9), s)
-                                          : dda_init(bmin, bmax, r3, cs, ld3(a + 6), ld3(a + 9), s);
-            if (!in) { o[0] = -1.0f; break; }
-            GridK gk;
-            gk.rm0 = r3[0] - 1u; gk.rm1 = r3[1] - 1u; gk.rm2 = r3[2] - 1u;
-            gk.str1 = r3[0]; gk.str2 = r3[0] * r3[1];
-            o[1] = (float)s.c0; o[2] = (float)s.c1; o[3] = (float)s.c2;
-            int nsteps = 0;
-            bool lin_ok = true;
-            while (nsteps < 64) {
-                const uint32_t c0 = s.c0, c1 = s.c1, c2 = s.c2;
-                lin_ok = lin_ok && s.lin == (c2 * r3[1] + c1) * r3[0] + c0;
-                bool crossed;
-                float te;
-                DDA_STEP(s, gk, 0u, crossed, te);
-                (void)crossed;
-                float* e = o + 4 + 4 * nsteps;
-                // at the exit cell next() returns +inf and leaves the cell
-                if (te == kInf) { e[0] = (float)c0; e[1] = (float)c1; e[2] = (float)c2; }
-                else { e[0] = (float)s.c0; e[1] = (float)s.c1; e[2] = (float)s.c2; }
-                e[3] = te;
-                ++nsteps;
-                if (te == kInf) break;
-            }
-            o[0] = lin_ok ? (float)nsteps : -2.0f;
-            break;
-        }
-        case ZRT_PROBE_TO_RGB: {
-            const float* a = (const float*)in + 3ull * i;
-            uint8_t c[3];
-            to_rgb(ld3(a), c);
-            float* o = (float*)out + 3ull * i;
-            o[0] = c[0]; o[1] = c[1]; o[2] = c[2];
-            break;
-        }
-        case ZRT_PROBE_RNG_F32:
-        case ZRT_PROBE_RNG_NORM: {
-            const uint32_t* a = (const uint32_t*)in + 3ull * i;
-            Rng r;
-            r.s = path_key((uint64_t)a[0], a[1], a[2]);
-            float* o = (float*)out + 16ull * i;
-            for (int k = 0; k < 16; ++k)
-                o[k] = which == ZRT_PROBE_RNG_F32 ? rng_float(r) : (float)rng_norm64(r, zig, zig + 257);
-            break;
-        }
-        case ZRT_PROBE_EXP_LOG: {
-            const double x = ((const double*)in)[i];
-            double* o = (double*)out + 2ull * i;
-            o[0] = det_exp(x);
-            o[1] = det_log(x);
-            break;
-        }
-        case ZRT_PROBE_TEXTURE: {
-            // aux: int32 {chans, w, h, umin, umax, vmin, vmax, 0} then texels
-            const int32_t* h = (const int32_t*)aux;
-            DevTex t;
-            t.off = 0; t.w = h[1]; t.h = h[2]; t.umin = h[3]; t.umax = h[4]; t.vmin = h[5]; t.vmax = h[6];
-            const float* tex = (const float*)(h + 8);
-            dev_tex_inline(t, tex, h[0]);
-            const float* a = (const float*)in + 2ull * i;
-            float* o = (float*)out + 3ull * i;
-            if (h[0] == 3) {
-                const v3 r = sample3(tex, t, a[0], a[1]);
-                o[0] = r.x; o[1] = r.y; o[2] = r.z;
-            } else {
-                o[0] = sample1(tex, t, a[0], a[1]); o[1] = 0; o[2] = 0;
-            }
-            break;
-        }
-        case ZRT_PROBE_QUOT: {
-            const float* a = (const float*)in + 2ull * i;
-            float* o = (float*)out + 2ull * i;
-            o[0] = quot_rn(a[0], a[1], mt_inv_det<false>(a[1]));
-            o[1] = a[0] / a[1];
-            break;
-        }
-        case ZRT_PROBE_RECIP: {
-            const float x = ((const float*)in)[i];
-            float* o = (float*)out + 2ull * i;
-            o[0] = mt_inv_det<false>(x);
-            o[1] = mt_inv_det<true>(x);
-            break;
-        }
-        default:
-            break;
-    }
-}
-
-// ZRT_PROBE_RECIP_SWEEP: every float bit pattern of [lo, lo + count), the
-// short reciprocal against the IEEE division, bit for bit (NaN == NaN).
-__global__ __launch_bounds__(kBlock) void recip_sweep_kernel(uint32_t lo, uint32_t count, uint32_t* out) {
-    uint32_t bad = 0, first = 0xFFFFFFFFu;
-    // (a 64-bit index: count + the grid's stride can pass 2^32, and a wrapped
-    // 32-bit k would stay below count for ever)
-    for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < count; k += (uint64_t)gridDim.x * kBlock) {
-        const float x = __uint_as_float(lo + (uint32_t)k);
-        const float a = mt_inv_det<false>(x), b = mt_inv_det<true>(x);
-        const bool same = __float_as_uint(a) == __float_as_uint(b) || (a != a && b != b);
-        if (!same) { ++bad; first = min(first, lo + (uint32_t)k); }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        bad += __shfl_xor(bad, o);
-        first = min(first, (uint32_t)__shfl_xor(first, o));
-    }
-    if ((threadIdx.x & 63u) == 0 && bad) {
-        atomicAdd(&out[0], bad);
-        atomicMin(&out[1], first);
-    }
-}
-
-// ZRT_PROBE_QUOT_SWEEP: every significand pair (a in [1, 2), b = 1 + s /
-// 2^23 for s in [s0, s0 + ns)), quot_rn against the IEEE division, bit for bit.
-__global__ __launch_bounds__(kBlock) void quot_sweep_kernel(uint32_t s0, uint32_t ns, uint32_t* out) {
-    const uint64_t total = (uint64_t)ns << 23;
-    uint32_t bad = 0;
-    unsigned long long first = ~0ull;
-    for (uint64_t k = (uint64_t)blockIdx.x * kBlock + threadIdx.x; k < total; k += (uint64_t)gridDim.x * kBlock) {
-        const uint32_t ab = 0x3F800000u | (uint32_t)(k & 0x7FFFFFu);
-        const uint32_t bb = 0x3F800000u | (s0 + (uint32_t)(k >> 23));
-        const float a = __uint_as_float(ab), b = __uint_as_float(bb);
-        const float q = quot_rn(a, b, mt_inv_det<false>(b));
-        if (__float_as_uint(q) != __float_as_uint(a / b)) {
-            ++bad;
-            first = min(first, ((unsigned long long)bb << 32) | ab);
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        bad += __shfl_xor(bad, o);
-        const unsigned lo = __shfl_xor((unsigned)first, o), hi = __shfl_xor((unsigned)(first >> 32), o);
-        first = min(first, ((unsigned long long)hi << 32) | lo);
-    }
-    if ((threadIdx.x & 63u) == 0 && bad) {
-        atomicAdd(&out[0], bad);
-        atomicMin(reinterpret_cast<unsigned long long*>(out + 2), first);
-    }
-}
-
-}  // namespace
-
-extern "C" int zrt_probe(int which, const void* in, void* out, uint32_t n, const void* aux, int device) {
-    if (!in || !out || n == 0) return ZRT_ERR_INVALID_ARG;
-    size_t in_sz = 0, out_sz = 0, aux_sz = 0;
-    switch (which) {
-        case ZRT_PROBE_TRIANGLE:
-        case ZRT_PROBE_TRIANGLE_EXACT:
-        case ZRT_PROBE_TRIANGLE_FLAT: in_sz = 60; out_sz = 16; break;
-        case ZRT_PROBE_BBOX: in_sz = 48; out_sz = 8; break;
-        case ZRT_PROBE_DDA: in_sz = 48; out_sz = 4 * (4 + 4 * 64); aux_sz = 12; break;
-        case ZRT_PROBE_TO_RGB: in_sz = 12; out_sz = 12; break;
-        case ZRT_PROBE_RNG_F32:
-        case ZRT_PROBE_RNG_NORM: in_sz = 12; out_sz = 64; break;
-        case ZRT_PROBE_EXP_LOG: in_sz = 8; out_sz = 16; break;
-        case ZRT_PROBE_RECIP: in_sz = 4; out_sz = 8; break;
-        case ZRT_PROBE_RECIP_SWEEP: in_sz = 8; out_sz = 16; break;
-        case ZRT_PROBE_QUOT: in_sz = 8; out_sz = 8; break;
-        case ZRT_PROBE_QUOT_SWEEP: in_sz = 8; out_sz = 16; break;
-        case ZRT_PROBE_TEXTURE: {
-            in_sz = 8; out_sz = 12;
-            if (!aux) return ZRT_ERR_INVALID_ARG;
-            const int32_t* h = (const int32_t*)aux;
-            if ((h[0] != 1 && h[0] != 3) || h[1] <= 0 || h[2] <= 0) return ZRT_ERR_INVALID_ARG;
-            aux_sz = 32 + 4ull * h[0] * h[1] * h[2];
-            break;
-        }
-        default: return ZRT_ERR_INVALID_ARG;
-    }
-    if (aux_sz && !aux) return ZRT_ERR_INVALID_ARG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return ZRT_ERR_NO_DEVICE;
-    DeviceGuard g(device);
-    void *d_in = nullptr, *d_out = nullptr, *d_aux = nullptr;
-    double* d_zig = nullptr;
-    double zig[514];
-    zig_tables(zig, zig + 257);
-    int rc = ZRT_OK;
-    auto cleanup = [&]() {
-        if (d_in) (void)hipFree(d_in);
-        if (d_out) (void)hipFree(d_out);
-        if (d_aux) (void)hipFree(d_aux);
-        if (d_zig) (void)hipFree(d_zig);
-    };
-    auto run = [&]() -> int {
-        HIP_TRY(hipMalloc(&d_in, in_sz * n));
-        HIP_TRY(hipMalloc(&d_out, out_sz * n));
-        HIP_TRY(hipMalloc((void**)&d_zig, sizeof zig));
-        HIP_TRY(hipMemcpy(d_in, in, in_sz * n, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_zig, zig, sizeof zig, hipMemcpyHostToDevice));
-        if (aux_sz) {
-            HIP_TRY(hipMalloc(&d_aux, aux_sz));
-            HIP_TRY(hipMemcpy(d_aux, aux, aux_sz, hipMemcpyHostToDevice));
-        }
-        if (which == ZRT_PROBE_QUOT_SWEEP) {
-            // out per range: {mismatches, 0, first (a bits, b bits) as a u64 min}
-            const uint32_t* r = (const uint32_t*)in;
-            std::vector<uint32_t> init(4ull * n, 0u);
-            for (uint32_t k = 0; k < n; ++k) init[4ull * k + 2] = init[4ull * k + 3] = 0xFFFFFFFFu;
-            HIP_TRY(hipMemcpy(d_out, init.data(), out_sz * n, hipMemcpyHostToDevice));
-            for (uint32_t k = 0; k < n; ++k) {
-                if (r[2 * k + 1] == 0) continue;
-                if ((uint64_t)r[2 * k] + r[2 * k + 1] > (1ull << 23)) return ZRT_ERR_INVALID_ARG;
-                hipLaunchKernelGGL(quot_sweep_kernel, dim3(16384), dim3(kBlock), 0, 0, r[2 * k], r[2 * k + 1],
-                                   (uint32_t*)d_out + 4ull * k);
-                HIP_TRY(hipGetLastError());
-            }
-        } else if (which == ZRT_PROBE_RECIP_SWEEP) {
-            const uint32_t* r = (const uint32_t*)in;
-            std::vector<uint32_t> init(4ull * n, 0u);
-            for (uint32_t k = 0; k < n; ++k) init[4ull * k + 1] = 0xFFFFFFFFu;
-            HIP_TRY(hipMemcpy(d_out, init.data(), out_sz * n, hipMemcpyHostToDevice));
-            for (uint32_t k = 0; k < n; ++k) {
-                if (r[2 * k + 1] == 0) continue;
-                if ((uint64_t)r[2 * k] + r[2 * k + 1] > 0x100000000ull) return ZRT_ERR_INVALID_ARG;
-                const uint32_t blocks = std::min<uint32_t>(8192u, (r[2 * k + 1] + kBlock - 1) / kBlock);
-                hipLaunchKernelGGL(recip_sweep_kernel, dim3(blocks), dim3(kBlock), 0, 0, r[2 * k], r[2 * k + 1],
-                                   (uint32_t*)d_out + 4ull * k);
-                HIP_TRY(hipGetLastError());
-            }
-        } else {
-            hipLaunchKernelGGL(probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, which, d_in, d_out, n,
-                               d_aux, d_zig);
-        }
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(out, d_out, out_sz * n, hipMemcpyDeviceToHost));
-        return ZRT_OK;
-    };
-    rc = run();
-    cleanup();
     return rc;
 }

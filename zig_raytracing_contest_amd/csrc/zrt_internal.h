@@ -26,6 +26,42 @@ ZHD void dev_tex_inline(DevTex& d, const float* texels, int chans) {
     for (int k = 0; k < chans; ++k) memcpy(f[k], texels + d.off + k, 4);
 }
 
+#if defined(__HIPCC__)
+// Texture(T).sample (stage3.zig:111-123).  A 1x1 texture -- the dummy of
+// every material slot without an image (stage1.zig:411-425) -- has all four
+// texel indices 0 (any clamp, @mod by 1), so it loads its texel once and
+// runs the same bilinear arithmetic on it (bit-identical: x - x is not
+// folded, NaN/inf weights propagate as before), instead of the index
+// arithmetic and four loads per channel.
+#ifndef ZRT_TEX1
+#define ZRT_TEX1 1
+#endif
+__device__ __forceinline__ v3 sample3(const float* texels, const DevTex& t, float u, float v) {
+    const float* b = texels + t.off;
+    if (ZRT_TEX1 && t.w == 1 && t.h == 1) {
+        const float fu = tex_frac(u), fv = tex_frac(v);
+        // the texel, inlined in the descriptor (dev_tex_inline)
+        const float x = __int_as_float(t.umin), y = __int_as_float(t.umax), z = __int_as_float(t.vmin);
+        return mk(bilerp(x, x, x, x, fu, fv), bilerp(y, y, y, y, fu, fv), bilerp(z, z, z, z, fu, fv));
+    }
+    const TexCoords c = tex_coords(t.w, t.h, t.umin, t.umax, t.vmin, t.vmax, u, v);
+    v3 r;
+    r.x = bilerp(b[3 * c.i11 + 0], b[3 * c.i21 + 0], b[3 * c.i12 + 0], b[3 * c.i22 + 0], c.fu, c.fv);
+    r.y = bilerp(b[3 * c.i11 + 1], b[3 * c.i21 + 1], b[3 * c.i12 + 1], b[3 * c.i22 + 1], c.fu, c.fv);
+    r.z = bilerp(b[3 * c.i11 + 2], b[3 * c.i21 + 2], b[3 * c.i12 + 2], b[3 * c.i22 + 2], c.fu, c.fv);
+    return r;
+}
+__device__ __forceinline__ float sample1(const float* texels, const DevTex& t, float u, float v) {
+    const float* b = texels + t.off;
+    if (ZRT_TEX1 && t.w == 1 && t.h == 1) {               // the 1x1 dummy (see sample3)
+        const float x = __int_as_float(t.umin);
+        return bilerp(x, x, x, x, tex_frac(u), tex_frac(v));
+    }
+    const TexCoords c = tex_coords(t.w, t.h, t.umin, t.umax, t.vmin, t.vmax, u, v);
+    return bilerp(b[c.i11], b[c.i21], b[c.i12], b[c.i22], c.fu, c.fv);
+}
+#endif
+
 // Ziggurat NormDist tables (Zig std ziggurat.zig ZigTableGen), computed on the
 // host with the deterministic exp/log of zrt_math.h.
 void zig_tables(double zx[257], double zf[257]);

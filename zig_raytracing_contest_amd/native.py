@@ -571,7 +571,7 @@ def timed_kernels():
     return lib().zrt_timed_kernels().decode().split(",")
 
 
-# bytes per item the probe reads / writes (render.hip zrt_probe)
+# bytes per item the probe reads / writes (probe.hip zrt_probe)
 _PROBE_IO = {PROBE_TRIANGLE: (60, 16), PROBE_TRIANGLE_FLAT: (60, 16), PROBE_BBOX: (48, 8),
              PROBE_DDA: (48, 4 * DDA_PROBE_WIDTH), PROBE_TO_RGB: (12, 12), PROBE_RNG_F32: (12, 64),
              PROBE_RNG_NORM: (12, 64), PROBE_EXP_LOG: (8, 16), PROBE_TEXTURE: (8, 12),
