@@ -282,7 +282,7 @@ static int context_packed(zrt_context* c) {
     // brick-major words where the grid allows them and the primary's
     // occupancy bricks are 4^3 (it reads them by pc >> 6); else field words
     // (and the dense brick masks exist: trace_ray reads them by pc >> 6)
-    c->packed = pack_layout(r, c->pk, ZRT_PACK_BM && c->occ_shift == 2u && c->d_bmask != nullptr);
+    c->packed = pack_layout(r, c->pk, c->occ_shift == 2u && c->d_bmask != nullptr);
     if (!c->packed) return ZRT_OK;
     const uint64_t n = 1ull << (c->pk.b0 + c->pk.b1 + c->pk.b2);
     if (32 * n > kCell32Max || (n > 16ull * c->ncells && 32 * n > (1ull << 30))) {
@@ -610,11 +610,11 @@ static int context_sat(zrt_context* c) {
     return ZRT_OK;
 }
 
-// The escape table for a context with OccX (the park walk); none for grids
-// whose summed-area table would pass 2^28 entries (the walk then never stops
-// early, as before).
+// The escape table (escape.h) for a context with OccX (the park walk); none
+// for grids whose summed-area table would pass 2^28 entries (the walk then
+// never stops early, as before).
 int context_escape(zrt_context* c) {
-    if (!ZRT_ESCAPE || !c->occx_ok || !c->d_sat) return ZRT_OK;
+    if (!c->occx_ok || !c->d_sat) return ZRT_OK;
     const uint32_t* r = c->grid.resolution;
     const uint64_t nbr = (uint64_t)c->occx_nb[0] * c->occx_nb[1] * c->occx_nb[2];
     HIP_TRY(hipMalloc((void**)&c->d_esc, 4ull * kEscWords * nbr));

@@ -1,6 +1,7 @@
-// Uniform-grid DDA (Grid.traceRay / Grid.Iterator, linalg.zig:443-496) and
-// the exact empty-brick skip, shared by the HIP kernels (render.hip) and the
-// host-side check tests/cpp/dda_skip_check.cpp (g++ -ffp-contract=off).
+// Uniform-grid DDA (Grid.traceRay / Grid.Iterator, linalg.zig:443-496), its
+// packed walk states and the exact fast-forward, shared by the HIP kernels
+// (render.hip) and the host-side check tests/cpp/dda_walk_check.cpp
+// (g++ -ffp-contract=off).
 #pragma once
 #include <stdint.h>
 
@@ -43,7 +44,8 @@ ZHD bool dda_init(const float* bmin, const float* bmax, const uint32_t* res, con
     s.tn2 = t_hit + ((((float)(s.c2 + (n2 ? 0u : 1u))) * cs[2] - local.z) / d.z);
     s.lin = (s.c2 * res[1] + s.c1) * res[0] + s.c0;
     // bit 3: some crossing sequence starts at -inf / NaN (a zero direction
-    // component on a boundary), where BRICK_SKIP4's merge argument fails
+    // component on a boundary), where the merge argument of the fast-forward
+    // (DDAV_FFN) and of the escape table fails
     const bool ok = s.tn0 > -kInf && s.tn1 > -kInf && s.tn2 > -kInf && s.td0 == s.td0 && s.td1 == s.td1 &&
                     s.td2 == s.td2;
     s.neg |= ok ? 0u : 8u;
@@ -61,9 +63,6 @@ ZHD bool dda_init(const float* bmin, const float* bmax, const uint32_t* res, con
 // state is dda_init's; otherwise the lane recomputes it with dda_init.  The
 // check costs ~2 VALU per operand; 11-VALU divisions become 4-VALU quotients
 // (DESIGN 5.5e).
-#ifndef ZRT_FAST_QUOT
-#define ZRT_FAST_QUOT 1
-#endif
 #if defined(__HIPCC__)
 // (bits << 1) - 2 of a float: its magnitude's bits doubled, minus 2 -- zero
 // wraps to the top, so a minimum >= 2 * bits(2^-64) - 2 says "0 or >= 2^-64"
@@ -179,7 +178,7 @@ struct GridK {
 // mod 2^32; axis 0's is s_0) -- so a step selects them by axis instead of deriving them from
 // the sign bits and the grid constants (DDA_STEP: 44 VALU per step in the
 // r02m ISA, this: 29).  Same booleans, same f32 adds, same cells and T_EXIT
-// as DDA_STEP (tests/cpp/dda_skip_check.cpp compares the two step by step).
+// as DDA_STEP (tests/cpp/dda_walk_check.cpp compares the two step by step).
 struct DdaW {
     float tn0, tn1, tn2, td0, td1, td2;
     uint32_t c0, c1, c2;
@@ -227,22 +226,6 @@ ZHD void ddaw_from(const Dda& d, const GridK& g, DdaW& w) {
         (T_EXIT) = cc_ == ec_ ? kInf : tc_;                                          \
     } while (0)
 
-// Field-wise select of a walk state (a struct-level `c ? a : b` may become a
-// load through a selected pointer, see DDA_STEP).  Fields that are equal in
-// A and B (the per-axis constants) fold away.
-#define DDAW_SEL(D, C, A, B)                                                          \
-    do {                                                                             \
-        (D).tn0 = (C) ? (A).tn0 : (B).tn0; (D).tn1 = (C) ? (A).tn1 : (B).tn1;        \
-        (D).tn2 = (C) ? (A).tn2 : (B).tn2; (D).td0 = (C) ? (A).td0 : (B).td0;        \
-        (D).td1 = (C) ? (A).td1 : (B).td1; (D).td2 = (C) ? (A).td2 : (B).td2;        \
-        (D).c0 = (C) ? (A).c0 : (B).c0; (D).c1 = (C) ? (A).c1 : (B).c1;              \
-        (D).c2 = (C) ? (A).c2 : (B).c2; (D).lin = (C) ? (A).lin : (B).lin;           \
-        (D).e0 = (C) ? (A).e0 : (B).e0; (D).e1 = (C) ? (A).e1 : (B).e1;              \
-        (D).e2 = (C) ? (A).e2 : (B).e2; (D).s0 = (C) ? (A).s0 : (B).s0;              \
-        (D).s1 = (C) ? (A).s1 : (B).s1; (D).s2 = (C) ? (A).s2 : (B).s2;              \
-        (D).l1 = (C) ? (A).l1 : (B).l1; (D).l2 = (C) ? (A).l2 : (B).l2;              \
-    } while (0)
-
 // The packed walk state (the park walk and the primary lane walk, grids of
 // at most 1024 cells per axis): the cell in one word of per-grid fields,
 // pc = c0 | c1 << o1 | c2 << o2, field a B_a = max(2, ceil(log2 res_a)) bits
@@ -253,7 +236,7 @@ ZHD void ddaw_from(const Dda& d, const GridK& g, DdaW& w) {
 // (+-1 << o_a mod 2^32); the brick-crossing test is one xor and mask; the
 // exit test compares the axis's field with the packed exit cells pe.  Same
 // booleans, same f32 adds, same cells and T_EXIT as DDA_STEP
-// (tests/cpp/dda_skip_check.cpp, step by step on random grids).  A step past
+// (tests/cpp/dda_walk_check.cpp, step by step on random grids).  A step past
 // the exit (T_EXIT = +inf) may carry into the next field; the walk ends there
 // (the park kernel's speculative second step only reads a clamped brick).
 // Brick-major words (bm = 1; grids of 4 to 1024 cells per axis, powers of
@@ -263,6 +246,9 @@ ZHD void ddaw_from(const Dda& d, const GridK& g, DdaW& w) {
 // index and its low six bits the in-brick index (no multiply, no field
 // extracts: 8 VALU less per OccX lookup).  A field is then two bit runs, and
 // a step adds +-lowbit(f_a) across the gap (pk_add: 3 VALU more per step).
+// Against field words on every grid: r05ag, 2 rounds, images identical: cfg3
+// 6076 / 6088 vs 6005 / 5999 (+1.3%), cfg2 +2.4%, cfg5 +1.2%; the park walk
+// trip 179 -> 165 VALU (profiles/r05/r05ag_ab_brick_major.log).
 // The kernels take the layout as a template parameter (PK_BM, which the step
 // macros below name).
 struct PackK {
@@ -380,18 +366,15 @@ ZHD bool pack_is_linear(const uint32_t res[3], const PackK& k) {
     return !k.bm && res[0] == (1u << k.b0) && res[1] == (1u << k.b1) && res[2] == (1u << k.b2);
 }
 // Axis a's cell coordinate of a packed word
-ZHD uint32_t pack_coord(const PackK& k, uint32_t pc, int a) {
-    const uint32_t o = a == 0 ? 0u : (a == 1 ? k.o1 : k.o2), b = a == 0 ? k.b0 : (a == 1 ? k.b1 : k.b2);
-    if (k.bm) return ((pc >> (2 * a)) & 3u) | (((pc >> (a == 0 ? 6u : o)) & ((1u << (b - 2u)) - 1u)) << 2);
-    return (pc >> o) & (b >= 32u ? ~0u : (1u << b) - 1u);
-}
 template <bool BM>
 ZHD uint32_t pack_coordt(const PackK& k, uint32_t pc, int a) {
     const uint32_t o = a == 0 ? 0u : (a == 1 ? k.o1 : k.o2), b = a == 0 ? k.b0 : (a == 1 ? k.b1 : k.b2);
     if (BM) return ((pc >> (2 * a)) & 3u) | (((pc >> (a == 0 ? 6u : o)) & ((1u << (b - 2u)) - 1u)) << 2);
     return (pc >> o) & (b >= 32u ? ~0u : (1u << b) - 1u);
 }
-// The packed word with axis a's coordinate (field F) replaced by c
+// The packed word with axis a's coordinate (field F) replaced by c (a masked
+// add of n * D is NOT n steps on a brick-major field: n's bits above the low
+// run would land in the gap)
 template <bool BM>
 ZHD uint32_t pk_setc(const PackK& k, uint32_t pc, uint32_t f, int a, uint32_t c) {
     const uint32_t o = a == 0 ? 0u : (a == 1 ? k.o1 : k.o2);
@@ -402,15 +385,12 @@ ZHD uint32_t pk_setc(const PackK& k, uint32_t pc, uint32_t f, int a, uint32_t c)
 // fields; for brick-major ones the gap between the field's two runs is filled
 // with ones (forward: the carry crosses it) or cleared (backward: the borrow
 // does), the sum masked to F and the other fields kept.  No carry leaves the
-// field.  (pk_addn: n cells.)
-#ifndef ZRT_PK_BITOP3
-#define ZRT_PK_BITOP3 1
-#endif
+// field.
 template <bool BM>
 ZHD uint32_t pk_add(uint32_t pc, uint32_t f, uint32_t d) {
     if (!BM) return pc + d;
     const uint32_t s = (uint32_t)((int32_t)d >> 31);
-#if defined(__HIP_DEVICE_COMPILE__) && defined(__gfx950__) && ZRT_PK_BITOP3
+#if defined(__HIP_DEVICE_COMPILE__) && defined(__gfx950__)
     // (v_bitop3 is a gfx950 instruction: an ARCH= build for another target
     // takes the plain expression below)
     // g = (pc & f) | (~f & ~s) as ONE v_bitop3 (table index pc*4 + f*2 + s:
@@ -422,14 +402,6 @@ ZHD uint32_t pk_add(uint32_t pc, uint32_t f, uint32_t d) {
     const uint32_t g = (pc & f) | (~f & ~s);
 #endif
     return ((g + d) & f) | (pc & ~f);
-}
-// (a masked add of n * D is NOT n steps on a brick-major field: n's bits
-// above the low run would land in the gap; pk_setc writes the coordinate)
-template <bool BM>
-ZHD uint32_t pk_addn(uint32_t pc, uint32_t f, uint32_t n, uint32_t d) {
-    if (!BM) return pc + n * d;
-    for (uint32_t i = 0; i < n; ++i) pc = pk_add<true>(pc, f, d);
-    return pc;
 }
 struct DdaV {
     float tn0, tn1, tn2, td0, td1, td2;
@@ -492,7 +464,7 @@ ZHD float opaque_f(float x) {
 // select's condition into booleans materialised in VGPRs nor wrap a select
 // in a branch (the r03k ISA of DDAV_STEPX: 4 execz branches and 8
 // SGPR-to-VGPR copies per four-step trip).  On the host (the step check in
-// tests/cpp/dda_skip_check.cpp) a LaneM is one lane's bool: same booleans,
+// tests/cpp/dda_walk_check.cpp) a LaneM is one lane's bool: same booleans,
 // same selects.
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef uint64_t LaneM;
@@ -522,158 +494,28 @@ ZHD uint32_t lm_selu(LaneM m, uint32_t t, uint32_t f) { return m ? t : f; }
 // DDAV_STEPX on lane masks: A0 = t0<t1 && t0<t2, A1 = !(t0<t1) && t1<t2,
 // else axis 2 (DDA_STEP's booleans); FV0..FV2: the field masks (in VGPRs
 // for the park walk: a select between two SGPR operands needs a copy
-// first).  The core selects the step's axis quantities and updates the
-// crossing ts; FM: the axis's field mask, DP: its packed cell step.
-#define DDAV_STEPM_CORE(S, FV0, FV1, FV2, FM, DP, TC)                                \
-    const float t0_ = (S).tn0, t1_ = (S).tn1, t2_ = (S).tn2;                         \
-    const LaneM m01_ = lm_of(t0_ < t1_), m02_ = lm_of(t0_ < t2_), m12_ = lm_of(t1_ < t2_); \
-    const LaneM a0_ = lm_and(m01_, m02_);                                            \
-    const LaneM a1_ = lm_andn(m12_, m01_);                                           \
-    const LaneM a01_ = lm_or(a0_, a1_);                                              \
-    const float tc_ = lm_sel(a0_, t0_, lm_sel(a1_, t1_, t2_));                       \
-    const float dt_ = lm_sel(a0_, (S).td0, lm_sel(a1_, (S).td1, (S).td2));           \
-    const uint32_t FM = lm_selu(a0_, (FV0), lm_selu(a1_, (FV1), (FV2)));             \
-    const uint32_t DP = lm_selu(a0_, (S).d0, lm_selu(a1_, (S).d1, (S).d2));          \
-    (TC) = tc_;                                                                      \
-    const float un_ = tc_ + dt_;                                                     \
-    (S).tn0 = lm_sel(a0_, un_, t0_);                                                 \
-    (S).tn1 = lm_sel(a1_, un_, t1_);                                                 \
-    (S).tn2 = lm_sel(a01_, t2_, un_);
-// EXM: the lane mask of the lanes whose step's axis is at its exit cell
+// first).  It selects the step's axis quantities (fm_: the axis's field
+// mask, dp_: its packed cell step) and updates the crossing ts.  EXM: the
+// lane mask of the lanes whose step's axis is at its exit cell.
 #define DDAV_STEPM(S, FV0, FV1, FV2, EXM, TC)                                        \
     do {                                                                             \
-        DDAV_STEPM_CORE(S, FV0, FV1, FV2, fm_, dp_, TC)                              \
+        const float t0_ = (S).tn0, t1_ = (S).tn1, t2_ = (S).tn2;                     \
+        const LaneM m01_ = lm_of(t0_ < t1_), m02_ = lm_of(t0_ < t2_), m12_ = lm_of(t1_ < t2_); \
+        const LaneM a0_ = lm_and(m01_, m02_);                                        \
+        const LaneM a1_ = lm_andn(m12_, m01_);                                       \
+        const LaneM a01_ = lm_or(a0_, a1_);                                          \
+        const float tc_ = lm_sel(a0_, t0_, lm_sel(a1_, t1_, t2_));                   \
+        const float dt_ = lm_sel(a0_, (S).td0, lm_sel(a1_, (S).td1, (S).td2));       \
+        const uint32_t fm_ = lm_selu(a0_, (FV0), lm_selu(a1_, (FV1), (FV2)));        \
+        const uint32_t dp_ = lm_selu(a0_, (S).d0, lm_selu(a1_, (S).d1, (S).d2));     \
+        (TC) = tc_;                                                                  \
+        const float un_ = tc_ + dt_;                                                 \
+        (S).tn0 = lm_sel(a0_, un_, t0_);                                             \
+        (S).tn1 = lm_sel(a1_, un_, t1_);                                             \
+        (S).tn2 = lm_sel(a01_, t2_, un_);                                            \
         (EXM) = lm_of((((S).pc ^ (S).pe) & fm_) == 0u);                              \
-        (S).pc = pk_add<PK_BM>((S).pc, fm_, dp_);                                           \
+        (S).pc = pk_add<PK_BM>((S).pc, fm_, dp_);                                    \
     } while (0)
-// The same with DDAV_STEPX's per-lane outputs (the lane walk)
-#define DDAV_STEPMB(S, FV0, FV1, FV2, LOWM, CROSSED, EXITED, TC)                     \
-    do {                                                                             \
-        DDAV_STEPM_CORE(S, FV0, FV1, FV2, fm_, dp_, TC)                              \
-        const uint32_t pn_ = pk_add<PK_BM>((S).pc, fm_, dp_);                               \
-        (CROSSED) = (((S).pc ^ pn_) & ~(LOWM)) != 0u;                                \
-        (EXITED) = (((S).pc ^ (S).pe) & fm_) == 0u;                                  \
-        (S).pc = pn_;                                                                \
-    } while (0)
-#define DDAV_SEL(D, C, A, B)                                                          \
-    do {                                                                             \
-        (D).tn0 = (C) ? (A).tn0 : (B).tn0; (D).tn1 = (C) ? (A).tn1 : (B).tn1;        \
-        (D).tn2 = (C) ? (A).tn2 : (B).tn2; (D).td0 = (C) ? (A).td0 : (B).td0;        \
-        (D).td1 = (C) ? (A).td1 : (B).td1; (D).td2 = (C) ? (A).td2 : (B).td2;        \
-        (D).pc = (C) ? (A).pc : (B).pc; (D).pe = (C) ? (A).pe : (B).pe;              \
-        (D).d0 = (C) ? (A).d0 : (B).d0; (D).d1 = (C) ? (A).d1 : (B).d1;              \
-        (D).d2 = (C) ? (A).d2 : (B).d2;                                              \
-    } while (0)
-
-// Empty-brick skip, 4^3 bricks (occ_shift 2): the state Iterator.next would
-// reach at the step that leaves the current brick, computed at once.  Axis
-// a's crossings form the sequence T_a(1) = tn_a, T_a(j+1) = T_a(j) + td_a
-// (the same f32 adds the DDA does); Iterator.next always takes the smallest
-// head, ties to the higher axis (DDA_STEP's booleans), so the steps are the
-// merge of the three sequences ordered by (t, -axis).  The brick is left by
-// the first, in that order, of the brick-exit crossings E_a = T_a(m_a)
-// (m_a = cells to the brick face along a), and every other axis b has then
-// taken exactly the crossings T_b(j), j < m_b, that precede it.  Not used
-// with a -inf/NaN sequence (neg bit 3).  EXITED: the skip left the grid
-// (Iterator.next returned +inf there).  T_EXIT: the exit t of the last cell
-// passed = the largest of the passed cells' exit ts (the merge is
-// nondecreasing), +inf if EXITED: traceRay's break test (stage3.zig:179-182)
-// fires inside the skipped cells iff nearest <= T_EXIT, and they hold no
-// triangle, so the skip is exact for any nearest.
-#define SKIP_AXIS(S, G, A)                                                                    \
-    const bool n##A##_ = ((S).neg >> A) & 1u;                                                 \
-    const uint32_t lo##A##_ = (S).c##A & ~3u;                                                 \
-    const uint32_t hi##A##_ = zmin(lo##A##_ + 3u, (G).rm##A);                                  \
-    const uint32_t m##A##_ = n##A##_ ? (S).c##A - lo##A##_ + 1u : hi##A##_ - (S).c##A + 1u;   \
-    const bool out##A##_ = n##A##_ ? lo##A##_ == 0u : hi##A##_ == (G).rm##A;                  \
-    const float T##A##1_ = (S).tn##A;                                                         \
-    const float T##A##2_ = T##A##1_ + (S).td##A;                                              \
-    const float T##A##3_ = T##A##2_ + (S).td##A;                                              \
-    const float T##A##4_ = T##A##3_ + (S).td##A;                                              \
-    const float E##A##_ = m##A##_ == 1u ? T##A##1_                                            \
-                        : (m##A##_ == 2u ? T##A##2_ : (m##A##_ == 3u ? T##A##3_ : T##A##4_));
-#define SKIP_COUNT(S, A, TIE)                                                                 \
-    uint32_t k##A##_ = 0;                                                                     \
-    k##A##_ += (1u < m##A##_ && (T##A##1_ < ex_ || (T##A##1_ == ex_ && (TIE)))) ? 1u : 0u;     \
-    k##A##_ += (2u < m##A##_ && (T##A##2_ < ex_ || (T##A##2_ == ex_ && (TIE)))) ? 1u : 0u;     \
-    k##A##_ += (3u < m##A##_ && (T##A##3_ < ex_ || (T##A##3_ == ex_ && (TIE)))) ? 1u : 0u;     \
-    k##A##_ = x##A##_ ? m##A##_ : k##A##_;                                                    \
-    (S).tn##A = k##A##_ == 0u ? T##A##1_                                                      \
-              : (k##A##_ == 1u ? T##A##2_                                                     \
-              : (k##A##_ == 2u ? T##A##3_ : (k##A##_ == 3u ? T##A##4_ : T##A##4_ + (S).td##A))); \
-    (S).c##A = n##A##_ ? (S).c##A - k##A##_ : (S).c##A + k##A##_;
-#define BRICK_SKIP4(S, G, EXITED, T_EXIT)                                                     \
-    do {                                                                                      \
-        SKIP_AXIS(S, G, 0)                                                                    \
-        SKIP_AXIS(S, G, 1)                                                                    \
-        SKIP_AXIS(S, G, 2)                                                                    \
-        const bool x0_ = E0_ < E1_ && E0_ < E2_;                                              \
-        const bool x1_ = !(E0_ < E1_) && E1_ < E2_;                                           \
-        const bool x2_ = !x0_ && !x1_;                                                        \
-        const float ex_ = x0_ ? E0_ : (x1_ ? E1_ : E2_);                                      \
-        SKIP_COUNT(S, 0, false)                                                               \
-        SKIP_COUNT(S, 1, x0_)                                                                 \
-        SKIP_COUNT(S, 2, !x2_)                                                                \
-        (EXITED) = x0_ ? out0_ : (x1_ ? out1_ : out2_);                                       \
-        (T_EXIT) = (EXITED) ? kInf : ex_;                                                     \
-        (S).lin = (S).c2 * (G).str2 + (S).c1 * (G).str1 + (S).c0;                             \
-    } while (0)
-
-// BRICK_SKIP4 on the packed state (DdaV, PackK): the primary lane walk's
-// empty-brick skip.  Same merge argument: per axis a the cells left inside
-// the 4^3 brick (or to the grid exit, whichever is nearer) m1_a, the
-// brick-exit crossing E_a = T_a(m1_a + 1) from the same f32 adds, the exit
-// axis X = the first E_a in (t, -axis) order, and every other axis takes the
-// crossings T_b(j) that precede E_X in that order (ties to the higher axis,
-// as Iterator.next's booleans); axis X takes m1_X + 1.  The signs come from
-// the packed steps (d_a < 0 as u32 top bit).  Not used with a -inf/NaN
-// crossing sequence (Dda.neg bit 3).  EXITED / TC as DDAV_STEPX: the break
-// test nearest <= T_EXIT of the last skipped cell is EXITED || nearest <= TC
-// (tests/cpp/dda_skip_check.cpp checks it against the cell walk).
-#if defined(__HIP_DEVICE_COMPILE__)
-#define ZRT_UBFE(X, O, W) __builtin_amdgcn_ubfe((X), (O), (W))
-#else
-#define ZRT_UBFE(X, O, W) ((W) == 0u ? 0u : (((X) >> (O)) & (0xFFFFFFFFu >> (32u - (W)))))
-#endif
-#define SKIPV_AXIS(S, K, A)                                                                    \
-    const uint32_t c##A##_ = pack_coord((K), (S).pc, A);                                        \
-    const uint32_t xn##A##_ = (uint32_t)((int32_t)(S).d##A >> 31);                              \
-    const uint32_t rem##A##_ = ~(c##A##_ ^ xn##A##_) & 3u;                                      \
-    const uint32_t te##A##_ = xn##A##_ ? c##A##_ : pack_coord((K), (S).pe, A) - c##A##_;        \
-    const uint32_t m1##A##_ = zmin(rem##A##_, te##A##_);                                        \
-    const bool out##A##_ = te##A##_ <= rem##A##_;                                               \
-    const float T##A##1_ = (S).tn##A;                                                           \
-    const float T##A##2_ = T##A##1_ + (S).td##A;                                                \
-    const float T##A##3_ = T##A##2_ + (S).td##A;                                                \
-    const float T##A##4_ = T##A##3_ + (S).td##A;                                                \
-    const float E##A##_ = m1##A##_ == 0u ? T##A##1_                                             \
-                        : (m1##A##_ == 1u ? T##A##2_ : (m1##A##_ == 2u ? T##A##3_ : T##A##4_));
-#define SKIPV_COUNT(S, A, TIE)                                                                 \
-    uint32_t k##A##_ = ((T##A##1_ < ex_ || (T##A##1_ == ex_ && (TIE))) ? 1u : 0u) +             \
-                       ((T##A##2_ < ex_ || (T##A##2_ == ex_ && (TIE))) ? 1u : 0u) +             \
-                       ((T##A##3_ < ex_ || (T##A##3_ == ex_ && (TIE))) ? 1u : 0u);              \
-    k##A##_ = x##A##_ ? m1##A##_ + 1u : k##A##_;                                                \
-    (S).tn##A = k##A##_ == 0u ? T##A##1_                                                        \
-              : (k##A##_ == 1u ? T##A##2_                                                       \
-              : (k##A##_ == 2u ? T##A##3_ : (k##A##_ == 3u ? T##A##4_ : T##A##4_ + (S).td##A)));
-#define BRICK_SKIPV(S, K, EXITED, TC)                                                          \
-    do {                                                                                       \
-        SKIPV_AXIS(S, K, 0)                                                                    \
-        SKIPV_AXIS(S, K, 1)                                                                    \
-        SKIPV_AXIS(S, K, 2)                                                                    \
-        const bool x0_ = E0_ < E1_ && E0_ < E2_;                                               \
-        const bool x1_ = !(E0_ < E1_) && E1_ < E2_;                                            \
-        const bool x2_ = !x0_ && !x1_;                                                         \
-        const float ex_ = x0_ ? E0_ : (x1_ ? E1_ : E2_);                                       \
-        SKIPV_COUNT(S, 0, false)                                                               \
-        SKIPV_COUNT(S, 1, x0_)                                                                 \
-        SKIPV_COUNT(S, 2, !x2_)                                                                \
-        (EXITED) = x0_ ? out0_ : (x1_ ? out1_ : out2_);                                        \
-        (TC) = ex_;                                                                            \
-        (S).pc = pk_addn<PK_BM>(pk_addn<PK_BM>(pk_addn<PK_BM>((S).pc, (K).f0, k0_, (S).d0), (K).f1, k1_, (S).d1), (K).f2, \
-                         k2_, (S).d2);                                                         \
-    } while (0)
-
 // Fast-forward of the packed walk through space known to be empty: every
 // Iterator.next step whose crossing t is below TAU, as plain f32 adds per
 // axis (the same adds, in the same order per axis, as the cell-by-cell
@@ -684,52 +526,15 @@ ZHD uint32_t lm_selu(LaneM m, uint32_t t, uint32_t f) { return m ? t : f; }
 // returned +inf there; the walk has ended).  The caller guarantees that the
 // cells those steps enter hold no triangle and that nearest > TAU (so no break
 // test fires among them); not used with a -inf/NaN crossing sequence
-// (Dda.neg bit 3).  tests/cpp/dda_skip_check.cpp checks it step for step.
-#define FF_AXIS(S, A, FA, TAU, EXITED)                                                         \
-    while ((S).tn##A < (TAU)) {                                                                \
-        if ((((S).pc ^ (S).pe) & (FA)) == 0u) { (EXITED) = true; break; }                     \
-        (S).tn##A += (S).td##A;                                                                \
-        (S).pc = pk_add<PK_BM>((S).pc, (FA), (S).d##A);                                               \
-    }
-#define DDAV_FF(S, F0, F1, F2, TAU, EXITED)                                                    \
-    do {                                                                                       \
-        (EXITED) = false;                                                                      \
-        FF_AXIS(S, 0, F0, TAU, EXITED)                                                         \
-        if (!(EXITED)) { FF_AXIS(S, 1, F1, TAU, EXITED) }                                      \
-        if (!(EXITED)) { FF_AXIS(S, 2, F2, TAU, EXITED) }                                      \
-    } while (0)
-
-// DDAV_FF with four conditional crossings per loop trip and the selects
-// branch-free (fewer exec-mask updates per crossing; same crossings, same
-// state, same EXITED).
-#define FF_AXIS4(S, A, FA, TAU, EXITED)                                                        \
-    for (;;) {                                                                                 \
-        _Pragma("unroll") for (int u_ = 0; u_ < 4; ++u_) {                                     \
-            const bool go_ = (S).tn##A < (TAU) && !(EXITED);                                   \
-            const bool at_ = (((S).pc ^ (S).pe) & (FA)) == 0u;                                 \
-            (EXITED) = (EXITED) || (go_ && at_);                                               \
-            const bool mv_ = go_ && !at_;                                                      \
-            (S).tn##A = mv_ ? (S).tn##A + (S).td##A : (S).tn##A;                               \
-            (S).pc = mv_ ? pk_add<PK_BM>((S).pc, (FA), (S).d##A) : (S).pc;                           \
-        }                                                                                      \
-        if (!((S).tn##A < (TAU)) || (EXITED)) break;                                           \
-    }
-#define DDAV_FF4(S, F0, F1, F2, TAU, EXITED)                                                   \
-    do {                                                                                       \
-        (EXITED) = false;                                                                      \
-        FF_AXIS4(S, 0, F0, TAU, EXITED)                                                        \
-        if (!(EXITED)) { FF_AXIS4(S, 1, F1, TAU, EXITED) }                                     \
-        if (!(EXITED)) { FF_AXIS4(S, 2, F2, TAU, EXITED) }                                     \
-    } while (0)
-
-// DDAV_FF with the packed cell stepped once per axis: per axis the crossings
-// below TAU as predicated f32 adds (four per loop trip) and their count n,
-// then the coordinate written once (pk_setc); EXITED when n reaches past the axis's exit
-// cell (FF_AXIS stops there: its crossing j is the exit one iff j - 1 cells
-// remained, so EXITED iff n > cells left).  The loop stops within four
-// crossings of n > left, so it runs at most left + 4 adds whatever TAU is.
-// Same crossings (the adds stop at the first t >= TAU), same state, same
-// EXITED as DDAV_FF; ~4 VALU per crossing instead of ~10.
+// (Dda.neg bit 3).  tests/cpp/dda_walk_check.cpp checks it against the cell
+// walk, step for step.
+// Per axis the crossings below TAU are predicated f32 adds (four per loop
+// trip) and their count n, then the coordinate is written once (pk_setc);
+// EXITED when n reaches past the axis's exit cell: crossing j is the exit one
+// iff j - 1 cells remained, so EXITED iff n > cells left.  The loop stops
+// within four crossings of n > left, so it runs at most left + 4 adds whatever
+// TAU is.  ~4 VALU per crossing, against ~10 for a packed step (pk_add) and an
+// exit test per crossing.
 #define FFN_AXIS(S, K, A, FA, TAU, EXITED)                                                     \
     {                                                                                          \
         const uint32_t c_ = pack_coordt<PK_BM>((K), (S).pc, A), e_ = pack_coordt<PK_BM>((K), (S).pe, A); \
@@ -751,33 +556,6 @@ ZHD uint32_t lm_selu(LaneM m, uint32_t t, uint32_t f) { return m ? t : f; }
         FFN_AXIS(S, K, 0, F0, TAU, EXITED)                                                     \
         if (!(EXITED)) { FFN_AXIS(S, K, 1, F1, TAU, EXITED) }                                  \
         if (!(EXITED)) { FFN_AXIS(S, K, 2, F2, TAU, EXITED) }                                  \
-    } while (0)
-
-// DDAV_FF for long jumps: per axis first a run of n crossings known to lie
-// below TAU and before the exit cell -- n from a float estimate with a safety
-// margin, capped by the cells left to the exit -- done as n plain adds (the
-// same adds in the same order: the state is the one the cell walk reaches
-// after them) and one packed-cell step of n cells, then FF_AXIS for the last
-// few.  Same crossings, same state, same EXITED as DDAV_FF.
-#define FFC_AXIS(S, K, A, FA, TAU, EXITED)                                                     \
-    {                                                                                          \
-        const float est_ = ((TAU) - (S).tn##A) / (S).td##A;                                    \
-        /* a lower bound on the crossings below TAU: the n adds' rounding drifts by at most */ \
-        /* n TAU 2^-24 <= 6e-5 n td while TAU < 1000 td, inside the 1e-4 n + 2 margin     */ \
-        uint32_t n_ = est_ > 3.0f && (TAU) < 1000.0f * (S).td##A ? (uint32_t)(est_ * 0.9999f) - 2u : 0u; \
-        const uint32_t c_ = pack_coord((K), (S).pc, A), e_ = pack_coord((K), (S).pe, A);      \
-        const uint32_t left_ = c_ > e_ ? c_ - e_ : e_ - c_;   /* cells before the exit one */  \
-        n_ = zmin(n_, left_);                                                                  \
-        for (uint32_t k_ = 0; k_ < n_; ++k_) (S).tn##A += (S).td##A;                           \
-        (S).pc = pk_addn<PK_BM>((S).pc, (FA), n_, (S).d##A);                                          \
-    }                                                                                          \
-    FF_AXIS(S, A, FA, TAU, EXITED)
-#define DDAV_FFC(S, K, F0, F1, F2, TAU, EXITED)                                                \
-    do {                                                                                       \
-        (EXITED) = false;                                                                      \
-        FFC_AXIS(S, K, 0, F0, TAU, EXITED)                                                     \
-        if (!(EXITED)) { FFC_AXIS(S, K, 1, F1, TAU, EXITED) }                                  \
-        if (!(EXITED)) { FFC_AXIS(S, K, 2, F2, TAU, EXITED) }                                  \
     } while (0)
 
 // Select of the park kernel's pair refill (render.hip): position of the r-th

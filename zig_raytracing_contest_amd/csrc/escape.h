@@ -136,7 +136,7 @@ ZHD bool esc_compute(const EscSat& S, const uint32_t res[3], const float cs[3], 
 // along the cone's dominant axis, the first slice whose box (dilated by one
 // cell) holds an occupied cell ends the march: every point of the block's
 // rays with normalized t < s0 |D|min lies in earlier, empty slices, so a walk
-// may fast-forward (DDAV_FF) over every crossing below that t.  +inf: the cone
+// may fast-forward (DDAV_FFN) over every crossing below that t.  +inf: the cone
 // meets no occupied cell at all, so every ray of the block misses
 // (traceRay's +inf).  0: no bound (a degenerate cone).
 // hi: the march goes on to the last slice [s0, s1] that holds an occupied

@@ -71,8 +71,7 @@ __global__ void probe_kernel(int which, const void* in, void* out, uint32_t n, c
             const float ics[3] = {1.0f / cs[0], 1.0f / cs[1], 1.0f / cs[2]};
             bool cs_ok = true;
             for (int k = 0; k < 3; ++k) cs_ok = cs_ok && fabsf(cs[k]) >= 0x1p-32f && fabsf(cs[k]) <= 0x1p32f;
-            const bool in = ZRT_FAST_QUOT ? dda_init_fq(bmin, bmax, r3, cs, ics, cs_ok, ld3(a + 6), ld3(a + 9), s)
-                                          : dda_init(bmin, bmax, r3, cs, ld3(a + 6), ld3(a + 9), s);
+            const bool in = dda_init_fq(bmin, bmax, r3, cs, ics, cs_ok, ld3(a + 6), ld3(a + 9), s);
             if (!in) { o[0] = -1.0f; break; }
             GridK gk;
             gk.rm0 = r3[0] - 1u; gk.rm1 = r3[1] - 1u; gk.rm2 = r3[2] - 1u;

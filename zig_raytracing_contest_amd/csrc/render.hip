@@ -58,70 +58,44 @@ constexpr uint32_t kWfChunk = ZRT_WF_CHUNK;
 // Triangle positions per ref (bakeInto's Pos: v0, e1 = v1 - v0, e2 = v2 - v0)
 // as 3 float4 (48 B, w unused).  36-byte records touch 25% fewer cache lines
 // per cell but cost the park kernel 9 VGPRs (r05f: cfg3 -9%).
-// ZRT_PLANES16: a scattering hit's bounce-plane record is (albedo, has
-// emissive) in one float4 (16 B, one store) plus a float4 emissive record
-// only when the material emits, against 24 B in two stores (stk4 + stk2):
-// the lamps are the only emissive materials of the stand-in scenes.  r05j,
-// alternating processes, 2 rounds, images identical: cfg3 5894 / 5899 vs
-// 5819 / 5812 (+1.4%), cfg5 +1.0%, cfg2 +1.1%; one-stream resolve 6.1 -> 4.3
-// ms per cfg3 frame (profiles/r05/r05j_ab_planes16.log)
-#ifndef ZRT_PLANES16
-#define ZRT_PLANES16 1
-#endif
-// ZRT_FRUSTUM: the primary walk fast-forwards (DDAV_FF) over the crossings
-// below its pixel block's frustum bound (escape.h frustum_bound lo); with
-// ZRT_FRUSTUM_HI it also stops once it has tested the cell whose exit is at
-// or past the block's far bound (hi)
-#ifndef ZRT_FRUSTUM
-#define ZRT_FRUSTUM 1
-#endif
-#ifndef ZRT_FRUSTUM_HI
-#define ZRT_FRUSTUM_HI 1
-#endif
-// the timed kernels' normalize: 1/length by recip_rn (zrt_math.h; the same
-// vector bit for bit)
-#ifndef ZRT_NORMALIZE_RN
-#define ZRT_NORMALIZE_RN 1
-#endif
-#if ZRT_NORMALIZE_RN
-#define ZRT_NORM_RN normalize_rn
-#else
-#define ZRT_NORM_RN normalize
-#endif
-// ZRT_FFN: the frustum fast-forward as DDAV_FFN (dda.h: per axis predicated
-// adds and a count, the packed coordinate written once) instead of DDAV_FF4
-// (a packed step per crossing); cfg3 camera rays cross 85.6 cells below their
-// block's bound (tools/frustum_sim.cpp), cfg5 75.5, cfg2 62.8
-#ifndef ZRT_FFN
-#define ZRT_FFN 1
-#endif
-// ZRT_PRIMARY_BMASK: the packed lane walk (primary, lane-walk bounces) on
-// brick-major words reads, on entering an occupied brick, the brick's 64-bit
-// cell mask from global memory and loads a cell's record only when its own
-// bit is set.  With the brick bit alone every cell of an occupied brick cost
-// a dependent record load and an empty test: cfg3 camera rays walk 44 cells
-// after the frustum bound, 18.9 in occupied bricks, 4.2 non-empty (host
-// model, tools/frustum_sim.cpp on the bench scenes; cfg5 27.3 / 11.5 / 2.8)
-#ifndef ZRT_PRIMARY_BMASK
-#define ZRT_PRIMARY_BMASK 1
-#endif
-// ZRT_WALK_FACE_SKIP: the packed lane walk (primary, lane-walk bounces) skips
-// a cell's refs that the cell it left already tested (test_cell_keep), as
-// the park kernel's test rounds do.  The r06aa A/B, before the exact cell
-// bits and the counted fast-forward, had it at -0.1% (cfg3); on the tree
-// after them (r06af, r06ag, 5 rounds) cfg3 +1.2%, cfg5 +0.3%, cfg2 +0.5%,
-// with 6 VGPRs of the 7-wave primary spilled outside its walk (6 waves: no
-// spill, cfg3 +0.9%)
-#ifndef ZRT_WALK_FACE_SKIP
-#define ZRT_WALK_FACE_SKIP 1
-#endif
-// dda_init_fq (dda.h) in the primary / lane-walk wf_kernel too (the park
-// kernel's refill always takes it when ZRT_FAST_QUOT)
-#ifndef ZRT_FAST_QUOT_WF
-#define ZRT_FAST_QUOT_WF 1
-#endif
+// A scattering hit's bounce-plane record is (albedo, has emissive) in one
+// float4 (16 B, one store) plus a float4 emissive record only when the
+// material emits; the alternative, 24 B in two stores (stk4 + a float2 in
+// stk2), lost: the lamps are the only emissive materials of the stand-in
+// scenes.  r05j, alternating processes, 2 rounds, images identical: cfg3
+// 5894 / 5899 vs 5819 / 5812 (+1.4%), cfg5 +1.0%, cfg2 +1.1%; one-stream
+// resolve 6.1 -> 4.3 ms per cfg3 frame (profiles/r05/r05j_ab_planes16.log)
+//
+// The primary walk fast-forwards (DDAV_FFN, dda.h: per axis predicated adds
+// and a count, the packed coordinate written once, against a packed step per
+// crossing) over the crossings below its pixel block's frustum bound
+// (escape.h frustum_bound lo), and stops once it has tested the cell whose
+// exit is at or past the block's far bound (hi); cfg3 camera rays cross 85.6
+// cells below their block's bound (tools/frustum_sim.cpp), cfg5 75.5, cfg2
+// 62.8.
+//
+// The timed kernels normalise with normalize_rn: 1/length by recip_rn
+// (zrt_math.h; the same vector as normalize, bit for bit).
+//
+// The packed lane walk (primary, lane-walk bounces) on brick-major words
+// reads, on entering an occupied brick, the brick's 64-bit cell mask from
+// global memory and loads a cell's record only when its own bit is set.
+// With the brick bit alone every cell of an occupied brick cost a dependent
+// record load and an empty test: cfg3 camera rays walk 44 cells after the
+// frustum bound, 18.9 in occupied bricks, 4.2 non-empty (host model,
+// tools/frustum_sim.cpp on the bench scenes; cfg5 27.3 / 11.5 / 2.8)
+//
+// The packed lane walk also skips a cell's refs that the cell it left already
+// tested (test_cell_keep), as the park kernel's test rounds do.  The r06aa
+// A/B, before the exact cell bits and the counted fast-forward, had it at
+// -0.1% (cfg3); on the tree after them (r06af, r06ag, 5 rounds) cfg3 +1.2%,
+// cfg5 +0.3%, cfg2 +0.5%, with 6 VGPRs of the 7-wave primary spilled outside
+// its walk (6 waves: no spill, cfg3 +0.9%)
+//
+// The primary / lane-walk wf_kernel sets its walk up with dda_init_fq (dda.h),
+// as the park kernel's refill does.
 // primary frustum bounds per (1 << ZRT_FRUSTUM_SHIFT)^2 pixel block: 4x4
-// since round 6, when the counted fast-forward (ZRT_FFN) made the crossings
+// since round 6, when the counted fast-forward (DDAV_FFN) made the crossings
 // below the bound cheap (r05ae had 8x8 = 4x4 = 2x2 at ~10 VALU per crossing);
 // r06ai / r06ak, 5 rounds: cfg3 +0.8 / +0.5%, cfg2 -0.3 / +0.1%, cfg5 0 / +0.1%
 #ifndef ZRT_FRUSTUM_SHIFT
@@ -360,7 +334,7 @@ __device__ __forceinline__ float trace_ray(const TraceParams& p, const uint32_t*
     Dda s0;
     // (the counting build and the IEEE-division kernels keep dda_init's
     // divisions; the timed kernels take dda_init_fq's quotients: same state)
-    if (ZRT_FAST_QUOT && ZRT_FAST_QUOT_WF && !MTX && !STATS) {
+    if (!MTX && !STATS) {
         if (!dda_init_fq(p.bmin, p.bmax, p.res, p.cs, p.ics, p.cs_ok != 0u, o, d, s0)) return nearest;
     } else if (!dda_init(p.bmin, p.bmax, p.res, p.cs, o, d, s0)) {
         return nearest;
@@ -377,48 +351,42 @@ __device__ __forceinline__ float trace_ray(const TraceParams& p, const uint32_t*
         // every step (r03 ISA)
         uint32_t f0 = p.pk.f0, f1 = p.pk.f1, f2 = p.pk.f2;
         asm("" : "+s"(f0), "+s"(f1), "+s"(f2));
-        if (ZRT_FRUSTUM && s0.neg < 8u) {
+        if (s0.neg < 8u) {
             // the cells before tau are empty (the pixel block's frustum bound):
             // their crossings as plain adds, the walk's exact state after them
-            // (DDAV_FF); nearest is +inf here, so no break test fires among them
+            // (DDAV_FFN); nearest is +inf here, so no break test fires among them
             if (tau == kInf) return nearest;               // no occupied cell on the ray: the miss
             if (tau > fminf(s.tn0, fminf(s.tn1, s.tn2))) {
                 bool exited;
                 // (four branch-free crossings per loop trip: r04s, cfg3 5730 vs
-                // 5695 Mrays/s with one per trip, DDAV_FF)
-                if (ZRT_FFN) DDAV_FFN(s, p.pk, f0, f1, f2, tau, exited);
-                else DDAV_FF4(s, f0, f1, f2, tau, exited);
+                // 5695 Mrays/s with one per trip)
+                DDAV_FFN(s, p.pk, f0, f1, f2, tau, exited);
                 if (exited) return nearest;
             }
         }
         bool occupied = brick_occupied_v<PK_BM>(p, occ, s.pc);
-        constexpr bool kBm = PK_BM && ZRT_PRIMARY_BMASK;
-        unsigned long long q = 0ull;        // kBm: the current brick's cell mask
-        if (kBm && occupied) q = p.bmask[s.pc >> 6];
+        unsigned long long q = 0ull;        // PK_BM: the current brick's cell mask
+        if (PK_BM && occupied) q = p.bmask[s.pc >> 6];
         // the walk's stop: the nearest hit so far, or (TFAR, a frustum far
         // bound) the t past which every cell of the ray is empty
-        float lim = ZRT_FRUSTUM_HI && s0.neg < 8u ? tfar : kInf;
-        // ZRT_WALK_FACE_SKIP: the crossing t of the step into the current
+        float lim = s0.neg < 8u ? tfar : kInf;
+        // the entry-face skip: the crossing t of the step into the current
         // cell (NaN: the segment's first tested cell, every ref tested)
         float tcl = __builtin_nanf("");
         for (;;) {
-            if (kBm ? ((q >> (s.pc & 63u)) & 1ull) != 0ull : occupied) {
+            if (PK_BM ? ((q >> (s.pc & 63u)) & 1ull) != 0ull : occupied) {
                 const uint32_t* rec = p.cell32 + 8ull * s.pc;
                 const uint2 cell = *reinterpret_cast<const uint2*>(rec);
-                if (ZRT_WALK_FACE_SKIP) {
-                    // the face entered: the stepped axis a is the one whose
-                    // next crossing is this step's own tc + td_a; exactly one
-                    // such axis, or (a tie at tc) every ref is tested
-                    const bool x0 = s.tn0 == tcl + s.td0, x1 = s.tn1 == tcl + s.td1, x2 = s.tn2 == tcl + s.td2;
-                    uint32_t keep = ~0u;
-                    if ((uint32_t)x0 + (uint32_t)x1 + (uint32_t)x2 == 1u) {
-                        const uint32_t face = x0 ? (s.d0 >> 31) : (x1 ? 2u + (s.d1 >> 31) : 4u + (s.d2 >> 31));
-                        keep = rec[2 + face];
-                    }
-                    test_cell_keep<TB, MTX>(p, cell.x, cell.y, keep, o, d, nearest, hu, hv, hidx);
-                } else {
-                    test_cell<TB, false, MTX>(p, cell.x, cell.y, o, d, nearest, hu, hv, hidx, n_tests, prof);
+                // the face entered: the stepped axis a is the one whose
+                // next crossing is this step's own tc + td_a; exactly one
+                // such axis, or (a tie at tc) every ref is tested
+                const bool x0 = s.tn0 == tcl + s.td0, x1 = s.tn1 == tcl + s.td1, x2 = s.tn2 == tcl + s.td2;
+                uint32_t keep = ~0u;
+                if ((uint32_t)x0 + (uint32_t)x1 + (uint32_t)x2 == 1u) {
+                    const uint32_t face = x0 ? (s.d0 >> 31) : (x1 ? 2u + (s.d1 >> 31) : 4u + (s.d2 >> 31));
+                    keep = rec[2 + face];
                 }
+                test_cell_keep<TB, MTX>(p, cell.x, cell.y, keep, o, d, nearest, hu, hv, hidx);
                 lim = fminf(lim, nearest);                 // = min(nearest, far bound)
             }
             bool crossed, exited;
@@ -430,7 +398,7 @@ __device__ __forceinline__ float trace_ray(const TraceParams& p, const uint32_t*
             tcl = tc;
             if (crossed) {
                 occupied = brick_occupied_v<PK_BM>(p, occ, s.pc);
-                if (kBm) q = occupied ? p.bmask[s.pc >> 6] : 0ull;
+                if (PK_BM) q = occupied ? p.bmask[s.pc >> 6] : 0ull;
             }
         }
         return nearest;
@@ -486,9 +454,9 @@ __device__ __forceinline__ void camera_ray(const TraceParams& p, uint32_t item, 
     const float jx = rng_float(rng);
     const float jy = rng_float(rng);
     o = mk(p.org[0], p.org[1], p.org[2]);
-    d = ZRT_NORM_RN(add(add(mk(p.llc[0], p.llc[1], p.llc[2]),
-                          scale(mk(p.right[0], p.right[1], p.right[2]), (float)px + jx)),
-                      scale(mk(p.up[0], p.up[1], p.up[2]), (float)py + jy)));
+    d = normalize_rn(add(add(mk(p.llc[0], p.llc[1], p.llc[2]),
+                            scale(mk(p.right[0], p.right[1], p.right[2]), (float)px + jx)),
+                        scale(mk(p.up[0], p.up[1], p.up[2]), (float)py + jy)));
 }
 
 // The RNG state camera_ray leaves (after the jitter draws), without the ray.
@@ -630,10 +598,10 @@ struct WfParams {
     TraceParams t;
     const float4* q_in;
     float4* q_out;
-    float4* stk4;             // bounce planes, slot-major: float4 (e, a.x) at [slot * T + item]
-    float2* stk2;             //   and float2 (a.y, a.z) at [slot * T + item] (24 B per pair)
-                              // ZRT_PLANES16: stk4 = (a, emissive bits != 0), stk2 = float4 e
-                              // at [slot * T + item], written for emissive hits only
+    float4* stk4;             // bounce planes, slot-major: float4 (a, emissive bits != 0) at [slot * T + item]
+    float2* stk2;             //   and float4 records e at [slot * T + item], written for emissive
+                              //   hits only (still declared float2*, two per record: the type is
+                              //   part of wf_resolve_kernel's symbol name)
     float4* term;             // [item]: terminal L.xyz, scatter mask bits
     uint32_t T;               // items in this pass
     uint32_t* fetch8;         // work counter per group of this launch
@@ -741,7 +709,7 @@ __device__ __forceinline__ bool shade_segment(const WfParams& w, const double* z
     const float u_tr = rng_float(rng);
     SHADE_STAMP(4, u_tr);                                   // transparency draw
     if (LAST) {
-        // the fold's last step at L = 0 (ZRT_PLANES16: e = +0 exactly when no
+        // the fold's last step at L = 0 (e = +0 exactly when no
         // e was stored, i.e. when every bit of the sampled e is zero: then
         // the sample is that +0)
         L = !(u_tr > transparency) ? add(emissive, mul(albedo, mk(0.0f, 0.0f, 0.0f))) : mk(0, 0, 0);
@@ -749,24 +717,20 @@ __device__ __forceinline__ bool shade_segment(const WfParams& w, const double* z
     }
     if (!(u_tr > transparency)) {                           // stage3.zig:207, :214-219
         // the (e, a) pair goes out before the normal draws, so the ziggurat
-        // (f64, 64-bit RNG) runs without the six colour registers live; 24 B
-        // per pair instead of two float4 (r03zk: cfg3 +0.5%, cfg2 +1.6%,
-        // cfg5 +1.3%: this write and wf_resolve_kernel's read are HBM-bound)
-        if (ZRT_PLANES16) {
-            // (a, has_e) in 16 B; e only for emissive hits (its own plane)
-            const uint32_t eb = __float_as_uint(emissive.x) | __float_as_uint(emissive.y) | __float_as_uint(emissive.z);
-            w.stk4[(uint64_t)slot * w.T + item] = make_float4(albedo.x, albedo.y, albedo.z, __uint_as_float(eb));
-            if (eb != 0u)
-                reinterpret_cast<float4*>(w.stk2)[(uint64_t)slot * w.T + item] =
-                    make_float4(emissive.x, emissive.y, emissive.z, 0.0f);
-        } else {
-            w.stk4[(uint64_t)slot * w.T + item] = make_float4(emissive.x, emissive.y, emissive.z, albedo.x);
-            w.stk2[(uint64_t)slot * w.T + item] = make_float2(albedo.y, albedo.z);
-        }
+        // (f64, 64-bit RNG) runs without the six colour registers live.
+        // (a, has_e) in 16 B; e only for emissive hits (its own plane).  (24 B
+        // per pair beat two float4 in r03zk: cfg3 +0.5%, cfg2 +1.6%, cfg5
+        // +1.3%: this write and wf_resolve_kernel's read are HBM-bound; the
+        // 16 B record beat the 24 B one in r05j, at the top of this file)
+        const uint32_t eb = __float_as_uint(emissive.x) | __float_as_uint(emissive.y) | __float_as_uint(emissive.z);
+        w.stk4[(uint64_t)slot * w.T + item] = make_float4(albedo.x, albedo.y, albedo.z, __uint_as_float(eb));
+        if (eb != 0u)
+            reinterpret_cast<float4*>(w.stk2)[(uint64_t)slot * w.T + item] =
+                make_float4(emissive.x, emissive.y, emissive.z, 0.0f);
         const float nx = (float)rng_norm64(rng, zx, zf);
         const float ny = (float)rng_norm64(rng, zx, zf);
         const float nz = (float)rng_norm64(rng, zx, zf);
-        d = ZRT_NORM_RN(add(nrm, ZRT_NORM_RN(mk(nx, ny, nz))));
+        d = normalize_rn(add(nrm, normalize_rn(mk(nx, ny, nz))));
         mask |= 1u << slot;
         SHADE_STAMP(5, d.x);                                // pair store + ziggurat draws
     }
@@ -913,7 +877,7 @@ __global__ __launch_bounds__(kTraceBlock, MINW) void wf_kernel(const WfParams w)
                 Rng rng0;
                 uint32_t blk = 0;
                 camera_ray(p, i, rng0, o, d, &blk);
-                if (ZRT_FRUSTUM && p.tlo) {
+                if (p.tlo) {
                     const float4 fb = p.tlo[blk];
                     tau = fb.x;
                     tfar = fb.y;
@@ -1050,30 +1014,11 @@ __device__ __forceinline__ uint32_t occx_brick(const WfParams& w, const DdaV& s)
 // r03za, on the round-3 kernels: 256 vs 128 cfg3 +0.5%, cfg5 +0.4%, cfg2
 // -0.5%; 64 -0.7 / -1.0 / -0.5%)
 constexpr uint32_t kParkChunk = ZRT_PARK_CHUNK;
-// ZRT_PARK_LATE_DRAIN (below, the refill round): r05q, 2 rounds, images
-// identical: cfg5 3576 / 3587 vs 3551 / 3553 (+0.8%, park -1%), cfg3 +0.1%,
-// cfg2 +0.5% (profiles/r05/r05q_ab_park_late_drain.log)
-#ifndef ZRT_PARK_LATE_DRAIN
-#define ZRT_PARK_LATE_DRAIN 1
-#endif
-// ZRT_PARK_QPF: at the end of a refill round the wave pulls the lines of the
-// next 64 queue entries of its chunk into L2 (one LDS-DMA dword per lane into
-// a per-wave scratch slot that nothing reads), so the next refill round's
-// record loads hit L2 instead of HBM.  The walk trips that follow do not wait
-// for vector memory; the next test round's vmcnt(0) is the first wait behind
-// the prefetch, and its ranges were issued after it.  Off: r06ab, 2 rounds,
-// images identical: cfg3 6972 vs 6992 (-0.3%), cfg2 -0.4%, cfg5 3845 vs 3892
-// (-1.2%) (profiles/r06/r06ab_ab_queue_prefetch.log): the extra request per
-// lane and refill costs more than the record loads' HBM latency, which the
-// SIMD's other park waves already hide (0; the #define: render_context.h)
-// ZRT_PARK_ADAPT: a launch with few entries per wave (the last bounces, an
-// 8-rank tile set) takes smaller chunks, down to 64, so the waves' last
-// chunks end closer together (the launch tail).  r05e, alternating processes,
-// 2 rounds, images identical: cfg3 5801 / 5810 vs 5765 / 5749 (+0.8%), cfg2
-// +0.6%, cfg5 +0.1% (profiles/r05/r05e_ab_p96_park_adapt.log)
-#ifndef ZRT_PARK_ADAPT
-#define ZRT_PARK_ADAPT 1
-#endif
+// A launch with few entries per wave (the last bounces, an 8-rank tile set)
+// takes smaller chunks, down to 64, so the waves' last chunks end closer
+// together (the launch tail).  r05e, alternating processes, 2 rounds, images
+// identical: cfg3 5801 / 5810 vs 5765 / 5749 (+0.8%) against fixed chunks,
+// cfg2 +0.6%, cfg5 +0.1% (profiles/r05/r05e_ab_p96_park_adapt.log)
 // Park release (round 6): a parked lane whose cell has no ref left to test
 // for the face it entered across (the entry-face mask is 0: every ref was
 // tested in the cell it left) costs a test round nothing but its latency,
@@ -1207,10 +1152,6 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
     __shared__ uint32_t s_esc[kParkWaves * 64];             // escape-table words (park_load_esc)
     uint32_t* const esc_slot = s_esc + 64u * (threadIdx.x >> 6);
     __shared__ uint8_t s_sel8[256 * 8];                     // bit position of the r-th set bit of a byte
-#if ZRT_PARK_QPF
-    __shared__ uint32_t s_qpf[kParkWaves * 64];             // queue-record prefetch landing slots (never read)
-    uint32_t* const qpf_slot = s_qpf + 64u * (threadIdx.x >> 6);
-#endif
     for (uint32_t i = threadIdx.x; i < 256u * 8u; i += blockDim.x) {
         SEL8_ENTRY(i, pos);
         s_sel8[i] = (uint8_t)pos;
@@ -1239,7 +1180,7 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
     uint32_t grp = blockIdx.x & 7u, tried = 0;
     uint32_t cb = 0, ce = 0, cgrp = 0;     // the wave's current chunk of queue entries
     uint32_t chunk = kParkChunk;
-    if (ZRT_PARK_ADAPT) {                  // (wave-uniform: the previous launch's final counts)
+    {                                      // (wave-uniform: the previous launch's final counts)
         uint32_t ntot = 0;
         for (uint32_t g = 0; g < 8u; ++g) ntot += w.n_in8[g * kCtr];
         const uint32_t per = ntot / (gridDim.x * (blockDim.x >> 6) * 4u);
@@ -1269,17 +1210,17 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
             PARK_COUNT(8, 1);
             PARK_COUNT(9, __popcll(__ballot(st == kDone)));
             if (__ballot(st == kDone) != 0ull) {
-                // the hit record for wf_shade_kernel; then drain the stores:
-                // otherwise the compiler guards the walk loop's reuse of their
-                // data registers with a vmcnt(0) INSIDE the loop, which then
-                // also waits for the previous step's range load, every step
-                // (r02f ISA; walk 1304 cycles per step)
+                // the hit record for wf_shade_kernel; its stores are drained
+                // before the walk (at the end of this round): otherwise the
+                // compiler guards the walk loop's reuse of their data registers
+                // with a vmcnt(0) INSIDE the loop, which then also waits for
+                // the previous step's range load, every step (r02f ISA; walk
+                // 1304 cycles per step)
                 const bool done = st == kDone;
                 if (done) {
                     w.hit[qi] = make_float4(nearest, hu, hv, __uint_as_float(hidx));
                     st = kIdle;
                 }
-                if (!ZRT_PARK_LATE_DRAIN) __builtin_amdgcn_s_waitcnt(0x3f70);   // vmcnt(0)
             }
             bool loaded = false;                                   // (wave-uniform)
             PARK_STAMP(10);
@@ -1314,8 +1255,8 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
                             W.o[lane] = make_float4(o.x, o.y, o.z, 0.0f);
                             W.d[lane] = make_float4(d.x, d.y, d.z, 0.0f);
                             Dda s0;
-                            if (ZRT_FAST_QUOT ? dda_init_fq(p.bmin, p.bmax, p.res, p.cs, p.ics, p.cs_ok != 0u, o, d, s0)
-                                              : dda_init(p.bmin, p.bmax, p.res, p.cs, o, d, s0)) {   // stage3.zig:153-156
+                            // stage3.zig:153-156
+                            if (dda_init_fq(p.bmin, p.bmax, p.res, p.cs, p.ics, p.cs_ok != 0u, o, d, s0)) {
                                 ddav_from_t<PK_BM>(s0, gk, pk, s);
                                 const uint32_t bin = (ESC || w.bfc) ? esc_dir_bin(d) : 0u;
                                 if (ESC) {
@@ -1325,10 +1266,10 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
                                     // q_in loads, vector memory completes in order
                                     // (vmcnt), and this store runs only after
                                     // dda_init consumed o and d, i.e. after the
-                                    // compiler's wait for those loads.  With
-                                    // ZRT_PARK_LATE_DRAIN the kDone drain no longer
-                                    // sits between them; the parity suite renders
-                                    // every scene with the table forced on)
+                                    // compiler's wait for those loads.  No kDone
+                                    // drain sits between them (it comes after the
+                                    // refill); the parity suite renders every scene
+                                    // with the table forced on)
                                     eoff = (bin >> 5) * 4u;
                                     emask = w.esc && s0.neg < 8u ? 1u << (bin & 31u) : 0u;
                                     eb = ~0u;
@@ -1365,16 +1306,23 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
                 loaded = loaded || take != 0u;
                 idle = __ballot(st == kIdle);
             }
-            // ZRT_PARK_LATE_DRAIN: the hit-record stores drain with the new
-            // paths' record loads (vector memory completes in order); only a
-            // round that loaded nothing drains them explicitly
-            if (ZRT_PARK_LATE_DRAIN && !loaded) __builtin_amdgcn_s_waitcnt(0x3f70);
-#if ZRT_PARK_QPF
-            if (ce > cb) {
-                const uint32_t j = min(cb + lane, ce - 1u);
-                park_load_esc(reinterpret_cast<const uint32_t*>(w.q_in + 3ull * ent_index<false>(w, cgrp, j)), qpf_slot);
-            }
-#endif
+            // the hit-record stores drain with the new paths' record loads
+            // (vector memory completes in order); only a round that loaded
+            // nothing drains them explicitly (vmcnt(0)).  Against a drain
+            // right after the stores: r05q, 2 rounds, images identical: cfg5
+            // 3576 / 3587 vs 3551 / 3553 (+0.8%, park -1%), cfg3 +0.1%, cfg2
+            // +0.5% (profiles/r05/r05q_ab_park_late_drain.log)
+            if (!loaded) __builtin_amdgcn_s_waitcnt(0x3f70);
+            // No prefetch of the chunk's next 64 queue entries here.  Pulling
+            // their lines into L2 at the end of a refill round (one LDS-DMA
+            // dword per lane into a per-wave slot that nothing reads, so that
+            // the next round's record loads hit L2 instead of HBM; the walk
+            // trips that follow do not wait for vector memory) lost: r06ab, 2
+            // rounds, images identical: cfg3 6972 vs 6992 (-0.3%), cfg2 -0.4%,
+            // cfg5 3845 vs 3892 (-1.2%)
+            // (profiles/r06/r06ab_ab_queue_prefetch.log): the extra request
+            // per lane and refill costs more than the record loads' HBM
+            // latency, which the SIMD's other park waves already hide
             PARK_STAMP(0);
             if (__ballot(st != kIdle) == 0ull) {
                 if (!more) break;
@@ -1573,53 +1521,19 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
 // after traceRay, stage3.zig:195-219) over the hit records wf_park_kernel
 // wrote, one lane per path with every lane of the wave busy, appending the
 // continuing paths to the next queue.  Same XCD group order as the trace.
-// One path of the shading half, its state decoded and its hit record h
-// loaded: shades, writes the terminal radiance of an ending path and appends
-// a continuing one (the whole wave calls it).
-__device__ __forceinline__ void shade_path(const WfParams& w, const double* zx, const double* zf,
-                                           const DevMat* mats, bool valid,
-                                           uint32_t item, v3 o, v3 d, uint32_t depth, uint32_t slot, Rng rng,
-                                           uint32_t mask, float4 h, const TriRec& tr, uint64_t below, uint32_t grp,
-                                           uint32_t& n_seg, unsigned long long* sp = nullptr) {
-    bool cont = false;
-    if (valid) {
-        v3 L = mk(0, 0, 0);
-        ++n_seg;                               // queued / primary paths have depth >= 1
-        cont = shade_segment(w, zx, zf, mats, item, h.x, h.y, h.z, tr, o, d, depth, slot, rng, mask, L, sp);
-        if (!cont) w.term[item] = make_float4(L.x, L.y, L.z, __uint_as_float(mask));
-    }
-    SHADE_STAMP(6, o.x);                       // the rest of the segment (misses, pass-through, terminal store)
-    wf_append(w, cont, below, o, d, item, depth, slot, rng, mask, grp);
-    SHADE_STAMP(7, o.x);                       // append
-}
-
-// One queue entry: its path record (a, b, c) and hit record h already loaded.
-__device__ __forceinline__ void shade_entry(const WfParams& w, const double* zx, const double* zf,
-                                            const DevMat* mats, bool valid,
-                                            float4 a, float4 b, float4 c, float4 h, const TriRec& tr,
-                                            uint64_t below, uint32_t grp, uint32_t& n_seg,
-                                            unsigned long long* sp = nullptr) {
-    Rng rng;
-    rng.s = ((uint64_t)__float_as_uint(c.y) << 32) | __float_as_uint(c.x);
-    shade_path(w, zx, zf, mats, valid, __float_as_uint(a.w), mk(a.x, a.y, a.z), mk(b.x, b.y, b.z),
-               __float_as_uint(b.w) & 0xFFFFu, __float_as_uint(b.w) >> 16, rng, __float_as_uint(c.z), h, tr,
-               below, grp, n_seg, sp);
-}
-// ZRT_SHADE_EARLY_APPEND: whether a path continues is known from its records
+//
+// Early append: whether a path continues is known from its records
 // alone (shade_segment: a hit with depth >= 2 continues, whether it scatters
 // or passes through; a miss ends), so the wave reserves its appends with one
 // returning atomic right after the records land and the atomic's latency
 // overlaps the shading chain (triangle data -> texels -> RNG) instead of
-// following it; the path is stored at its reserved position.  r05m,
-// alternating processes, 2 rounds, images identical: cfg3 6019 / 6008 vs 5895
-// / 5877 (+2.2%), cfg5 +0.6%, cfg2 ±0; one-stream shade 23.3-27.0 -> 18.3-18.6
-// ms per cfg3 frame (profiles/r05/r05m_ab_shade_early_append.log)
-#ifndef ZRT_SHADE_EARLY_APPEND
-#define ZRT_SHADE_EARLY_APPEND 1
-#endif
-#ifndef ZRT_SHADE_LAST
-#define ZRT_SHADE_LAST 1
-#endif
+// following it; the path is stored at its reserved position.  Against an
+// append after each entry's shading: r05m, alternating processes, 2 rounds,
+// images identical: cfg3 6019 / 6008 vs 5895 / 5877 (+2.2%), cfg5 +0.6%, cfg2
+// ±0; one-stream shade 23.3-27.0 -> 18.3-18.6 ms per cfg3 frame
+// (profiles/r05/r05m_ab_shade_early_append.log)
+//
+// The last bounce's launch has a kernel of its own (wf_shade_kernel's LAST);
 // its entries per lane per fetch and launch bound: r06f, 3 rounds of
 // alternating processes at full spp, images identical, against no LAST
 // kernel (6518 / 3851 / 4165 Mrays/s cfg3 / cfg5 / cfg2): 4 entries (78
@@ -1674,7 +1588,7 @@ __device__ __forceinline__ bool shade_entry_keep(const WfParams& w, const double
 // instead of L2.
 constexpr uint32_t kLdsMats = 64;
 // LAST: the launch of a pass's last bounce (every entry has depth 1): the
-// terminal radiance only (shade_segment<true>), no append (ZRT_SHADE_LAST)
+// terminal radiance only (shade_segment<true>), no append
 template <bool LMATS, bool LAST = false>
 #ifndef ZRT_SHADE_MINW
 #define ZRT_SHADE_MINW 1
@@ -1741,7 +1655,7 @@ __global__ __launch_bounds__(kTraceBlock, LAST ? ZRT_SHADE_LAST_MINW : ZRT_SHADE
                                              tri_rec(p, hit[e] ? h[e].x : kInf, __float_as_uint(h[e].w)), so, n_seg,
                                              sp);
             }
-        } else if (ZRT_SHADE_EARLY_APPEND) {
+        } else {
             bool pc[NE];
             uint64_t m[NE];
             uint32_t tot = 0;
@@ -1773,11 +1687,6 @@ __global__ __launch_bounds__(kTraceBlock, LAST ? ZRT_SHADE_LAST_MINW : ZRT_SHADE
                                    so.rng, so.mask);
                 before += (uint32_t)__popcll(m[e]);
             }
-        } else {
-#pragma unroll
-            for (int e = 0; e < NE; ++e)
-                shade_entry(w, zx, zf, mats, hit[e], a[e], b[e], c[e], h[e],
-                            tri_rec(p, hit[e] ? h[e].x : kInf, __float_as_uint(h[e].w)), below, grp, n_seg, sp);
         }
     }
     const unsigned long long s0 = wave_sum(n_seg);
@@ -1821,20 +1730,14 @@ __global__ __launch_bounds__(kBlock) void wf_resolve_kernel(const float4* __rest
                 const uint32_t mask = __float_as_uint(tm.w);
                 for (int slot = (int)max_bounce - 1; slot >= 0; --slot) {
                     if ((mask >> slot) & 1u) {
-                        if (ZRT_PLANES16) {
-                            // e = +0 exactly when the hit stored no emissive plane
-                            const float4 a = stk4[(uint64_t)slot * T + item];
-                            v3 e = mk(0.0f, 0.0f, 0.0f);
-                            if (__float_as_uint(a.w) != 0u) {
-                                const float4 ee = reinterpret_cast<const float4*>(stk2)[(uint64_t)slot * T + item];
-                                e = mk(ee.x, ee.y, ee.z);
-                            }
-                            L = add(e, mul(mk(a.x, a.y, a.z), L));
-                        } else {
-                            const float4 e = stk4[(uint64_t)slot * T + item];
-                            const float2 a = stk2[(uint64_t)slot * T + item];
-                            L = add(mk(e.x, e.y, e.z), mul(mk(e.w, a.x, a.y), L));
+                        // e = +0 exactly when the hit stored no emissive plane
+                        const float4 a = stk4[(uint64_t)slot * T + item];
+                        v3 e = mk(0.0f, 0.0f, 0.0f);
+                        if (__float_as_uint(a.w) != 0u) {
+                            const float4 ee = reinterpret_cast<const float4*>(stk2)[(uint64_t)slot * T + item];
+                            e = mk(ee.x, ee.y, ee.z);
                         }
+                        L = add(e, mul(mk(a.x, a.y, a.z), L));
                     }
                 }
                 float* dst = s_l + i * kResRow + 3u * k;
@@ -1902,7 +1805,7 @@ using WfFn = void (*)(const WfParams);
 // without SLP pairing (Makefile) the packed primary fits 7 waves (72 VGPRs,
 // no spill): r05ap, cfg3 6412 / 6400 vs 6346 / 6357 (+0.9%), cfg2 +0.7%,
 // cfg5 +0.3% (profiles/r05/r05ap_ab_primary7_select.log).  Round 6: the
-// entry-face skip (ZRT_WALK_FACE_SKIP) spills 6-10 VGPRs at 7 waves, some in
+// entry-face skip (trace_ray) spills 6-10 VGPRs at 7 waves, some in
 // the walk loop of the frustum instantiation; at 6 waves it spills nothing
 // and measured the same (r06af / r06ag: cfg3 +0.9 / +1.3% vs +1.3 / +1.2%
 // at 7 over the 7-wave tree without the skip).  With one triangle load in
@@ -2150,7 +2053,7 @@ struct RadParams {
 // products are +0; a -0 component becomes +0), then camera_ray's normalize.
 __device__ __forceinline__ v3 rad_direction(v3 d) {
     const v3 z = mk(0.0f, 0.0f, 0.0f);
-    return ZRT_NORM_RN(add(add(d, z), z));
+    return normalize_rn(add(add(d, z), z));
 }
 // What camera_rng leaves for (pixel key, sample s): the stream after the two
 // jitter draws.
@@ -2459,7 +2362,7 @@ static void bounce_params(WfParams& W, const zrt_context::PassSet& ps, uint32_t 
 // radiance 1 per item; `hit_items` hit records (the park kernel hands one per
 // item to the shade kernel; a query's first segments leave one per ray), 0: none.
 static int grow_pass_set(zrt_context::PassSet& ps, uint64_t T, uint32_t nb, uint32_t mb, uint64_t hit_items) {
-    const uint64_t planes2 = T * nb * (ZRT_PLANES16 ? 2 : 1);
+    const uint64_t planes2 = T * nb * 2;
     int rc;
     if ((rc = grow(&ps.q0, &ps.q0_cap, 3 * T)) != ZRT_OK) return rc;
     if ((rc = grow(&ps.q1, &ps.q1_cap, 3 * T)) != ZRT_OK) return rc;
@@ -2544,7 +2447,7 @@ static int resolve_plan(zrt_context* c, uint32_t flags, bool counting, bool want
     pl.f_walk = pl.mtx ? kWfBounceExact : (pl.packed ? (pl.pbm ? kWfBounceBM : kWfBounce) : kWfBounceWide);
     const bool lmats = c->nmat <= kLdsMats;
     pl.s_next = lmats ? (WfFn)wf_shade_kernel<true> : (WfFn)wf_shade_kernel<false>;
-    pl.s_last = !ZRT_SHADE_LAST ? pl.s_next : lmats ? (WfFn)wf_shade_kernel<true, true> : (WfFn)wf_shade_kernel<false, true>;
+    pl.s_last = lmats ? (WfFn)wf_shade_kernel<true, true> : (WfFn)wf_shade_kernel<false, true>;
     pl.lds_wf = 4ull * c->occ_words;
     pl.lds_shade = lmats ? c->nmat * sizeof(DevMat) : 0;
     pl.occx_ldsw = (uint32_t)occx_lds_words(c->occx_nbw, c->occx_moff, c->occx_words);
@@ -3013,9 +2916,9 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
     const uint32_t nb = std::max<uint32_t>(mb, 1);
     // per-item bytes of a pass: counting megakernel = the float4 sample
     // radiance; wavefront = 2 queues x 48 B + terminal 16 B + the bounce
-    // planes per slot ((a, has_e) 16 B + e 16 B with ZRT_PLANES16, else 24 B)
+    // planes per slot ((a, has_e) 16 B + e 16 B)
     // (+ the 16 B hit record the park kernel hands the shade kernel)
-    const uint64_t per_item = counting ? 16ull : 96ull + 16ull + 16ull + (ZRT_PLANES16 ? 32ull : 24ull) * nb;
+    const uint64_t per_item = counting ? 16ull : 96ull + 16ull + 16ull + 32ull * nb;
     const bool big = (uint64_t)P * cfg->num_samples >= kSetsMinSamples;
     const bool ktimes = (cfg->flags & ZRT_FLAG_KERNEL_TIMES) != 0;
     const PassSplit sp = split_passes(c, cfg, P, counting, big, per_item);
@@ -3121,7 +3024,7 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
     // block, r04fk3; 0.42 ms one thread per block) and save ~18% of the
     // primary launch: frames of 2^23 samples or more (a 3-spp 1080p frame's
     // primary takes ~0.5 ms: break-even)
-    if (ZRT_FRUSTUM && c->d_sat && !counting && pl.packed && !(cfg->flags & ZRT_FLAG_NO_FRUSTUM) &&
+    if (c->d_sat && !counting && pl.packed && !(cfg->flags & ZRT_FLAG_NO_FRUSTUM) &&
         ((uint64_t)P * cfg->num_samples >= kFrustumMinSamples || (cfg->flags & ZRT_FLAG_FRUSTUM)) &&
         (rc = launch_frustum(c, cam, cfg, nranks, tp)) != ZRT_OK)
         return rc;
@@ -3389,7 +3292,7 @@ extern "C" int zrt_context_radiance(zrt_context* c, const zrt_radiance_batch* b,
     // within the memory budget of a render's pass (its per-item bytes,
     // device_budget); S <= 65535 always fits at 64 rays
     zrt_context::PassSet& ps = c->set[0];
-    const uint64_t per_item = 96ull + 16ull + 16ull + (ZRT_PLANES16 ? 32ull : 24ull) * nb;
+    const uint64_t per_item = 96ull + 16ull + 16ull + 32ull * nb;
     const uint64_t per_ray = per_item * S + 24ull + 15ull + (b->on_device ? 0ull : 24ull);
     const size_t held = 4ull * (c->rays_cap + c->nrays_cap + c->lin_cap) + c->rgb_cap + c->bfc_bytes + held_bytes(ps);
     const size_t budget = device_budget(c, held);

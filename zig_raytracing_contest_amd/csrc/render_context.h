@@ -27,22 +27,6 @@
 #ifndef ZRT_PARK_BLOCK_T
 #define ZRT_PARK_BLOCK_T 1024
 #endif
-// (the queue prefetch of wf_park_kernel, render.hip: its slots count in kOccxBudget)
-#ifndef ZRT_PARK_QPF
-#define ZRT_PARK_QPF 0
-#endif
-// ZRT_ESCAPE: the park walk stops a segment once its escape-table bit
-// (escape.h) says every later cell of its ray is empty
-#ifndef ZRT_ESCAPE
-#define ZRT_ESCAPE 1
-#endif
-// brick-major packed cell words for the grids that allow them (dda.h): r05ag,
-// 2 rounds, images identical: cfg3 6076 / 6088 vs 6005 / 5999 (+1.3%), cfg2
-// +2.4%, cfg5 +1.2%; the park walk trip 179 -> 165 VALU
-// (profiles/r05/r05ag_ab_brick_major.log)
-#ifndef ZRT_PACK_BM
-#define ZRT_PACK_BM 1
-#endif
 #ifndef ZRT_OCC_LDS_KB
 #define ZRT_OCC_LDS_KB 16
 #endif
@@ -111,8 +95,7 @@ constexpr size_t kLdsPerCu = 160 * 1024;
 constexpr size_t kParkSlotsBytes = (kParkBlock / 64) * sizeof(ParkSlot);
 constexpr size_t kOccxBudget = kLdsPerCu - kParkSlotsBytes - 514 * sizeof(double) - kParkWaves * 192 * 4 - 256 -
                                 256 * 8 -   // the select table
-                                kParkWaves * 64 * 4 -  // the escape slots
-                                (ZRT_PARK_QPF ? kParkWaves * 64 * 4 : 0);   // the prefetch slots
+                                kParkWaves * 64 * 4;   // the escape slots
 
 // OccX blob layout for nb bricks (nbw 32-brick words) and `occupied` masks:
 // bits | u16 (1 + prefix) per word | (8-byte aligned) the zero mask + masks.
@@ -189,8 +172,8 @@ struct zrt_context {
         float4* q0 = nullptr; size_t q0_cap = 0;
         float4* q1 = nullptr; size_t q1_cap = 0;
         float4* term = nullptr; size_t term_cap = 0;
-        float4* stk4 = nullptr; size_t stk4_cap = 0;   // bounce planes: (e, a.x) per (slot, item)
-        float2* stk2 = nullptr; size_t stk2_cap = 0;   //   (a.y, a.z) per (slot, item)
+        float4* stk4 = nullptr; size_t stk4_cap = 0;   // bounce planes: (a, has e) per (slot, item)
+        float2* stk2 = nullptr; size_t stk2_cap = 0;   //   e as a float4 (two float2) per (slot, item)
         uint32_t* wfc = nullptr; size_t wfc_cap = 0;
         float4* hit = nullptr; size_t hit_cap = 0;
         hipEvent_t ev_join = nullptr;      // set k > 0: its last pass is done

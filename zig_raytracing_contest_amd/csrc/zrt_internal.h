@@ -33,12 +33,9 @@ ZHD void dev_tex_inline(DevTex& d, const float* texels, int chans) {
 // runs the same bilinear arithmetic on it (bit-identical: x - x is not
 // folded, NaN/inf weights propagate as before), instead of the index
 // arithmetic and four loads per channel.
-#ifndef ZRT_TEX1
-#define ZRT_TEX1 1
-#endif
 __device__ __forceinline__ v3 sample3(const float* texels, const DevTex& t, float u, float v) {
     const float* b = texels + t.off;
-    if (ZRT_TEX1 && t.w == 1 && t.h == 1) {
+    if (t.w == 1 && t.h == 1) {
         const float fu = tex_frac(u), fv = tex_frac(v);
         // the texel, inlined in the descriptor (dev_tex_inline)
         const float x = __int_as_float(t.umin), y = __int_as_float(t.umax), z = __int_as_float(t.vmin);
@@ -53,7 +50,7 @@ __device__ __forceinline__ v3 sample3(const float* texels, const DevTex& t, floa
 }
 __device__ __forceinline__ float sample1(const float* texels, const DevTex& t, float u, float v) {
     const float* b = texels + t.off;
-    if (ZRT_TEX1 && t.w == 1 && t.h == 1) {               // the 1x1 dummy (see sample3)
+    if (t.w == 1 && t.h == 1) {                           // the 1x1 dummy (see sample3)
         const float x = __int_as_float(t.umin);
         return bilerp(x, x, x, x, tex_frac(u), tex_frac(v));
     }

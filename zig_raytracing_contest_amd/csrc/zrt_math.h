@@ -292,9 +292,6 @@ ZHD double rng_norm64(Rng& r, const double* zx, const double* zf) {
 }
 
 // ---- Moller-Trumbore, back faces culled (linalg.zig:696-722) --------------
-#ifndef ZRT_MT_RCP
-#define ZRT_MT_RCP 1
-#endif
 // 1.0f / det, correctly rounded.  On the device: the compiler's IEEE f32
 // division sequence (rcp, then the fma refinements) without its
 // v_div_scale / v_div_fmas / v_div_fixup steps, which are identities for a
@@ -310,7 +307,7 @@ ZHD double rng_norm64(Rng& r, const double* zx, const double* zf) {
 // on every float of the domain (tests/test_gpu_parity.py).
 template <bool IEEE = false>
 ZHD float mt_inv_det(float det) {
-#if defined(__HIP_DEVICE_COMPILE__) && ZRT_MT_RCP
+#if defined(__HIP_DEVICE_COMPILE__)
     if (!IEEE) {
         const float r = __builtin_amdgcn_rcpf(det);
         const float f1 = __builtin_fmaf(__builtin_fmaf(-det, r, 1.0f), r, r);
@@ -339,7 +336,7 @@ ZHD float quot_rn(float a, float b, float y) {
 // itself for zero, subnormal, larger, infinite or NaN x (a branch that a
 // normalize of a ray direction never takes).
 ZHD float recip_rn(float x) {
-#if defined(__HIP_DEVICE_COMPILE__) && ZRT_MT_RCP
+#if defined(__HIP_DEVICE_COMPILE__)
     float r = mt_inv_det<false>(x);
     if (__builtin_expect(!(fabsf(x) >= 0x1p-126f && fabsf(x) <= 0x1p126f), 0)) r = 1.0f / x;
     return r;
