@@ -290,6 +290,64 @@ typedef struct zrt_ray_batch {
  * ZRT_FLAG_COUNT_STATS, counted as a counting render counts them. */
 int zrt_context_trace(zrt_context* ctx, const zrt_ray_batch* batch, zrt_stats* stats_or_null);
 
+/* ---- segment queries (ABI 2, added) ------------------------------------- */
+
+/* Rays with an end: shadow rays to a light, ambient-occlusion rays of a short
+ * radius, line-of-sight tests between two points.  For ray (o, d) with bound
+ * t_max this is Scene.traceRay (stage3.zig:152-186) with nearest_hit.t
+ * initialised to t_max instead of +inf (stage3.zig:154) and nothing else
+ * changed: cells in DDA order, a cell's refs begin -> end, a hit kept when
+ * `nearest > t and t > 0`, the walk stopped once nearest <= the next crossing
+ * and in any case at the grid's exit.  So
+ *   - a ref with t == t_max is NOT kept (the comparison is strict);
+ *   - the first cell is always tested, and the walk ends at the first
+ *     crossing at or beyond t_max: a short ray walks a few cells, not the grid;
+ *   - t_max = +inf is zrt_context_trace, bit for bit;
+ *   - t_max <= 0, -inf or NaN is a miss (for NaN no comparison is ever true,
+ *     and the walk ends at the grid's exit as every walk does);
+ *   - t and t_max are in the ray's own parameter, as zrt_hit.t is; directions
+ *     need not be unit length.  A shadow ray written as d = L - P, t_max = 1 is
+ *     correct, but such a d leaves the fast kernels' domain (0.5 <= d.d <= 1.5)
+ *     and takes the exact, slower walk: a caller who wants the fast kernels
+ *     normalises d and passes the distance as t_max.
+ * Closest mode: hits[i] is the zrt_hit of that walk; a miss is (+inf, 0, 0,
+ * 0xFFFFFFFF) as in zrt_context_trace, whatever t_max was.
+ * Any mode (ZRT_SEGMENT_ANY): occluded[i] = 1 if closest mode would report a
+ * hit, else 0.  The walk of a ray may end after the first cell in which a hit
+ * was kept (until then both modes hold nearest = t_max, visit the same cells
+ * and test the same refs; afterwards closest mode can never return to a miss);
+ * a counting call's does, the timed kernels run the closest walk, which
+ * measured as fast. */
+#define ZRT_SEGMENT_ANY 0x40000u     /* zrt_segment_batch.flags only */
+typedef struct zrt_segment_batch {
+    uint64_t num_rays;
+    const float* rays;               /* num_rays * 6, as zrt_ray_batch */
+    const float* t_max;              /* num_rays, or null: t_max_all for every ray */
+    zrt_hit* hits;                   /* closest mode: num_rays, or null if only `occluded` is wanted */
+    uint8_t* occluded;               /* num_rays bytes (0 / 1), or null in closest mode */
+    uint32_t on_device;              /* as zrt_ray_batch; applies to all four pointers */
+    uint32_t flags;                  /* zrt_ray_batch's flags | ZRT_SEGMENT_ANY */
+    float t_max_all;
+    uint32_t _reserved;              /* 0 */
+} zrt_segment_batch;                 /* 56 B */
+
+/* Synchronous, one thread at a time per context; alternates freely with
+ * renders, zrt_context_trace and zrt_context_radiance; chunks of at most 2^20
+ * rays (the staging of a host batch grows by the bound and the byte: 5 B per
+ * ray), the park kernel as in zrt_context_trace (ZRT_TRACE_PARK,
+ * ZRT_FLAG_LANE_WALK), unasked from 2^16 rays.
+ * num_rays == 0 returns ZRT_OK and touches nothing.  ZRT_ERR_INVALID_ARG before
+ * any device work: a null context or batch, null rays, both outputs null,
+ * ZRT_SEGMENT_ANY with non-null hits or null occluded, a non-zero _reserved, a
+ * flag zrt_context_trace would refuse.
+ * stats (may be null): segments = num_rays, samples = 0, render_ms,
+ * trace_kernel_ms and trace_launches as in zrt_context_trace.  hits = the rays
+ * not missed: in closest mode with ZRT_FLAG_COUNT_STATS only, in any mode in
+ * EVERY call (the bytes give it for free).  cells_visited and triangle_tests
+ * with ZRT_FLAG_COUNT_STATS, counted as the walk above runs, any mode's stop
+ * after the first cell with a kept hit included. */
+int zrt_context_segments(zrt_context* ctx, const zrt_segment_batch* batch, zrt_stats* stats_or_null);
+
 /* ---- radiance queries (ABI 2, added) ------------------------------------ */
 
 /* Scene.traceRayRecursive (stage3.zig:188-220) -- the path tracer itself --

@@ -117,6 +117,11 @@ class RenderScene:
             res["source_triangle"] = src
         return res
 
+    def segments(self, origins, dirs, t_max, any_hit: bool = False, flags: int = 0, stats: bool = False):
+        """Scene.traceRay for rays with an end t_max (a scalar or one per
+        ray), nearest or any hit: see native.Context.segments."""
+        return self.context.segments(origins, dirs, t_max, any_hit=any_hit, flags=flags, stats=stats)
+
     def radiance(self, origins, dirs, spp: int, max_bounce: int, seed: int = 0, index_base: int = 0,
                  flags: int = 0, rgb: bool = False, stats: bool = False):
         """Scene.traceRayRecursive (stage3.zig:188-220) for a batch of rays,

@@ -325,12 +325,19 @@ __device__ __forceinline__ void test_cell_keep(const TraceParams& p, uint32_t b,
 // TAU (packed walk): a frustum bound (escape.h frustum_bound lo) for this ray: the
 // crossings below it enter only empty cells; +inf: the ray meets no
 // occupied cell at all.
-template <bool STATS, int TB, bool PACKED = false, bool PK_BM = false, bool MTX = false>
+// NEAREST0 (segment queries, zrt_context_segments): the value nearest_hit.t
+// starts at (stage3.zig:154), +inf for every other caller; nothing else of
+// the walk changes.  The return value is bit-equal to it exactly when no ref
+// was kept (a kept t is below it, and nothing is below or above a NaN).
+// BOUNDED is set with it (the code for it is compiled into no other caller).
+// ANY: the walk also ends after the first cell in which a ref was kept.
+template <bool STATS, int TB, bool PACKED = false, bool PK_BM = false, bool MTX = false, bool ANY = false,
+          bool BOUNDED = false>
 __device__ __forceinline__ float trace_ray(const TraceParams& p, const uint32_t* occ, v3 o, v3 d,
                                            float& hu, float& hv, uint32_t& hidx, uint32_t& n_cells,
                                            uint32_t& n_tests, uint64_t* prof, uint32_t* wcnt = nullptr,
-                                           float tau = 0.0f, float tfar = kInf) {
-    float nearest = kInf;
+                                           float tau = 0.0f, float tfar = kInf, const float nearest0 = kInf) {
+    float nearest = nearest0;
     Dda s0;
     // (the counting build and the IEEE-division kernels keep dda_init's
     // divisions; the timed kernels take dda_init_fq's quotients: same state)
@@ -370,6 +377,11 @@ __device__ __forceinline__ float trace_ray(const TraceParams& p, const uint32_t*
         // the walk's stop: the nearest hit so far, or (TFAR, a frustum far
         // bound) the t past which every cell of the ray is empty
         float lim = s0.neg < 8u ? tfar : kInf;
+        // (a bounded segment stops at its bound from the first cell on, empty
+        // cells included; never true for nearest0 = +inf or NaN)
+        if constexpr (BOUNDED) {
+            if (nearest0 < lim) lim = nearest0;
+        }
         // the entry-face skip: the crossing t of the step into the current
         // cell (NaN: the segment's first tested cell, every ref tested)
         float tcl = __builtin_nanf("");
@@ -395,6 +407,7 @@ __device__ __forceinline__ float trace_ray(const TraceParams& p, const uint32_t*
             pkl.f0 = f0; pkl.f1 = f1; pkl.f2 = f2;
             DDAV_STEPX(s, pkl, p.occ_lowm, crossed, exited, tc);
             if (exited || lim <= tc) break;                // stage3.zig:179-182 (T_EXIT = +inf at the exit)
+            if (ANY && __float_as_uint(nearest) != __float_as_uint(nearest0)) break;   // a ref was kept
             tcl = tc;
             if (crossed) {
                 occupied = brick_occupied_v<PK_BM>(p, occ, s.pc);
@@ -433,6 +446,14 @@ __device__ __forceinline__ float trace_ray(const TraceParams& p, const uint32_t*
         float t_exit;
         DDAW_STEP(s, sh, crossed, t_exit);
         if (nearest <= t_exit) break;                      // stage3.zig:179-182
+        if (ANY && __float_as_uint(nearest) != __float_as_uint(nearest0)) break;       // a ref was kept
+        // a NaN bound makes no comparison true, the one with T_EXIT = +inf
+        // included, which ends every other walk at the grid's exit: there the
+        // step out of the exit cell itself (the stepped axis's cell index left
+        // [0, res - 1], in either direction mod 2^32) ends it
+        if constexpr (BOUNDED) {
+            if (nearest0 != nearest0 && (s.c0 > gk.rm0 || s.c1 > gk.rm1 || s.c2 > gk.rm2)) break;
+        }
         if (crossed) occupied = brick_occupied(p, occ, s.c0, s.c1, s.c2);
     }
     return nearest;
@@ -1143,7 +1164,27 @@ __device__ __forceinline__ uint32_t wave_excl_sum(uint32_t x, uint32_t lane, uin
 #endif
 // ESC: with the escape table (context_escape decides per scene); PK_BM:
 // brick-major packed words (dda.h)
-template <bool ESC, bool PK_BM>
+// QM, the query mode: kParkRender, a render's and zrt_context_trace's
+// segments (nearest starts at +inf); kParkClosest, the bounded segments of
+// zrt_context_segments: nearest starts at the queue record's second .w word
+// (the bound; a render keeps the depth there and this kernel never used it)
+// and the hit record's ref starts at 0xFFFFFFFF, which no baked ref is, so a
+// miss shows in the record whatever the bound was.  Any-hit calls run this
+// mode too and keep the record's yes / no: a third mode, in which a parked lane
+// whose test round kept a candidate was done at once, answered the same and
+// was not faster (measured and dropped).
+// What the kernel skips stays valid for any initial nearest, because each
+// skip drops only refs or cells that cannot produce a KEPT hit at all:
+//  * entry-face masks: the skipped ref was tested, with the same ray and so
+//    the same t, in the cell just left; not kept there (t >= nearest or
+//    t <= 0) it is not kept here, nearest only falls;
+//  * cull masks: the skipped ref fails Moller-Trumbore's determinant test for
+//    every direction of the bin: no t at all, whatever nearest is;
+//  * the escape stop: no cell further along the ray holds a ref, so no test
+//    follows and the hit so far, or the miss, stands;
+//  * the park release only delays lanes with nothing to test.
+constexpr int kParkRender = 0, kParkClosest = 1;
+template <bool ESC, bool PK_BM, int QM = kParkRender>
 __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const WfParams w) {
     const TraceParams& p = w.t;
     extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[];
@@ -1243,15 +1284,17 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
                 if (st == kIdle && rank < take) {
                     {
                         qi = ent_index<false>(w, cgrp, cb + rank);
+                        float bound = kInf;                        // (a query's: the record's second .w)
                         {
                             const float4 qa = w.q_in[3ull * qi], qb = w.q_in[3ull * qi + 1];
                             o = mk(qa.x, qa.y, qa.z);
                             d = mk(qb.x, qb.y, qb.z);
+                            if (QM != kParkRender) bound = qb.w;
                         }
                         {                                          // queued paths have depth >= 1
-                            nearest = kInf;
+                            nearest = bound;
                             hu = hv = 0.0f;
-                            hidx = 0;
+                            hidx = QM != kParkRender ? 0xFFFFFFFFu : 0u;
                             W.o[lane] = make_float4(o.x, o.y, o.z, 0.0f);
                             W.d[lane] = make_float4(d.x, d.y, d.z, 0.0f);
                             Dda s0;
@@ -2025,6 +2068,181 @@ constexpr uint64_t kTraceParkMin = 1ull << 19;
 constexpr uint32_t kTraceFlags = ZRT_FLAG_COUNT_STATS | ZRT_FLAG_LANE_WALK | ZRT_FLAG_MT_EXACT | ZRT_FLAG_ESCAPE |
                                  ZRT_FLAG_NO_ESCAPE | ZRT_FLAG_RELEASE | ZRT_FLAG_NO_RELEASE | ZRT_FLAG_BFCULL |
                                  ZRT_FLAG_NO_BFCULL | ZRT_TRACE_PARK;
+static_assert((ZRT_SEGMENT_ANY & (kTraceFlags | ZRT_RADIANCE_PER_SAMPLE | 0xFFFFu)) == 0u, "a bit of its own");
+
+// ---------------------------------------------------------------------------
+// Segment queries (zrt_context_segments): Scene.traceRay with nearest_hit.t
+// starting at the ray's bound t_max instead of +inf (stage3.zig:154), in
+// closest or any-hit form.  The kernels are the batch queries'
+// with three differences: the initial nearest (trace_ray's nearest0, the park
+// kernel's query modes), the any-hit exit, and the result: a miss is what left
+// nearest bit-equal to the bound (lane walk) or the ref at 0xFFFFFFFF (park
+// records), not t == +inf -- the bound may be anything, NaN included -- and
+// is stored as (+inf, 0, 0, 0xFFFFFFFF) and / or the byte 0.
+struct SegParams {
+    RayParams r;              // r.hits: a zrt_hit per ray, or null
+    const float* t_max;       // this chunk: a bound per ray, or null: t_max_all
+    float t_max_all;
+    uint8_t* occ;             // this chunk: a byte per ray (1: not missed), or null
+    uint32_t count;           // seg_walk_kernel: count the rays not missed (any-hit calls; STATS counts anyway)
+};
+
+__device__ __forceinline__ float seg_bound(const SegParams& q, uint32_t i) { return q.t_max ? q.t_max[i] : q.t_max_all; }
+// (the byte is a lane's own plain store: global_store_byte)
+__device__ __forceinline__ void seg_store(const SegParams& q, uint32_t i, bool miss, float t, float u, float v,
+                                          uint32_t ref) {
+    if (q.r.hits) {
+        uint32_t* h = q.r.hits + 4ull * i;
+        h[0] = __float_as_uint(miss ? kInf : t);
+        h[1] = miss ? 0u : __float_as_uint(u);
+        h[2] = miss ? 0u : __float_as_uint(v);
+        h[3] = miss ? 0xFFFFFFFFu : ref;
+    }
+    if (q.occ) q.occ[i] = miss ? (uint8_t)0 : (uint8_t)1;
+}
+
+// rays_walk_kernel for bounded segments: the same work distribution, the same
+// `which` split, tau = -inf and tfar = +inf.  The rays not missed are counted
+// (stats[3]) by a counting call and by every any-hit call (q.count).
+// ANY: the any-hit exit of trace_ray, instantiated for the counting kernel
+// only, whose counters it defines; the timed any-hit walks were measured
+// against the closest ones and dropped.
+template <bool STATS, bool PACKED, bool PK_BM, bool MTX, bool ANY>
+__global__ __launch_bounds__(kTraceBlock, STATS ? 1 : kWfMinWaves) void seg_walk_kernel(const SegParams q) {
+    const RayParams& r = q.r;
+    const TraceParams& p = r.w.t;
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_occ[];
+    __shared__ uint32_t s_wcnt[2 * (kTraceBlock / 64)];
+    if (r.which == kRaysRest && r.ctr[2] == 0u) return;            // (the whole grid: nothing left)
+    for (uint32_t i = threadIdx.x; i < p.occ_words; i += blockDim.x) s_occ[i] = p.occ[i];
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t* const work = r.ctr + (r.which == kRaysRest ? 1u : 0u);
+    uint64_t prof[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t n_seg = 0, n_cells = 0, n_tests = 0, n_hits = 0, n_rest = 0;
+    for (;;) {
+        uint32_t base = 0;
+        if (lane == 0) base = atomicAdd(work, 64u * kWfChunk);
+        base = __builtin_amdgcn_readfirstlane(base);
+        if (base >= r.n) break;
+        for (uint32_t sub = 0; sub < kWfChunk; ++sub) {
+            const uint32_t i = base + 64u * sub + lane;
+            if (i >= r.n) continue;
+            v3 o, d;
+            ray_load(r.rays, i, o, d);
+            const bool fast = ray_fast(d);
+            if (r.which == kRaysFast && !fast) { ++n_rest; continue; }
+            if (r.which == kRaysRest && fast) continue;
+            const float bound = seg_bound(q, i);
+            float hu = 0.0f, hv = 0.0f;
+            uint32_t hidx = 0;
+            const float t = trace_ray<STATS, kTriBatch, PACKED, PK_BM, MTX, ANY, true>(p, s_occ, o, d, hu, hv, hidx,
+                                                                                       n_cells, n_tests, prof, s_wcnt,
+                                                                                       -kInf, kInf, bound);
+            const bool miss = __float_as_uint(t) == __float_as_uint(bound);
+            ++n_seg;
+            if (!miss) ++n_hits;
+            seg_store(q, i, miss, t, hu, hv, hidx);
+        }
+    }
+    if (r.which == kRaysFast) {
+        const unsigned long long s = wave_sum(n_rest);
+        if (lane == 0 && s != 0ull) atomicAdd(&r.ctr[2], (uint32_t)s);
+    }
+    if (STATS) {
+        const unsigned long long s0 = wave_sum(n_seg), s1 = wave_sum(n_cells), s2 = wave_sum(n_tests);
+        if (lane == 0) {
+            atomicAdd(&p.stats[0], s0);
+            atomicAdd(&p.stats[1], s1);
+            atomicAdd(&p.stats[2], s2);
+        }
+    }
+    if (STATS || q.count != 0u) {
+        const unsigned long long s3 = wave_sum(n_hits);
+        if (lane == 0 && s3 != 0ull) atomicAdd(&p.stats[3], s3);
+    }
+}
+
+// rays_pack_kernel with the bound in the record's second .w word, where the
+// park kernel's query modes take it from.
+__global__ __launch_bounds__(kBlock) void seg_pack_kernel(const SegParams q) {
+    const RayParams& r = q.r;
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < 8u) r.n_in8[i * kCtr] = xcd_q0(r.n, i + 1u) - xcd_q0(r.n, i);
+    bool rest = false;
+    if (i < r.n) {
+        v3 o, d;
+        ray_load(r.rays, i, o, d);
+        r.q[3ull * i] = make_float4(o.x, o.y, o.z, __uint_as_float(i));
+        r.q[3ull * i + 1] = make_float4(d.x, d.y, d.z, seg_bound(q, i));
+        rest = !ray_fast(d);
+    }
+    const uint64_t m = __ballot(rest);
+    if (m != 0ull && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(m)) atomicAdd(&r.ctr[2], (uint32_t)__popcll(m));
+}
+
+// The park kernel's hit records as zrt_hit and / or the byte.  COUNT (any-hit
+// calls): the rays not missed into stats[3], those outside the fast domain
+// left to the kRaysRest launch that retraces them and counts them itself.
+// A counting block takes kSegOutRays * kBlock consecutive rays and adds its
+// count with one atomic (one per wave of 64 rays queued 65536 atomics of a
+// 2^22-ray call on one address: 0.75 ms, more than a third of the park kernel's
+// own time, profiles/segment_bench_cfg3_first.log).
+constexpr uint32_t kSegOutRays = 8;
+template <bool COUNT>
+__global__ __launch_bounds__(kBlock) void seg_out_kernel(const SegParams q) {
+    const RayParams& r = q.r;
+    __shared__ uint32_t s_n;
+    constexpr uint32_t per = COUNT ? kSegOutRays : 1u;
+    if (COUNT) {
+        if (threadIdx.x == 0) s_n = 0u;
+        __syncthreads();
+    }
+    const bool some_rest = COUNT && r.ctr[2] != 0u;
+    uint32_t cnt = 0;
+    for (uint32_t k = 0; k < per; ++k) {
+        const uint32_t i = (blockIdx.x * per + k) * kBlock + threadIdx.x;
+        if (i >= r.n) continue;
+        const float4 h = r.w.hit[i];
+        const uint32_t ref = __float_as_uint(h.w);
+        const bool miss = ref == 0xFFFFFFFFu;
+        seg_store(q, i, miss, h.x, h.y, h.z, ref);
+        if (COUNT && !miss) {
+            bool mine = true;
+            if (some_rest) {
+                v3 o, d;
+                ray_load(r.rays, i, o, d);
+                mine = ray_fast(d);
+            }
+            cnt += mine ? 1u : 0u;
+        }
+    }
+    if (COUNT) {
+        const unsigned long long s = wave_sum(cnt);
+        if ((threadIdx.x & 63u) == 0u && s != 0ull) atomicAdd(&s_n, (uint32_t)s);
+        __syncthreads();
+        if (threadIdx.x == 0 && s_n != 0u) atomicAdd(&r.w.t.stats[3], (unsigned long long)s_n);
+    }
+}
+
+using SegFn = void (*)(const SegParams);
+const SegFn kSegWalkBM = (SegFn)seg_walk_kernel<false, true, true, false, false>;
+const SegFn kSegWalk = (SegFn)seg_walk_kernel<false, true, false, false, false>;
+const SegFn kSegWalkWide = (SegFn)seg_walk_kernel<false, false, false, false, false>;
+const SegFn kSegWalkExact = (SegFn)seg_walk_kernel<false, false, false, true, false>;
+// [any]: closest, any-hit
+const SegFn kSegWalkCount[2] = {(SegFn)seg_walk_kernel<true, false, false, true, false>,
+                                (SegFn)seg_walk_kernel<true, false, false, true, true>};
+const SegFn kSegOut[2] = {(SegFn)seg_out_kernel<false>, (SegFn)seg_out_kernel<true>};
+// batch size from which a segment call takes the park path unasked: 2^16, the
+// smallest size tools/segment_bench.py measures; there and at 2^20 and 2^22 the
+// park path won on all three bounded ray sets (ao at two radii, shadow) in
+// both rounds, 3.5-3.8x at 2^16 on ao (profiles/segment_bench_cfg3.json).
+// Bounded rays start on surfaces and spread: the incoherent kind, which the
+// park path serves better at any size (kTraceParkMin's comment)
+constexpr uint64_t kSegParkMin = 1ull << 16;
+// bytes per ray a segment call adds to a batch query's staging: the bound and the byte
+constexpr uint64_t kSegStageBytes = 5;
 
 // ---------------------------------------------------------------------------
 // Radiance queries (zrt_context_radiance): Scene.traceRayRecursive
@@ -2216,7 +2434,10 @@ extern "C" const char* zrt_timed_kernels(void) {
     // of the scenes with edges of 2^62 or more, not timed)
     return "wf_kernelILi" ZRT_STR(ZRT_WF_MINW0) "ELb1ELb1ELb1ELb0EE,wf_kernelILi" ZRT_STR(ZRT_WF_MINW0)
            "ELb1ELb1ELb0ELb0EE,"
-           "wf_park_kernelILb1ELb1E,wf_park_kernelILb0ELb1E,wf_park_kernelILb1ELb0E,wf_park_kernelILb0ELb0E,"
+           // (the park kernel's last argument: the query mode, a render's first,
+           // then zrt_context_segments', under the same rules)
+           "wf_park_kernelILb1ELb1ELi0E,wf_park_kernelILb0ELb1ELi0E,wf_park_kernelILb1ELb0ELi0E,wf_park_kernelILb0ELb0ELi0E,"
+           "wf_park_kernelILb1ELb1ELi1E,wf_park_kernelILb0ELb1ELi1E,wf_park_kernelILb1ELb0ELi1E,wf_park_kernelILb0ELb0ELi1E,"
            "wf_shade_kernelILb1ELb0EE,wf_shade_kernelILb1ELb1EE,wf_kernelILi" ZRT_STR(ZRT_WF_MINW) "ELb0ELb1ELb1ELb0EE,wf_kernelILi" ZRT_STR(
                ZRT_WF_MINW) "ELb0ELb1ELb0ELb0EE";
 #undef ZRT_STR
@@ -2396,6 +2617,13 @@ struct LaunchPlan {
     uint32_t test_min, refill_min, rel_min, rel_emin;
 };
 
+// The park kernel of a plan (escape table, word layout) in query mode QM.
+template <int QM>
+static WfFn park_fn(bool esc, bool pbm) {
+    return pbm ? (esc ? (WfFn)wf_park_kernel<true, true, QM> : (WfFn)wf_park_kernel<false, true, QM>)
+               : (esc ? (WfFn)wf_park_kernel<true, false, QM> : (WfFn)wf_park_kernel<false, false, QM>);
+}
+
 static void plan_park_block(LaunchPlan& pl, int block) {
     pl.park_block = block;
     pl.lds_park = 4ull * pl.occx_ldsw + (size_t)(block / 64) * sizeof(ParkSlot);
@@ -2442,8 +2670,7 @@ static int resolve_plan(zrt_context* c, uint32_t flags, bool counting, bool want
         }
     }
     pl.bfc = c->d_bfc && !(flags & ZRT_FLAG_NO_BFCULL) && (c->bfc_on || (flags & ZRT_FLAG_BFCULL));
-    pl.f_park = pl.pbm ? (pl.esc ? (WfFn)wf_park_kernel<true, true> : (WfFn)wf_park_kernel<false, true>)
-                       : (pl.esc ? (WfFn)wf_park_kernel<true, false> : (WfFn)wf_park_kernel<false, false>);
+    pl.f_park = park_fn<kParkRender>(pl.esc, pl.pbm);
     pl.f_walk = pl.mtx ? kWfBounceExact : (pl.packed ? (pl.pbm ? kWfBounceBM : kWfBounce) : kWfBounceWide);
     const bool lmats = c->nmat <= kLdsMats;
     pl.s_next = lmats ? (WfFn)wf_shade_kernel<true> : (WfFn)wf_shade_kernel<false>;
@@ -2549,19 +2776,48 @@ struct RayLaunch {
     RayFn f_exact;
     bool park;
     uint32_t grid_fast, grid_exact, grid_park;
+    WfFn f_park;              // the plan's park kernel in this call's query mode
+    // a segment call (seg): the bounded kernels in place of f_fast / f_exact
+    // (s_fast null as f_fast), of rays_pack_kernel / rays_out_kernel, and what
+    // SegParams holds besides the rays
+    bool seg;
+    SegFn s_fast, s_exact, s_out;
+    const float* t_max;
+    float t_max_all;
+    uint8_t* occ;
+    bool count;               // an any-hit call: its kernels count the rays not missed
 };
-static int ray_launch(const zrt_context* c, const LaunchPlan& pl, bool counting, bool park, uint32_t grid_park,
-                      RayLaunch& rl) {
+// `seg`: -1 a batch or radiance query, 0 / 1 a segment call in closest / any-hit form
+static int ray_launch(const zrt_context* c, const LaunchPlan& pl, bool counting, bool park, RayLaunch& rl,
+                      int seg = -1) {
     int rc;
     rl = RayLaunch{};
-    rl.f_fast = (counting || pl.mtx) ? nullptr : pl.packed ? (pl.pbm ? kRaysWalkBM : kRaysWalk) : kRaysWalkWide;
-    rl.f_exact = counting ? kRaysWalkCount : kRaysWalkExact;
+    const bool fast = !(counting || pl.mtx);
     rl.park = park;
-    rl.grid_park = grid_park;
-    if (rl.f_fast && !park &&
-        (rc = resident_blocks(c, (const void*)rl.f_fast, kTraceThreads, pl.lds_wf, &rl.grid_fast)) != ZRT_OK)
+    rl.seg = seg >= 0;
+    const void *k_fast = nullptr, *k_exact;
+    if (rl.seg) {
+        // (any-hit calls: the closest kernels, the yes / no kept; only a counting
+        // call walks with the any-hit exit, which its counters are defined by)
+        rl.f_park = park_fn<kParkClosest>(pl.esc, pl.pbm);
+        rl.s_fast = !fast ? nullptr : pl.packed ? (pl.pbm ? kSegWalkBM : kSegWalk) : kSegWalkWide;
+        rl.s_exact = counting ? kSegWalkCount[seg] : kSegWalkExact;
+        rl.count = seg != 0;
+        rl.s_out = kSegOut[seg];
+        k_fast = (const void*)rl.s_fast;
+        k_exact = (const void*)rl.s_exact;
+    } else {
+        rl.f_park = pl.f_park;
+        rl.f_fast = !fast ? nullptr : pl.packed ? (pl.pbm ? kRaysWalkBM : kRaysWalk) : kRaysWalkWide;
+        rl.f_exact = counting ? kRaysWalkCount : kRaysWalkExact;
+        k_fast = (const void*)rl.f_fast;
+        k_exact = (const void*)rl.f_exact;
+    }
+    // occupancy-sized persistent grids
+    if (park && (rc = resident_blocks(c, (const void*)rl.f_park, pl.park_block, pl.lds_park, &rl.grid_park)) != ZRT_OK)
         return rc;
-    return resident_blocks(c, (const void*)rl.f_exact, kTraceThreads, pl.lds_wf, &rl.grid_exact);
+    if (k_fast && !park && (rc = resident_blocks(c, k_fast, kTraceThreads, pl.lds_wf, &rl.grid_fast)) != ZRT_OK) return rc;
+    return resident_blocks(c, k_exact, kTraceThreads, pl.lds_wf, &rl.grid_exact);
 }
 
 // A chunk's n first segments on the context's stream, over the identity queue
@@ -2579,19 +2835,37 @@ static int trace_first_segments(const zrt_context* c, const LaunchPlan& pl, cons
     Q.w.t.S = 1;
     Q.w.t.total = n;
     Q.w.t.sdiv = div_magic(1);
+    // a segment call: the same launches with its kernels (SegParams around Q)
+    auto thread_per_ray = [&](void (*f)(const RayParams), SegFn sf) {
+        // (the counting seg_out_kernel: kSegOutRays rays per thread)
+        const uint32_t per = sf == kSegOut[1] ? kSegOutRays : 1u;
+        if (rl.seg)
+            hipLaunchKernelGGL(sf, dim3((nblk + per - 1) / per), dim3(kBlock), 0, c->stream,
+                               SegParams{Q, rl.t_max, rl.t_max_all, rl.occ, rl.count ? 1u : 0u});
+        else
+            hipLaunchKernelGGL(f, dim3(nblk), dim3(kBlock), 0, c->stream, Q);
+    };
+    auto walk = [&](RayFn f, SegFn sf, uint32_t grid) {
+        if (rl.seg)
+            hipLaunchKernelGGL(sf, dim3(std::min(grid, nblk)), dim3(kTraceThreads), pl.lds_wf, c->stream,
+                               SegParams{Q, rl.t_max, rl.t_max_all, rl.occ, rl.count ? 1u : 0u});
+        else
+            hipLaunchKernelGGL(f, dim3(std::min(grid, nblk)), dim3(kTraceThreads), pl.lds_wf, c->stream, Q);
+    };
+    const bool fast = rl.seg ? rl.s_fast != nullptr : rl.f_fast != nullptr;
     if (rl.park) {
         Q.which = kRaysAll;
-        if (pack_out) hipLaunchKernelGGL(rays_pack_kernel, dim3(nblk), dim3(kBlock), 0, c->stream, Q);
-        hipLaunchKernelGGL(pl.f_park, dim3(rl.grid_park), dim3(pl.park_block), pl.lds_park, c->stream, Q.w);
-        if (pack_out) hipLaunchKernelGGL(rays_out_kernel, dim3(nblk), dim3(kBlock), 0, c->stream, Q);
+        if (pack_out) thread_per_ray(rays_pack_kernel, seg_pack_kernel);
+        hipLaunchKernelGGL(rl.f_park, dim3(rl.grid_park), dim3(pl.park_block), pl.lds_park, c->stream, Q.w);
+        if (pack_out) thread_per_ray(rays_out_kernel, rl.s_out);
         *launches += pack_out ? 3 : 1;
-    } else if (rl.f_fast) {
+    } else if (fast) {
         Q.which = kRaysFast;
-        hipLaunchKernelGGL(rl.f_fast, dim3(std::min(rl.grid_fast, nblk)), dim3(kTraceThreads), pl.lds_wf, c->stream, Q);
+        walk(rl.f_fast, rl.s_fast, rl.grid_fast);
         ++*launches;
     }
-    Q.which = rl.park || rl.f_fast ? kRaysRest : kRaysAll;
-    hipLaunchKernelGGL(rl.f_exact, dim3(std::min(rl.grid_exact, nblk)), dim3(kTraceThreads), pl.lds_wf, c->stream, Q);
+    Q.which = rl.park || fast ? kRaysRest : kRaysAll;
+    walk(rl.f_exact, rl.s_exact, rl.grid_exact);
     ++*launches;
     HIP_TRY(hipGetLastError());
     return ZRT_OK;
@@ -3128,18 +3402,31 @@ extern "C" int zrt_context_profile(const zrt_context* c, zrt_kernel_profile* out
 //               -> rays_out_kernel, then the kRaysRest launch as above.
 // The park path shares pass set 0's queue, hit records and counters with the
 // renders; each use writes what it reads first, so nothing carries over.
-extern "C" int zrt_context_trace(zrt_context* c, const zrt_ray_batch* b, zrt_stats* stats) {
-    if (!c || !b) return ZRT_ERR_INVALID_ARG;
-    if ((b->flags & ~kTraceFlags) != 0u || b->on_device > 1u) return ZRT_ERR_INVALID_ARG;
+//
+// zrt_context_segments is the same call -- plan, chunk loop,
+// launches, stats -- with the bounded kernels (ray_launch's `seg`) and two
+// more per-ray arrays: the bounds, staged behind a chunk's rays, and the
+// occlusion bytes, staged behind its hit records.
+struct RayQuery {
+    uint64_t num_rays;
+    const float* rays;
+    zrt_hit* hits;            // (a segment call: may be null)
+    uint32_t on_device, flags;
+    int seg;                  // -1: zrt_context_trace; 0 / 1: segments, closest / any-hit
+    const float* t_max;
+    float t_max_all;
+    uint8_t* occ;
+};
+static int query_rays(zrt_context* c, const RayQuery* b, zrt_stats* stats) {
     zrt_stats st{};
-    if (b->num_rays == 0) { if (stats) *stats = st; return ZRT_OK; }
-    if (!b->rays || !b->hits) return ZRT_ERR_INVALID_ARG;
     DeviceGuard g(c->device);
+    const bool seg = b->seg >= 0;
 
     const bool counting = (b->flags & ZRT_FLAG_COUNT_STATS) != 0;
     LaunchPlan pl;
     int rc;
-    if ((rc = resolve_plan(c, b->flags, counting, (b->flags & ZRT_TRACE_PARK) || b->num_rays >= kTraceParkMin,
+    if ((rc = resolve_plan(c, b->flags, counting,
+                           (b->flags & ZRT_TRACE_PARK) || b->num_rays >= (seg ? kSegParkMin : kTraceParkMin),
                            b->num_rays >= kSetsMinSamples, pl)) != ZRT_OK)
         return rc;
     const bool park = pl.park;
@@ -3148,14 +3435,16 @@ extern "C" int zrt_context_trace(zrt_context* c, const zrt_ray_batch* b, zrt_sta
     // memory (device_budget; of pass set 0 this call reuses the queue and the
     // hit records only, so only those count as held)
     zrt_context::PassSet& ps = c->set[0];
-    const uint64_t per_ray = (b->on_device ? 0ull : 40ull) + (park ? 64ull : 0ull);
+    const uint64_t per_ray = (b->on_device ? 0ull : 40ull + (seg ? kSegStageBytes : 0ull)) + (park ? 64ull : 0ull);
     const size_t held = 4ull * (c->rays_cap + c->hits_cap) + 16ull * (ps.q0_cap + ps.hit_cap) + c->bfc_bytes;
     const size_t budget = device_budget(c, held);
     uint64_t chunk = std::min<uint64_t>(kTraceChunk, b->num_rays);
     if (per_ray) chunk = std::max<uint64_t>(64, std::min<uint64_t>(chunk, budget / per_ray));
+    // staging words of a host batch's chunk: rays (+ bounds), hit records (+ bytes)
+    const uint64_t rays_words = 6 * chunk + (seg ? chunk : 0), hits_words = 4 * chunk + (seg ? (chunk + 3) / 4 : 0);
     if (!b->on_device) {
-        if ((rc = grow(&c->d_rays, &c->rays_cap, 6 * chunk)) != ZRT_OK) return rc;
-        if ((rc = grow(&c->d_hits, &c->hits_cap, 4 * chunk)) != ZRT_OK) return rc;
+        if ((rc = grow(&c->d_rays, &c->rays_cap, rays_words)) != ZRT_OK) return rc;
+        if ((rc = grow(&c->d_hits, &c->hits_cap, hits_words)) != ZRT_OK) return rc;
     }
     const size_t ctr_words = wfc_words(0);         // (a render's smallest; this call uses 16 counters)
     if (park) {
@@ -3164,19 +3453,17 @@ extern "C" int zrt_context_trace(zrt_context* c, const zrt_ray_batch* b, zrt_sta
         if ((rc = grow(&ps.wfc, &ps.wfc_cap, ctr_words)) != ZRT_OK) return rc;
     }
     // capacity guard: every buffer a launch below writes holds a chunk
-    if ((!b->on_device && (shortfall("rays", c->d_rays, c->rays_cap, 6 * chunk) ||
-                           shortfall("hits", c->d_hits, c->hits_cap, 4 * chunk))) ||
+    if ((!b->on_device && (shortfall("rays", c->d_rays, c->rays_cap, rays_words) ||
+                           shortfall("hits", c->d_hits, c->hits_cap, hits_words))) ||
         (park && (shortfall("q0", ps.q0, ps.q0_cap, 3 * chunk) || shortfall("hit records", ps.hit, ps.hit_cap, chunk) ||
                   shortfall("counters", ps.wfc, ps.wfc_cap, ctr_words))))
         return ZRT_ERR_INVALID_ARG;
     if ((rc = event_pool(c->ev_trace, 2)) != ZRT_OK) return rc;
 
     // occupancy-sized persistent grids (no more blocks than a chunk has work for)
-    uint32_t grid_park = 0;
-    if (park && (rc = resident_blocks(c, (const void*)pl.f_park, pl.park_block, pl.lds_park, &grid_park)) != ZRT_OK)
-        return rc;
     RayLaunch rl;
-    if ((rc = ray_launch(c, pl, counting, park, grid_park, rl)) != ZRT_OK) return rc;
+    if ((rc = ray_launch(c, pl, counting, park, rl, b->seg)) != ZRT_OK) return rc;
+    rl.t_max_all = b->t_max_all;
 
     RayParams R;
     memset(&R, 0, sizeof R);
@@ -3202,11 +3489,18 @@ extern "C" int zrt_context_trace(zrt_context* c, const zrt_ray_batch* b, zrt_sta
         const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, b->num_rays - off);
         if (b->on_device) {
             R.rays = b->rays + 6 * off;
-            R.hits = reinterpret_cast<uint32_t*>(b->hits + off);
+            R.hits = b->hits ? reinterpret_cast<uint32_t*>(b->hits + off) : nullptr;
+            rl.t_max = b->t_max ? b->t_max + off : nullptr;
+            rl.occ = b->occ ? b->occ + off : nullptr;
         } else {
             HIP_TRY(hipMemcpyAsync(c->d_rays, b->rays + 6 * off, 24ull * n, hipMemcpyHostToDevice, c->stream));
             R.rays = c->d_rays;
-            R.hits = c->d_hits;
+            R.hits = b->hits ? c->d_hits : nullptr;
+            if (b->t_max) {
+                HIP_TRY(hipMemcpyAsync(c->d_rays + 6 * chunk, b->t_max + off, 4ull * n, hipMemcpyHostToDevice, c->stream));
+                rl.t_max = c->d_rays + 6 * chunk;
+            }
+            if (b->occ) rl.occ = reinterpret_cast<uint8_t*>(c->d_hits + 4 * chunk);
             HIP_TRY(hipEventRecord(c->ev_trace[0], c->stream));
         }
         HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
@@ -3215,7 +3509,8 @@ extern "C" int zrt_context_trace(zrt_context* c, const zrt_ray_batch* b, zrt_sta
         if ((rc = trace_first_segments(c, pl, rl, R, n, true, &launches)) != ZRT_OK) return rc;
         if (!b->on_device) {
             HIP_TRY(hipEventRecord(c->ev_trace[1], c->stream));
-            HIP_TRY(copy_sync(b->hits + off, c->d_hits, 16ull * n, hipMemcpyDeviceToHost, c->stream));
+            if (b->hits) HIP_TRY(copy_sync(b->hits + off, c->d_hits, 16ull * n, hipMemcpyDeviceToHost, c->stream));
+            if (b->occ) HIP_TRY(copy_sync(b->occ + off, rl.occ, n, hipMemcpyDeviceToHost, c->stream));
             float t = 0.0f;
             HIP_TRY(hipEventElapsedTime(&t, c->ev_trace[0], c->ev_trace[1]));
             st.trace_kernel_ms += t;
@@ -3223,15 +3518,40 @@ extern "C" int zrt_context_trace(zrt_context* c, const zrt_ray_batch* b, zrt_sta
     }
     if ((rc = finish_query(c, b->on_device != 0, launches, st)) != ZRT_OK) return rc;
     st.segments = b->num_rays;
-    if (counting) {
+    if (counting || b->seg == 1) {                 // (an any-hit call counts its bytes in every call)
         unsigned long long hs[4];
         HIP_TRY(copy_sync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
-        st.cells_visited = hs[1];
-        st.triangle_tests = hs[2];
+        if (counting) {
+            st.cells_visited = hs[1];
+            st.triangle_tests = hs[2];
+        }
         st.hits = hs[3];
     }
     if (stats) *stats = st;
     return ZRT_OK;
+}
+
+extern "C" int zrt_context_trace(zrt_context* c, const zrt_ray_batch* b, zrt_stats* stats) {
+    if (!c || !b) return ZRT_ERR_INVALID_ARG;
+    if ((b->flags & ~kTraceFlags) != 0u || b->on_device > 1u) return ZRT_ERR_INVALID_ARG;
+    if (b->num_rays == 0) { if (stats) *stats = zrt_stats{}; return ZRT_OK; }
+    if (!b->rays || !b->hits) return ZRT_ERR_INVALID_ARG;
+    const RayQuery q{b->num_rays, b->rays, b->hits, b->on_device, b->flags, -1, nullptr, 0.0f, nullptr};
+    return query_rays(c, &q, stats);
+}
+
+// Bounded segments, closest or any-hit: see include/zrt.h and DESIGN 5.13.
+extern "C" int zrt_context_segments(zrt_context* c, const zrt_segment_batch* b, zrt_stats* stats) {
+    if (!c || !b) return ZRT_ERR_INVALID_ARG;
+    if ((b->flags & ~(kTraceFlags | ZRT_SEGMENT_ANY)) != 0u || b->on_device > 1u || b->_reserved != 0u)
+        return ZRT_ERR_INVALID_ARG;
+    const bool any = (b->flags & ZRT_SEGMENT_ANY) != 0;
+    if (any && b->hits) return ZRT_ERR_INVALID_ARG;
+    if (b->num_rays == 0) { if (stats) *stats = zrt_stats{}; return ZRT_OK; }
+    if (!b->rays || (!b->hits && !b->occluded)) return ZRT_ERR_INVALID_ARG;
+    const RayQuery q{b->num_rays, b->rays, b->hits, b->on_device, b->flags & ~ZRT_SEGMENT_ANY, any ? 1 : 0,
+                     b->t_max, b->t_max_all, b->occluded};
+    return query_rays(c, &q, stats);
 }
 
 // Scene.traceRayRecursive (stage3.zig:188-220) for a batch of rays: see
@@ -3322,7 +3642,7 @@ extern "C" int zrt_context_radiance(zrt_context* c, const zrt_radiance_batch* b,
     RayLaunch rl{};
     uint32_t grid_fan = 0;
     if (!per_sample) {
-        if ((rc = ray_launch(c, pl, false, park_first, grids.park, rl)) != ZRT_OK) return rc;
+        if ((rc = ray_launch(c, pl, false, park_first, rl)) != ZRT_OK) return rc;
         if ((rc = resident_blocks(c, (const void*)f_fan, kTraceThreads, pl.lds_shade, &grid_fan)) != ZRT_OK) return rc;
     }
 

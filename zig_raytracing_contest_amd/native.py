@@ -28,6 +28,7 @@ FLAG_RELEASE, FLAG_NO_RELEASE = 0x800, 0x1000
 FLAG_BFCULL, FLAG_NO_BFCULL = 0x2000, 0x4000
 TRACE_PARK = 0x10000       # ZRT_TRACE_PARK (zrt_ray_batch / zrt_radiance_batch flags only)
 RADIANCE_PER_SAMPLE = 0x20000   # ZRT_RADIANCE_PER_SAMPLE (zrt_radiance_batch.flags only)
+SEGMENT_ANY = 0x40000      # ZRT_SEGMENT_ANY (zrt_segment_batch.flags only)
 MISS = 0xFFFFFFFF          # zrt_hit.triangle of a ray that hit nothing
 # zrt_kernel_profile classes (include/zrt.h)
 KERNEL_CLASSES = ("primary", "park", "shade", "bounce", "resolve", "count")
@@ -127,6 +128,12 @@ class RayBatch(C.Structure):
                 ("on_device", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class SegmentBatch(C.Structure):
+    _fields_ = [("num_rays", C.c_uint64), ("rays", C.c_void_p), ("t_max", C.c_void_p), ("hits", C.c_void_p),
+                ("occluded", C.c_void_p), ("on_device", C.c_uint32), ("flags", C.c_uint32),
+                ("t_max_all", C.c_float), ("_reserved", C.c_uint32)]
+
+
 class RadianceBatch(C.Structure):
     _fields_ = [("num_rays", C.c_uint64), ("rays", C.c_void_p), ("radiance", C.c_void_p), ("rgb", C.c_void_p),
                 ("on_device", C.c_uint32), ("flags", C.c_uint32), ("num_samples", C.c_uint32),
@@ -141,7 +148,7 @@ EXPORTS = [
     "zrt_gltf_load", "zrt_gltf_soup", "zrt_gltf_materials", "zrt_gltf_camera", "zrt_gltf_free",
     "zrt_camera_from_matrix", "zrt_probe", "zrt_timed_kernels", "zrt_context_profile", "zrt_context_trace",
     "zrt_group_create", "zrt_group_create_built", "zrt_group_render", "zrt_group_context", "zrt_group_destroy",
-    "zrt_context_radiance",
+    "zrt_context_radiance", "zrt_context_segments",
 ]
 
 
@@ -180,6 +187,7 @@ def lib():
     L.zrt_context_destroy.argtypes = [C.c_void_p]
     L.zrt_context_destroy.restype = None
     L.zrt_context_radiance.argtypes = [C.c_void_p, C.POINTER(RadianceBatch), C.POINTER(Stats)]
+    L.zrt_context_segments.argtypes = [C.c_void_p, C.POINTER(SegmentBatch), C.POINTER(Stats)]
     if hasattr(L, "zrt_group_create"):     # ABI 2 (an ABI-1 build: tools/ A/B baselines only)
         L.zrt_group_create.argtypes = [C.POINTER(Scene), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
         L.zrt_group_create_built.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -432,6 +440,84 @@ class Context:
         st = self.trace_raw(n, rays.ctypes.data if n else None, hits.ctypes.data if n else None, False, flags)
         return {"t": hits["t"].copy(), "u": hits["u"].copy(), "v": hits["v"].copy(),
                 "triangle": hits["triangle"].copy(), "stats": st}
+
+    def segments_raw(self, num_rays: int, rays_ptr, t_max_ptr, hits_ptr, occluded_ptr, on_device: bool,
+                     flags: int = 0, t_max_all: float = float("inf"), reserved: int = 0):
+        """zrt_context_segments on raw pointers; returns the stats dict."""
+        batch = SegmentBatch(int(num_rays), rays_ptr, t_max_ptr, hits_ptr, occluded_ptr, 1 if on_device else 0,
+                             int(flags), float(t_max_all), int(reserved))
+        st = Stats()
+        check(lib().zrt_context_segments(self._h, C.byref(batch), C.byref(st)), "zrt_context_segments")
+        return st.as_dict()
+
+    def segments(self, origins, dirs, t_max, any_hit: bool = False, flags: int = 0, stats: bool = False):
+        """Scene.traceRay for n rays with an end (zrt_context_segments): ray i
+        is traced with its nearest hit starting at t_max[i] -- `t_max` a
+        scalar for every ray or n values, in the ray's own parameter (`dirs`
+        need not be unit length; unit directions take the fast kernels).  A
+        ref at exactly t_max is not a hit; t_max <= 0 or NaN is a miss.
+
+        Two (n, 3) float32 numpy arrays give {"t", "u", "v", "triangle"} as in
+        trace() (a miss is (+inf, 0, 0, MISS)), "occluded", an (n,) bool
+        array, and "stats".  With any_hit=True only "occluded" and "stats"
+        come back, the walk of a ray ending at its first hit; "stats" then
+        holds "hits" in every call.
+
+        Two (n, 3) float32 CUDA tensors (torch-ROCm) on the context's device
+        (and `t_max` a float or an (n,) float32 tensor there) are traced in
+        place, after a sync of torch's current stream: {"hits": an (n, 4)
+        float32 CUDA tensor as in trace() (not with any_hit), "occluded": an
+        (n,) torch.bool CUDA tensor, "stats"}."""
+        flags = int(flags) | (FLAG_COUNT_STATS if stats else 0) | (SEGMENT_ANY if any_hit else 0)
+        if type(origins).__module__.split(".")[0] == "torch":
+            import torch
+            if not (origins.is_cuda and dirs.is_cuda and origins.device == dirs.device):
+                raise ValueError("segments: torch inputs must be CUDA tensors on the context's device")
+            if origins.dtype != torch.float32 or dirs.dtype != torch.float32:
+                raise ValueError("segments: float32 tensors expected")
+            if origins.dim() != 2 or origins.shape[1] != 3 or origins.shape != dirs.shape:
+                raise ValueError("segments: two (n, 3) tensors expected")
+            n = int(origins.shape[0])
+            tm, tm_all = None, float("inf")
+            if torch.is_tensor(t_max) and t_max.dim() > 0:
+                if t_max.device != origins.device or t_max.dtype != torch.float32 or t_max.shape != (n,):
+                    raise ValueError("segments: t_max must be a float or an (n,) float32 tensor on the rays' device")
+                tm = t_max.contiguous()
+            else:
+                tm_all = float(t_max)
+            rays = torch.cat([origins, dirs], dim=1).contiguous()
+            hits = None if any_hit else torch.empty((n, 4), dtype=torch.float32, device=origins.device)
+            occ = torch.empty((n,), dtype=torch.bool, device=origins.device)     # one byte per ray, 0 / 1
+            torch.cuda.current_stream(origins.device).synchronize()
+            st = self.segments_raw(n, rays.data_ptr() if n else None, tm.data_ptr() if tm is not None and n else None,
+                                   hits.data_ptr() if hits is not None and n else None,
+                                   occ.data_ptr() if n else None, True, flags, tm_all)
+            res = {"occluded": occ, "stats": st}
+            if hits is not None:
+                res["hits"] = hits
+            return res
+        o = np.asarray(origins, np.float32)
+        d = np.asarray(dirs, np.float32)
+        if o.ndim != 2 or o.shape[1] != 3 or o.shape != d.shape:
+            raise ValueError("segments: two (n, 3) arrays expected")
+        n = o.shape[0]
+        tm, tm_all = None, float("inf")
+        if np.ndim(t_max) == 0:
+            tm_all = float(t_max)
+        else:
+            tm = np.ascontiguousarray(t_max, np.float32)
+            if tm.shape != (n,):
+                raise ValueError("segments: t_max must be a scalar or n values")
+        rays = np.ascontiguousarray(np.concatenate([o, d], axis=1))
+        hits = None if any_hit else np.empty(n, HIT_DTYPE)
+        occ = np.zeros(n, np.uint8)
+        st = self.segments_raw(n, rays.ctypes.data if n else None, tm.ctypes.data if tm is not None and n else None,
+                               hits.ctypes.data if hits is not None and n else None,
+                               occ.ctypes.data if n else None, False, flags, tm_all)
+        res = {"occluded": occ.view(np.bool_), "stats": st}
+        if hits is not None:
+            res.update(t=hits["t"].copy(), u=hits["u"].copy(), v=hits["v"].copy(), triangle=hits["triangle"].copy())
+        return res
 
     def radiance_raw(self, num_rays: int, rays_ptr, radiance_ptr, rgb_ptr, on_device: bool, spp: int,
                      max_bounce: int, seed: int = 0, index_base: int = 0, flags: int = 0):
