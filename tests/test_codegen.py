@@ -241,5 +241,33 @@ def test_kernel_argument_check_sees_a_kernarg_address():
                         "v_readlane_b32 s0, v70, 31"], 2, (0, 3)) == "spill"
 
 
+def test_isa_diff_controls():
+    """tools/isa_diff.py on synthetic disassembly: addresses, encodings and
+    the symbol in a branch comment do not count; one changed instruction is
+    reported as that instruction, another length as a diff; a rename pairs a
+    kernel with its old name, and a kernel without a partner is reported."""
+    import isa_diff
+
+    def kern(sym, base, body):
+        return [(base + 4 * k, f"\t{t}    // {base + 4 * k:012X}: BF8C0000 <{sym}+0x{4 * k:x}>") for k, t in enumerate(body)]
+
+    body = ["s_load_dword s3, s[0:1], 0x248", "s_waitcnt lgkmcnt(0)", "v_cmp_eq_f32_e32 vcc, s3, v0",
+            "s_cbranch_execz 27", "s_endpgm"]
+    old = {"a(P)": kern("_Z1a1P", 0x1000, body)}
+    assert isa_diff.compare(old["a(P)"], kern("_Z1b1Q", 0x5000, body)) == []
+    lines, bad = isa_diff.report(old, {"b(Q)": kern("_Z1b1Q", 0x5000, body)}, {"a(P)": "b(Q)"})
+    assert bad == 0 and lines == ["b(Q) (was a(P)): same (5 instructions)"]
+
+    changed = body[:2] + ["v_cmp_neq_f32_e32 vcc, s3, v0"] + body[3:]
+    d = isa_diff.compare(old["a(P)"], kern("_Z1a1P", 0x1000, changed))
+    assert d == ["2: v_cmp_eq_f32_e32 vcc, s3, v0  ->  v_cmp_neq_f32_e32 vcc, s3, v0"]
+
+    d = isa_diff.compare(old["a(P)"], kern("_Z1a1P", 0x1000, body[:4] + ["s_nop 0"] + body[4:]))
+    assert [l for l in d if not l.startswith("@@")] == ["+s_nop 0"]
+
+    lines, bad = isa_diff.report(old, {"b(Q)": kern("_Z1b1Q", 0x5000, body)})
+    assert bad == 2 and lines == ["a(P): only in old", "b(Q): only in new"]
+
+
 def ins_after(ins, e, n=40):
     return [t.strip() for _, t in ins[e + 1:e + 1 + n]]

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Device time of segment queries (zrt_context_segments) on the cfg3 contest
 scene against zrt_context_trace on the same rays in the same process -- the
-yardstick: its kernels are untouched by the segment call -- for 2^16, 2^20 and
+yardstick: its kernels compile in none of the bound's code -- for 2^16, 2^20 and
 2^22 rays, lane walk and park path, on
 
   control   trace_bench.py's incoherent set at t_max = +inf (the new call must

@@ -1895,9 +1895,18 @@ const WfFn kWfPrimaryExact = (WfFn)wf_kernel<kWfMinWaves, true, false, false, tr
 const WfFn kWfBounceExact = (WfFn)wf_kernel<kWfMinWaves, false, false, false, true>;
 
 // ---------------------------------------------------------------------------
-// Batch ray queries (zrt_context_trace): Scene.traceRay (stage3.zig:152-186)
-// for caller-given rays through the render's own walks -- trace_ray per lane,
-// or wf_park_kernel over an identity queue (ray i = queue entry i).
+// Batch ray queries (zrt_context_trace) and segment queries
+// (zrt_context_segments): Scene.traceRay (stage3.zig:152-186) for caller-given
+// rays through the render's own walks -- trace_ray per lane, or wf_park_kernel
+// over an identity queue (ray i = queue entry i).  One set of kernels: the
+// segment call's are the SEG instantiations, in which nearest_hit.t starts at
+// the ray's bound t_max instead of +inf (stage3.zig:154), in closest or
+// any-hit form.  Three things differ: the initial nearest
+// (trace_ray's nearest0, the park kernel's query modes), the any-hit exit, and
+// the result: a miss is what left nearest bit-equal to the bound (lane walk)
+// or the ref at 0xFFFFFFFF (park records), not t == +inf -- the bound may be
+// anything, NaN included -- and is stored as (+inf, 0, 0, 0xFFFFFFFF) and / or
+// the byte 0.
 //
 // Directions need not be unit length, which the render's are.  Its kernels
 // lean on that in three places:
@@ -1918,16 +1927,21 @@ const WfFn kWfBounceExact = (WfFn)wf_kernel<kWfMinWaves, false, false, false, tr
 // reference's arithmetic for any direction.  The frustum bounds do not apply
 // to a query: tau = -inf (no fast-forward, not even over crossings at
 // negative t, which tau = 0 would skip) and tfar = +inf.
-struct RayParams {
+struct QueryParams {
     WfParams w;               // w.t: grid and scene; the park path's queue, hit records and counters
     const float* rays;        // this chunk: 6 floats per ray (origin, direction)
-    uint32_t* hits;           // this chunk: a zrt_hit per ray as 4 u32 (4-byte aligned)
-    float4* q;                // rays_pack_kernel: the queue (w.q_in)
-    uint32_t* n_in8;          // rays_pack_kernel: the queue's region counts (w.n_in8)
+    uint32_t* hits;           // this chunk: a zrt_hit per ray as 4 u32 (4-byte aligned); a segment call: or null
+    float4* q;                // query_pack_kernel: the queue (w.q_in)
+    uint32_t* n_in8;          // query_pack_kernel: the queue's region counts (w.n_in8)
     uint32_t n;               // rays of this chunk (the host cuts a batch into chunks of <= kTraceChunk)
     uint32_t which;           // kRaysAll, kRaysFast or kRaysRest
     uint32_t* ctr;            // [0], [1]: work counters of the chunk's two walk launches;
                               // [2]: its rays outside the fast domain
+    // a segment call (the SEG kernels; zero in every other)
+    const float* t_max;       // this chunk: a bound per ray, or null: t_max_all
+    float t_max_all;
+    uint8_t* occ;             // this chunk: a byte per ray (1: not missed), or null
+    uint32_t count;           // query_walk_kernel: count the rays not missed (any-hit calls; STATS counts anyway)
 };
 constexpr uint32_t kRaysAll = 0, kRaysFast = 1, kRaysRest = 2;
 
@@ -1940,15 +1954,22 @@ __device__ __forceinline__ void ray_load(const float* rays, uint32_t i, v3& o, v
     o = mk(q[0], q[1], q[2]);
     d = mk(q[3], q[4], q[5]);
 }
-// The zrt_hit of a ray; a miss (nearest stayed +inf: a kept t is below it) is
-// (+inf, 0, 0, 0xFFFFFFFF), which the reference leaves undefined.
-__device__ __forceinline__ void ray_store_hit(uint32_t* hits, uint32_t i, float t, float u, float v, uint32_t ref) {
-    const bool miss = t == kInf;
-    uint32_t* h = hits + 4ull * i;
-    h[0] = __float_as_uint(t);
-    h[1] = miss ? 0u : __float_as_uint(u);
-    h[2] = miss ? 0u : __float_as_uint(v);
-    h[3] = miss ? 0xFFFFFFFFu : ref;
+__device__ __forceinline__ float query_bound(const QueryParams& q, uint32_t i) { return q.t_max ? q.t_max[i] : q.t_max_all; }
+// The zrt_hit of a ray and / or its byte (a lane's own plain store:
+// global_store_byte); a miss is (+inf, 0, 0, 0xFFFFFFFF), which the reference
+// leaves undefined.  Without SEG a miss is t == +inf (nearest stayed there: a
+// kept t is below it), hits is not null and there is no byte.
+template <bool SEG>
+__device__ __forceinline__ void query_store(const QueryParams& q, uint32_t i, bool miss, float t, float u, float v,
+                                            uint32_t ref) {
+    if (!SEG || q.hits) {
+        uint32_t* h = q.hits + 4ull * i;
+        h[0] = __float_as_uint(miss ? kInf : t);
+        h[1] = miss ? 0u : __float_as_uint(u);
+        h[2] = miss ? 0u : __float_as_uint(v);
+        h[3] = miss ? 0xFFFFFFFFu : ref;
+    }
+    if (SEG && q.occ) q.occ[i] = miss ? (uint8_t)0 : (uint8_t)1;
 }
 
 // One lane = one ray, walked and tested by the lane itself (trace_ray), on a
@@ -1964,152 +1985,14 @@ __device__ __forceinline__ void ray_store_hit(uint32_t* hits, uint32_t i, float 
 // most res0 + res1 + res2 steps; a cell's tests are bounded by its range.
 // STATS: per-lane work counters, the counting render's conventions
 // (trace_kernel): a cell per loop trip, a test per ref tried.
-template <bool STATS, bool PACKED, bool PK_BM, bool MTX>
-__global__ __launch_bounds__(kTraceBlock, STATS ? 1 : kWfMinWaves) void rays_walk_kernel(const RayParams r) {
-    const TraceParams& p = r.w.t;
-    extern __shared__ __attribute__((aligned(16))) uint32_t s_occ[];
-    __shared__ uint32_t s_wcnt[2 * (kTraceBlock / 64)];
-    if (r.which == kRaysRest && r.ctr[2] == 0u) return;            // (the whole grid: nothing left)
-    for (uint32_t i = threadIdx.x; i < p.occ_words; i += blockDim.x) s_occ[i] = p.occ[i];
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u;
-    uint32_t* const work = r.ctr + (r.which == kRaysRest ? 1u : 0u);
-    uint64_t prof[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    uint32_t n_seg = 0, n_cells = 0, n_tests = 0, n_hits = 0, n_rest = 0;
-    for (;;) {
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(work, 64u * kWfChunk);
-        base = __builtin_amdgcn_readfirstlane(base);
-        if (base >= r.n) break;
-        for (uint32_t sub = 0; sub < kWfChunk; ++sub) {
-            const uint32_t i = base + 64u * sub + lane;
-            if (i >= r.n) continue;
-            v3 o, d;
-            ray_load(r.rays, i, o, d);
-            const bool fast = ray_fast(d);
-            if (r.which == kRaysFast && !fast) { ++n_rest; continue; }
-            if (r.which == kRaysRest && fast) continue;
-            float hu = 0.0f, hv = 0.0f;
-            uint32_t hidx = 0;
-            const float t = trace_ray<STATS, kTriBatch, PACKED, PK_BM, MTX>(p, s_occ, o, d, hu, hv, hidx, n_cells,
-                                                                            n_tests, prof, s_wcnt, -kInf, kInf);
-            ++n_seg;
-            if (t != kInf) ++n_hits;
-            ray_store_hit(r.hits, i, t, hu, hv, hidx);
-        }
-    }
-    if (r.which == kRaysFast) {
-        const unsigned long long s = wave_sum(n_rest);
-        if (lane == 0 && s != 0ull) atomicAdd(&r.ctr[2], (uint32_t)s);
-    }
-    if (STATS) {
-        const unsigned long long s0 = wave_sum(n_seg), s1 = wave_sum(n_cells), s2 = wave_sum(n_tests),
-                                 s3 = wave_sum(n_hits);
-        if (lane == 0) {
-            atomicAdd(&p.stats[0], s0);
-            atomicAdd(&p.stats[1], s1);
-            atomicAdd(&p.stats[2], s2);
-            atomicAdd(&p.stats[3], s3);
-        }
-    }
-}
-
-// The park path's queue for a chunk of n rays: ray i is queue entry i.  With
-// S = 1 and P = n, region g of the queue (region_base) is entries
-// [xcd_q0(n, g), xcd_q0(n, g + 1)), so eight full regions are the identity
-// layout and their counts the differences.  A record's (o, item) and
-// (d, depth) words are all wf_park_kernel reads; the hit record of entry i is
-// w.hit[i].  Rays outside the fast domain are counted for the launch that
-// retraces them (rays_walk_kernel, kRaysRest); the park kernel walks them
-// like any ray (it ends for any input, as above: its exit test compares cell
-// fields) and their records are overwritten.
-__global__ __launch_bounds__(kBlock) void rays_pack_kernel(const RayParams r) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < 8u) r.n_in8[i * kCtr] = xcd_q0(r.n, i + 1u) - xcd_q0(r.n, i);
-    bool rest = false;
-    if (i < r.n) {
-        v3 o, d;
-        ray_load(r.rays, i, o, d);
-        r.q[3ull * i] = make_float4(o.x, o.y, o.z, __uint_as_float(i));
-        r.q[3ull * i + 1] = make_float4(d.x, d.y, d.z, __uint_as_float(1u));
-        rest = !ray_fast(d);
-    }
-    const uint64_t m = __ballot(rest);
-    if (m != 0ull && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(m)) atomicAdd(&r.ctr[2], (uint32_t)__popcll(m));
-}
-
-// The park kernel's hit records (t, u, v, ref) as zrt_hit: the same refs as
-// the lane walk's, the miss fields set.
-__global__ __launch_bounds__(kBlock) void rays_out_kernel(const RayParams r) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= r.n) return;
-    const float4 h = r.w.hit[i];
-    ray_store_hit(r.hits, i, h.x, h.y, h.z, __float_as_uint(h.w));
-}
-
-using RayFn = void (*)(const RayParams);
-const RayFn kRaysWalkBM = (RayFn)rays_walk_kernel<false, true, true, false>;
-const RayFn kRaysWalk = (RayFn)rays_walk_kernel<false, true, false, false>;
-const RayFn kRaysWalkWide = (RayFn)rays_walk_kernel<false, false, false, false>;
-const RayFn kRaysWalkExact = (RayFn)rays_walk_kernel<false, false, false, true>;
-const RayFn kRaysWalkCount = (RayFn)rays_walk_kernel<true, false, false, true>;
-// rays per chunk of a batch: queue indices and work counters stay far below
-// 2^32, and the staging and queue memory of a call is bounded (104 B per ray)
-constexpr uint64_t kTraceChunk = 1ull << 20;
-// batch size from which a call takes the park path unasked (ZRT_TRACE_PARK
-// forces it, ZRT_FLAG_LANE_WALK forbids it): 2^19, the smallest size at which
-// the park path won in both repeats on BOTH ray sets of tools/trace_bench.py
-// (cfg3 scene, profiles/trace_bench_cfg3.json: camera rays 0.100 vs 0.137 ms,
-// incoherent rays 0.48 vs 1.12 ms per call).  Below it the winner depends on
-// the rays, which the call cannot know: incoherent rays are 2-3.6x faster
-// through the park path at every size from 2^10 up, coherent rays that all
-// miss 1.2-5x faster through the lane walk (DESIGN 5.11)
-constexpr uint64_t kTraceParkMin = 1ull << 19;
-constexpr uint32_t kTraceFlags = ZRT_FLAG_COUNT_STATS | ZRT_FLAG_LANE_WALK | ZRT_FLAG_MT_EXACT | ZRT_FLAG_ESCAPE |
-                                 ZRT_FLAG_NO_ESCAPE | ZRT_FLAG_RELEASE | ZRT_FLAG_NO_RELEASE | ZRT_FLAG_BFCULL |
-                                 ZRT_FLAG_NO_BFCULL | ZRT_TRACE_PARK;
-static_assert((ZRT_SEGMENT_ANY & (kTraceFlags | ZRT_RADIANCE_PER_SAMPLE | 0xFFFFu)) == 0u, "a bit of its own");
-
-// ---------------------------------------------------------------------------
-// Segment queries (zrt_context_segments): Scene.traceRay with nearest_hit.t
-// starting at the ray's bound t_max instead of +inf (stage3.zig:154), in
-// closest or any-hit form.  The kernels are the batch queries'
-// with three differences: the initial nearest (trace_ray's nearest0, the park
-// kernel's query modes), the any-hit exit, and the result: a miss is what left
-// nearest bit-equal to the bound (lane walk) or the ref at 0xFFFFFFFF (park
-// records), not t == +inf -- the bound may be anything, NaN included -- and
-// is stored as (+inf, 0, 0, 0xFFFFFFFF) and / or the byte 0.
-struct SegParams {
-    RayParams r;              // r.hits: a zrt_hit per ray, or null
-    const float* t_max;       // this chunk: a bound per ray, or null: t_max_all
-    float t_max_all;
-    uint8_t* occ;             // this chunk: a byte per ray (1: not missed), or null
-    uint32_t count;           // seg_walk_kernel: count the rays not missed (any-hit calls; STATS counts anyway)
-};
-
-__device__ __forceinline__ float seg_bound(const SegParams& q, uint32_t i) { return q.t_max ? q.t_max[i] : q.t_max_all; }
-// (the byte is a lane's own plain store: global_store_byte)
-__device__ __forceinline__ void seg_store(const SegParams& q, uint32_t i, bool miss, float t, float u, float v,
-                                          uint32_t ref) {
-    if (q.r.hits) {
-        uint32_t* h = q.r.hits + 4ull * i;
-        h[0] = __float_as_uint(miss ? kInf : t);
-        h[1] = miss ? 0u : __float_as_uint(u);
-        h[2] = miss ? 0u : __float_as_uint(v);
-        h[3] = miss ? 0xFFFFFFFFu : ref;
-    }
-    if (q.occ) q.occ[i] = miss ? (uint8_t)0 : (uint8_t)1;
-}
-
-// rays_walk_kernel for bounded segments: the same work distribution, the same
-// `which` split, tau = -inf and tfar = +inf.  The rays not missed are counted
-// (stats[3]) by a counting call and by every any-hit call (q.count).
+// SEG: trace_ray's BOUNDED code, compiled into these instantiations only; the
+// rays not missed are also counted (stats[3]) by every any-hit call (r.count).
 // ANY: the any-hit exit of trace_ray, instantiated for the counting kernel
 // only, whose counters it defines; the timed any-hit walks were measured
 // against the closest ones and dropped.
-template <bool STATS, bool PACKED, bool PK_BM, bool MTX, bool ANY>
-__global__ __launch_bounds__(kTraceBlock, STATS ? 1 : kWfMinWaves) void seg_walk_kernel(const SegParams q) {
-    const RayParams& r = q.r;
+template <bool STATS, bool PACKED, bool PK_BM, bool MTX, bool ANY, bool SEG>
+__global__ __launch_bounds__(kTraceBlock, STATS ? 1 : kWfMinWaves) void query_walk_kernel(const QueryParams r) {
+    static_assert(SEG || !ANY, "the any-hit exit is a segment call's");
     const TraceParams& p = r.w.t;
     extern __shared__ __attribute__((aligned(16))) uint32_t s_occ[];
     __shared__ uint32_t s_wcnt[2 * (kTraceBlock / 64)];
@@ -2133,16 +2016,16 @@ __global__ __launch_bounds__(kTraceBlock, STATS ? 1 : kWfMinWaves) void seg_walk
             const bool fast = ray_fast(d);
             if (r.which == kRaysFast && !fast) { ++n_rest; continue; }
             if (r.which == kRaysRest && fast) continue;
-            const float bound = seg_bound(q, i);
+            const float bound = SEG ? query_bound(r, i) : kInf;
             float hu = 0.0f, hv = 0.0f;
             uint32_t hidx = 0;
-            const float t = trace_ray<STATS, kTriBatch, PACKED, PK_BM, MTX, ANY, true>(p, s_occ, o, d, hu, hv, hidx,
-                                                                                       n_cells, n_tests, prof, s_wcnt,
-                                                                                       -kInf, kInf, bound);
-            const bool miss = __float_as_uint(t) == __float_as_uint(bound);
+            const float t = trace_ray<STATS, kTriBatch, PACKED, PK_BM, MTX, ANY, SEG>(p, s_occ, o, d, hu, hv, hidx,
+                                                                                      n_cells, n_tests, prof, s_wcnt,
+                                                                                      -kInf, kInf, bound);
+            const bool miss = SEG ? __float_as_uint(t) == __float_as_uint(bound) : t == kInf;
             ++n_seg;
             if (!miss) ++n_hits;
-            seg_store(q, i, miss, t, hu, hv, hidx);
+            query_store<SEG>(r, i, miss, t, hu, hv, hidx);
         }
     }
     if (r.which == kRaysFast) {
@@ -2157,43 +2040,63 @@ __global__ __launch_bounds__(kTraceBlock, STATS ? 1 : kWfMinWaves) void seg_walk
             atomicAdd(&p.stats[2], s2);
         }
     }
-    if (STATS || q.count != 0u) {
+    if (STATS || (SEG && r.count != 0u)) {
         const unsigned long long s3 = wave_sum(n_hits);
         if (lane == 0 && s3 != 0ull) atomicAdd(&p.stats[3], s3);
     }
 }
 
-// rays_pack_kernel with the bound in the record's second .w word, where the
-// park kernel's query modes take it from.
-__global__ __launch_bounds__(kBlock) void seg_pack_kernel(const SegParams q) {
-    const RayParams& r = q.r;
+// The park path's queue for a chunk of n rays: ray i is queue entry i.  With
+// S = 1 and P = n, region g of the queue (region_base) is entries
+// [xcd_q0(n, g), xcd_q0(n, g + 1)), so eight full regions are the identity
+// layout and their counts the differences.  A record's (o, item) and
+// (d, depth) words are all wf_park_kernel reads; the hit record of entry i is
+// w.hit[i].  Rays outside the fast domain are counted for the launch that
+// retraces them (query_walk_kernel, kRaysRest); the park kernel walks them
+// like any ray (it ends for any input, as above: its exit test compares cell
+// fields) and their records are overwritten.
+// The body of a one-thread-per-ray kernel: thread i < n writes entry i from
+// what ray(i, o, d, w) gives it -- the ray and the (d, .) word: the depth 1, or
+// a segment's bound, where the park kernel's query modes take it from.
+template <class Ray>
+__device__ __forceinline__ void identity_queue_fill(float4* q, uint32_t* n_in8, uint32_t* ctr, uint32_t n, Ray ray) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < 8u) r.n_in8[i * kCtr] = xcd_q0(r.n, i + 1u) - xcd_q0(r.n, i);
+    if (i < 8u) n_in8[i * kCtr] = xcd_q0(n, i + 1u) - xcd_q0(n, i);
     bool rest = false;
-    if (i < r.n) {
+    if (i < n) {
         v3 o, d;
-        ray_load(r.rays, i, o, d);
-        r.q[3ull * i] = make_float4(o.x, o.y, o.z, __uint_as_float(i));
-        r.q[3ull * i + 1] = make_float4(d.x, d.y, d.z, seg_bound(q, i));
+        float w;
+        ray(i, o, d, w);
+        q[3ull * i] = make_float4(o.x, o.y, o.z, __uint_as_float(i));
+        q[3ull * i + 1] = make_float4(d.x, d.y, d.z, w);
         rest = !ray_fast(d);
     }
     const uint64_t m = __ballot(rest);
-    if (m != 0ull && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(m)) atomicAdd(&r.ctr[2], (uint32_t)__popcll(m));
+    if (m != 0ull && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(m)) atomicAdd(&ctr[2], (uint32_t)__popcll(m));
 }
 
-// The park kernel's hit records as zrt_hit and / or the byte.  COUNT (any-hit
+template <bool SEG>
+__global__ __launch_bounds__(kBlock) void query_pack_kernel(const QueryParams r) {
+    identity_queue_fill(r.q, r.n_in8, r.ctr, r.n, [&](uint32_t i, v3& o, v3& d, float& w) {
+        ray_load(r.rays, i, o, d);
+        w = SEG ? query_bound(r, i) : __uint_as_float(1u);
+    });
+}
+
+// The park kernel's hit records (t, u, v, ref) as zrt_hit and / or the byte:
+// the same refs as the lane walk's, the miss fields set.  COUNT (any-hit
 // calls): the rays not missed into stats[3], those outside the fast domain
 // left to the kRaysRest launch that retraces them and counts them itself.
-// A counting block takes kSegOutRays * kBlock consecutive rays and adds its
+// A counting block takes kOutCountRays * kBlock consecutive rays and adds its
 // count with one atomic (one per wave of 64 rays queued 65536 atomics of a
 // 2^22-ray call on one address: 0.75 ms, more than a third of the park kernel's
 // own time, profiles/segment_bench_cfg3_first.log).
-constexpr uint32_t kSegOutRays = 8;
-template <bool COUNT>
-__global__ __launch_bounds__(kBlock) void seg_out_kernel(const SegParams q) {
-    const RayParams& r = q.r;
+constexpr uint32_t kOutCountRays = 8;
+template <bool SEG, bool COUNT>
+__global__ __launch_bounds__(kBlock) void query_out_kernel(const QueryParams r) {
+    static_assert(SEG || !COUNT, "only an any-hit segment call counts here");
     __shared__ uint32_t s_n;
-    constexpr uint32_t per = COUNT ? kSegOutRays : 1u;
+    constexpr uint32_t per = COUNT ? kOutCountRays : 1u;
     if (COUNT) {
         if (threadIdx.x == 0) s_n = 0u;
         __syncthreads();
@@ -2205,8 +2108,8 @@ __global__ __launch_bounds__(kBlock) void seg_out_kernel(const SegParams q) {
         if (i >= r.n) continue;
         const float4 h = r.w.hit[i];
         const uint32_t ref = __float_as_uint(h.w);
-        const bool miss = ref == 0xFFFFFFFFu;
-        seg_store(q, i, miss, h.x, h.y, h.z, ref);
+        const bool miss = SEG ? ref == 0xFFFFFFFFu : h.x == kInf;
+        query_store<SEG>(r, i, miss, h.x, h.y, h.z, ref);
         if (COUNT && !miss) {
             bool mine = true;
             if (some_rest) {
@@ -2225,15 +2128,43 @@ __global__ __launch_bounds__(kBlock) void seg_out_kernel(const SegParams q) {
     }
 }
 
-using SegFn = void (*)(const SegParams);
-const SegFn kSegWalkBM = (SegFn)seg_walk_kernel<false, true, true, false, false>;
-const SegFn kSegWalk = (SegFn)seg_walk_kernel<false, true, false, false, false>;
-const SegFn kSegWalkWide = (SegFn)seg_walk_kernel<false, false, false, false, false>;
-const SegFn kSegWalkExact = (SegFn)seg_walk_kernel<false, false, false, true, false>;
-// [any]: closest, any-hit
-const SegFn kSegWalkCount[2] = {(SegFn)seg_walk_kernel<true, false, false, true, false>,
-                                (SegFn)seg_walk_kernel<true, false, false, true, true>};
-const SegFn kSegOut[2] = {(SegFn)seg_out_kernel<false>, (SegFn)seg_out_kernel<true>};
+using QueryFn = void (*)(const QueryParams);
+// The kernels of a call, [0] zrt_context_trace (and a radiance call's first
+// segments), [1] / [2] zrt_context_segments in closest / any-hit form.  walk:
+// brick-major packed, packed, wide, the IEEE division, counting.  Any-hit calls
+// take the closest walks, the yes / no kept; only a counting call walks with
+// the any-hit exit, which its counters are defined by.
+struct QueryKernels {
+    QueryFn walk[5], pack, out;
+    uint32_t out_rays;        // rays per thread of `out`
+};
+template <bool SEG, bool ANY>
+static QueryKernels query_kernels() {
+    return {{(QueryFn)query_walk_kernel<false, true, true, false, false, SEG>,
+             (QueryFn)query_walk_kernel<false, true, false, false, false, SEG>,
+             (QueryFn)query_walk_kernel<false, false, false, false, false, SEG>,
+             (QueryFn)query_walk_kernel<false, false, false, true, false, SEG>,
+             (QueryFn)query_walk_kernel<true, false, false, true, ANY, SEG>},
+            (QueryFn)query_pack_kernel<SEG>, (QueryFn)query_out_kernel<SEG, ANY>, ANY ? kOutCountRays : 1u};
+}
+const QueryKernels kQuery[3] = {query_kernels<false, false>(), query_kernels<true, false>(), query_kernels<true, true>()};
+// rays per chunk of a batch: queue indices and work counters stay far below
+// 2^32, and the staging and queue memory of a call is bounded (104 B per ray)
+constexpr uint64_t kTraceChunk = 1ull << 20;
+// batch size from which a call takes the park path unasked (ZRT_TRACE_PARK
+// forces it, ZRT_FLAG_LANE_WALK forbids it): 2^19, the smallest size at which
+// the park path won in both repeats on BOTH ray sets of tools/trace_bench.py
+// (cfg3 scene, profiles/trace_bench_cfg3.json: camera rays 0.100 vs 0.137 ms,
+// incoherent rays 0.48 vs 1.12 ms per call).  Below it the winner depends on
+// the rays, which the call cannot know: incoherent rays are 2-3.6x faster
+// through the park path at every size from 2^10 up, coherent rays that all
+// miss 1.2-5x faster through the lane walk (DESIGN 5.11)
+constexpr uint64_t kTraceParkMin = 1ull << 19;
+constexpr uint32_t kTraceFlags = ZRT_FLAG_COUNT_STATS | ZRT_FLAG_LANE_WALK | ZRT_FLAG_MT_EXACT | ZRT_FLAG_ESCAPE |
+                                 ZRT_FLAG_NO_ESCAPE | ZRT_FLAG_RELEASE | ZRT_FLAG_NO_RELEASE | ZRT_FLAG_BFCULL |
+                                 ZRT_FLAG_NO_BFCULL | ZRT_TRACE_PARK;
+static_assert((ZRT_SEGMENT_ANY & (kTraceFlags | ZRT_RADIANCE_PER_SAMPLE | 0xFFFFu)) == 0u, "a bit of its own");
+
 // batch size from which a segment call takes the park path unasked: 2^16, the
 // smallest size tools/segment_bench.py measures; there and at 2^20 and 2^22 the
 // park path won on all three bounded ray sets (ao at two radii, shadow) in
@@ -2258,10 +2189,10 @@ struct RadParams {
     WfParams w;               // w.t: P = n rays, S samples per ray; queues, planes, counters of the launch
     const float* rays;        // this chunk: 6 floats per ray (origin, direction as given)
     float* nrays;             // rad_pack_kernel: the rays with their directions normalised, 6 floats each
-                              // (rays_walk_kernel's input)
+                              // (query_walk_kernel's input)
     float4* q;                // the pack kernels: the queue they fill (launch 0's q_in)
     uint32_t* n_in8;          //   and its region counts
-    uint32_t* ctr;            // [2]: rays outside the fast domain (rays_walk_kernel, kRaysRest)
+    uint32_t* ctr;            // [2]: rays outside the fast domain (query_walk_kernel, kRaysRest)
     uint32_t n;               // rays of this chunk
     uint32_t key0;            // RNG stream key ("pixel") of the chunk's ray 0; keys wrap at 2^32
 };
@@ -2284,27 +2215,19 @@ __device__ __forceinline__ Rng rad_rng(uint64_t seed, uint32_t key, uint32_t s) 
 }
 
 // One thread per ray: ray i, its direction normalised, as queue entry i of the
-// identity layout (rays_pack_kernel: P = n, S = 1) for the park kernel, and as
-// six floats for the lane walk.  A normalised direction is in the fast domain
+// identity layout (identity_queue_fill: P = n, S = 1) for the park kernel, and
+// as six floats for the lane walk.  A normalised direction is in the fast domain
 // (ray_fast) unless the given one was NaN, infinite, zero or of a squared
 // length that overflows or vanishes; those are counted for the kRaysRest launch.
 __global__ __launch_bounds__(kBlock) void rad_pack_kernel(const RadParams r) {
-    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < 8u) r.n_in8[i * kCtr] = xcd_q0(r.n, i + 1u) - xcd_q0(r.n, i);
-    bool rest = false;
-    if (i < r.n) {
-        v3 o, d;
+    identity_queue_fill(r.q, r.n_in8, r.ctr, r.n, [&](uint32_t i, v3& o, v3& d, float& w) {
         ray_load(r.rays, i, o, d);
         d = rad_direction(d);
-        r.q[3ull * i] = make_float4(o.x, o.y, o.z, __uint_as_float(i));
-        r.q[3ull * i + 1] = make_float4(d.x, d.y, d.z, __uint_as_float(1u));
         float* q = r.nrays + 6ull * i;
         q[0] = o.x; q[1] = o.y; q[2] = o.z;
         q[3] = d.x; q[4] = d.y; q[5] = d.z;
-        rest = !ray_fast(d);
-    }
-    const uint64_t m = __ballot(rest);
-    if (m != 0ull && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(m)) atomicAdd(&r.ctr[2], (uint32_t)__popcll(m));
+        w = __uint_as_float(1u);
+    });
 }
 
 // ZRT_RADIANCE_PER_SAMPLE: one thread per item = ray * S + s, its path record
@@ -2772,52 +2695,35 @@ static int launch_bounce(const LaunchPlan& pl, const BounceGrids& g, const WfPar
 // ray: rays in the fast domain (ray_fast) through the park kernel or the
 // context's fast lane walk, the others through the IEEE-division walk.
 struct RayLaunch {
-    RayFn f_fast;             // null (mtx, a counting call): every ray takes f_exact
-    RayFn f_exact;
+    QueryFn f_fast;           // null (mtx, a counting call): every ray takes f_exact
+    QueryFn f_exact;
+    QueryFn f_pack, f_out;    // the park path's queue fill and results
+    uint32_t out_rays;        // rays per thread of f_out
     bool park;
     uint32_t grid_fast, grid_exact, grid_park;
     WfFn f_park;              // the plan's park kernel in this call's query mode
-    // a segment call (seg): the bounded kernels in place of f_fast / f_exact
-    // (s_fast null as f_fast), of rays_pack_kernel / rays_out_kernel, and what
-    // SegParams holds besides the rays
-    bool seg;
-    SegFn s_fast, s_exact, s_out;
-    const float* t_max;
-    float t_max_all;
-    uint8_t* occ;
-    bool count;               // an any-hit call: its kernels count the rays not missed
 };
 // `seg`: -1 a batch or radiance query, 0 / 1 a segment call in closest / any-hit form
 static int ray_launch(const zrt_context* c, const LaunchPlan& pl, bool counting, bool park, RayLaunch& rl,
                       int seg = -1) {
     int rc;
     rl = RayLaunch{};
-    const bool fast = !(counting || pl.mtx);
+    const QueryKernels& k = kQuery[seg + 1];
     rl.park = park;
-    rl.seg = seg >= 0;
-    const void *k_fast = nullptr, *k_exact;
-    if (rl.seg) {
-        // (any-hit calls: the closest kernels, the yes / no kept; only a counting
-        // call walks with the any-hit exit, which its counters are defined by)
-        rl.f_park = park_fn<kParkClosest>(pl.esc, pl.pbm);
-        rl.s_fast = !fast ? nullptr : pl.packed ? (pl.pbm ? kSegWalkBM : kSegWalk) : kSegWalkWide;
-        rl.s_exact = counting ? kSegWalkCount[seg] : kSegWalkExact;
-        rl.count = seg != 0;
-        rl.s_out = kSegOut[seg];
-        k_fast = (const void*)rl.s_fast;
-        k_exact = (const void*)rl.s_exact;
-    } else {
-        rl.f_park = pl.f_park;
-        rl.f_fast = !fast ? nullptr : pl.packed ? (pl.pbm ? kRaysWalkBM : kRaysWalk) : kRaysWalkWide;
-        rl.f_exact = counting ? kRaysWalkCount : kRaysWalkExact;
-        k_fast = (const void*)rl.f_fast;
-        k_exact = (const void*)rl.f_exact;
-    }
+    // (any-hit calls: the closest park kernel, the yes / no kept)
+    rl.f_park = seg >= 0 ? park_fn<kParkClosest>(pl.esc, pl.pbm) : pl.f_park;
+    rl.f_fast = counting || pl.mtx ? nullptr : k.walk[pl.packed ? (pl.pbm ? 0 : 1) : 2];
+    rl.f_exact = k.walk[counting ? 4 : 3];
+    rl.f_pack = k.pack;
+    rl.f_out = k.out;
+    rl.out_rays = k.out_rays;
     // occupancy-sized persistent grids
     if (park && (rc = resident_blocks(c, (const void*)rl.f_park, pl.park_block, pl.lds_park, &rl.grid_park)) != ZRT_OK)
         return rc;
-    if (k_fast && !park && (rc = resident_blocks(c, k_fast, kTraceThreads, pl.lds_wf, &rl.grid_fast)) != ZRT_OK) return rc;
-    return resident_blocks(c, k_exact, kTraceThreads, pl.lds_wf, &rl.grid_exact);
+    if (rl.f_fast && !park &&
+        (rc = resident_blocks(c, (const void*)rl.f_fast, kTraceThreads, pl.lds_wf, &rl.grid_fast)) != ZRT_OK)
+        return rc;
+    return resident_blocks(c, (const void*)rl.f_exact, kTraceThreads, pl.lds_wf, &rl.grid_exact);
 }
 
 // A chunk's n first segments on the context's stream, over the identity queue
@@ -2825,9 +2731,9 @@ static int ray_launch(const zrt_context* c, const LaunchPlan& pl, bool counting,
 // fast lane walk, then the kRaysRest launch over the rays those left (it ends
 // at once when they counted none); without a fast kernel the kRaysAll launch
 // alone.  `pack_out`: Q.rays are the caller's rays as given, so
-// rays_pack_kernel fills the queue before the park kernel and rays_out_kernel
-// writes its hit records to Q.hits after it.
-static int trace_first_segments(const zrt_context* c, const LaunchPlan& pl, const RayLaunch& rl, RayParams& Q, uint32_t n,
+// query_pack_kernel fills the queue before the park kernel and
+// query_out_kernel writes its hit records to Q.hits / Q.occ after it.
+static int trace_first_segments(const zrt_context* c, const LaunchPlan& pl, const RayLaunch& rl, QueryParams& Q, uint32_t n,
                                 bool pack_out, uint32_t* launches) {
     const uint32_t nblk = (n + kBlock - 1) / kBlock;             // one thread per ray; also all a walk launch needs
     Q.n = n;
@@ -2835,37 +2741,23 @@ static int trace_first_segments(const zrt_context* c, const LaunchPlan& pl, cons
     Q.w.t.S = 1;
     Q.w.t.total = n;
     Q.w.t.sdiv = div_magic(1);
-    // a segment call: the same launches with its kernels (SegParams around Q)
-    auto thread_per_ray = [&](void (*f)(const RayParams), SegFn sf) {
-        // (the counting seg_out_kernel: kSegOutRays rays per thread)
-        const uint32_t per = sf == kSegOut[1] ? kSegOutRays : 1u;
-        if (rl.seg)
-            hipLaunchKernelGGL(sf, dim3((nblk + per - 1) / per), dim3(kBlock), 0, c->stream,
-                               SegParams{Q, rl.t_max, rl.t_max_all, rl.occ, rl.count ? 1u : 0u});
-        else
-            hipLaunchKernelGGL(f, dim3(nblk), dim3(kBlock), 0, c->stream, Q);
+    auto walk = [&](QueryFn f, uint32_t grid) {
+        hipLaunchKernelGGL(f, dim3(std::min(grid, nblk)), dim3(kTraceThreads), pl.lds_wf, c->stream, Q);
     };
-    auto walk = [&](RayFn f, SegFn sf, uint32_t grid) {
-        if (rl.seg)
-            hipLaunchKernelGGL(sf, dim3(std::min(grid, nblk)), dim3(kTraceThreads), pl.lds_wf, c->stream,
-                               SegParams{Q, rl.t_max, rl.t_max_all, rl.occ, rl.count ? 1u : 0u});
-        else
-            hipLaunchKernelGGL(f, dim3(std::min(grid, nblk)), dim3(kTraceThreads), pl.lds_wf, c->stream, Q);
-    };
-    const bool fast = rl.seg ? rl.s_fast != nullptr : rl.f_fast != nullptr;
     if (rl.park) {
         Q.which = kRaysAll;
-        if (pack_out) thread_per_ray(rays_pack_kernel, seg_pack_kernel);
+        if (pack_out) hipLaunchKernelGGL(rl.f_pack, dim3(nblk), dim3(kBlock), 0, c->stream, Q);
         hipLaunchKernelGGL(rl.f_park, dim3(rl.grid_park), dim3(pl.park_block), pl.lds_park, c->stream, Q.w);
-        if (pack_out) thread_per_ray(rays_out_kernel, rl.s_out);
+        if (pack_out)
+            hipLaunchKernelGGL(rl.f_out, dim3((nblk + rl.out_rays - 1) / rl.out_rays), dim3(kBlock), 0, c->stream, Q);
         *launches += pack_out ? 3 : 1;
-    } else if (fast) {
+    } else if (rl.f_fast) {
         Q.which = kRaysFast;
-        walk(rl.f_fast, rl.s_fast, rl.grid_fast);
+        walk(rl.f_fast, rl.grid_fast);
         ++*launches;
     }
-    Q.which = rl.park || fast ? kRaysRest : kRaysAll;
-    walk(rl.f_exact, rl.s_exact, rl.grid_exact);
+    Q.which = rl.park || rl.f_fast ? kRaysRest : kRaysAll;
+    walk(rl.f_exact, rl.grid_exact);
     ++*launches;
     HIP_TRY(hipGetLastError());
     return ZRT_OK;
@@ -3390,21 +3282,21 @@ extern "C" int zrt_context_profile(const zrt_context* c, zrt_kernel_profile* out
 }
 
 // Scene.traceRay (stage3.zig:152-186) for a batch of rays: see include/zrt.h
-// and the kernels' comment (rays_walk_kernel).  The launch plan is the one a
+// and the kernels' comment (query_walk_kernel).  The launch plan is the one a
 // render resolves (resolve_plan); the park path from kTraceParkMin rays, or as
 // ZRT_TRACE_PARK asks.  Per chunk of at most kTraceChunk rays, all on the
 // context's stream (trace_first_segments):
-//   lane walk:  rays_walk_kernel (fast kernel of the context, kRaysFast), then
+//   lane walk:  query_walk_kernel (fast kernel of the context, kRaysFast), then
 //               the IEEE-division kernel over the rays it left (kRaysRest);
 //               an mt_exact context, ZRT_FLAG_MT_EXACT or a counting call:
 //               that kernel alone over every ray (kRaysAll);
-//   park path:  rays_pack_kernel -> wf_park_kernel (the render's, unchanged)
-//               -> rays_out_kernel, then the kRaysRest launch as above.
+//   park path:  query_pack_kernel -> wf_park_kernel (the render's, unchanged)
+//               -> query_out_kernel, then the kRaysRest launch as above.
 // The park path shares pass set 0's queue, hit records and counters with the
 // renders; each use writes what it reads first, so nothing carries over.
 //
 // zrt_context_segments is the same call -- plan, chunk loop,
-// launches, stats -- with the bounded kernels (ray_launch's `seg`) and two
+// launches, stats -- with the kernels' SEG instantiations (ray_launch's `seg`) and two
 // more per-ray arrays: the bounds, staged behind a chunk's rays, and the
 // occlusion bytes, staged behind its hit records.
 struct RayQuery {
@@ -3463,10 +3355,11 @@ static int query_rays(zrt_context* c, const RayQuery* b, zrt_stats* stats) {
     // occupancy-sized persistent grids (no more blocks than a chunk has work for)
     RayLaunch rl;
     if ((rc = ray_launch(c, pl, counting, park, rl, b->seg)) != ZRT_OK) return rc;
-    rl.t_max_all = b->t_max_all;
 
-    RayParams R;
+    QueryParams R;
     memset(&R, 0, sizeof R);
+    R.t_max_all = b->t_max_all;
+    R.count = b->seg == 1 ? 1u : 0u;               // an any-hit call: its kernels count the rays not missed
     scene_params(c, R.w.t);
     R.w.t.max_bounce = 1;
     R.w.t.counter = c->d_counter;
@@ -3490,27 +3383,27 @@ static int query_rays(zrt_context* c, const RayQuery* b, zrt_stats* stats) {
         if (b->on_device) {
             R.rays = b->rays + 6 * off;
             R.hits = b->hits ? reinterpret_cast<uint32_t*>(b->hits + off) : nullptr;
-            rl.t_max = b->t_max ? b->t_max + off : nullptr;
-            rl.occ = b->occ ? b->occ + off : nullptr;
+            R.t_max = b->t_max ? b->t_max + off : nullptr;
+            R.occ = b->occ ? b->occ + off : nullptr;
         } else {
             HIP_TRY(hipMemcpyAsync(c->d_rays, b->rays + 6 * off, 24ull * n, hipMemcpyHostToDevice, c->stream));
             R.rays = c->d_rays;
             R.hits = b->hits ? c->d_hits : nullptr;
             if (b->t_max) {
                 HIP_TRY(hipMemcpyAsync(c->d_rays + 6 * chunk, b->t_max + off, 4ull * n, hipMemcpyHostToDevice, c->stream));
-                rl.t_max = c->d_rays + 6 * chunk;
+                R.t_max = c->d_rays + 6 * chunk;
             }
-            if (b->occ) rl.occ = reinterpret_cast<uint8_t*>(c->d_hits + 4 * chunk);
+            if (b->occ) R.occ = reinterpret_cast<uint8_t*>(c->d_hits + 4 * chunk);
             HIP_TRY(hipEventRecord(c->ev_trace[0], c->stream));
         }
         HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
-        // the work counters; rays_pack_kernel writes the region counts
+        // the work counters; query_pack_kernel writes the region counts
         if (park) HIP_TRY(hipMemsetAsync(ps.wfc, 0, 4ull * 16 * kCtr, c->stream));
         if ((rc = trace_first_segments(c, pl, rl, R, n, true, &launches)) != ZRT_OK) return rc;
         if (!b->on_device) {
             HIP_TRY(hipEventRecord(c->ev_trace[1], c->stream));
             if (b->hits) HIP_TRY(copy_sync(b->hits + off, c->d_hits, 16ull * n, hipMemcpyDeviceToHost, c->stream));
-            if (b->occ) HIP_TRY(copy_sync(b->occ + off, rl.occ, n, hipMemcpyDeviceToHost, c->stream));
+            if (b->occ) HIP_TRY(copy_sync(b->occ + off, R.occ, n, hipMemcpyDeviceToHost, c->stream));
             float t = 0.0f;
             HIP_TRY(hipEventElapsedTime(&t, c->ev_trace[0], c->ev_trace[1]));
             st.trace_kernel_ms += t;
@@ -3563,7 +3456,7 @@ extern "C" int zrt_context_segments(zrt_context* c, const zrt_segment_batch* b, 
 //   shared first segment (default):
 //     rad_pack_kernel -> the chunk's first segments as zrt_context_trace traces
 //     them (trace_first_segments: wf_park_kernel over the identity queue, or
-//     rays_walk_kernel; then the kRaysRest launch) -> rad_fanout_kernel: n * S
+//     query_walk_kernel; then the kRaysRest launch) -> rad_fanout_kernel: n * S
 //     shaded continuations;
 //   ZRT_RADIANCE_PER_SAMPLE:
 //     rad_pack_samples_kernel -> launch 0 as a bounce launch over n * S records;
@@ -3698,7 +3591,7 @@ extern "C" int zrt_context_radiance(zrt_context* c, const zrt_radiance_batch* b,
             hipLaunchKernelGGL(rad_pack_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, R);
             ++launches;
             // the first segments: one per ray, launch 0's queue as the identity queue
-            RayParams Q;
+            QueryParams Q;
             memset(&Q, 0, sizeof Q);
             Q.w = W;
             Q.w.t.max_bounce = 1;

@@ -395,6 +395,26 @@ class Context:
         res["stats"] = st.as_dict()
         return res
 
+    @staticmethod
+    def _rays(what, origins, dirs):
+        """The input checks of a query call `what` and its rays as one (n, 6)
+        array: (torch or None, n, rays) -- torch for two CUDA tensors, whose
+        rays are a CUDA tensor, None for anything numpy takes."""
+        if type(origins).__module__.split(".")[0] == "torch":
+            import torch
+            if not (origins.is_cuda and dirs.is_cuda and origins.device == dirs.device):
+                raise ValueError(f"{what}: torch inputs must be CUDA tensors on the context's device")
+            if origins.dtype != torch.float32 or dirs.dtype != torch.float32:
+                raise ValueError(f"{what}: float32 tensors expected")
+            if origins.dim() != 2 or origins.shape[1] != 3 or origins.shape != dirs.shape:
+                raise ValueError(f"{what}: two (n, 3) tensors expected")
+            return torch, int(origins.shape[0]), torch.cat([origins, dirs], dim=1).contiguous()
+        o = np.asarray(origins, np.float32)
+        d = np.asarray(dirs, np.float32)
+        if o.ndim != 2 or o.shape[1] != 3 or o.shape != d.shape:
+            raise ValueError(f"{what}: two (n, 3) arrays expected")
+        return None, o.shape[0], np.ascontiguousarray(np.concatenate([o, d], axis=1))
+
     def trace_raw(self, num_rays: int, rays_ptr, hits_ptr, on_device: bool, flags: int = 0):
         """zrt_context_trace on raw pointers; returns the stats dict."""
         batch = RayBatch(int(num_rays), rays_ptr, hits_ptr, 1 if on_device else 0, int(flags))
@@ -416,26 +436,12 @@ class Context:
         pattern), "stats"}; `hits[:, 3].view(torch.int32)` is the ref (-1: a
         miss).  The call returns with the tensor complete."""
         flags = int(flags) | (FLAG_COUNT_STATS if stats else 0)
-        if type(origins).__module__.split(".")[0] == "torch":
-            import torch
-            if not (origins.is_cuda and dirs.is_cuda and origins.device == dirs.device):
-                raise ValueError("trace: torch inputs must be CUDA tensors on the context's device")
-            if origins.dtype != torch.float32 or dirs.dtype != torch.float32:
-                raise ValueError("trace: float32 tensors expected")
-            if origins.dim() != 2 or origins.shape[1] != 3 or origins.shape != dirs.shape:
-                raise ValueError("trace: two (n, 3) tensors expected")
-            n = int(origins.shape[0])
-            rays = torch.cat([origins, dirs], dim=1).contiguous()
+        torch, n, rays = self._rays("trace", origins, dirs)
+        if torch:
             hits = torch.empty((n, 4), dtype=torch.float32, device=origins.device)
             torch.cuda.current_stream(origins.device).synchronize()
             st = self.trace_raw(n, rays.data_ptr() if n else None, hits.data_ptr() if n else None, True, flags)
             return {"hits": hits, "stats": st}
-        o = np.asarray(origins, np.float32)
-        d = np.asarray(dirs, np.float32)
-        if o.ndim != 2 or o.shape[1] != 3 or o.shape != d.shape:
-            raise ValueError("trace: two (n, 3) arrays expected")
-        n = o.shape[0]
-        rays = np.ascontiguousarray(np.concatenate([o, d], axis=1))
         hits = np.empty(n, HIT_DTYPE)
         st = self.trace_raw(n, rays.ctypes.data if n else None, hits.ctypes.data if n else None, False, flags)
         return {"t": hits["t"].copy(), "u": hits["u"].copy(), "v": hits["v"].copy(),
@@ -469,15 +475,8 @@ class Context:
         float32 CUDA tensor as in trace() (not with any_hit), "occluded": an
         (n,) torch.bool CUDA tensor, "stats"}."""
         flags = int(flags) | (FLAG_COUNT_STATS if stats else 0) | (SEGMENT_ANY if any_hit else 0)
-        if type(origins).__module__.split(".")[0] == "torch":
-            import torch
-            if not (origins.is_cuda and dirs.is_cuda and origins.device == dirs.device):
-                raise ValueError("segments: torch inputs must be CUDA tensors on the context's device")
-            if origins.dtype != torch.float32 or dirs.dtype != torch.float32:
-                raise ValueError("segments: float32 tensors expected")
-            if origins.dim() != 2 or origins.shape[1] != 3 or origins.shape != dirs.shape:
-                raise ValueError("segments: two (n, 3) tensors expected")
-            n = int(origins.shape[0])
+        torch, n, rays = self._rays("segments", origins, dirs)
+        if torch:
             tm, tm_all = None, float("inf")
             if torch.is_tensor(t_max) and t_max.dim() > 0:
                 if t_max.device != origins.device or t_max.dtype != torch.float32 or t_max.shape != (n,):
@@ -485,7 +484,6 @@ class Context:
                 tm = t_max.contiguous()
             else:
                 tm_all = float(t_max)
-            rays = torch.cat([origins, dirs], dim=1).contiguous()
             hits = None if any_hit else torch.empty((n, 4), dtype=torch.float32, device=origins.device)
             occ = torch.empty((n,), dtype=torch.bool, device=origins.device)     # one byte per ray, 0 / 1
             torch.cuda.current_stream(origins.device).synchronize()
@@ -496,11 +494,6 @@ class Context:
             if hits is not None:
                 res["hits"] = hits
             return res
-        o = np.asarray(origins, np.float32)
-        d = np.asarray(dirs, np.float32)
-        if o.ndim != 2 or o.shape[1] != 3 or o.shape != d.shape:
-            raise ValueError("segments: two (n, 3) arrays expected")
-        n = o.shape[0]
         tm, tm_all = None, float("inf")
         if np.ndim(t_max) == 0:
             tm_all = float(t_max)
@@ -508,7 +501,6 @@ class Context:
             tm = np.ascontiguousarray(t_max, np.float32)
             if tm.shape != (n,):
                 raise ValueError("segments: t_max must be a scalar or n values")
-        rays = np.ascontiguousarray(np.concatenate([o, d], axis=1))
         hits = None if any_hit else np.empty(n, HIT_DTYPE)
         occ = np.zeros(n, np.uint8)
         st = self.segments_raw(n, rays.ctypes.data if n else None, tm.ctypes.data if tm is not None and n else None,
@@ -544,16 +536,8 @@ class Context:
         filled (no counting variant exists); the argument is kept for symmetry
         with trace()."""
         del stats
-        if type(origins).__module__.split(".")[0] == "torch":
-            import torch
-            if not (origins.is_cuda and dirs.is_cuda and origins.device == dirs.device):
-                raise ValueError("radiance: torch inputs must be CUDA tensors on the context's device")
-            if origins.dtype != torch.float32 or dirs.dtype != torch.float32:
-                raise ValueError("radiance: float32 tensors expected")
-            if origins.dim() != 2 or origins.shape[1] != 3 or origins.shape != dirs.shape:
-                raise ValueError("radiance: two (n, 3) tensors expected")
-            n = int(origins.shape[0])
-            rays = torch.cat([origins, dirs], dim=1).contiguous()
+        torch, n, rays = self._rays("radiance", origins, dirs)
+        if torch:
             out = torch.empty((n, 3), dtype=torch.float32, device=origins.device)
             out8 = torch.empty((n, 3), dtype=torch.uint8, device=origins.device) if rgb else None
             torch.cuda.current_stream(origins.device).synchronize()
@@ -564,12 +548,6 @@ class Context:
             if rgb:
                 res["rgb"] = out8
             return res
-        o = np.asarray(origins, np.float32)
-        d = np.asarray(dirs, np.float32)
-        if o.ndim != 2 or o.shape[1] != 3 or o.shape != d.shape:
-            raise ValueError("radiance: two (n, 3) arrays expected")
-        n = o.shape[0]
-        rays = np.ascontiguousarray(np.concatenate([o, d], axis=1))
         out = np.empty((n, 3), np.float32)
         out8 = np.empty((n, 3), np.uint8) if rgb else None
         st = self.radiance_raw(n, rays.ctypes.data if n else None, out.ctypes.data if n else None,
