@@ -405,6 +405,61 @@ typedef struct zrt_radiance_batch {
  * zrt_context_trace. */
 int zrt_context_radiance(zrt_context* ctx, const zrt_radiance_batch* batch, zrt_stats* stats_or_null);
 
+/* ---- surface queries (ABI 2, added) ------------------------------------- */
+
+/* What is at a ray's first hit: the shading inputs traceRayRecursive computes
+ * between stage3.zig:199 and :206 -- the interpolated normal and texture
+ * coordinate, the material, and its base colour, emission and transparency
+ * sampled there -- and the origin it continues from (stage3.zig:209 / :216).
+ * G-buffer planes, the hit points of a direct-light pass (shadow rays through
+ * zrt_context_segments), lightmap and probe baking, picking.  For ray i:
+ *   hits[i]      zrt_context_trace's record of the ray, bit for bit;
+ *   surfaces[i]  from that record's (t, u, v, ref), in the reference's
+ *                operation order: left to right, nothing contracted, the third
+ *                weight 1 - u - v as (1 - u) - v.
+ * Directions are taken as given, as in zrt_context_trace, and position is in
+ * the ray's own parameter.  A NaN or inf the arithmetic produces is stored as
+ * it is.  A miss stores fifteen zero words and material = 0xFFFFFFFF: the sky
+ * colour is the caller's (getEnvColor presumes a unit direction, this call
+ * does not).  A transparent hit is reported like any other: whether a path
+ * passes through it is a random draw of the path tracer's. */
+typedef struct zrt_surface {
+    float position[3];               /* ray.at(t + floatEps(f32)): o + d * (t + eps), stage3.zig:209/216 --
+                                        the origin the reference continues from, ready for shadow / AO rays */
+    uint32_t material;               /* Data.material_idx of the hit ref; 0xFFFFFFFF on a miss */
+    float normal[3];                 /* interpolate("normal", u, v), stage3.zig:59; NOT normalised, as there */
+    float transparency;              /* material.transparency.sample(texcoord) */
+    float base_color[3];             /* material.base_color.sample(texcoord) */
+    float texcoord_s;                /* interpolate("texcoord", u, v)[0], stage3.zig:63 */
+    float emissive[3];               /* material.emissive.sample(texcoord) */
+    float texcoord_t;                /* ...[1], stage3.zig:64 */
+} zrt_surface;                       /* 64 B */
+
+typedef struct zrt_surface_batch {
+    uint64_t num_rays;
+    const float* rays;               /* num_rays * 6, as zrt_ray_batch */
+    zrt_surface* surfaces;           /* num_rays; on_device: 16-byte aligned, else ZRT_ERR_INVALID_ARG */
+    zrt_hit* hits;                   /* num_rays, or null */
+    uint32_t on_device;              /* as zrt_ray_batch; applies to all three pointers */
+    uint32_t flags;                  /* exactly zrt_ray_batch's flags */
+} zrt_surface_batch;                 /* 40 B */
+
+/* Synchronous, one thread at a time per context; alternates freely with
+ * renders and the three other queries (every use writes what it reads first).
+ * The rays are traced as zrt_context_trace traces them -- the same kernels
+ * under the same thresholds and flags -- and one gather launch per chunk of at
+ * most 2^20 rays fills the records (the staging of a host batch grows by the
+ * 64-byte record; a device batch with null hits keeps its hit records in the
+ * context, 16 B per ray).
+ * num_rays == 0 returns ZRT_OK and touches nothing.  ZRT_ERR_INVALID_ARG before
+ * any device work: a null context or batch, null rays or surfaces, a flag
+ * zrt_context_trace would refuse, on_device > 1, a device `surfaces` pointer
+ * that is not 16-byte aligned.
+ * stats (may be null): as zrt_context_trace (segments = num_rays, samples = 0;
+ * cells_visited, triangle_tests and hits with ZRT_FLAG_COUNT_STATS);
+ * trace_launches counts the gather launch too. */
+int zrt_context_surface(zrt_context* ctx, const zrt_surface_batch* batch, zrt_stats* stats_or_null);
+
 /* A device group: one context per entry of `devices` (HIP ordinals, repeats
  * allowed), the scene resident on each, rendered by one call -- Scene.render's
  * spawn + join of its workers (stage3.zig:247-256) across GPUs in one

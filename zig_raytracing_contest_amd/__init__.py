@@ -122,6 +122,19 @@ class RenderScene:
         ray), nearest or any hit: see native.Context.segments."""
         return self.context.segments(origins, dirs, t_max, any_hit=any_hit, flags=flags, stats=stats)
 
+    def surface(self, origins, dirs, flags: int = 0, stats: bool = False, hits: bool = False):
+        """The shading inputs at each ray's first hit (stage3.zig:199-206):
+        see native.Context.surface.  With numpy inputs, hits=True and a
+        host-built scene the result also holds "source_triangle", as trace()'s."""
+        res = self.context.surface(origins, dirs, flags=flags, stats=stats, hits=hits)
+        if self.geometry is not None and "triangle" in res:
+            ref = res["triangle"]
+            hit = ref != native.MISS
+            src = np.full(ref.shape, native.MISS, np.uint32)
+            src[hit] = self.geometry.indices()[ref[hit]]
+            res["source_triangle"] = src
+        return res
+
     def radiance(self, origins, dirs, spp: int, max_bounce: int, seed: int = 0, index_base: int = 0,
                  flags: int = 0, rgb: bool = False, stats: bool = False):
         """Scene.traceRayRecursive (stage3.zig:188-220) for a batch of rays,

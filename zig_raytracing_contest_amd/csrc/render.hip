@@ -2176,6 +2176,69 @@ constexpr uint64_t kSegParkMin = 1ull << 16;
 constexpr uint64_t kSegStageBytes = 5;
 
 // ---------------------------------------------------------------------------
+// Surface queries (zrt_context_surface): the shading inputs at a
+// ray's first hit -- traceRayRecursive between stage3.zig:199 and :206 and the
+// continuation origin of :209 / :216 -- gathered from the hit records a trace
+// call's kernels left for the chunk.  One lane per ray on a plain grid, one
+// pass: hit record -> triangle Data -> material -> texels.
+struct SurfaceParams {
+    const float* rays;        // this chunk: 6 floats per ray (origin, direction as given)
+    const uint32_t* hits;     // this chunk: the zrt_hit of every ray as 4 u32 (4-byte aligned)
+    float4* surf;             // this chunk: a zrt_surface per ray as 4 float4 (16-byte aligned)
+    const float4* tri_data;   // TraceParams::tri_data
+    const DevMat* mats;
+    const float* texels;
+    uint32_t n;               // rays of this chunk
+};
+// The arithmetic is shade_segment's (its lines "stage3.zig:199-206" to `no`),
+// restated here because shade_segment is welded to the RNG draw and the queue
+// append: keep the two in step.  The four Data loads of a hit lane are issued
+// together before any texel load (tri_rec's reason); a miss lane loads nothing
+// after its hit record and ray.  The materials are read from global memory
+// whatever their number: a copy in LDS for up to kLdsMats of them, the shade
+// kernel's LMATS, was built and measured beside this and did not win in every
+// round, so one path serves both sides of that limit.
+__global__ __launch_bounds__(kBlock) void surface_kernel(const SurfaceParams r) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= r.n) return;
+    uint4 h;
+    if ((reinterpret_cast<uintptr_t>(r.hits) & 15u) == 0u) {        // (uniform: the context's own records always are)
+        h = reinterpret_cast<const uint4*>(r.hits)[i];
+    } else {
+        const uint32_t* q = r.hits + 4ull * i;
+        h = make_uint4(q[0], q[1], q[2], q[3]);
+    }
+    v3 o, d;
+    ray_load(r.rays, i, o, d);
+    float4* const out = r.surf + 4ull * i;
+    const float t = __uint_as_float(h.x), hu = __uint_as_float(h.y), hv = __uint_as_float(h.z);
+    if (t == kInf) {                                                // a miss (query_store)
+        const float4 z4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        out[0] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xFFFFFFFFu));
+        out[1] = z4;
+        out[2] = z4;
+        out[3] = z4;
+        return;
+    }
+    const float4* tdp = r.tri_data + 4ull * h.w;
+    const float4 d0 = tdp[0], d1 = tdp[1], d2 = tdp[2], d3 = tdp[3];   // stage3.zig:199-206
+    const float w0 = 1.0f - hu - hv;
+    const float tc0 = (d2.y * w0 + d2.w * hu) + d3.y * hv;
+    const float tc1 = (d2.z * w0 + d3.x * hu) + d3.z * hv;
+    const DevMat& m = r.mats[__float_as_uint(d3.w)];
+    const v3 albedo = sample3(r.texels, m.tex[0], tc0, tc1);
+    const v3 emissive = sample3(r.texels, m.tex[1], tc0, tc1);
+    const float transparency = sample1(r.texels, m.tex[2], tc0, tc1);
+    const v3 nrm = add(add(scale(mk(d0.x, d0.y, d0.z), w0), scale(mk(d0.w, d1.x, d1.y), hu)),
+                       scale(mk(d1.z, d1.w, d2.x), hv));
+    const v3 no = add(o, scale(d, t + kFltEps));
+    out[0] = make_float4(no.x, no.y, no.z, d3.w);
+    out[1] = make_float4(nrm.x, nrm.y, nrm.z, transparency);
+    out[2] = make_float4(albedo.x, albedo.y, albedo.z, tc0);
+    out[3] = make_float4(emissive.x, emissive.y, emissive.z, tc1);
+}
+
+// ---------------------------------------------------------------------------
 // Radiance queries (zrt_context_radiance): Scene.traceRayRecursive
 // (stage3.zig:188-220) for caller-given rays, S samples each, through the
 // render's own queues, park, shade and resolve kernels.  A chunk
@@ -3299,6 +3362,11 @@ extern "C" int zrt_context_profile(const zrt_context* c, zrt_kernel_profile* out
 // launches, stats -- with the kernels' SEG instantiations (ray_launch's `seg`) and two
 // more per-ray arrays: the bounds, staged behind a chunk's rays, and the
 // occlusion bytes, staged behind its hit records.
+//
+// zrt_context_surface is the trace call with one more launch per
+// chunk, surface_kernel over the chunk's hit records, and one more per-ray
+// array: the records, staged in a buffer of their own.  A device batch without
+// `hits` keeps the chunk's hit records in the context's staging buffer.
 struct RayQuery {
     uint64_t num_rays;
     const float* rays;
@@ -3308,6 +3376,7 @@ struct RayQuery {
     const float* t_max;
     float t_max_all;
     uint8_t* occ;
+    zrt_surface* surf;        // zrt_context_surface: a record per ray (seg = -1), else null
 };
 static int query_rays(zrt_context* c, const RayQuery* b, zrt_stats* stats) {
     zrt_stats st{};
@@ -3327,8 +3396,11 @@ static int query_rays(zrt_context* c, const RayQuery* b, zrt_stats* stats) {
     // memory (device_budget; of pass set 0 this call reuses the queue and the
     // hit records only, so only those count as held)
     zrt_context::PassSet& ps = c->set[0];
-    const uint64_t per_ray = (b->on_device ? 0ull : 40ull + (seg ? kSegStageBytes : 0ull)) + (park ? 64ull : 0ull);
-    const size_t held = 4ull * (c->rays_cap + c->hits_cap) + 16ull * (ps.q0_cap + ps.hit_cap) + c->bfc_bytes;
+    const bool own_hits = b->surf && b->on_device && !b->hits;    // the gather reads records the caller did not ask for
+    const uint64_t per_ray = (b->on_device ? (own_hits ? 16ull : 0ull)
+                                           : 40ull + (seg ? kSegStageBytes : 0ull) + (b->surf ? 64ull : 0ull)) +
+                             (park ? 64ull : 0ull);
+    const size_t held = 4ull * (c->rays_cap + c->hits_cap) + 16ull * (ps.q0_cap + ps.hit_cap + c->surf_cap) + c->bfc_bytes;
     const size_t budget = device_budget(c, held);
     uint64_t chunk = std::min<uint64_t>(kTraceChunk, b->num_rays);
     if (per_ray) chunk = std::max<uint64_t>(64, std::min<uint64_t>(chunk, budget / per_ray));
@@ -3336,6 +3408,9 @@ static int query_rays(zrt_context* c, const RayQuery* b, zrt_stats* stats) {
     const uint64_t rays_words = 6 * chunk + (seg ? chunk : 0), hits_words = 4 * chunk + (seg ? (chunk + 3) / 4 : 0);
     if (!b->on_device) {
         if ((rc = grow(&c->d_rays, &c->rays_cap, rays_words)) != ZRT_OK) return rc;
+        if ((rc = grow(&c->d_hits, &c->hits_cap, hits_words)) != ZRT_OK) return rc;
+        if (b->surf && (rc = grow(&c->d_surf, &c->surf_cap, 4 * chunk)) != ZRT_OK) return rc;
+    } else if (own_hits) {
         if ((rc = grow(&c->d_hits, &c->hits_cap, hits_words)) != ZRT_OK) return rc;
     }
     const size_t ctr_words = wfc_words(0);         // (a render's smallest; this call uses 16 counters)
@@ -3346,7 +3421,9 @@ static int query_rays(zrt_context* c, const RayQuery* b, zrt_stats* stats) {
     }
     // capacity guard: every buffer a launch below writes holds a chunk
     if ((!b->on_device && (shortfall("rays", c->d_rays, c->rays_cap, rays_words) ||
-                           shortfall("hits", c->d_hits, c->hits_cap, hits_words))) ||
+                           shortfall("hits", c->d_hits, c->hits_cap, hits_words) ||
+                           (b->surf && shortfall("surfaces", c->d_surf, c->surf_cap, 4 * chunk)))) ||
+        (own_hits && shortfall("hits", c->d_hits, c->hits_cap, hits_words)) ||
         (park && (shortfall("q0", ps.q0, ps.q0_cap, 3 * chunk) || shortfall("hit records", ps.hit, ps.hit_cap, chunk) ||
                   shortfall("counters", ps.wfc, ps.wfc_cap, ctr_words))))
         return ZRT_ERR_INVALID_ARG;
@@ -3377,18 +3454,25 @@ static int query_rays(zrt_context* c, const RayQuery* b, zrt_stats* stats) {
 
     HIP_TRY(hipMemsetAsync(c->d_stats, 0, 512, c->stream));
     HIP_TRY(hipEventRecord(c->ev_begin, c->stream));
+    SurfaceParams S;
+    memset(&S, 0, sizeof S);
+    S.tri_data = c->d_data;
+    S.mats = c->d_mats;
+    S.texels = c->d_texels;
     uint32_t launches = 0;
     for (uint64_t off = 0; off < b->num_rays; off += chunk) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, b->num_rays - off);
         if (b->on_device) {
             R.rays = b->rays + 6 * off;
-            R.hits = b->hits ? reinterpret_cast<uint32_t*>(b->hits + off) : nullptr;
+            R.hits = b->hits ? reinterpret_cast<uint32_t*>(b->hits + off) : own_hits ? c->d_hits : nullptr;
+            S.surf = reinterpret_cast<float4*>(b->surf + off);
             R.t_max = b->t_max ? b->t_max + off : nullptr;
             R.occ = b->occ ? b->occ + off : nullptr;
         } else {
             HIP_TRY(hipMemcpyAsync(c->d_rays, b->rays + 6 * off, 24ull * n, hipMemcpyHostToDevice, c->stream));
             R.rays = c->d_rays;
-            R.hits = b->hits ? c->d_hits : nullptr;
+            R.hits = b->hits || b->surf ? c->d_hits : nullptr;
+            S.surf = c->d_surf;
             if (b->t_max) {
                 HIP_TRY(hipMemcpyAsync(c->d_rays + 6 * chunk, b->t_max + off, 4ull * n, hipMemcpyHostToDevice, c->stream));
                 R.t_max = c->d_rays + 6 * chunk;
@@ -3400,9 +3484,18 @@ static int query_rays(zrt_context* c, const RayQuery* b, zrt_stats* stats) {
         // the work counters; query_pack_kernel writes the region counts
         if (park) HIP_TRY(hipMemsetAsync(ps.wfc, 0, 4ull * 16 * kCtr, c->stream));
         if ((rc = trace_first_segments(c, pl, rl, R, n, true, &launches)) != ZRT_OK) return rc;
+        if (b->surf) {                                 // the gather: one thread per ray over the records just written
+            S.rays = R.rays;
+            S.hits = R.hits;
+            S.n = n;
+            hipLaunchKernelGGL(surface_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, S);
+            ++launches;
+            HIP_TRY(hipGetLastError());
+        }
         if (!b->on_device) {
             HIP_TRY(hipEventRecord(c->ev_trace[1], c->stream));
             if (b->hits) HIP_TRY(copy_sync(b->hits + off, c->d_hits, 16ull * n, hipMemcpyDeviceToHost, c->stream));
+            if (b->surf) HIP_TRY(copy_sync(b->surf + off, c->d_surf, 64ull * n, hipMemcpyDeviceToHost, c->stream));
             if (b->occ) HIP_TRY(copy_sync(b->occ + off, R.occ, n, hipMemcpyDeviceToHost, c->stream));
             float t = 0.0f;
             HIP_TRY(hipEventElapsedTime(&t, c->ev_trace[0], c->ev_trace[1]));
@@ -3429,7 +3522,19 @@ extern "C" int zrt_context_trace(zrt_context* c, const zrt_ray_batch* b, zrt_sta
     if ((b->flags & ~kTraceFlags) != 0u || b->on_device > 1u) return ZRT_ERR_INVALID_ARG;
     if (b->num_rays == 0) { if (stats) *stats = zrt_stats{}; return ZRT_OK; }
     if (!b->rays || !b->hits) return ZRT_ERR_INVALID_ARG;
-    const RayQuery q{b->num_rays, b->rays, b->hits, b->on_device, b->flags, -1, nullptr, 0.0f, nullptr};
+    const RayQuery q{b->num_rays, b->rays, b->hits, b->on_device, b->flags, -1, nullptr, 0.0f, nullptr, nullptr};
+    return query_rays(c, &q, stats);
+}
+
+// The shading inputs at each ray's first hit: see include/zrt.h and DESIGN 5.14.
+extern "C" int zrt_context_surface(zrt_context* c, const zrt_surface_batch* b, zrt_stats* stats) {
+    if (!c || !b) return ZRT_ERR_INVALID_ARG;
+    if ((b->flags & ~kTraceFlags) != 0u || b->on_device > 1u) return ZRT_ERR_INVALID_ARG;
+    if (b->num_rays == 0) { if (stats) *stats = zrt_stats{}; return ZRT_OK; }
+    if (!b->rays || !b->surfaces) return ZRT_ERR_INVALID_ARG;
+    // surface_kernel stores a record as four 16-byte words
+    if (b->on_device && (reinterpret_cast<uintptr_t>(b->surfaces) & 15u) != 0u) return ZRT_ERR_INVALID_ARG;
+    const RayQuery q{b->num_rays, b->rays, b->hits, b->on_device, b->flags, -1, nullptr, 0.0f, nullptr, b->surfaces};
     return query_rays(c, &q, stats);
 }
 
@@ -3443,7 +3548,7 @@ extern "C" int zrt_context_segments(zrt_context* c, const zrt_segment_batch* b, 
     if (b->num_rays == 0) { if (stats) *stats = zrt_stats{}; return ZRT_OK; }
     if (!b->rays || (!b->hits && !b->occluded)) return ZRT_ERR_INVALID_ARG;
     const RayQuery q{b->num_rays, b->rays, b->hits, b->on_device, b->flags & ~ZRT_SEGMENT_ANY, any ? 1 : 0,
-                     b->t_max, b->t_max_all, b->occluded};
+                     b->t_max, b->t_max_all, b->occluded, nullptr};
     return query_rays(c, &q, stats);
 }
 

@@ -185,6 +185,8 @@ struct zrt_context {
     // zrt_context_trace: a host batch's chunk on the device (6 floats, 4 u32 per ray)
     float* d_rays = nullptr; size_t rays_cap = 0;
     uint32_t* d_hits = nullptr; size_t hits_cap = 0;
+    // zrt_context_surface: a host batch's chunk of records (4 float4 per ray)
+    float4* d_surf = nullptr; size_t surf_cap = 0;
     // zrt_context_radiance: a chunk's rays with normalised directions (6 floats per ray)
     float* d_nrays = nullptr; size_t nrays_cap = 0;
     std::vector<hipEvent_t> ev_pass;   // per pass: its resolve done

@@ -134,6 +134,22 @@ class SegmentBatch(C.Structure):
                 ("t_max_all", C.c_float), ("_reserved", C.c_uint32)]
 
 
+class Surface(C.Structure):
+    _fields_ = [("position", C.c_float * 3), ("material", C.c_uint32), ("normal", C.c_float * 3),
+                ("transparency", C.c_float), ("base_color", C.c_float * 3), ("texcoord_s", C.c_float),
+                ("emissive", C.c_float * 3), ("texcoord_t", C.c_float)]
+
+
+SURFACE_DTYPE = np.dtype([("position", "<f4", (3,)), ("material", "<u4"), ("normal", "<f4", (3,)),
+                          ("transparency", "<f4"), ("base_color", "<f4", (3,)), ("texcoord_s", "<f4"),
+                          ("emissive", "<f4", (3,)), ("texcoord_t", "<f4")])
+
+
+class SurfaceBatch(C.Structure):
+    _fields_ = [("num_rays", C.c_uint64), ("rays", C.c_void_p), ("surfaces", C.c_void_p), ("hits", C.c_void_p),
+                ("on_device", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class RadianceBatch(C.Structure):
     _fields_ = [("num_rays", C.c_uint64), ("rays", C.c_void_p), ("radiance", C.c_void_p), ("rgb", C.c_void_p),
                 ("on_device", C.c_uint32), ("flags", C.c_uint32), ("num_samples", C.c_uint32),
@@ -148,7 +164,7 @@ EXPORTS = [
     "zrt_gltf_load", "zrt_gltf_soup", "zrt_gltf_materials", "zrt_gltf_camera", "zrt_gltf_free",
     "zrt_camera_from_matrix", "zrt_probe", "zrt_timed_kernels", "zrt_context_profile", "zrt_context_trace",
     "zrt_group_create", "zrt_group_create_built", "zrt_group_render", "zrt_group_context", "zrt_group_destroy",
-    "zrt_context_radiance", "zrt_context_segments",
+    "zrt_context_radiance", "zrt_context_segments", "zrt_context_surface",
 ]
 
 
@@ -188,6 +204,7 @@ def lib():
     L.zrt_context_destroy.restype = None
     L.zrt_context_radiance.argtypes = [C.c_void_p, C.POINTER(RadianceBatch), C.POINTER(Stats)]
     L.zrt_context_segments.argtypes = [C.c_void_p, C.POINTER(SegmentBatch), C.POINTER(Stats)]
+    L.zrt_context_surface.argtypes = [C.c_void_p, C.POINTER(SurfaceBatch), C.POINTER(Stats)]
     if hasattr(L, "zrt_group_create"):     # ABI 2 (an ABI-1 build: tools/ A/B baselines only)
         L.zrt_group_create.argtypes = [C.POINTER(Scene), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
         L.zrt_group_create_built.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -509,6 +526,53 @@ class Context:
         res = {"occluded": occ.view(np.bool_), "stats": st}
         if hits is not None:
             res.update(t=hits["t"].copy(), u=hits["u"].copy(), v=hits["v"].copy(), triangle=hits["triangle"].copy())
+        return res
+
+    def surface_raw(self, num_rays: int, rays_ptr, surfaces_ptr, hits_ptr, on_device: bool, flags: int = 0):
+        """zrt_context_surface on raw pointers; returns the stats dict."""
+        batch = SurfaceBatch(int(num_rays), rays_ptr, surfaces_ptr, hits_ptr, 1 if on_device else 0, int(flags))
+        st = Stats()
+        check(lib().zrt_context_surface(self._h, C.byref(batch), C.byref(st)), "zrt_context_surface")
+        return st.as_dict()
+
+    def surface(self, origins, dirs, flags: int = 0, stats: bool = False, hits: bool = False):
+        """What is at each ray's first hit (zrt_context_surface): the inputs
+        traceRayRecursive shades with (stage3.zig:199-206) and the origin it
+        continues from.  `dirs` need not be unit length; the rays are traced as
+        trace() traces them.
+
+        Two (n, 3) float32 numpy arrays give one array per field of
+        zrt_surface -- "position", "normal", "base_color", "emissive" (n, 3)
+        float32; "transparency", "texcoord_s", "texcoord_t" (n,) float32;
+        "material" (n,) uint32 -- and "stats".  A miss is all zeros with
+        material = MISS.  The normal is not normalised.  With hits=True also
+        trace()'s "t", "u", "v", "triangle".
+
+        Two (n, 3) float32 CUDA tensors (torch-ROCm) on the context's device
+        are traced in place, after a sync of torch's current stream:
+        {"surfaces": an (n, 16) float32 CUDA tensor of the records' words
+        (`[:, 3].view(torch.int32)` is the material, -1: a miss), "stats"}, and
+        with hits=True "hits" as in trace()."""
+        flags = int(flags) | (FLAG_COUNT_STATS if stats else 0)
+        torch, n, rays = self._rays("surface", origins, dirs)
+        if torch:
+            surf = torch.empty((n, 16), dtype=torch.float32, device=origins.device)
+            rec = torch.empty((n, 4), dtype=torch.float32, device=origins.device) if hits else None
+            torch.cuda.current_stream(origins.device).synchronize()
+            st = self.surface_raw(n, rays.data_ptr() if n else None, surf.data_ptr() if n else None,
+                                  rec.data_ptr() if hits and n else None, True, flags)
+            res = {"surfaces": surf, "stats": st}
+            if hits:
+                res["hits"] = rec
+            return res
+        surf = np.empty(n, SURFACE_DTYPE)
+        rec = np.empty(n, HIT_DTYPE) if hits else None
+        st = self.surface_raw(n, rays.ctypes.data if n else None, surf.ctypes.data if n else None,
+                              rec.ctypes.data if hits and n else None, False, flags)
+        res = {k: surf[k].copy() for k in SURFACE_DTYPE.names}
+        if hits:
+            res.update(t=rec["t"].copy(), u=rec["u"].copy(), v=rec["v"].copy(), triangle=rec["triangle"].copy())
+        res["stats"] = st
         return res
 
     def radiance_raw(self, num_rays: int, rays_ptr, radiance_ptr, rgb_ptr, on_device: bool, spp: int,
