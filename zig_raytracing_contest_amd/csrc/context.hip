@@ -541,7 +541,7 @@ __global__ __launch_bounds__(kBlock) void occ_cells_kernel(const uint2* __restri
 }
 
 // Escape table (escape.h): a summed-area table of cell occupancy, then one
-// thread per (4^3 brick, direction bin).
+// thread per (region of a 4^3 brick, direction bin).
 __global__ __launch_bounds__(kBlock) void esc_sat_fill_kernel(const uint2* __restrict__ cells, uint32_t r0, uint32_t r1,
                                                               uint32_t ncells, uint32_t n0, uint32_t n01,
                                                               uint32_t* __restrict__ sat) {
@@ -576,15 +576,18 @@ __global__ __launch_bounds__(kBlock) void esc_sat_scan_kernel(uint32_t* __restri
 }
 __global__ __launch_bounds__(kBlock) void esc_build_kernel(const uint32_t* __restrict__ sat, uint32_t r0, uint32_t r1,
                                                            uint32_t r2, float cs0, float cs1, float cs2, uint32_t nb0,
-                                                           uint32_t nb1, uint32_t nbr, uint32_t* __restrict__ esc) {
+                                                           uint32_t nb1, uint32_t nbr, EscShape sh,
+                                                           uint32_t* __restrict__ esc) {
     const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (t >= (uint64_t)nbr * kEscNBin) return;
-    const uint32_t br = (uint32_t)(t / kEscNBin), bin = (uint32_t)(t % kEscNBin);
+    const uint32_t lg = esc_regions_lg(sh);
+    if (t >= ((uint64_t)nbr << lg) * kEscNBin) return;
+    const uint32_t rg = (uint32_t)(t / kEscNBin), bin = (uint32_t)(t % kEscNBin);
+    const uint32_t br = rg >> lg, sub = rg & ((1u << lg) - 1u);
     const uint32_t res[3] = {r0, r1, r2};
     const float cs[3] = {cs0, cs1, cs2};
     const EscSat S{sat, r0 + 1u, (r0 + 1u) * (r1 + 1u)};
-    if (esc_compute(S, res, cs, br % nb0, (br / nb0) % nb1, br / (nb0 * nb1), bin))
-        atomicOr(&esc[(uint64_t)br * kEscWords + (bin >> 5)], 1u << (bin & 31u));
+    if (esc_compute_region(S, res, cs, sh, br % nb0, (br / nb0) % nb1, br / (nb0 * nb1), sub, bin))
+        atomicOr(&esc[(uint64_t)rg * kEscWords + (bin >> 5)], 1u << (bin & 31u));
 }
 
 // Least fraction of set escape bits for the park launches to use the table.
@@ -613,22 +616,32 @@ static int context_sat(zrt_context* c) {
 // The escape table (escape.h) for a context with OccX (the park walk); none
 // for grids whose summed-area table would pass 2^28 entries (the walk then
 // never stops early, as before).
-int context_escape(zrt_context* c) {
+int context_escape(zrt_context* c, bool forced) {
     if (!c->occx_ok || !c->d_sat) return ZRT_OK;
     const uint32_t* r = c->grid.resolution;
     const uint64_t nbr = (uint64_t)c->occx_nb[0] * c->occx_nb[1] * c->occx_nb[2];
-    HIP_TRY(hipMalloc((void**)&c->d_esc, 4ull * kEscWords * nbr));
-    HIP_TRY(hipMemsetAsync(c->d_esc, 0, 4ull * kEscWords * nbr, c->stream));
-    const uint64_t nthr = nbr * kEscNBin;
-    hipLaunchKernelGGL(esc_build_kernel, dim3((uint32_t)((nthr + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
-                       (const uint32_t*)c->d_sat, r[0], r[1], r[2], c->grid.cell_size[0], c->grid.cell_size[1],
-                       c->grid.cell_size[2], c->occx_nb[0], c->occx_nb[1], (uint32_t)nbr, c->d_esc);
-    HIP_TRY(hipGetLastError());
+    StageClock sc;
+    // one table at shape `sh` into *out (threads < 2^31 blocks: the caller's budget)
+    auto build = [&](const EscShape& sh, uint32_t** out) -> int {
+        const uint64_t bytes = (4ull * kEscWords * nbr) << esc_regions_lg(sh);
+        HIP_TRY(hipMalloc((void**)out, bytes));
+        HIP_TRY(hipMemsetAsync(*out, 0, bytes, c->stream));
+        const uint64_t nthr = (nbr << esc_regions_lg(sh)) * kEscNBin;
+        hipLaunchKernelGGL(esc_build_kernel, dim3((uint32_t)((nthr + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
+                           (const uint32_t*)c->d_sat, r[0], r[1], r[2], c->grid.cell_size[0], c->grid.cell_size[1],
+                           c->grid.cell_size[2], c->occx_nb[0], c->occx_nb[1], (uint32_t)nbr, sh, *out);
+        HIP_TRY(hipGetLastError());
+        return ZRT_OK;
+    };
+    // The brick-level table: the park kernel's, unless a finer shape fits below.
+    int rc;
+    if ((rc = build(kEscBrick, &c->d_esc)) != ZRT_OK) return rc;
     // Use it when enough of its bits are set: each walk trip of the park
     // kernel then issues a table query per brick entered (~4% of a launch on
     // scenes whose rays never escape, r04g), and the check itself costs ~1.5%.
     // Measured (r04): contest stand-in 23% of the bits set, +8% frame rate;
     // Cornell box 6%, -1.5%; Sponza-scale 1.6%, -4%.
+    // (The statistic stays the brick-level one whatever shape the walk asks.)
     std::vector<uint32_t> h(kEscWords * nbr);
     HIP_TRY(hipMemcpyAsync(h.data(), c->d_esc, 4ull * kEscWords * nbr, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -636,6 +649,35 @@ int context_escape(zrt_context* c) {
     for (uint32_t x : h) set += (uint64_t)__builtin_popcount(x);
     c->esc_density = (double)set / ((double)nbr * kEscNBin);
     c->esc_on = c->esc_density >= kEscMinDensity;
+    sc.mark(c, "escape table (bricks)");
+    // The table the walk asks: keyed by sub-brick regions (escape.h
+    // esc_shape_for: 16 per brick, 16 times the bytes and the build time, once
+    // per context; cfg3: 25 MB, 35 ms against 1.6 MB, 2.5 ms), if it fits a
+    // quarter of the free memory, the park kernel's 32-bit byte offsets and a
+    // launch's 2^31 blocks; else the brick-level table stays.  Only where the
+    // launches will use it: the scene's statistic says so, or this call's flag.
+    // ZRT_ESC_BRICK=1 keeps it too (tools/ A/B runs and the tests).
+    const float cs[3] = {c->grid.cell_size[0], c->grid.cell_size[1], c->grid.cell_size[2]};
+    const EscShape sh = esc_shape_for(cs);
+    const uint32_t lg = esc_regions_lg(sh);
+    const uint64_t bytes = (4ull * kEscWords * nbr) << lg;
+    size_t free_b = 0, total_b = 0;
+    const bool fits = (c->esc_on || forced) && esc_cells_regular(cs) && !getenv("ZRT_ESC_BRICK") &&
+                      hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes <= free_b / 4 && bytes < (1ull << 32) &&
+                      ((nbr << lg) * kEscNBin) / kBlock < (1ull << 31);
+    if (fits) {
+        uint32_t* fine = nullptr;
+        if ((rc = build(sh, &fine)) != ZRT_OK) {
+            (void)hipFree(fine);
+            return rc;
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        (void)hipFree(c->d_esc);
+        c->d_esc = fine;
+        c->esc_extra = bytes - 4ull * kEscWords * nbr;
+        c->esc_key = esc_walk_key(sh);
+        sc.mark(c, "escape table (regions)");
+    }
     return ZRT_OK;
 }
 

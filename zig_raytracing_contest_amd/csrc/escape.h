@@ -5,7 +5,8 @@
 // visits until nearest <= t_next_crossing.  If no cell after the current one
 // holds a triangle, nothing after it can change the result: the walk may
 // stop there with the nearest hit so far (a miss stays +inf).  The table
-// proves that conservatively, per 4^3 brick B and direction bin:
+// proves that conservatively, per start box B (a 4^3 brick, or a region of
+// one: EscShape below) and direction bin:
 //   * a bin is a cone of directions: the dominant axis a and its sign (the
 //     cube face), and the slopes u = d_b / |d_a|, v = d_c / |d_a| of the
 //     other two axes in one of kEscBins x kEscBins cells of [-1, 1]^2;
@@ -73,7 +74,6 @@ ZHD uint32_t esc_box(const EscSat& S, uint32_t x0, uint32_t x1, uint32_t y0, uin
            S.s[Z0 + Y1 + X0] + S.s[Z0 + Y0 + X1] - S.s[Z0 + Y0 + X0];
 }
 
-// The bit of brick (bx, by, bz) and `bin` (see the header comment).
 // A grid with a zero-extent (or non-finite) axis -- every triangle in one
 // plane, Grid.init's cell_size 0 (linalg.zig:412-441) -- has walks whose
 // crossings on that axis do not advance t, which the cell-unit geometry below
@@ -82,8 +82,13 @@ ZHD bool esc_cells_regular(const float cs[3]) {
     return cs[0] > 0.0f && cs[1] > 0.0f && cs[2] > 0.0f && cs[0] < kInf && cs[1] < kInf && cs[2] < kInf;
 }
 
-ZHD bool esc_compute(const EscSat& S, const uint32_t res[3], const float cs[3], uint32_t bx, uint32_t by,
-                     uint32_t bz, uint32_t bin) {
+// The bit of the start box of cells [c0, c1) (per axis, inside the grid) and
+// `bin`: the header's proof with that box for B.  `dil`: the dilation in
+// cells, 1 everywhere but in the host check's control (0: walks whose f32
+// crossing times are coarse then leave the region along a bin's edge,
+// tests/cpp/escape_region_check.cpp).
+ZHD bool esc_compute_box(const EscSat& S, const uint32_t res[3], const float cs[3], const uint32_t c0[3],
+                         const uint32_t c1[3], uint32_t bin, double dil = 1.0) {
     if (!esc_cells_regular(cs)) return false;
     const uint32_t fc = bin / (kEscBins * kEscBins), iu = (bin / kEscBins) % kEscBins, iv = bin % kEscBins;
     const int a = (int)(fc / 2u), sg = (fc & 1u) ? -1 : 1;
@@ -91,11 +96,10 @@ ZHD bool esc_compute(const EscSat& S, const uint32_t res[3], const float cs[3], 
     const double nb = (double)kEscBins;
     const double u0 = -1.0 + 2.0 * iu / nb - kEscEps, u1 = -1.0 + 2.0 * (iu + 1) / nb + kEscEps;
     const double v0 = -1.0 + 2.0 * iv / nb - kEscEps, v1 = -1.0 + 2.0 * (iv + 1) / nb + kEscEps;
-    const uint32_t B[3] = {bx, by, bz};
     double lo[3], hi[3];
     for (int k = 0; k < 3; ++k) {
-        lo[k] = 4.0 * B[k];
-        hi[k] = fmin(4.0 * B[k] + 4.0, (double)res[k]);
+        lo[k] = (double)c0[k];
+        hi[k] = (double)c1[k];
     }
     // a cell-unit step along a moves cs_a / cs_b cells along b
     const double kb = (double)cs[a] / (double)cs[b], kc = (double)cs[a] / (double)cs[c];
@@ -107,7 +111,8 @@ ZHD bool esc_compute(const EscSat& S, const uint32_t res[3], const float cs[3], 
         const double ylo = lo[b] + kb * fmin(smin * u0, smax * u0), yhi = hi[b] + kb * fmax(smin * u1, smax * u1);
         const double zlo = lo[c] + kc * fmin(smin * v0, smax * v0), zhi = hi[c] + kc * fmax(smin * v1, smax * v1);
         // the cells the interval touches, one more on each side
-        const double yf0 = floor(ylo) - 1.0, yf1 = ceil(yhi), zf0 = floor(zlo) - 1.0, zf1 = ceil(zhi);
+        const double yf0 = floor(ylo) - dil, yf1 = ceil(yhi) - 1.0 + dil;
+        const double zf0 = floor(zlo) - dil, zf1 = ceil(zhi) - 1.0 + dil;
         if (yf1 < 0.0 || yf0 > res[b] - 1.0 || zf1 < 0.0 || zf0 > res[c] - 1.0) {
             // the region lies beside the grid in this slab; it only moves
             // further out when neither slope range straddles 0 on that side
@@ -125,6 +130,89 @@ ZHD bool esc_compute(const EscSat& S, const uint32_t res[3], const float cs[3], 
         if (esc_box(S, lo3[0], hi3[0], lo3[1], hi3[1], lo3[2], hi3[2]) != 0u) return false;
     }
     return true;
+}
+// The bit of brick (bx, by, bz) and `bin`: the brick's cells as the start box.
+ZHD bool esc_compute(const EscSat& S, const uint32_t res[3], const float cs[3], uint32_t bx, uint32_t by,
+                     uint32_t bz, uint32_t bin) {
+    const uint32_t B[3] = {bx, by, bz};
+    uint32_t c0[3], c1[3];
+    for (int k = 0; k < 3; ++k) {
+        c0[k] = 4u * B[k];
+        c1[k] = 4u * B[k] + 4u < res[k] ? 4u * B[k] + 4u : res[k];
+    }
+    return esc_compute_box(S, res, cs, c0, c1, bin);
+}
+
+// Start regions smaller than the brick.  The smaller the start box, the
+// narrower its swept region and the more bits are set: rays that skim a
+// ground plane leave a 4^3 brick's dilated region (6 cells wide) through
+// occupied cells, a single cell's (3 wide) often not.  A brick is cut into
+// regions of 2^l0 x 2^l1 x 2^l2 cells (EscShape, each l in 0..2; {2, 2, 2} is
+// the brick itself), and the table holds kEscWords words per region, a
+// brick's regions together: region (brick br, sub-index sub) at word
+// (br * esc_regions + sub) * kEscWords.  The walk still asks once per brick
+// entered, for the region that holds the cell it is in: every cell it visits
+// after that cell lies in that region's swept cone, dilated (the proof above
+// with the region for B), so a set bit ends the walk as a brick's does.  A
+// region is a subset of its brick, its swept region in every slab a subset of
+// the brick's (every bound above is monotone in the box), so a region's bit
+// is set wherever its brick's is.
+struct EscShape {
+    uint32_t l0, l1, l2;
+};
+constexpr uint32_t esc_log2(uint32_t g) { return g == 4u ? 2u : (g == 2u ? 1u : 0u); }
+constexpr EscShape kEscBrick = {2u, 2u, 2u};
+// log2 of the regions per brick
+ZHD constexpr uint32_t esc_regions_lg(const EscShape& h) { return 6u - h.l0 - h.l1 - h.l2; }
+// The sub-index of the region that holds the brick's cell i = x | y << 2 | z << 4.
+ZHD constexpr uint32_t esc_sub_of(const EscShape& h, uint32_t i) {
+    return ((i & 3u) >> h.l0) | ((((i >> 2) & 3u) >> h.l1) << (2u - h.l0)) |
+           ((((i >> 4) & 3u) >> h.l2) << (4u - h.l0 - h.l1));
+}
+// The cells [c0, c1) of region `sub` of brick (bx, by, bz), clipped to the
+// grid; false: the region lies outside it (no cell, no walk ever asks).
+ZHD bool esc_region_box(const EscShape& h, const uint32_t res[3], uint32_t bx, uint32_t by, uint32_t bz, uint32_t sub,
+                        uint32_t c0[3], uint32_t c1[3]) {
+    const uint32_t B[3] = {bx, by, bz}, l[3] = {h.l0, h.l1, h.l2};
+    const uint32_t s[3] = {sub & ((4u >> h.l0) - 1u), (sub >> (2u - h.l0)) & ((4u >> h.l1) - 1u),
+                           sub >> (4u - h.l0 - h.l1)};
+    for (int k = 0; k < 3; ++k) {
+        c0[k] = 4u * B[k] + (s[k] << l[k]);
+        if (c0[k] >= res[k]) return false;
+        c1[k] = c0[k] + (1u << l[k]) < res[k] ? c0[k] + (1u << l[k]) : res[k];
+    }
+    return true;
+}
+// The shape a context builds: one cell along the two axes with the larger
+// cells, the brick's four along the axis with the smallest (the first such
+// axis): 16 regions per brick.  On the contest stand-in (128^3, 1 x 4 x 1)
+// against the brick-level table, full frames, alternating processes:
+// 1 x 4 x 1 +2.6%, 1 x 1 x 1 +2.7% at 4 times the memory and build time,
+// 2 x 2 x 2 +1.4% (profiles/r10).
+ZHD EscShape esc_shape_for(const float cs[3]) {
+    int m = 0;
+    for (int k = 1; k < 3; ++k)
+        if (cs[k] < cs[m]) m = k;
+    return EscShape{m == 0 ? 2u : 0u, m == 1 ? 2u : 0u, m == 2 ? 2u : 0u};
+}
+// What the park walk needs of the table's shape, in one word (WfParams::esc_key):
+// lg = log2 of the regions per brick in bits [0, 8), and two masks that pick
+// the sub-index out of the in-brick cell index i = x | y << 2 | z << 4:
+//     sub = (i & m_lo) | ((i >> 2) & m_hi), m_lo in bits [8, 16), m_hi from 16.
+// 0: the brick-level table.  For esc_shape_for's shapes and the brick only
+// (of the three axes' 2-bit groups two are kept whole).
+ZHD uint32_t esc_walk_key(const EscShape& h) {
+    if (h.l0 == 2u && h.l1 == 0u && h.l2 == 0u) return 4u | (0u << 8) | (15u << 16);
+    if (h.l0 == 0u && h.l1 == 2u && h.l2 == 0u) return 4u | (3u << 8) | (12u << 16);
+    if (h.l0 == 0u && h.l1 == 0u && h.l2 == 2u) return 4u | (15u << 8) | (0u << 16);
+    return 0u;
+}
+ZHD uint32_t esc_key_sub(uint32_t key, uint32_t i) { return (i & ((key >> 8) & 0xFFu)) | ((i >> 2) & (key >> 16)); }
+ZHD bool esc_compute_region(const EscSat& S, const uint32_t res[3], const float cs[3], const EscShape& h, uint32_t bx,
+                            uint32_t by, uint32_t bz, uint32_t sub, uint32_t bin, double dil = 1.0) {
+    uint32_t c0[3], c1[3];
+    if (!esc_region_box(h, res, bx, by, bz, sub, c0, c1)) return false;
+    return esc_compute_box(S, res, cs, c0, c1, bin, dil);
 }
 
 // Primary-ray frustum bound (the primary launch, render.hip frustum_kernel).

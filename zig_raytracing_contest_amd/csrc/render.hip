@@ -625,6 +625,8 @@ struct WfParams {
                               //   part of wf_resolve_kernel's symbol name)
     float4* term;             // [item]: terminal L.xyz, scatter mask bits
     uint32_t T;               // items in this pass
+    uint32_t esc_key;         // escape table (below): its shape (escape.h esc_walk_key; 0: a word
+                              //   group per brick).  In T's padding, so that no other field moves
     uint32_t* fetch8;         // work counter per group of this launch
     const uint32_t* n_in8;    // paths per region of q_in
     uint32_t* n_out8;         // paths per region of q_out
@@ -638,8 +640,9 @@ struct WfParams {
     uint32_t refill_min;      // finished lanes before a wave shades and refills
     uint32_t rel_min;         // park release: a round with fewer parked lanes with refs is skipped (0: off)
     uint32_t rel_emin;        //   ... if at least this many parked lanes have none
-    // escape table (escape.h): kEscWords u32 per 4^3 brick, bit b of word
-    // w = direction bin 32 w + b; null: not built (the walk never stops early)
+    // escape table (escape.h): kEscWords u32 per region of a 4^3 brick, a
+    // brick's regions together (esc_key), bit b of word w = direction bin
+    // 32 w + b; null: not built (the walk never stops early)
     const uint32_t* esc;
     // back-face cull masks (escape.h): kBfcNBin u32 per packed cell word, then
     // one all-ones word; null: the first cell of a segment tests every ref
@@ -1242,6 +1245,9 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
     // crossing sequence)
     uint32_t eoff = 0, emask = 0;
     uint32_t eb = ~0u;                     // the brick of the lane's last escape-table query
+    // the table's shape (escape.h esc_walk_key), wave-uniform
+    const uint32_t esc_key = ESC ? __builtin_amdgcn_readfirstlane(w.esc_key) : 0u;
+    const uint32_t esc_lg = esc_key & 0xFFu, esc_mlo = (esc_key >> 8) & 0xFFu, esc_mhi = esc_key >> 16;
     PARK_PROF_DECL
 
     for (;;) {
@@ -1466,8 +1472,16 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
                     // change while the lane walks inside the brick)
                     const uint32_t b = occx_brick<PK_BM>(w, s);
                     if (st == kWalk && emask != 0u && b != eb) {
+                        // the region of the brick that holds the lane's cell
+                        // (escape.h EscShape: its sub-index is bits of the
+                        // in-brick cell index x | y << 2 | z << 4, the low six
+                        // bits of a brick-major word, the fields' low bits
+                        // summed by occx_cell's multiply otherwise); with the
+                        // brick-level table (key 0) the brick itself
+                        const uint32_t ci = PK_BM ? s.pc : __umul24(s.pc & pk.low2, pk.kmul) >> pk.kshr;
+                        const uint32_t rg = (b << esc_lg) | (ci & esc_mlo) | ((ci >> 2) & esc_mhi);
                         park_load_esc(reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(w.esc) +
-                                                                        b * (4u * kEscWords) + eoff),
+                                                                        rg * (4u * kEscWords) + eoff),
                                       esc_slot);
                         eb = b;
                     }
@@ -2624,8 +2638,9 @@ static void plan_park_block(LaunchPlan& pl, int block) {
 // `want_park`: what the entry point asks besides (a small query takes the lane
 // walk unasked); `big`: a call of kSetsMinSamples samples or more.
 // The escape table and the back-face cull masks are built here, at the first
-// big call that parks or the first a flag forces: 2.1 ms on cfg3 at 384 bins
-// (r04eb2), more than the table saves a 3-spp 1080p frame.  Each is used where
+// big call that parks or the first a flag forces: 2.5 ms on cfg3 at 384 bins
+// and 35 ms more for its region table where the launches use it (r10d), more
+// than the table saves a 3-spp 1080p frame.  Each is used where
 // the scene's statistic says it pays (context_escape, context_bfcull) or as
 // the flags force it; the image is the same either way.
 static int resolve_plan(zrt_context* c, uint32_t flags, bool counting, bool want_park, bool big, LaunchPlan& pl) {
@@ -2644,7 +2659,7 @@ static int resolve_plan(zrt_context* c, uint32_t flags, bool counting, bool want
     pl.rel = !(flags & ZRT_FLAG_NO_RELEASE) && (c->rel_on || (flags & ZRT_FLAG_RELEASE));
     if (!c->esc_tried && pl.park && !(flags & ZRT_FLAG_NO_ESCAPE) && (big || (flags & ZRT_FLAG_ESCAPE))) {
         c->esc_tried = true;
-        if ((rc = context_escape(c)) != ZRT_OK) return rc;
+        if ((rc = context_escape(c, (flags & ZRT_FLAG_ESCAPE) != 0)) != ZRT_OK) return rc;
     }
     pl.esc = c->d_esc && !(flags & ZRT_FLAG_NO_ESCAPE) && (c->esc_on || (flags & ZRT_FLAG_ESCAPE));
     if (pl.park && !(flags & ZRT_FLAG_NO_BFCULL)) {
@@ -2687,6 +2702,7 @@ static void park_params(const zrt_context* c, const LaunchPlan& pl, WfParams& W)
     W.rel_min = pl.rel ? pl.rel_min : 0u;
     W.rel_emin = pl.rel_emin;
     W.esc = c->d_esc;
+    W.esc_key = c->esc_key;
     W.bfc = pl.bfc ? c->d_bfc : nullptr;
     W.bfc_ones = c->bfc_bytes ? c->bfc_bytes / 4 - 1 : 0;
 }
@@ -2906,7 +2922,7 @@ static PassSplit split_passes(const zrt_context* c, const zrt_render_config* cfg
 #if defined(ZRT_SWEEP) || defined(ZRT_SETS_ENV)
     if (const char* e = getenv("ZRT_SETS")) want_sets = (uint32_t)std::max(1, std::min((int)kMaxPassSets, atoi(e)));
 #endif
-    size_t held = 16ull * c->out_cap + c->bfc_bytes;   // (the cull masks: the split must not depend on them)
+    size_t held = 16ull * c->out_cap + c->bfc_bytes + c->esc_extra;   // (the cull masks, the escape table's regions: the split must not depend on them)
     for (const zrt_context::PassSet& ps : c->set) held += held_bytes(ps);
     sp.s_pass = pass_samples(c, cfg, per_item, P, counting ? 1u : want_sets, held);
     sp.npasses = (uint32_t)((spp + sp.s_pass - 1) / sp.s_pass);
@@ -3400,7 +3416,7 @@ static int query_rays(zrt_context* c, const RayQuery* b, zrt_stats* stats) {
     const uint64_t per_ray = (b->on_device ? (own_hits ? 16ull : 0ull)
                                            : 40ull + (seg ? kSegStageBytes : 0ull) + (b->surf ? 64ull : 0ull)) +
                              (park ? 64ull : 0ull);
-    const size_t held = 4ull * (c->rays_cap + c->hits_cap) + 16ull * (ps.q0_cap + ps.hit_cap + c->surf_cap) + c->bfc_bytes;
+    const size_t held = 4ull * (c->rays_cap + c->hits_cap) + 16ull * (ps.q0_cap + ps.hit_cap + c->surf_cap) + c->bfc_bytes + c->esc_extra;
     const size_t budget = device_budget(c, held);
     uint64_t chunk = std::min<uint64_t>(kTraceChunk, b->num_rays);
     if (per_ray) chunk = std::max<uint64_t>(64, std::min<uint64_t>(chunk, budget / per_ray));
@@ -3612,7 +3628,7 @@ extern "C" int zrt_context_radiance(zrt_context* c, const zrt_radiance_batch* b,
     zrt_context::PassSet& ps = c->set[0];
     const uint64_t per_item = 96ull + 16ull + 16ull + 32ull * nb;
     const uint64_t per_ray = per_item * S + 24ull + 15ull + (b->on_device ? 0ull : 24ull);
-    const size_t held = 4ull * (c->rays_cap + c->nrays_cap + c->lin_cap) + c->rgb_cap + c->bfc_bytes + held_bytes(ps);
+    const size_t held = 4ull * (c->rays_cap + c->nrays_cap + c->lin_cap) + c->rgb_cap + c->bfc_bytes + c->esc_extra + held_bytes(ps);
     const size_t budget = device_budget(c, held);
     uint64_t chunk = std::min<uint64_t>(kTraceChunk, 0x7FFFFF00ull / S);
     chunk = std::max<uint64_t>(64, std::min<uint64_t>(chunk, budget / per_ray));

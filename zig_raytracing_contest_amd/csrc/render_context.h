@@ -146,6 +146,8 @@ struct zrt_context {
     bool rel_on = false;
     bool esc_tried = false;         // context_escape ran (at the first render that can use it)
     double esc_density = 0.0;       // fraction of its (brick, bin) bits set
+    uint32_t esc_key = 0;           // the table's shape for the walk (escape.h esc_walk_key; 0: brick-level)
+    size_t esc_extra = 0;           // its bytes beyond the brick-level table's (counted as held)
     // back-face cull masks (escape.h, context_bfcull): built at the first
     // render that can use them, if they fit kBfcBudget / mem_share
     uint32_t* d_bfc = nullptr;
@@ -214,7 +216,7 @@ static hipError_t copy_sync(void* dst, const void* src, size_t n, hipMemcpyKind 
 
 // context.hip's for resolve_plan, render.hip's for zrt_device_warmup (hidden: not part of libzrt.so's interface)
 #pragma GCC visibility push(hidden)
-int context_escape(zrt_context* c);
+int context_escape(zrt_context* c, bool forced);
 int context_bfcull(zrt_context* c, bool forced);
 int render_warmup();
 #pragma GCC visibility pop
