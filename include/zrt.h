@@ -120,7 +120,8 @@ typedef struct zrt_render_config {
 
 #define ZRT_FLAG_COUNT_STATS  0x1u   /* count cells/tests/hits (slower kernel variant) */
 #define ZRT_FLAG_LANE_WALK    0x2u   /* every launch walks + tests per lane (no park kernel) */
-/* 0x4, 0x8: reserved (round-2 kernel variants that were measured slower and removed) */
+/* 0x4: reserved (a round-2 kernel variant that was measured slower and removed) */
+#define ZRT_FLAG_NO_HOP       0x8u   /* the park kernel never hops (wins over ZRT_FLAG_HOP); same image */
 #define ZRT_FLAG_ONE_SET      0x10u  /* every pass on the context's one stream (no second pass set, no
                                         lead): kernels never overlap, so their durations are exclusive
                                         (the roofline measurement); same image */
@@ -150,6 +151,11 @@ typedef struct zrt_render_config {
                                         the memory budget; by default only on scenes whose statistic says
                                         they pay); same image */
 #define ZRT_FLAG_NO_BFCULL    0x4000u /* never (wins over ZRT_FLAG_BFCULL); same image */
+#define ZRT_FLAG_HOP          0x8000u /* a park-kernel lane that walks on from a parked cell passes through
+                                        the next cell without parking there when the parked cell's record
+                                        says that a ray arriving from it has no ref left to test in that
+                                        cell (hop bits; the default wherever the park kernel runs); same
+                                        image */
 
 /* Per-call statistics.  segments = Scene.traceRay calls (primary + bounce +
  * transparency pass-through); Mrays/s = segments / render time. */

@@ -251,9 +251,58 @@ __global__ __launch_bounds__(kBlock) void cell32_kernel(const uint2* __restrict_
     }
 }
 
+// Hop bits (wf_park_kernel's one-cell lookahead), second pass over the cell
+// records.  Bits 26..31 of the six mask words of a cell of 1..26 refs are
+// free: every reader takes a mask's low `n` bits.  They hold six hop bits,
+// INVERTED: bit 26 + f CLEARED says that a ray leaving this cell by a step
+// in the direction of face index f (2 * axis + toward minus) may walk
+// through the next cell as if it were empty -- that neighbour lies inside
+// the grid, holds 1..32 refs, and its entry-face mask for the same f keeps
+// none of them: each was tested in this cell, which the ray leaves only
+// after testing all of its own.  Inverted, so that every all-ones word (the
+// first cell's, the cull table's, a boundary face, a cell of 32 refs or more)
+// reads as "no hop".  Cells of 27 refs or more have no room: the kernel takes
+// no hop bit from them; like the words of an empty cell, theirs get ones in
+// every bit above the mask's own, so that any word reads "no hop" by its bits
+// alone.
+// The neighbour's word may be rewritten by its own thread meanwhile, in bits
+// the bits above its n only; its low n bits, all that is read here, were
+// final when pass 1 ended.
+__global__ __launch_bounds__(kBlock) void cell32_hop_kernel(const uint2* __restrict__ cells, uint32_t r0, uint32_t r1,
+                                                            uint32_t r2, uint32_t ncells, const PackK pk,
+                                                            uint32_t* __restrict__ out) {
+    for (uint32_t ci = blockIdx.x * kBlock + threadIdx.x; ci < ncells; ci += gridDim.x * kBlock) {
+        const uint2 c = cells[ci];
+        const uint32_t n = c.y - c.x;
+        if (n >= 32u) continue;
+        const uint32_t x = ci % r0, y = (ci / r0) % r1, z = ci / r0 / r1;
+        uint32_t* rec = out + 8ull * pack_cellv(pk, x, y, z);
+        if (n > kHopMaxRefs) {                     // no room: the bits above the mask's read "no hop" all the same
+            for (uint32_t f = 0; f < 6; ++f) rec[2 + f] |= ~((1u << n) - 1u);
+            continue;
+        }
+        uint32_t hop = 0x3Fu;
+        for (uint32_t f = 0; f < 6 && n != 0u; ++f) {
+            const uint32_t axis = f >> 1, toward_neg = f & 1u;
+            const uint32_t cc = axis == 0 ? x : (axis == 1 ? y : z), rr = axis == 0 ? r0 : (axis == 1 ? r1 : r2);
+            // the cell entered: one step along the ray's direction
+            if (toward_neg ? cc == 0u : cc + 1u >= rr) continue;
+            const uint32_t d = toward_neg ? ~0u : 1u;
+            const uint32_t* nrec = out + 8ull * pack_cellv(pk, axis == 0 ? x + d : x, axis == 1 ? y + d : y,
+                                                           axis == 2 ? z + d : z);
+            const uint32_t nn = nrec[1] - nrec[0];
+            if (nn == 0u || nn > 32u) continue;
+            const uint32_t low = nn == 32u ? ~0u : (1u << nn) - 1u;
+            if ((nrec[2 + f] & low) == 0u) hop &= ~(1u << f);
+        }
+        for (uint32_t f = 0; f < 6; ++f) rec[2 + f] = (rec[2 + f] & ((1u << kHopShift) - 1u)) | (hop << kHopShift);
+    }
+}
+
 // Park release statistic (context_release): over the occupied cells of the
-// packed records, how many (cell, entry face) masks are 0 -- out[0] masks
-// of occupied cells, out[1] zero masks among them.
+// packed records, how many (cell, entry face) masks are 0 in the cell's low n
+// bits (the bits above them of a cell of at most 26 refs are hop bits) --
+// out[0] masks of occupied cells, out[1] zero masks among them.
 __global__ __launch_bounds__(kBlock) void release_stat_kernel(const uint32_t* __restrict__ rec, uint64_t n,
                                                               unsigned long long* __restrict__ out) {
     unsigned long long faces = 0, zero = 0;
@@ -261,7 +310,8 @@ __global__ __launch_bounds__(kBlock) void release_stat_kernel(const uint32_t* __
         const uint32_t* r = rec + 8 * i;
         if (r[1] > r[0]) {
             faces += 6;
-            for (int f = 0; f < 6; ++f) zero += r[2 + f] == 0u ? 1 : 0;
+            const uint32_t n = r[1] - r[0], low = n >= 32u ? ~0u : (1u << n) - 1u;
+            for (int f = 0; f < 6; ++f) zero += (r[2 + f] & low) == 0u ? 1 : 0;
         }
     }
     faces = wave_sum(faces);
@@ -294,6 +344,9 @@ static int context_packed(zrt_context* c) {
     hipLaunchKernelGGL(cell32_kernel, dim3(std::min<uint32_t>((c->ncells + kBlock - 1) / kBlock, 16384)), dim3(kBlock),
                        0, c->stream, c->d_cells, r[0], r[1], r[2], c->ncells, c->pk, c->d_pos,
                        c->d_cell32);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cell32_hop_kernel, dim3(std::min<uint32_t>((c->ncells + kBlock - 1) / kBlock, 16384)),
+                       dim3(kBlock), 0, c->stream, c->d_cells, r[0], r[1], r[2], c->ncells, c->pk, c->d_cell32);
     HIP_TRY(hipGetLastError());
     // the park release pays on scenes whose rays often park in a cell with
     // nothing left to test for their entry face: r06q/r06r, alternating
@@ -351,6 +404,9 @@ __global__ __launch_bounds__(kBlock) void bfc_build_kernel(const uint32_t* __res
             cleared += n - (uint32_t)__popc(m & all);
             words += 1;
             empty += (m & all) == 0u ? 1 : 0;
+            // the cell's hop bits (cell32_hop_kernel; the same six in each of its
+            // mask words), so that a lane walking on from its first cell may hop too
+            if (n <= kHopMaxRefs) m = (m & ((1u << kHopShift) - 1u)) | (rec[8 * pc + 2] & ~((1u << kHopShift) - 1u));
         }
         if (out) out[i] = m;                       // (null: the statistic only)
     }

@@ -640,6 +640,7 @@ struct WfParams {
     uint32_t refill_min;      // finished lanes before a wave shades and refills
     uint32_t rel_min;         // park release: a round with fewer parked lanes with refs is skipped (0: off)
     uint32_t rel_emin;        //   ... if at least this many parked lanes have none
+    uint32_t hop;             // refs of a cell at most whose record's hop bits a lane uses (kHopMaxRefs; 0: no hop)
     // escape table (escape.h): kEscWords u32 per region of a 4^3 brick, a
     // brick's regions together (esc_key), bit b of word w = direction bin
     // 32 w + b; null: not built (the walk never stops early)
@@ -1141,7 +1142,7 @@ __device__ __forceinline__ uint32_t wave_excl_sum(uint32_t x, uint32_t lane, uin
 // their activity (printed by zrt_context_render as zrt_park_profile; the
 // stamps cost ~10% and never run in the product build).
 #ifdef ZRT_SWEEP
-#define PARK_PROF_DECL unsigned long long pprof[21] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; \
+#define PARK_PROF_DECL unsigned long long pprof[23] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; \
     uint64_t ptick = __builtin_amdgcn_s_memtime();
 #define PARK_STAMP(k) do { const uint64_t t_ = __builtin_amdgcn_s_memtime(); pprof[k] += t_ - ptick; ptick = t_; } while (0)
 #define PARK_COUNT(k, v) (pprof[k] += (v))
@@ -1150,6 +1151,43 @@ __device__ __forceinline__ uint32_t wave_excl_sum(uint32_t x, uint32_t lane, uin
 #define PARK_STAMP(k) do { } while (0)
 #define PARK_COUNT(k, v) do { } while (0)
 #endif
+
+// The hop (one-cell lookahead): two parks in three find nothing to test on
+// cfg3 (r10e) -- the cell's refs were all tested in the cell the ray just
+// left -- and each such park is directly preceded by a park in that adjacent
+// cell.  The earlier cell's record says so (its hop bits, context.hip
+// cell32_hop_kernel), and a lane walking on from a parked cell reads them from
+// its own landed mask word, behind the round's vmcnt(0).  It keeps, in `hm`,
+// the field masks of the axes along which its next step may pass through the
+// cell it enters (the hop bit of that axis's face, by the lane's own step
+// sign); the lane's next trip then ignores the occupancy of its first step's
+// cell if that step ran along such an axis.  The axis is read off the stepped
+// word (pc ^ previous pc lies inside one field), so ties step as DDAV_STEPM
+// steps them, and nothing else of the trip changes: a first step that leaves
+// the grid or passes `nearest` ends the segment as before, the hopped cell's
+// own break test (nearest <= its exit t) runs at the second step as for an
+// empty cell, the escape query and `prev` see an ordinary walked cell.  Hits,
+// ties and break tests are the reference's.
+// hm is 0 except between a lane's release from a parked cell and its next
+// trip, which clears it (a lane parks, finishes or idles only from a trip or
+// a refill, so it is 0 whenever a lane starts a segment).
+// Against committing one DDAV_STEPM step at the release (45 VALU per round and
+// release, about as many of those as trips): DESIGN 5.2e.
+// GO: the lane walks on from its parked cell; HB: its record's hop bits.
+#define PARK_HOP(GO, HB)                                                                          \
+    do {                                                                                          \
+        PARK_COUNT(22, __popcll(__ballot(GO)));                                                   \
+        if (__ballot((GO) && (HB) != 0u) != 0ull) {                                               \
+            const uint32_t hb_ = (HB), hb1_ = hb_ >> 1;       /* bit 2a: toward plus, 2a + 1: minus */ \
+            const uint32_t e0_ = lm_selu(lm_of((int32_t)s.d0 < 0), hb1_, hb_);                    \
+            const uint32_t e1_ = lm_selu(lm_of((int32_t)s.d1 < 0), hb1_, hb_);                    \
+            const uint32_t e2_ = lm_selu(lm_of((int32_t)s.d2 < 0), hb1_, hb_);                    \
+            const uint32_t m_ = ((uint32_t)__builtin_amdgcn_sbfe((int32_t)e0_, 0, 1) & fv0) |     \
+                                ((uint32_t)__builtin_amdgcn_sbfe((int32_t)e1_, 2, 1) & fv1) |     \
+                                ((uint32_t)__builtin_amdgcn_sbfe((int32_t)e2_, 4, 1) & fv2);      \
+            hm = lm_selu(lm_of(GO), m_, hm);                                                      \
+        }                                                                                         \
+    } while (0)
 
 // ZRT_PARK_WPE: the park kernel compiled for 5 waves per SIMD (at most 96
 // VGPRs; it still runs 4, one 1024-thread workgroup per CU), so 4 x 96 leave
@@ -1215,8 +1253,8 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
     ParkSlot& W = reinterpret_cast<ParkSlot*>(s_dyn + w.occx_ldsw)[threadIdx.x >> 6];
 
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t below = lane ? (~0ull >> (64u - lane)) : 0ull;
     const uint32_t test_min = w.test_min, refill_min = w.refill_min, rel_min = w.rel_min;
+    const uint32_t hop_max = w.hop;        // cells of at most this many refs carry hop bits (PARK_HOP); 0: no hop
     const GridK gk = grid_consts(p);
     constexpr uint32_t kIdle = 0, kWalk = 1, kPark = 2, kDone = 3;
     uint32_t st = kIdle;
@@ -1245,6 +1283,7 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
     // crossing sequence)
     uint32_t eoff = 0, emask = 0;
     uint32_t eb = ~0u;                     // the brick of the lane's last escape-table query
+    uint32_t hm = 0;                       // the hop's field masks (PARK_HOP)
     // the table's shape (escape.h esc_walk_key), wave-uniform
     const uint32_t esc_key = ESC ? __builtin_amdgcn_readfirstlane(w.esc_key) : 0u;
     const uint32_t esc_lg = esc_key & 0xFFu, esc_mlo = (esc_key >> 8) & 0xFFu, esc_mhi = esc_key >> 16;
@@ -1286,7 +1325,10 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
                     cgrp = grp;
                 }
                 const uint32_t take = min((uint32_t)__popcll(idle), ce - cb);
-                const uint32_t rank = (uint32_t)__popcll(idle & below);
+                // the idle lanes below this one (mbcnt: no per-lane 64-bit mask
+                // held in a VGPR pair over the walk trips)
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32),
+                                                                __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
                 if (st == kIdle && rank < take) {
                     {
                         qi = ent_index<false>(w, cgrp, cb + rank);
@@ -1420,6 +1462,16 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
                     dd[k] = lm_or(ex[k], lm_of(nearest <= te[k]));
                     stop[k] = lm_or(dd[k], lm_of(occx_cell<PK_BM>(q[k], ss[k], pk)));
                 }
+                {   // the hop (PARK_HOP): the first step's cell is passed through if
+                    // the step ran along an axis of hm
+                    // (sweep builds count the hops here, where only walking lanes are
+                    // active: like the trip's other counters, the wave's count is kept
+                    // only if its lane 0 walks)
+                    const LaneM hop = lm_of(((ss[0].pc ^ s.pc) & hm) != 0u);
+                    PARK_COUNT(21, __popcll(lm_and(hop, lm_andn(stop[0], dd[0]))));
+                    stop[0] = lm_or(dd[0], lm_andn(stop[0], hop));
+                    hm = 0u;
+                }
                 // the first stopping step wins: from the last step back (the
                 // last step's selects are identities)
                 DdaV sel = ss[kS - 1];
@@ -1471,7 +1523,7 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
                     // one query per brick the ray enters (its word does not
                     // change while the lane walks inside the brick)
                     const uint32_t b = occx_brick<PK_BM>(w, s);
-                    if (st == kWalk && emask != 0u && b != eb) {
+                    if (__builtin_expect(st == kWalk && emask != 0u && b != eb, 0)) {   // (kept out of the trip's straight line)
                         // the region of the brick that holds the lane's cell
                         // (escape.h EscShape: its sub-index is bits of the
                         // in-brick cell index x | y << 2 | z << 4, the low six
@@ -1497,8 +1549,12 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
             // the parked cell's refs still to test: those the mask keeps
             // (cells of at most 32 refs; larger ones test every ref)
             const uint32_t rb = rng_slot[lane], re = rng_slot[64 + lane], cnt = re - rb;
-            const uint32_t keep = cnt < 32u ? rng_slot[128 + lane] & ((1u << cnt) - 1u) : rng_slot[128 + lane];
+            const uint32_t mw = rng_slot[128 + lane];
+            const uint32_t keep = cnt < 32u ? mw & ((1u << cnt) - 1u) : mw;
             const uint32_t n = ready ? (cnt <= 32u ? (uint32_t)__popc(keep) : cnt) : 0u;
+            // the record's hop bits (PARK_HOP): inverted, in a word of a cell
+            // of at most 26 refs; an all-ones word (the first cell's) has none
+            const uint32_t hb = cnt <= hop_max ? ~mw >> kHopShift : 0u;
             // park release (above): a round with fewer than rel_min parked
             // lanes that have refs to test is not run while lanes walk
             if (rel_min != 0u && __ballot(st == kWalk) != 0ull &&
@@ -1506,10 +1562,18 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
                 (uint32_t)__popcll(__ballot(ready && n == 0u)) >= w.rel_emin) {
                 PARK_COUNT(19, __popcll(__ballot(ready && n == 0u)));
                 if (ready && n == 0u) st = kWalk;
+                PARK_HOP(ready && n == 0u, hb);
                 continue;
             }
             uint32_t tot = 0;
-            const uint32_t off = wave_excl_sum(n, lane, tot);
+            // the lane index of the round's own address arithmetic (the scan's row,
+            // the best / uv slots): an opaque copy, so that what derives from it
+            // is computed here and not kept in registers over the walk trips,
+            // which sit at the 96-VGPR edge (with the hop's hm two such values
+            // went to scratch)
+            uint32_t rl = lane;
+            asm volatile("" : "+v"(rl));
+            const uint32_t off = wave_excl_sum(n, rl, tot);
             PARK_COUNT(5, 1);
             PARK_COUNT(6, (tot + 63u) / 64u);
             PARK_COUNT(7, tot);
@@ -1519,7 +1583,8 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
             rng_slot[lane] = rb;                                   // (the slots are free until the walk)
             rng_slot[64 + lane] = off;
             rng_slot[128 + lane] = cnt <= 32u ? keep : ~0u;
-            W.best[lane] = ~0ull;
+            W.d[rl].w = __uint_as_float(hb);                       // (kept in LDS over the sub-rounds, not in a VGPR)
+            W.best[rl] = ~0ull;
             uint32_t carry = 0;
             for (uint32_t r = 0; r < tot; r += 64u) {
                 // owner of pair slot r + lane: the last parked lane starting
@@ -1552,16 +1617,17 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
                 __builtin_amdgcn_wave_barrier();
             }
             if (n != 0u) {
-                const unsigned long long k = W.best[lane];
+                const unsigned long long k = W.best[rl];
                 if (k != ~0ull) {
                     nearest = __uint_as_float((uint32_t)(k >> 32));
                     hidx = (uint32_t)k;
-                    const float2 uv = W.uv[lane];
+                    const float2 uv = W.uv[rl];
                     hu = uv.x;
                     hv = uv.y;
                 }
             }
             if (ready) st = kWalk;                                 // the cell is done: step out of it next
+            if (hop_max != 0u) PARK_HOP(ready, __float_as_uint(W.d[rl].w));
         }
         PARK_STAMP(2);
     }
@@ -1570,7 +1636,7 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
     if (lane == 0)
         for (int k = 0; k < 13; ++k) atomicAdd(&p.stats[16 + k], pprof[k]);
     if (lane == 0)
-        for (int k = 13; k < 21; ++k) atomicAdd(&p.stats[48 + k - 13], pprof[k]);
+        for (int k = 13; k < 23; ++k) atomicAdd(&p.stats[48 + k - 13], pprof[k]);   // (21, 22: PARK_HOP)
 #endif
 }
 
@@ -2176,7 +2242,7 @@ constexpr uint64_t kTraceChunk = 1ull << 20;
 constexpr uint64_t kTraceParkMin = 1ull << 19;
 constexpr uint32_t kTraceFlags = ZRT_FLAG_COUNT_STATS | ZRT_FLAG_LANE_WALK | ZRT_FLAG_MT_EXACT | ZRT_FLAG_ESCAPE |
                                  ZRT_FLAG_NO_ESCAPE | ZRT_FLAG_RELEASE | ZRT_FLAG_NO_RELEASE | ZRT_FLAG_BFCULL |
-                                 ZRT_FLAG_NO_BFCULL | ZRT_TRACE_PARK;
+                                 ZRT_FLAG_NO_BFCULL | ZRT_FLAG_HOP | ZRT_FLAG_NO_HOP | ZRT_TRACE_PARK;
 static_assert((ZRT_SEGMENT_ANY & (kTraceFlags | ZRT_RADIANCE_PER_SAMPLE | 0xFFFFu)) == 0u, "a bit of its own");
 
 // batch size from which a segment call takes the park path unasked: 2^16, the
@@ -2395,7 +2461,7 @@ __global__ __launch_bounds__(kTraceBlock, 1) void rad_fanout_kernel(const RadPar
 using RadFn = void (*)(const RadParams);
 constexpr uint32_t kRadianceFlags = ZRT_FLAG_LANE_WALK | ZRT_FLAG_MT_EXACT | ZRT_FLAG_ESCAPE | ZRT_FLAG_NO_ESCAPE |
                                     ZRT_FLAG_RELEASE | ZRT_FLAG_NO_RELEASE | ZRT_FLAG_BFCULL | ZRT_FLAG_NO_BFCULL |
-                                    ZRT_TRACE_PARK | ZRT_RADIANCE_PER_SAMPLE;
+                                    ZRT_FLAG_HOP | ZRT_FLAG_NO_HOP | ZRT_TRACE_PARK | ZRT_RADIANCE_PER_SAMPLE;
 
 // max_bounce picks the stack depth the counting kernel is compiled for.
 TraceFn count_fn(uint32_t max_bounce) {
@@ -2606,7 +2672,7 @@ struct LaunchPlan {
     bool packed, pbm;         // packed walk state; brick-major packed words (dda.h)
     bool park_ok;             // the context and the flags allow the park kernel
     bool park;                //   ... and this call launches it
-    bool rel, esc, bfc;       // the park launches use the release, the escape table, the cull masks
+    bool rel, esc, bfc, hop;  // the park launches use the release, the escape table, the cull masks, the hop
     WfFn f_park, f_walk;      // a bounce launch: the park kernel (+ the shading half), or the lane walk
     WfFn s_next, s_last;      // the shading half; of a pass's last bounce (terminal radiance only, LAST)
     int park_block;           // threads of a park workgroup
@@ -2671,6 +2737,9 @@ static int resolve_plan(zrt_context* c, uint32_t flags, bool counting, bool want
         }
     }
     pl.bfc = c->d_bfc && !(flags & ZRT_FLAG_NO_BFCULL) && (c->bfc_on || (flags & ZRT_FLAG_BFCULL));
+    // the hop (PARK_HOP): wherever the packed cell records exist, unless the
+    // flags say otherwise (same image either way)
+    pl.hop = !(flags & ZRT_FLAG_NO_HOP);
     pl.f_park = park_fn<kParkRender>(pl.esc, pl.pbm);
     pl.f_walk = pl.mtx ? kWfBounceExact : (pl.packed ? (pl.pbm ? kWfBounceBM : kWfBounce) : kWfBounceWide);
     const bool lmats = c->nmat <= kLdsMats;
@@ -2701,6 +2770,7 @@ static void park_params(const zrt_context* c, const LaunchPlan& pl, WfParams& W)
     W.refill_min = pl.refill_min;
     W.rel_min = pl.rel ? pl.rel_min : 0u;
     W.rel_emin = pl.rel_emin;
+    W.hop = pl.hop ? kHopMaxRefs : 0u;
     W.esc = c->d_esc;
     W.esc_key = c->esc_key;
     W.bfc = pl.bfc ? c->d_bfc : nullptr;
@@ -3073,8 +3143,8 @@ static int report_stats(const unsigned long long* hs, bool counting, bool park) 
     if (getenv("ZRT_PARK_PROFILE") && park)
         fprintf(stderr, "{\"zrt_walk_steps\": {\"lane_steps\": %llu, \"empty_brick_steps\": %llu, "
                 "\"empty_brick_entries\": %llu, \"escapes\": %llu, \"parked_tested\": %llu, \"parked_no_refs\": %llu, "
-                "\"released_early\": %llu, \"cyc_round_wait\": %llu}}\n",
-                hs[48], hs[49], hs[50], hs[51], hs[52], hs[53], hs[54], hs[55]);
+                "\"released_early\": %llu, \"cyc_round_wait\": %llu, \"hops_taken\": %llu, \"hops_refused\": %llu}}\n",
+                hs[48], hs[49], hs[50], hs[51], hs[52], hs[53], hs[54], hs[55], hs[56], hs[57] - hs[56]);
     if (getenv("ZRT_PARK_PROFILE") && !counting)
         fprintf(stderr, "{\"zrt_primary_profile\": {\"cyc_walk\": %llu, \"cyc_shade\": %llu, \"cyc_fetch_append\": %llu}}\n",
                 hs[29], hs[30], hs[31]);

@@ -47,6 +47,9 @@ constexpr int kParkBlock = ZRT_PARK_BLOCK_T;         // wf_park_kernel: one work
 constexpr int kParkWaves = kParkBlock / 64;
 constexpr uint32_t kTriFloats = 12u;                 // floats per ref of a context's triangle positions
 constexpr uint32_t kMaxPassSets = 4;                 // pass sets (streams) of a render at most
+// hop bits of a cell record's mask words (context.hip cell32_hop_kernel): six
+// inverted bits from kHopShift up, in cells of at most kHopMaxRefs refs
+constexpr uint32_t kHopMaxRefs = 26, kHopShift = 26;
 
 __device__ __forceinline__ unsigned long long wave_sum(unsigned long long x) {
 #pragma unroll
@@ -61,7 +64,7 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long x) {
 // Per-wave LDS of the test rounds.
 struct ParkSlot {
     float4 o[64];                    // lane's ray origin; w: nearest entering the round
-    float4 d[64];                    // lane's ray direction; w (bits): ref of its pair slot 0
+    float4 d[64];                    // lane's ray direction; w (bits): the hop bits of its parked cell
     unsigned long long best[64];     // per parked lane: (t bits << 32) | ref of its best pair
     float2 uv[64];                   // (u, v) of that pair
     uint32_t mark[64];               // lane + 1 of the parked lane whose pairs start at this slot

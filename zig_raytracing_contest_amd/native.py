@@ -26,6 +26,7 @@ FLAG_ONE_SET, FLAG_KERNEL_TIMES = 0x10, 0x20
 FLAG_MT_EXACT = 0x400
 FLAG_RELEASE, FLAG_NO_RELEASE = 0x800, 0x1000
 FLAG_BFCULL, FLAG_NO_BFCULL = 0x2000, 0x4000
+FLAG_HOP, FLAG_NO_HOP = 0x8000, 0x8
 TRACE_PARK = 0x10000       # ZRT_TRACE_PARK (zrt_ray_batch / zrt_radiance_batch flags only)
 RADIANCE_PER_SAMPLE = 0x20000   # ZRT_RADIANCE_PER_SAMPLE (zrt_radiance_batch.flags only)
 SEGMENT_ANY = 0x40000      # ZRT_SEGMENT_ANY (zrt_segment_batch.flags only)
