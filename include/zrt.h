@@ -466,6 +466,69 @@ typedef struct zrt_surface_batch {
  * trace_launches counts the gather launch too. */
 int zrt_context_surface(zrt_context* ctx, const zrt_surface_batch* batch, zrt_stats* stats_or_null);
 
+/* ---- transmittance queries (ABI 2, added) ------------------------------- */
+
+/* Shadow rays that pass through transparent hits as the path tracer does.  At
+ * a hit traceRayRecursive draws U and continues straight from ray.at(t + eps)
+ * when U > transparency (stage3.zig:207-212; the field holds the alpha, 1 is
+ * opaque).  This call returns the expected value of that chain along a bounded
+ * ray: the product of the pass probabilities of every surface the path tracer
+ * would meet on the way -- deterministic, no draw.  For ray (o, d), bound
+ * t_max and cap max_crossings, in f32, nothing contracted, in this order:
+ *   T = 1; n = 0; o_0 = o; b_0 = t_max
+ *   loop k = 0, 1, ...:
+ *       h = the closest-mode zrt_context_segments result of (o_k, d, b_k)
+ *       if h is a miss: stop
+ *       a = zrt_surface.transparency of (o_k, d, h)
+ *       n = n + 1
+ *       p = 1.0f - a
+ *       if !(p > 0): T = +0; stop        -- opaque, or a NaN alpha (`!(U > NaN)`
+ *                                           scatters in the path tracer too)
+ *       T = T * min(p, 1.0f)
+ *       if n == max_crossings: stop      -- the product so far stands
+ *       s = h.t + floatEps(f32)
+ *       o_{k+1} = o_k + d * s            -- zrt_surface.position
+ *       b_{k+1} = b_k - s                -- +inf stays +inf; <= 0: the next
+ *                                           segment is a miss
+ * transmittance[i] = T, crossings[i] = n.  Directions are taken as given, as in
+ * zrt_context_trace; t_max is in the ray's own parameter, per ray or t_max_all
+ * when the pointer is null; +inf, <= 0 and NaN behave as in
+ * zrt_context_segments (NaN or <= 0: T = 1, n = 0).  The cap is part of the
+ * contract, not a safety net: at large coordinates o + d * s can round back to
+ * o and the same surface is hit again; the path tracer is bounded by max_bounce
+ * there, this call by max_crossings, and crossings[i] == max_crossings tells
+ * the caller that the chain was cut. */
+typedef struct zrt_transmittance_batch {
+    uint64_t num_rays;
+    const float* rays;               /* num_rays * 6, as zrt_ray_batch */
+    const float* t_max;              /* num_rays, or null: t_max_all for every ray */
+    float* transmittance;            /* num_rays */
+    uint32_t* crossings;             /* num_rays (n above), or null */
+    uint32_t on_device;              /* as zrt_ray_batch; applies to all four pointers */
+    uint32_t flags;                  /* exactly zrt_ray_batch's flags */
+    float t_max_all;
+    uint32_t max_crossings;          /* 1..256 */
+} zrt_transmittance_batch;           /* 56 B */
+
+/* Synchronous, one thread at a time per context; alternates freely with
+ * renders and the four other queries (every use writes what it reads first);
+ * chunks of at most 2^20 rays.  The lane walk traces a ray's whole chain in one
+ * launch, and is what every batch takes unasked: it measured as fast or faster
+ * at 2^16 and 2^20 rays.  The park path (ZRT_TRACE_PARK only)
+ * runs one park launch and one step launch per crossing round over the rays
+ * still under way, at most max_crossings rounds, and hands a small remainder
+ * to one lane launch.
+ * num_rays == 0 returns ZRT_OK and touches nothing.  ZRT_ERR_INVALID_ARG before
+ * any device work: a null context or batch, null rays or transmittance, a flag
+ * zrt_context_trace would refuse, on_device > 1, max_crossings 0 or above 256.
+ * stats (may be null), in every call: segments = the Scene.traceRay calls the
+ * loop above makes, hits = the sum of n, samples = 0, render_ms,
+ * trace_kernel_ms and trace_launches as in zrt_context_trace.  With
+ * ZRT_FLAG_COUNT_STATS cells_visited and triangle_tests, summed over those
+ * segments, each counted as a closest-mode counting zrt_context_segments call
+ * counts it. */
+int zrt_context_transmittance(zrt_context* ctx, const zrt_transmittance_batch* batch, zrt_stats* stats_or_null);
+
 /* A device group: one context per entry of `devices` (HIP ordinals, repeats
  * allowed), the scene resident on each, rendered by one call -- Scene.render's
  * spawn + join of its workers (stage3.zig:247-256) across GPUs in one

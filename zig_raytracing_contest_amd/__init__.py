@@ -135,6 +135,13 @@ class RenderScene:
             res["source_triangle"] = src
         return res
 
+    def transmittance(self, origins, dirs, t_max=float("inf"), max_crossings: int = 16, flags: int = 0,
+                      stats: bool = False, crossings: bool = False):
+        """The expected pass-through of the path tracer's transparency chain
+        along rays with an end t_max: see native.Context.transmittance."""
+        return self.context.transmittance(origins, dirs, t_max, max_crossings=max_crossings, flags=flags,
+                                          stats=stats, crossings=crossings)
+
     def radiance(self, origins, dirs, spp: int, max_bounce: int, seed: int = 0, index_base: int = 0,
                  flags: int = 0, rgb: bool = False, stats: bool = False):
         """Scene.traceRayRecursive (stage3.zig:188-220) for a batch of rays,

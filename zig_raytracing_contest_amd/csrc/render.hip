@@ -2319,6 +2319,249 @@ __global__ __launch_bounds__(kBlock) void surface_kernel(const SurfaceParams r) 
 }
 
 // ---------------------------------------------------------------------------
+// Transmittance queries (zrt_context_transmittance): the expected
+// value of the path tracer's pass-through chain (stage3.zig:207-212) along a
+// bounded ray.  Per ray: T = 1, n = 0, then closest-mode bounded segments
+// (trace_ray BOUNDED, or the park kernel's kParkClosest mode), each hit's alpha
+// a = material.transparency.sample(texcoord) folded in as p = 1 - a -- opaque
+// or NaN ends the chain at T = +0, else T *= min(p, 1) -- and the next segment
+// started at ray.at(t + eps) with the bound shortened by t + eps, until a miss
+// or max_crossings crossings.  Every loop over crossings, on the device and on
+// the host, is also bounded by max_crossings (1..256, checked by the entry
+// point): at large coordinates o + d * s can round back to o.
+struct TransmitParams {
+    QueryParams q;            // rays, bounds, n, which, ctr; q.w.t the scene; the park path: q.w.hit, q.w.n_in8
+    float* T;                 // this chunk: the transmittance of every ray
+    uint32_t* cross;          // this chunk: the crossings of every ray (the lane path: or null)
+    uint32_t max_cross;       // 1..256
+    uint32_t first;           // transmit_step_kernel: the chunk's first round (T = 1, n = 0 are not read)
+    const float4* q_in;       // transmit_step_kernel: the queue the park kernel just traced
+    float4* q_out;            //   and the one the surviving rays go to, with its region counts
+    uint32_t* n_out8;
+};
+// The alpha at a hit.  The arithmetic is surface_kernel's / shade_segment's
+// (their lines `w0`, `tc0`, `tc1` and the transparency sample), restated here
+// with only the loads the alpha needs -- Data words d2 and d3, the material,
+// texture 2: keep the three in step.
+__device__ __forceinline__ float transmit_alpha(const TraceParams& p, float hu, float hv, uint32_t ref) {
+    const float4* tdp = p.tri_data + 4ull * ref;
+    const float4 d2 = tdp[2], d3 = tdp[3];                          // stage3.zig:199-206
+    const float w0 = 1.0f - hu - hv;
+    const float tc0 = (d2.y * w0 + d2.w * hu) + d3.y * hv;
+    const float tc1 = (d2.z * w0 + d3.x * hu) + d3.z * hv;
+    const DevMat& m = p.mats[__float_as_uint(d3.w)];
+    return sample1(p.texels, m.tex[2], tc0, tc1);
+}
+// One crossing at parameter t with alpha a.  True: the chain goes on from
+// (o, bound) as updated -- `no = o + d * (t + kFltEps)` as surface_kernel and
+// shade_segment compute it, the same operations in the same order.
+__device__ __forceinline__ bool transmit_cross(float a, float t, uint32_t cap, v3& o, v3 d, float& bound, float& T,
+                                               uint32_t& n) {
+    ++n;
+    const float pp = 1.0f - a;
+    if (!(pp > 0.0f)) {                                             // opaque, or a NaN alpha: `!(U > NaN)` scatters too
+        T = 0.0f;
+        return false;
+    }
+    T = T * fminf(pp, 1.0f);
+    if (n == cap) return false;
+    const float s = t + kFltEps;
+    o = add(o, scale(d, s));
+    bound = bound - s;                                              // (+inf stays +inf; <= 0: the next segment misses)
+    return true;
+}
+
+// The lane path: query_walk_kernel<.., SEG = true> with the whole chain of a
+// ray in its lane, one launch for every crossing (same `which` split, same
+// walk variants, same work counters).  Segments and crossings are counted in
+// every call (stats[0], stats[3]); STATS adds cells and tests, each segment
+// counted as a closest-mode counting segment call counts it.
+// `which` = kRaysQueue (the park path's tail): the rays are the live entries of
+// a queue transmit_step_kernel appended -- (o_k, ray) (d, b_k), T and n so far
+// in r.T / r.cross -- and their chains are finished here, k starting at n.
+constexpr uint32_t kRaysQueue = 3;
+// Slot j of a queue of nq slots (P = nq, S = 1): its region g, and whether
+// that region's count (n8) reaches it.
+__device__ __forceinline__ bool queue_slot_live(uint32_t nq, const uint32_t* n8, uint32_t j, uint32_t& g) {
+    g = 0;
+    for (uint32_t k = 1; k < 8u; ++k) g += j >= xcd_q0(nq, k) ? 1u : 0u;
+    return j < nq && j - xcd_q0(nq, g) < n8[g * kCtr];
+}
+// 5 waves per SIMD: at query_walk_kernel's 6 (80 VGPRs) the chain state around
+// the walk spills 3-7 VGPRs in the three fast instantiations; at 5 none does.
+constexpr int kTransmitMinWaves = 5;
+template <bool STATS, bool PACKED, bool PK_BM, bool MTX>
+__global__ __launch_bounds__(kTraceBlock, STATS ? 1 : kTransmitMinWaves) void transmit_walk_kernel(const TransmitParams r) {
+    const TraceParams& p = r.q.w.t;
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_occ[];
+    __shared__ uint32_t s_wcnt[2 * (kTraceBlock / 64)];
+    if (r.q.which == kRaysRest && r.q.ctr[2] == 0u) return;         // (the whole grid: nothing left)
+    for (uint32_t i = threadIdx.x; i < p.occ_words; i += blockDim.x) s_occ[i] = p.occ[i];
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool tail = r.q.which == kRaysQueue;                      // (uniform)
+    uint32_t* const work = r.q.ctr + (r.q.which == kRaysRest ? 1u : tail ? 3u : 0u);
+    uint64_t prof[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t n_seg = 0, n_cells = 0, n_tests = 0, n_hits = 0, n_rest = 0;
+    for (;;) {
+        uint32_t base = 0;
+        if (lane == 0) base = atomicAdd(work, 64u * kWfChunk);
+        base = __builtin_amdgcn_readfirstlane(base);
+        if (base >= r.q.n) break;
+        for (uint32_t sub = 0; sub < kWfChunk; ++sub) {
+            uint32_t i = base + 64u * sub + lane;                   // the ray; the tail: the queue slot, then its ray
+            if (i >= r.q.n) continue;
+            v3 o, d;
+            float bound, T = 1.0f;
+            uint32_t n = 0;
+            if (tail) {
+                uint32_t g;
+                if (!queue_slot_live(r.q.n, r.q.w.n_in8, i, g)) continue;
+                const float4 qa = r.q_in[3ull * i], qb = r.q_in[3ull * i + 1];
+                o = mk(qa.x, qa.y, qa.z);
+                d = mk(qb.x, qb.y, qb.z);
+                bound = qb.w;
+                i = __float_as_uint(qa.w);
+                if (i >= r.q.n) continue;                           // (never: no store without it)
+                T = r.T[i];
+                n = r.cross[i];
+                n_hits -= n;                                        // (counted by the rounds before)
+            } else {
+                ray_load(r.q.rays, i, o, d);
+                const bool fast = ray_fast(d);
+                if (r.q.which == kRaysFast && !fast) { ++n_rest; continue; }
+                if (r.q.which == kRaysRest && fast) continue;
+                bound = query_bound(r.q, i);
+            }
+            for (uint32_t k = n; k < r.max_cross; ++k) {
+                float hu = 0.0f, hv = 0.0f;
+                uint32_t hidx = 0;
+                const float t = trace_ray<STATS, kTriBatch, PACKED, PK_BM, MTX, false, true>(p, s_occ, o, d, hu, hv, hidx,
+                                                                                             n_cells, n_tests, prof, s_wcnt,
+                                                                                             -kInf, kInf, bound);
+                ++n_seg;
+                if (__float_as_uint(t) == __float_as_uint(bound)) break;       // a miss (trace_ray, NEAREST0)
+                if (!transmit_cross(transmit_alpha(p, hu, hv, hidx), t, r.max_cross, o, d, bound, T, n)) break;
+            }
+            n_hits += n;
+            r.T[i] = T;
+            if (r.cross) r.cross[i] = n;
+        }
+    }
+    if (r.q.which == kRaysFast) {
+        const unsigned long long s = wave_sum(n_rest);
+        if (lane == 0 && s != 0ull) atomicAdd(&r.q.ctr[2], (uint32_t)s);
+    }
+    const unsigned long long s0 = wave_sum(n_seg), s3 = wave_sum(n_hits);
+    if (lane == 0 && s0 != 0ull) atomicAdd(&p.stats[0], s0);
+    if (lane == 0 && s3 != 0ull) atomicAdd(&p.stats[3], s3);
+    if (STATS) {
+        const unsigned long long s1 = wave_sum(n_cells), s2 = wave_sum(n_tests);
+        if (lane == 0) {
+            atomicAdd(&p.stats[1], s1);
+            atomicAdd(&p.stats[2], s2);
+        }
+    }
+}
+
+// The park path's step between two park launches: one thread per slot of the
+// queue the park kernel just traced (region g holds q.w.n_in8[g] entries from
+// xcd_q0(n, g) on, as query_pack_kernel left them or as this kernel's previous
+// round appended them).  A live entry's hit record (q.w.hit[slot]) is folded
+// into T and n of its ray (the record's item word), and a chain that goes on is
+// appended to the same region of the other queue as (o', ray) (d, bound'):
+// region g never receives more than it held, so it fits.  The order inside a
+// region is free, results are per ray.  Rays outside the fast domain were
+// walked by the park kernel like any ray and are dropped here, T and n
+// untouched: the kRaysRest launch of the lane path owns their chains.  A
+// wave's 64 slots lie in one region (region bounds are multiples of 64 or n).
+// Returns at once on an empty queue.
+__global__ __launch_bounds__(kBlock) void transmit_step_kernel(const TransmitParams r) {
+    __shared__ uint32_t s_cnt[2];
+    const WfParams& w = r.q.w;
+    const uint32_t nq = r.q.n;
+    uint32_t live_any = 0;
+    for (uint32_t g = 0; g < 8u; ++g) live_any |= w.n_in8[g * kCtr];
+    if (live_any == 0u) return;                                     // (uniform over the grid)
+    if (threadIdx.x < 2u) s_cnt[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint32_t j = blockIdx.x * kBlock + threadIdx.x;
+    uint32_t g;
+    bool live = queue_slot_live(nq, w.n_in8, j, g);
+    v3 o = mk(0, 0, 0), d = mk(0, 0, 0);
+    float bound = 0.0f;
+    uint32_t i = 0;
+    if (live) {
+        const float4 qa = r.q_in[3ull * j], qb = r.q_in[3ull * j + 1];
+        o = mk(qa.x, qa.y, qa.z);
+        d = mk(qb.x, qb.y, qb.z);
+        i = __float_as_uint(qa.w);
+        bound = qb.w;
+        live = ray_fast(d) && i < nq;                               // (i < nq: holds for every record written; no store without it)
+    }
+    bool cont = false;
+    uint32_t hit = 0;
+    if (live) {
+        const float4 h = w.hit[j];
+        const uint32_t ref = __float_as_uint(h.w);
+        float T = r.first ? 1.0f : r.T[i];
+        uint32_t n = r.first ? 0u : r.cross[i];
+        if (ref != 0xFFFFFFFFu) {                                   // (a miss: the park kernel's kParkClosest record)
+            hit = 1u;
+            cont = transmit_cross(transmit_alpha(w.t, h.y, h.z, ref), h.x, r.max_cross, o, d, bound, T, n);
+        }
+        r.T[i] = T;
+        r.cross[i] = n;
+    }
+    // append the survivors: one returning atomic per region of the wave (wf_append's scheme)
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t below = (1ull << lane) - 1ull;
+    uint64_t pend = __ballot(cont);
+    while (pend) {
+        const uint32_t lead = (uint32_t)__builtin_ctzll(pend);
+        const uint32_t gl = (uint32_t)__builtin_amdgcn_readlane((int)g, (int)lead);
+        const uint64_t m = __ballot(cont && g == gl);
+        uint32_t ob = 0;
+        if (lane == lead) ob = atomicAdd(&r.n_out8[gl * kCtr], (uint32_t)__popcll(m));
+        ob = (uint32_t)__builtin_amdgcn_readlane((int)ob, (int)lead) + xcd_q0(nq, gl);
+        if (cont && g == gl) {
+            const uint32_t pos = ob + (uint32_t)__popcll(m & below);
+            if (pos < xcd_q0(nq, gl + 1u)) {                        // (always: a region receives at most what it held)
+                r.q_out[3ull * pos] = make_float4(o.x, o.y, o.z, __uint_as_float(i));
+                r.q_out[3ull * pos + 1] = make_float4(d.x, d.y, d.z, bound);
+            }
+        }
+        pend &= ~m;
+    }
+    const unsigned long long s0 = wave_sum(live ? 1u : 0u), s3 = wave_sum(hit);
+    if (lane == 0) {
+        if (s0 != 0ull) atomicAdd(&s_cnt[0], (uint32_t)s0);
+        if (s3 != 0ull) atomicAdd(&s_cnt[1], (uint32_t)s3);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s_cnt[0] != 0u) atomicAdd(&w.t.stats[0], (unsigned long long)s_cnt[0]);
+        if (s_cnt[1] != 0u) atomicAdd(&w.t.stats[3], (unsigned long long)s_cnt[1]);
+    }
+}
+
+// The park path's tail: once a round leaves this many rays or fewer under way,
+// one kRaysQueue launch of the lane kernel finishes their chains instead of
+// further (park, step) rounds, whose fixed cost per round (the park workgroups'
+// LDS fill, two launches and the read-back) outweighs the park kernel's
+// advantage on few rays (tools/transmit_bench.py).
+// ZRT_TRANSMIT_TAIL in the environment overrides it (0: never), for that bench
+// and for the tests that run every round.
+constexpr uint64_t kTransmitTailMax = 1ull << 16;
+using TransmitFn = void (*)(const TransmitParams);
+// walk: brick-major packed, packed, wide, the IEEE division, counting (QueryKernels' order)
+const TransmitFn kTransmitWalk[5] = {(TransmitFn)transmit_walk_kernel<false, true, true, false>,
+                                     (TransmitFn)transmit_walk_kernel<false, true, false, false>,
+                                     (TransmitFn)transmit_walk_kernel<false, false, false, false>,
+                                     (TransmitFn)transmit_walk_kernel<false, false, false, true>,
+                                     (TransmitFn)transmit_walk_kernel<true, false, false, true>};
+
+// ---------------------------------------------------------------------------
 // Radiance queries (zrt_context_radiance): Scene.traceRayRecursive
 // (stage3.zig:188-220) for caller-given rays, S samples each, through the
 // render's own queues, park, shade and resolve kernels.  A chunk
@@ -3636,6 +3879,207 @@ extern "C" int zrt_context_segments(zrt_context* c, const zrt_segment_batch* b, 
     const RayQuery q{b->num_rays, b->rays, b->hits, b->on_device, b->flags & ~ZRT_SEGMENT_ANY, any ? 1 : 0,
                      b->t_max, b->t_max_all, b->occluded, nullptr};
     return query_rays(c, &q, stats);
+}
+
+// Transmittance along bounded rays: see include/zrt.h, the kernels' comment
+// (TransmitParams) and DESIGN 5.15.  A sibling of query_rays -- the same plan,
+// chunk loop, staging and stats -- because its launches per chunk differ:
+//   lane path:  transmit_walk_kernel as query_rays launches query_walk_kernel
+//               (kRaysFast then kRaysRest, or kRaysAll), whole chains per lane;
+//   park path:  query_pack_kernel<SEG> -> per round k < max_crossings:
+//               wf_park_kernel (bounded closest mode, unchanged) over queue
+//               k & 1 -> transmit_step_kernel, which appends the surviving
+//               rays to the other queue; the host reads that queue's eight
+//               region counts back, leaves the loop when they are all zero and
+//               hands kTransmitTailMax survivors or fewer to one kRaysQueue
+//               launch of the fast lane kernel (ZRT_TRANSMIT_ROUNDS=fixed in
+//               the environment: no read-back, max_crossings rounds whose
+//               kernels return on an empty queue; measured in DESIGN 5.15);
+//               then the kRaysRest launch of the IEEE-division lane kernel for
+//               the rays outside the fast domain.
+// Round k has its own work counters and region counts in pass set 0's counter
+// block (bounce_params' layout), zeroed once per chunk.  Staging of a host
+// batch: rays and bounds in d_rays, T and n in d_hits; a device batch without
+// `crossings` on the park path keeps n there.
+extern "C" int zrt_context_transmittance(zrt_context* c, const zrt_transmittance_batch* b, zrt_stats* stats) {
+    if (!c || !b) return ZRT_ERR_INVALID_ARG;
+    if ((b->flags & ~kTraceFlags) != 0u || b->on_device > 1u || b->max_crossings == 0u || b->max_crossings > 256u)
+        return ZRT_ERR_INVALID_ARG;
+    if (b->num_rays == 0) { if (stats) *stats = zrt_stats{}; return ZRT_OK; }
+    if (!b->rays || !b->transmittance) return ZRT_ERR_INVALID_ARG;
+    zrt_stats st{};
+    DeviceGuard g(c->device);
+    const bool counting = (b->flags & ZRT_FLAG_COUNT_STATS) != 0;
+    const uint32_t cap = b->max_crossings;
+    LaunchPlan pl;
+    int rc;
+    // The park path only where ZRT_TRACE_PARK asks for it: unlike a segment
+    // call's (kSegParkMin), this call's lane path was as fast or faster at
+    // 2^16 and 2^20 rays on both scenes of tools/transmit_bench.py (DESIGN
+    // 5.15: the chains' later rounds hold few rays, which the park launches'
+    // fixed cost does not suit), so no batch size takes it unasked.
+    if ((rc = resolve_plan(c, b->flags, counting, (b->flags & ZRT_TRACE_PARK) != 0, b->num_rays >= kSetsMinSamples,
+                           pl)) != ZRT_OK)
+        return rc;
+    const bool park = pl.park;
+    const char* rounds_env = getenv("ZRT_TRANSMIT_ROUNDS");
+    const bool fixed_rounds = rounds_env && strcmp(rounds_env, "fixed") == 0;
+    uint64_t tail_max = kTransmitTailMax;
+    if (const char* e = getenv("ZRT_TRANSMIT_TAIL")) tail_max = (uint64_t)std::max(0ll, atoll(e));
+
+    // chunk size, as query_rays: the staging words of a host batch, the park
+    // path's two queues and hit records (2 * 48 + 16 B per ray)
+    zrt_context::PassSet& ps = c->set[0];
+    const bool own_n = b->on_device && park && !b->crossings;
+    const uint64_t per_ray = (b->on_device ? (own_n ? 4ull : 0ull) : 36ull) + (park ? 112ull : 0ull);
+    const size_t held = 4ull * (c->rays_cap + c->hits_cap) + 16ull * (ps.q0_cap + ps.q1_cap + ps.hit_cap) + c->bfc_bytes +
+                        c->esc_extra;
+    const size_t budget = device_budget(c, held);
+    uint64_t chunk = std::min<uint64_t>(kTraceChunk, b->num_rays);
+    if (per_ray) chunk = std::max<uint64_t>(64, std::min<uint64_t>(chunk, budget / per_ray));
+    const uint64_t rays_words = 7 * chunk, tn_words = b->on_device ? chunk : 2 * chunk;
+    if (!b->on_device) {
+        if ((rc = grow(&c->d_rays, &c->rays_cap, rays_words)) != ZRT_OK) return rc;
+        if ((rc = grow(&c->d_hits, &c->hits_cap, tn_words)) != ZRT_OK) return rc;
+    } else if (own_n) {
+        if ((rc = grow(&c->d_hits, &c->hits_cap, tn_words)) != ZRT_OK) return rc;
+    }
+    // counters of a chunk's rounds: 8 work counters and 8 region counts per round, one more round's region counts
+    const size_t ctr_words = kCtr * 16ull * (cap + 1ull);
+    if (park) {
+        if ((rc = grow(&ps.q0, &ps.q0_cap, 3 * chunk)) != ZRT_OK) return rc;
+        if ((rc = grow(&ps.q1, &ps.q1_cap, 3 * chunk)) != ZRT_OK) return rc;
+        if ((rc = grow(&ps.hit, &ps.hit_cap, chunk)) != ZRT_OK) return rc;
+        if ((rc = grow(&ps.wfc, &ps.wfc_cap, ctr_words)) != ZRT_OK) return rc;
+    }
+    // capacity guard: every buffer a launch below writes holds a chunk
+    if ((!b->on_device && (shortfall("rays", c->d_rays, c->rays_cap, rays_words) ||
+                           shortfall("T, n", c->d_hits, c->hits_cap, tn_words))) ||
+        (own_n && shortfall("n", c->d_hits, c->hits_cap, tn_words)) ||
+        (park && (shortfall("q0", ps.q0, ps.q0_cap, 3 * chunk) || shortfall("q1", ps.q1, ps.q1_cap, 3 * chunk) ||
+                  shortfall("hit records", ps.hit, ps.hit_cap, chunk) ||
+                  shortfall("counters", ps.wfc, ps.wfc_cap, ctr_words))))
+        return ZRT_ERR_INVALID_ARG;
+    if ((rc = event_pool(c->ev_trace, 2)) != ZRT_OK) return rc;
+
+    // the kernels and their occupancy-sized persistent grids (ray_launch's choices)
+    const TransmitFn f_fast = counting || pl.mtx ? nullptr : kTransmitWalk[pl.packed ? (pl.pbm ? 0 : 1) : 2];
+    const TransmitFn f_exact = kTransmitWalk[counting ? 4 : 3];
+    const WfFn f_park = park_fn<kParkClosest>(pl.esc, pl.pbm);
+    uint32_t grid_fast = 0, grid_exact = 0, grid_park = 0;
+    if (park && (rc = resident_blocks(c, (const void*)f_park, pl.park_block, pl.lds_park, &grid_park)) != ZRT_OK) return rc;
+    if (f_fast && (rc = resident_blocks(c, (const void*)f_fast, kTraceThreads, pl.lds_wf, &grid_fast)) != ZRT_OK)
+        return rc;                                     // (the park path: its tail launch)
+    if ((rc = resident_blocks(c, (const void*)f_exact, kTraceThreads, pl.lds_wf, &grid_exact)) != ZRT_OK) return rc;
+
+    TransmitParams R;
+    memset(&R, 0, sizeof R);
+    R.q.t_max_all = b->t_max_all;
+    R.max_cross = cap;
+    scene_params(c, R.q.w.t);
+    R.q.w.t.max_bounce = 1;
+    R.q.w.t.counter = c->d_counter;
+    R.q.w.t.stats = c->d_stats;
+    R.q.ctr = c->d_counter;
+    if (park) {
+        R.q.w.hit = ps.hit;
+        park_params(c, pl, R.q.w);
+    }
+
+    HIP_TRY(hipMemsetAsync(c->d_stats, 0, 512, c->stream));
+    HIP_TRY(hipEventRecord(c->ev_begin, c->stream));
+    uint32_t launches = 0;
+    for (uint64_t off = 0; off < b->num_rays; off += chunk) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, b->num_rays - off);
+        const uint32_t nblk = (n + kBlock - 1) / kBlock;
+        if (b->on_device) {
+            R.q.rays = b->rays + 6 * off;
+            R.q.t_max = b->t_max ? b->t_max + off : nullptr;
+            R.T = b->transmittance + off;
+            R.cross = b->crossings ? b->crossings + off : own_n ? c->d_hits : nullptr;
+        } else {
+            HIP_TRY(hipMemcpyAsync(c->d_rays, b->rays + 6 * off, 24ull * n, hipMemcpyHostToDevice, c->stream));
+            R.q.rays = c->d_rays;
+            if (b->t_max) {
+                HIP_TRY(hipMemcpyAsync(c->d_rays + 6 * chunk, b->t_max + off, 4ull * n, hipMemcpyHostToDevice, c->stream));
+                R.q.t_max = c->d_rays + 6 * chunk;
+            }
+            R.T = reinterpret_cast<float*>(c->d_hits);
+            R.cross = c->d_hits + chunk;
+            HIP_TRY(hipEventRecord(c->ev_trace[0], c->stream));
+        }
+        HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
+        R.q.n = n;
+        R.q.w.t.P = n;
+        R.q.w.t.S = 1;
+        R.q.w.t.total = n;
+        R.q.w.t.sdiv = div_magic(1);
+        auto walk = [&](TransmitFn f, uint32_t grid, uint32_t which) {
+            R.q.which = which;
+            hipLaunchKernelGGL(f, dim3(std::min(grid, nblk)), dim3(kTraceThreads), pl.lds_wf, c->stream, R);
+            ++launches;
+        };
+        if (park) {
+            HIP_TRY(hipMemsetAsync(ps.wfc, 0, 4ull * ctr_words, c->stream));
+            QueryParams Q = R.q;                       // the queue fill: query_pack_kernel<SEG>, (d, bound) records
+            Q.which = kRaysAll;
+            Q.q = ps.q0;
+            Q.n_in8 = region_counts(ps, 0);
+            hipLaunchKernelGGL(kQuery[1].pack, dim3(nblk), dim3(kBlock), 0, c->stream, Q);
+            ++launches;
+            for (uint32_t k = 0; k < cap; ++k) {       // (bounded by the cap whatever the device says)
+                float4* const qin = (k & 1u) ? ps.q1 : ps.q0;
+                R.q.w.q_in = qin;
+                R.q.w.fetch8 = ps.wfc + kCtr * (16 * k);
+                R.q.w.n_in8 = region_counts(ps, k);
+                R.q_in = qin;
+                R.q_out = (k & 1u) ? ps.q0 : ps.q1;
+                R.n_out8 = region_counts(ps, k + 1);
+                R.first = k == 0u ? 1u : 0u;
+                hipLaunchKernelGGL(f_park, dim3(grid_park), dim3(pl.park_block), pl.lds_park, c->stream, R.q.w);
+                hipLaunchKernelGGL(transmit_step_kernel, dim3(nblk), dim3(kBlock), 0, c->stream, R);
+                launches += 2;
+                HIP_TRY(hipGetLastError());
+                if (k + 1u == cap) break;              // (a ray that got this far has n == cap: none was appended)
+                if (!fixed_rounds) {
+                    uint32_t left[8 * kCtr];
+                    HIP_TRY(copy_sync(left, R.n_out8, sizeof left, hipMemcpyDeviceToHost, c->stream));
+                    uint64_t alive = 0;
+                    for (uint32_t gq = 0; gq < 8u; ++gq) alive += left[gq * kCtr];
+                    if (alive == 0u) break;
+                    if (alive <= tail_max) {           // the tail: the survivors' whole chains in one lane launch
+                        R.q_in = R.q_out;
+                        R.q.w.n_in8 = R.n_out8;
+                        walk(f_fast, grid_fast, kRaysQueue);
+                        break;
+                    }
+                }
+            }
+        } else if (f_fast) {
+            walk(f_fast, grid_fast, kRaysFast);
+        }
+        walk(f_exact, grid_exact, park || f_fast ? kRaysRest : kRaysAll);
+        HIP_TRY(hipGetLastError());
+        if (!b->on_device) {
+            HIP_TRY(hipEventRecord(c->ev_trace[1], c->stream));
+            HIP_TRY(copy_sync(b->transmittance + off, R.T, 4ull * n, hipMemcpyDeviceToHost, c->stream));
+            if (b->crossings) HIP_TRY(copy_sync(b->crossings + off, R.cross, 4ull * n, hipMemcpyDeviceToHost, c->stream));
+            float t = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&t, c->ev_trace[0], c->ev_trace[1]));
+            st.trace_kernel_ms += t;
+        }
+    }
+    if ((rc = finish_query(c, b->on_device != 0, launches, st)) != ZRT_OK) return rc;
+    unsigned long long hs[4];
+    HIP_TRY(copy_sync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+    st.segments = hs[0];
+    st.hits = hs[3];
+    if (counting) {
+        st.cells_visited = hs[1];
+        st.triangle_tests = hs[2];
+    }
+    if (stats) *stats = st;
+    return ZRT_OK;
 }
 
 // Scene.traceRayRecursive (stage3.zig:188-220) for a batch of rays: see

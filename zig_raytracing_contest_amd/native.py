@@ -151,6 +151,12 @@ class SurfaceBatch(C.Structure):
                 ("on_device", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class TransmittanceBatch(C.Structure):
+    _fields_ = [("num_rays", C.c_uint64), ("rays", C.c_void_p), ("t_max", C.c_void_p), ("transmittance", C.c_void_p),
+                ("crossings", C.c_void_p), ("on_device", C.c_uint32), ("flags", C.c_uint32),
+                ("t_max_all", C.c_float), ("max_crossings", C.c_uint32)]
+
+
 class RadianceBatch(C.Structure):
     _fields_ = [("num_rays", C.c_uint64), ("rays", C.c_void_p), ("radiance", C.c_void_p), ("rgb", C.c_void_p),
                 ("on_device", C.c_uint32), ("flags", C.c_uint32), ("num_samples", C.c_uint32),
@@ -165,7 +171,7 @@ EXPORTS = [
     "zrt_gltf_load", "zrt_gltf_soup", "zrt_gltf_materials", "zrt_gltf_camera", "zrt_gltf_free",
     "zrt_camera_from_matrix", "zrt_probe", "zrt_timed_kernels", "zrt_context_profile", "zrt_context_trace",
     "zrt_group_create", "zrt_group_create_built", "zrt_group_render", "zrt_group_context", "zrt_group_destroy",
-    "zrt_context_radiance", "zrt_context_segments", "zrt_context_surface",
+    "zrt_context_radiance", "zrt_context_segments", "zrt_context_surface", "zrt_context_transmittance",
 ]
 
 
@@ -206,6 +212,7 @@ def lib():
     L.zrt_context_radiance.argtypes = [C.c_void_p, C.POINTER(RadianceBatch), C.POINTER(Stats)]
     L.zrt_context_segments.argtypes = [C.c_void_p, C.POINTER(SegmentBatch), C.POINTER(Stats)]
     L.zrt_context_surface.argtypes = [C.c_void_p, C.POINTER(SurfaceBatch), C.POINTER(Stats)]
+    L.zrt_context_transmittance.argtypes = [C.c_void_p, C.POINTER(TransmittanceBatch), C.POINTER(Stats)]
     if hasattr(L, "zrt_group_create"):     # ABI 2 (an ABI-1 build: tools/ A/B baselines only)
         L.zrt_group_create.argtypes = [C.POINTER(Scene), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
         L.zrt_group_create_built.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -576,7 +583,71 @@ class Context:
         res["stats"] = st
         return res
 
-    def radiance_raw(self, num_rays: int, rays_ptr, radiance_ptr, rgb_ptr, on_device: bool, spp: int,
+    def transmittance_raw(self, num_rays: int, rays_ptr, t_max_ptr, transmittance_ptr, crossings_ptr, on_device: bool,
+                          flags: int = 0, t_max_all: float = float("inf"), max_crossings: int = 16):
+        """zrt_context_transmittance on raw pointers; returns the stats dict."""
+        batch = TransmittanceBatch(int(num_rays), rays_ptr, t_max_ptr, transmittance_ptr, crossings_ptr,
+                                   1 if on_device else 0, int(flags), float(t_max_all), int(max_crossings))
+        st = Stats()
+        check(lib().zrt_context_transmittance(self._h, C.byref(batch), C.byref(st)), "zrt_context_transmittance")
+        return st.as_dict()
+
+    def transmittance(self, origins, dirs, t_max=float("inf"), max_crossings: int = 16, flags: int = 0,
+                      stats: bool = False, crossings: bool = False):
+        """Shadow rays that pass through transparent hits as the path tracer
+        does (zrt_context_transmittance): per ray the product of 1 - alpha over
+        the surfaces met before t_max -- `t_max` a scalar for every ray or n
+        values, in the ray's own parameter -- 0 from the first opaque one on, 1
+        if there is none; at most `max_crossings` (1..256) surfaces per ray.
+
+        Two (n, 3) float32 numpy arrays give {"transmittance": (n,) float32,
+        "stats"} and with crossings=True "crossings", (n,) uint32: the surfaces
+        each ray met (== max_crossings: the chain was cut there).  "stats"
+        holds "segments" and "hits" (the sum of the crossings) in every call,
+        the cell and test counters with stats=True.
+
+        Two (n, 3) float32 CUDA tensors (torch-ROCm) on the context's device
+        (and `t_max` a float or an (n,) float32 tensor there) are traced in
+        place, after a sync of torch's current stream: "transmittance" an (n,)
+        float32 and "crossings" an (n,) int32 CUDA tensor."""
+        flags = int(flags) | (FLAG_COUNT_STATS if stats else 0)
+        torch, n, rays = self._rays("transmittance", origins, dirs)
+        if torch:
+            tm, tm_all = None, float("inf")
+            if torch.is_tensor(t_max) and t_max.dim() > 0:
+                if t_max.device != origins.device or t_max.dtype != torch.float32 or t_max.shape != (n,):
+                    raise ValueError("transmittance: t_max must be a float or an (n,) float32 tensor on the rays' device")
+                tm = t_max.contiguous()
+            else:
+                tm_all = float(t_max)
+            T = torch.empty((n,), dtype=torch.float32, device=origins.device)
+            cr = torch.empty((n,), dtype=torch.int32, device=origins.device) if crossings else None
+            torch.cuda.current_stream(origins.device).synchronize()
+            st = self.transmittance_raw(n, rays.data_ptr() if n else None,
+                                        tm.data_ptr() if tm is not None and n else None, T.data_ptr() if n else None,
+                                        cr.data_ptr() if crossings and n else None, True, flags, tm_all, max_crossings)
+            res = {"transmittance": T, "stats": st}
+            if crossings:
+                res["crossings"] = cr
+            return res
+        tm, tm_all = None, float("inf")
+        if np.ndim(t_max) == 0:
+            tm_all = float(t_max)
+        else:
+            tm = np.ascontiguousarray(t_max, np.float32)
+            if tm.shape != (n,):
+                raise ValueError("transmittance: t_max must be a scalar or n values")
+        T = np.empty(n, np.float32)
+        cr = np.empty(n, np.uint32) if crossings else None
+        st = self.transmittance_raw(n, rays.ctypes.data if n else None, tm.ctypes.data if tm is not None and n else None,
+                                    T.ctypes.data if n else None, cr.ctypes.data if crossings and n else None, False,
+                                    flags, tm_all, max_crossings)
+        res = {"transmittance": T, "stats": st}
+        if crossings:
+            res["crossings"] = cr
+        return res
+
+    def radiance_raw(self,num_rays: int, rays_ptr, radiance_ptr, rgb_ptr, on_device: bool, spp: int,
                      max_bounce: int, seed: int = 0, index_base: int = 0, flags: int = 0):
         """zrt_context_radiance on raw pointers; returns the stats dict."""
         batch = RadianceBatch(int(num_rays), rays_ptr, radiance_ptr, rgb_ptr, 1 if on_device else 0, int(flags),
