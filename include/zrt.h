@@ -529,6 +529,77 @@ typedef struct zrt_transmittance_batch {
  * counts it. */
 int zrt_context_transmittance(zrt_context* ctx, const zrt_transmittance_batch* batch, zrt_stats* stats_or_null);
 
+/* ---- feature planes (ABI 2, added) -------------------------------------- */
+
+/* The auxiliary planes of a frame: base colour, normal, emission, depth and
+ * transparency of the first hit and the hit count, per pixel, averaged over
+ * exactly the jittered camera samples a zrt_context_render of the same camera,
+ * seed and sample count traces -- what a denoiser or a compositor reads beside
+ * the beauty image.  The camera rays are made on the device (their jitter is
+ * the library's own RNG stream), so nothing per ray crosses the bus.
+ *
+ * All planes are packed in zrt_tile_pixels(w, h, tile_size, rank, num_ranks)
+ * order, n_owned that call's count, as zrt_outputs.linear_packed is.
+ *
+ * For an owned pixel with image index `pixel` = (px, py) and for
+ * s = 0 .. num_samples - 1 in this order:
+ *   ray_s  the ray a zrt_context_render of the same camera, seed and pixel
+ *          traces for sample s: origin camera.origin, direction
+ *          normalize(llc + right * ((float)px + U0) + up * ((float)py + U1))
+ *          (Camera.getRay, stage3.zig:27-35, :238), U0 and U1 the first two
+ *          floats of the stream (seed, pixel, s), normalised as the render
+ *          does: scaled by 1.0f / sqrt((x*x + y*y) + z*z);
+ *   h_s    the zrt_context_trace record of ray_s;
+ *   r_s    the zrt_surface of (ray_s, h_s).
+ * Five f32 sums and one counter start at +0 and 0.  A miss adds nothing.  A hit
+ * adds r_s.base_color, r_s.normal and r_s.emissive, component by component;
+ * h_s.t to the depth sum (the direction is unit length, so t is the distance
+ * from the camera); r_s.transparency; and 1 to hits.  The normal is added as
+ * interpolated, not normalised: that is what stage3.zig:214 uses.  Each float
+ * plane stores sum * (1.0f / (float)num_samples), the render's own
+ * inv_num_samples rule (stage3.zig:223, :242); hits stores the count.  A NaN or
+ * inf the arithmetic produces is stored as it is.  A transparent first hit
+ * counts like any other hit.  No sky colour on a miss: hits / num_samples is the
+ * pixel's coverage, the sky is the caller's. */
+typedef struct zrt_feature_outputs {
+    float* base_color;       /* n_owned * 3, or null */
+    float* normal;           /* n_owned * 3, or null */
+    float* emissive;         /* n_owned * 3, or null */
+    float* depth;            /* n_owned, or null */
+    float* transparency;     /* n_owned, or null */
+    uint32_t* hits;          /* n_owned, or null */
+    uint32_t on_device;      /* 0: host pointers; 1: device pointers on the context's device, 4-byte aligned */
+    uint32_t _reserved;      /* 0 */
+} zrt_feature_outputs;       /* 56 B */
+
+/* cfg: seed, num_samples (1..65535), rank, num_ranks, tile_size and
+ * samples_per_pass mean what they mean in zrt_context_render; max_bounce,
+ * device, num_devices and devices are ignored.  cfg->flags accepts what a
+ * render accepts: the flags of the bounce launches (ESCAPE, RELEASE, BFCULL,
+ * HOP, their NO_ forms, ONE_SET, KERNEL_TIMES) do nothing here;
+ * ZRT_FLAG_MT_EXACT, ZRT_FLAG_LANE_WALK and ZRT_FLAG_FRUSTUM /
+ * ZRT_FLAG_NO_FRUSTUM select kernels as they do for a render's primary launch
+ * (the planes are the same either way); ZRT_FLAG_COUNT_STATS selects the
+ * counting instantiation.  The planes are the same bits for any
+ * samples_per_pass; unasked, a pass takes as many samples as 4 GiB of item
+ * records (48 B per sample) hold, below 2^31 items.
+ * Synchronous, one thread at a time per context; alternates freely with
+ * renders and the five queries (every use writes what it reads first) and
+ * leaves zrt_context_profile's record of the last render untouched.
+ * ZRT_ERR_INVALID_ARG before any device work, the outputs untouched: a null
+ * context, camera, cfg or outputs, all six plane pointers null, on_device > 1,
+ * a non-zero _reserved, num_samples outside 1..65535, and whatever camera, rank
+ * or tile value zrt_context_render refuses.  A rank that owns no pixel returns
+ * ZRT_OK and touches nothing.
+ * stats (may be null), in every call: segments = samples = n_owned *
+ * num_samples, hits = the sum of the hits plane, render_ms, trace_kernel_ms
+ * and trace_launches as in zrt_context_trace (the launches: the frustum bounds
+ * if used, then a walk and a resolve per pass).  With ZRT_FLAG_COUNT_STATS
+ * cells_visited and triangle_tests too: a counting render's at max_bounce = 1,
+ * which traces exactly these segments. */
+int zrt_context_features(zrt_context* ctx, const zrt_camera* camera, const zrt_render_config* cfg,
+                         const zrt_feature_outputs* out, zrt_stats* stats_or_null);
+
 /* A device group: one context per entry of `devices` (HIP ordinals, repeats
  * allowed), the scene resident on each, rendered by one call -- Scene.render's
  * spawn + join of its workers (stage3.zig:247-256) across GPUs in one

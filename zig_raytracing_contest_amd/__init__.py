@@ -142,6 +142,12 @@ class RenderScene:
         return self.context.transmittance(origins, dirs, t_max, max_crossings=max_crossings, flags=flags,
                                           stats=stats, crossings=crossings)
 
+    def features(self, camera: native.Camera, num_samples: int = 3, seed: int = 0, **kw):
+        """The auxiliary planes (first-hit base colour, normal, emission,
+        depth, transparency, hit count) of the frame render(camera,
+        num_samples, seed=seed) gives: see native.Context.features."""
+        return self.context.features(camera, num_samples, seed=seed, **kw)
+
     def radiance(self, origins, dirs, spp: int, max_bounce: int, seed: int = 0, index_base: int = 0,
                  flags: int = 0, rgb: bool = False, stats: bool = False):
         """Scene.traceRayRecursive (stage3.zig:188-220) for a batch of rays,

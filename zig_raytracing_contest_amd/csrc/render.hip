@@ -2270,14 +2270,38 @@ struct SurfaceParams {
     const float* texels;
     uint32_t n;               // rays of this chunk
 };
-// The arithmetic is shade_segment's (its lines "stage3.zig:199-206" to `no`),
-// restated here because shade_segment is welded to the RNG draw and the queue
-// append: keep the two in step.  The four Data loads of a hit lane are issued
-// together before any texel load (tri_rec's reason); a miss lane loads nothing
-// after its hit record and ray.  The materials are read from global memory
-// whatever their number: a copy in LDS for up to kLdsMats of them, the shade
-// kernel's LMATS, was built and measured beside this and did not win in every
+// The shading inputs of a hit, stage3.zig:199-206: the arithmetic is
+// shade_segment's (its lines "stage3.zig:199-206" to `nrm`), restated here
+// because shade_segment is welded to the RNG draw and the queue append: keep
+// the two in step.  surface_kernel and feature_walk_kernel share this one.  The
+// four Data loads of a hit lane are issued together before any texel load
+// (tri_rec's reason).  The materials are read from global memory whatever
+// their number: a copy in LDS for up to kLdsMats of them, the shade kernel's
+// LMATS, was built and measured beside surface_kernel and did not win in every
 // round, so one path serves both sides of that limit.
+struct SurfaceInputs {
+    v3 nrm, albedo, emissive;
+    float transparency, tc0, tc1;
+    float mat;                // Data.material_idx, the bits of d3.w
+};
+__device__ __forceinline__ SurfaceInputs surface_gather(const float4* tri_data, const DevMat* mats, const float* texels,
+                                                        float hu, float hv, uint32_t ref) {
+    const float4* tdp = tri_data + 4ull * ref;
+    const float4 d0 = tdp[0], d1 = tdp[1], d2 = tdp[2], d3 = tdp[3];   // stage3.zig:199-206
+    SurfaceInputs g;
+    const float w0 = 1.0f - hu - hv;
+    g.tc0 = (d2.y * w0 + d2.w * hu) + d3.y * hv;
+    g.tc1 = (d2.z * w0 + d3.x * hu) + d3.z * hv;
+    const DevMat& m = mats[__float_as_uint(d3.w)];
+    g.albedo = sample3(texels, m.tex[0], g.tc0, g.tc1);
+    g.emissive = sample3(texels, m.tex[1], g.tc0, g.tc1);
+    g.transparency = sample1(texels, m.tex[2], g.tc0, g.tc1);
+    g.nrm = add(add(scale(mk(d0.x, d0.y, d0.z), w0), scale(mk(d0.w, d1.x, d1.y), hu)),
+                scale(mk(d1.z, d1.w, d2.x), hv));
+    g.mat = d3.w;
+    return g;
+}
+// One lane per ray; a miss lane loads nothing after its hit record and ray.
 __global__ __launch_bounds__(kBlock) void surface_kernel(const SurfaceParams r) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= r.n) return;
@@ -2300,23 +2324,173 @@ __global__ __launch_bounds__(kBlock) void surface_kernel(const SurfaceParams r) 
         out[3] = z4;
         return;
     }
-    const float4* tdp = r.tri_data + 4ull * h.w;
-    const float4 d0 = tdp[0], d1 = tdp[1], d2 = tdp[2], d3 = tdp[3];   // stage3.zig:199-206
-    const float w0 = 1.0f - hu - hv;
-    const float tc0 = (d2.y * w0 + d2.w * hu) + d3.y * hv;
-    const float tc1 = (d2.z * w0 + d3.x * hu) + d3.z * hv;
-    const DevMat& m = r.mats[__float_as_uint(d3.w)];
-    const v3 albedo = sample3(r.texels, m.tex[0], tc0, tc1);
-    const v3 emissive = sample3(r.texels, m.tex[1], tc0, tc1);
-    const float transparency = sample1(r.texels, m.tex[2], tc0, tc1);
-    const v3 nrm = add(add(scale(mk(d0.x, d0.y, d0.z), w0), scale(mk(d0.w, d1.x, d1.y), hu)),
-                       scale(mk(d1.z, d1.w, d2.x), hv));
+    const SurfaceInputs g = surface_gather(r.tri_data, r.mats, r.texels, hu, hv, h.w);
     const v3 no = add(o, scale(d, t + kFltEps));
-    out[0] = make_float4(no.x, no.y, no.z, d3.w);
-    out[1] = make_float4(nrm.x, nrm.y, nrm.z, transparency);
-    out[2] = make_float4(albedo.x, albedo.y, albedo.z, tc0);
-    out[3] = make_float4(emissive.x, emissive.y, emissive.z, tc1);
+    out[0] = make_float4(no.x, no.y, no.z, g.mat);
+    out[1] = make_float4(g.nrm.x, g.nrm.y, g.nrm.z, g.transparency);
+    out[2] = make_float4(g.albedo.x, g.albedo.y, g.albedo.z, g.tc0);
+    out[3] = make_float4(g.emissive.x, g.emissive.y, g.emissive.z, g.tc1);
 }
+
+// ---------------------------------------------------------------------------
+// Feature planes (zrt_context_features): base colour, normal,
+// emission, depth, transparency and hit count of the first hit per pixel, over
+// the camera samples of a render.  A pass is a render's pass without the path
+// tracer: feature_walk_kernel is the primary launch's fetch, camera ray and
+// lane walk followed by surface_kernel's gather, and leaves one record per
+// item; feature_resolve_kernel is wf_resolve_kernel's ordered per-pixel sum
+// over those records.  No RNG state beyond the two jitter floats, no scatter,
+// no queue append.
+//
+// An item's record, three float4 at rec[3 * item] (items pixel-major, as the
+// render's): (base colour, t) (normal, transparency) (emissive, 0).  t = +inf
+// marks a miss, whose other two words are not written and not used.
+struct FeatureParams {
+    WfParams w;               // w.t: grid, scene, camera and pass; w.fetch8: the pass's eight work counters
+    float4* rec;
+};
+// Launch bounds and instantiations are wf_kernel's primary ones (kWfPrimary*):
+// the packed walks at kWfMinWaves0 waves, the wide and IEEE-division walks at
+// kWfMinWaves; STATS is the counting build's walk (trace_kernel's trace_ray).
+// The hits are counted in every instantiation (zrt_stats.hits).
+template <bool STATS, bool PACKED, bool PK_BM, bool MTX>
+__global__ __launch_bounds__(kTraceBlock, STATS ? 1 : (PACKED ? kWfMinWaves0 : kWfMinWaves))
+void feature_walk_kernel(const FeatureParams r) {
+    const WfParams& w = r.w;
+    const TraceParams& p = w.t;
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_occ[];
+    __shared__ uint32_t s_wcnt[2 * (kTraceBlock / 64)];
+    for (uint32_t i = threadIdx.x; i < p.occ_words; i += blockDim.x) s_occ[i] = p.occ[i];
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    uint64_t prof[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t n_cells = 0, n_tests = 0, n_hits = 0;
+    uint32_t grp = blockIdx.x & 7u, tried = 0;
+    for (;;) {
+        uint32_t base = 0, lim = 0;
+        if (!wf_fetch<true>(w, 64u * kWfChunk, grp, tried, base, lim)) break;
+        for (uint32_t sub = 0; sub < kWfChunk && base + 64u * sub < lim; ++sub) {
+            const uint32_t j = base + 64u * sub + lane;
+            if (j >= lim) continue;
+            const uint32_t i = ent_index<true>(w, grp, j);
+            v3 o, d;
+            Rng rng0;
+            uint32_t blk = 0;
+            float tau = 0.0f, tfar = kInf;
+            camera_ray(p, i, rng0, o, d, &blk);
+            if (p.tlo) {
+                const float4 fb = p.tlo[blk];
+                tau = fb.x;
+                tfar = fb.y;
+            }
+            float hu = 0.0f, hv = 0.0f;
+            uint32_t hidx = 0;
+            const float t = trace_ray<STATS, kTriBatch, PACKED, PK_BM, MTX>(p, s_occ, o, d, hu, hv, hidx, n_cells, n_tests,
+                                                                            prof, s_wcnt, tau, tfar);
+            float4* const out = r.rec + 3ull * i;
+            if (t == kInf) {
+                out[0] = make_float4(0.0f, 0.0f, 0.0f, kInf);
+                continue;
+            }
+            ++n_hits;
+            const SurfaceInputs g = surface_gather(p.tri_data, p.mats, p.texels, hu, hv, hidx);
+            out[0] = make_float4(g.albedo.x, g.albedo.y, g.albedo.z, t);
+            out[1] = make_float4(g.nrm.x, g.nrm.y, g.nrm.z, g.transparency);
+            out[2] = make_float4(g.emissive.x, g.emissive.y, g.emissive.z, 0.0f);
+        }
+    }
+    if (STATS) {
+        const unsigned long long s1 = wave_sum(n_cells), s2 = wave_sum(n_tests);
+        if (lane == 0) {
+            atomicAdd(&p.stats[1], s1);
+            atomicAdd(&p.stats[2], s2);
+        }
+    }
+    const unsigned long long s3 = wave_sum(n_hits);
+    if (lane == 0 && s3 != 0ull) atomicAdd(&p.stats[3], s3);
+}
+
+// The planes a call asked for (null: not asked), n_owned entries each.
+struct FeaturePlanes {
+    float *base_color, *normal, *emissive, *depth, *transparency;
+    uint32_t* hits;
+};
+// The ordered per-pixel sums, wf_resolve_kernel's shape: a block takes kResPix
+// pixels and loads their records kResSmp samples at a time, consecutive lanes
+// on consecutive float4 of the items (a pixel's 16 records: a 768-byte run),
+// parks the eleven values of each in LDS, and one thread per pixel then adds
+// them in sample order, a miss adding nothing.  Between passes the sums and
+// the count wait in acc (three float4 per pixel, the record's layout with the
+// count's bits in the last word); the last pass scales by 1 / spp
+// (stage3.zig:223, :242) and writes the planes asked for.
+constexpr uint32_t kFeatVals = 11, kFeatRow = kResSmp * kFeatVals + 1;   // +1: no LDS bank conflict
+__global__ __launch_bounds__(kBlock) void feature_resolve_kernel(const float4* __restrict__ rec, uint32_t P, uint32_t S,
+                                                                 float4* acc, int first, int last, float inv_spp,
+                                                                 const FeaturePlanes out) {
+    __shared__ float s_r[kResPix * kFeatRow];
+    const uint32_t q0 = blockIdx.x * kResPix;
+    const uint32_t np = min(kResPix, P - q0);
+    const uint32_t tid = threadIdx.x;
+    const uint32_t q = q0 + tid;
+    v3 bc = mk(0, 0, 0), nr = mk(0, 0, 0), em = mk(0, 0, 0);
+    float dp = 0.0f, tr = 0.0f;
+    uint32_t nh = 0;
+    if (tid < np && !first) {
+        const float4 a0 = acc[3ull * q], a1 = acc[3ull * q + 1], a2 = acc[3ull * q + 2];
+        bc = mk(a0.x, a0.y, a0.z); dp = a0.w;
+        nr = mk(a1.x, a1.y, a1.z); tr = a1.w;
+        em = mk(a2.x, a2.y, a2.z); nh = __float_as_uint(a2.w);
+    }
+    for (uint32_t c = 0; c < S; c += kResSmp) {
+        const uint32_t ns = min(kResSmp, S - c);
+        for (uint32_t m = tid; m < kResPix * kResSmp * 3u; m += kBlock) {
+            const uint32_t i = m / (kResSmp * 3u), k3 = m % (kResSmp * 3u);   // the block's pixel i, word k3 of its run
+            if (i < np && k3 < 3u * ns) {
+                const float4 v = rec[3ull * ((uint64_t)(q0 + i) * S + c) + k3];
+                const uint32_t k = k3 / 3u, f = k3 % 3u;                      // sample c + k, its word f
+                float* dst = s_r + i * kFeatRow + kFeatVals * k + 4u * f;
+                dst[0] = v.x; dst[1] = v.y; dst[2] = v.z;
+                if (f < 2u) dst[3] = v.w;
+            }
+        }
+        __syncthreads();
+        if (tid < np) {
+            const float* src = s_r + tid * kFeatRow;
+            for (uint32_t k = 0; k < ns; ++k, src += kFeatVals) {
+                if (src[3] == kInf) continue;                                // a miss: its other words are stale
+                bc = add(bc, mk(src[0], src[1], src[2]));
+                dp += src[3];
+                nr = add(nr, mk(src[4], src[5], src[6]));
+                tr += src[7];
+                em = add(em, mk(src[8], src[9], src[10]));
+                ++nh;
+            }
+        }
+        __syncthreads();
+    }
+    if (tid >= np) return;
+    if (!last) {
+        acc[3ull * q] = make_float4(bc.x, bc.y, bc.z, dp);
+        acc[3ull * q + 1] = make_float4(nr.x, nr.y, nr.z, tr);
+        acc[3ull * q + 2] = make_float4(em.x, em.y, em.z, __uint_as_float(nh));
+        return;
+    }
+    const v3 inv = mk(inv_spp, inv_spp, inv_spp);
+    auto put3 = [&](float* plane, v3 sum) {
+        const v3 l = mul(sum, inv);
+        plane[3 * (size_t)q] = l.x; plane[3 * (size_t)q + 1] = l.y; plane[3 * (size_t)q + 2] = l.z;
+    };
+    if (out.base_color) put3(out.base_color, bc);
+    if (out.normal) put3(out.normal, nr);
+    if (out.emissive) put3(out.emissive, em);
+    if (out.depth) out.depth[q] = dp * inv_spp;
+    if (out.transparency) out.transparency[q] = tr * inv_spp;
+    if (out.hits) out.hits[q] = nh;
+}
+
+using FeatureFn = void (*)(const FeatureParams);
+// staging of a pass unasked: 4 GiB of item records (zrt_context_features)
+constexpr uint64_t kFeatStageBytes = 4ull << 30, kFeatItemBytes = 48;
 
 // ---------------------------------------------------------------------------
 // Transmittance queries (zrt_context_transmittance): the expected
@@ -2748,7 +2922,9 @@ extern "C" const char* zrt_timed_kernels(void) {
            "wf_park_kernelILb1ELb1ELi0E,wf_park_kernelILb0ELb1ELi0E,wf_park_kernelILb1ELb0ELi0E,wf_park_kernelILb0ELb0ELi0E,"
            "wf_park_kernelILb1ELb1ELi1E,wf_park_kernelILb0ELb1ELi1E,wf_park_kernelILb1ELb0ELi1E,wf_park_kernelILb0ELb0ELi1E,"
            "wf_shade_kernelILb1ELb0EE,wf_shade_kernelILb1ELb1EE,wf_kernelILi" ZRT_STR(ZRT_WF_MINW) "ELb0ELb1ELb1ELb0EE,wf_kernelILi" ZRT_STR(
-               ZRT_WF_MINW) "ELb0ELb1ELb0ELb0EE";
+               ZRT_WF_MINW) "ELb0ELb1ELb0ELb0EE,"
+           // zrt_context_features' walk (STATS, PACKED, PK_BM, MTX), under the primary's rules
+           "feature_walk_kernelILb0ELb1ELb1ELb0EE,feature_walk_kernelILb0ELb1ELb0ELb0EE";
 #undef ZRT_STR
 #undef ZRT_STR2
 }
@@ -3670,6 +3846,165 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
 extern "C" int zrt_context_profile(const zrt_context* c, zrt_kernel_profile* out) {
     if (!c || !out) return ZRT_ERR_INVALID_ARG;
     *out = c->prof;
+    return ZRT_OK;
+}
+
+// The feature planes of a frame: see include/zrt.h and DESIGN 5.16.  A render
+// without the path tracer, on the context's stream and one set of buffers: per
+// pass feature_walk_kernel (the instantiation the plan gives a primary launch)
+// over the pass's items, then feature_resolve_kernel.  The item records are
+// staged in pass set 0's first queue (3 float4 per item, the queue's own
+// shape), the work counters are that set's, so a context that renders holds
+// nothing twice; the sums between passes and a host call's planes have buffers
+// of their own.  c->prof is a render's and stays.
+extern "C" int zrt_context_features(zrt_context* c, const zrt_camera* cam, const zrt_render_config* cfg,
+                                    const zrt_feature_outputs* out, zrt_stats* stats) {
+    if (!c || !cam || !cfg || !out) return ZRT_ERR_INVALID_ARG;
+    if (!out->base_color && !out->normal && !out->emissive && !out->depth && !out->transparency && !out->hits)
+        return ZRT_ERR_INVALID_ARG;
+    if (out->on_device > 1u || out->_reserved != 0u) return ZRT_ERR_INVALID_ARG;
+    if (cfg->num_samples == 0 || cfg->num_samples > 65535) return ZRT_ERR_INVALID_ARG;
+    if (cam->w == 0 || cam->h == 0 || (uint64_t)cam->w * cam->h > 0xFFFFFFFFull) return ZRT_ERR_INVALID_ARG;
+    const uint32_t nranks = cfg->num_ranks ? cfg->num_ranks : 1;
+    if (cfg->rank >= nranks || (cfg->tile_size ? cfg->tile_size : 64u) % 8u != 0u) return ZRT_ERR_INVALID_ARG;   // (tile_pixels' rules)
+    const bool counting = (cfg->flags & ZRT_FLAG_COUNT_STATS) != 0;
+    DeviceGuard g(c->device);
+
+    int rc;
+    if ((rc = rank_pixels(c, cam, cfg, nranks)) != ZRT_OK) return rc;
+    const uint32_t P = (uint32_t)c->pix.size();
+    zrt_stats st{};
+    if (P == 0) { if (stats) *stats = st; return ZRT_OK; }
+    const uint32_t spp = cfg->num_samples;
+
+    // samples per pass: as given, else as few passes as kFeatStageBytes of item
+    // records (and the device budget) allow, split evenly; items of a pass < 2^31
+    zrt_context::PassSet& ps = c->set[0];
+    const uint64_t cap = std::max<uint64_t>(1, 0x7FFFFF00ull / P);
+    uint64_t s_pass;
+    if (cfg->samples_per_pass) {
+        s_pass = std::min<uint64_t>(std::min<uint64_t>(cfg->samples_per_pass, spp), cap);
+    } else {
+        size_t held = 16ull * (c->out_cap + c->facc_cap) + 4ull * c->fout_cap + c->bfc_bytes + c->esc_extra;
+        for (const zrt_context::PassSet& s : c->set) held += held_bytes(s);
+        const uint64_t budget = std::min<uint64_t>(kFeatStageBytes, device_budget(c, held));
+        const uint64_t fit = std::min<uint64_t>(cap, std::max<uint64_t>(1, budget / (kFeatItemBytes * P)));
+        const uint64_t np = (spp + fit - 1) / fit;
+        s_pass = (spp + np - 1) / np;
+    }
+    const uint32_t npasses = (uint32_t)((spp + s_pass - 1) / s_pass);
+    const uint64_t T = s_pass * P;
+
+    // the walk a primary launch of this context and these flags takes
+    LaunchPlan pl;
+    if ((rc = resolve_plan(c, cfg->flags, counting, false, false, pl)) != ZRT_OK) return rc;
+    const FeatureFn f_walk = counting  ? (FeatureFn)feature_walk_kernel<true, false, false, true>
+                             : pl.mtx  ? (FeatureFn)feature_walk_kernel<false, false, false, true>
+                             : !pl.packed ? (FeatureFn)feature_walk_kernel<false, false, false, false>
+                             : pl.pbm  ? (FeatureFn)feature_walk_kernel<false, true, true, false>
+                                       : (FeatureFn)feature_walk_kernel<false, true, false, false>;
+
+    const bool host = out->on_device == 0u;
+    if ((rc = grow(&ps.q0, &ps.q0_cap, 3 * T)) != ZRT_OK) return rc;
+    if ((rc = grow(&ps.wfc, &ps.wfc_cap, wfc_words(0))) != ZRT_OK) return rc;
+    if (npasses > 1 && (rc = grow(&c->d_facc, &c->facc_cap, 3ull * P)) != ZRT_OK) return rc;
+    if (host && (rc = grow(&c->d_fout, &c->fout_cap, 12ull * P)) != ZRT_OK) return rc;
+    if ((rc = event_pool(c->ev_trace, 2)) != ZRT_OK) return rc;
+    // capacity guard: every buffer a launch below writes holds what it writes
+    if (shortfall("pixel list", c->d_pix, c->pix_cap, P) || shortfall("item records", ps.q0, ps.q0_cap, 3 * T) ||
+        shortfall("counters", ps.wfc, ps.wfc_cap, 8ull * kCtr) ||
+        (npasses > 1 && shortfall("feature sums", c->d_facc, c->facc_cap, 3ull * P)) ||
+        (host && shortfall("feature planes", c->d_fout, c->fout_cap, 12ull * P)) ||
+        (uint64_t)npasses * s_pass < spp || s_pass * P > T)
+        return ZRT_ERR_INVALID_ARG;
+    uint32_t grid = 0;
+    if ((rc = resident_blocks(c, (const void*)f_walk, kTraceThreads, pl.lds_wf, &grid)) != ZRT_OK) return rc;
+
+    // a host call's planes: base colour, normal, emissive (3 P floats each),
+    // depth, transparency, hits (P each) in d_fout; only those asked for are written
+    FeaturePlanes planes{out->base_color, out->normal, out->emissive, out->depth, out->transparency, out->hits};
+    if (host) {
+        float* const b = c->d_fout;
+        planes = FeaturePlanes{out->base_color ? b : nullptr,
+                               out->normal ? b + 3ull * P : nullptr,
+                               out->emissive ? b + 6ull * P : nullptr,
+                               out->depth ? b + 9ull * P : nullptr,
+                               out->transparency ? b + 10ull * P : nullptr,
+                               out->hits ? reinterpret_cast<uint32_t*>(b + 11ull * P) : nullptr};
+    }
+
+    FeatureParams F;
+    memset(&F, 0, sizeof F);
+    TraceParams& tp = F.w.t;
+    scene_params(c, tp);
+    for (int i = 0; i < 3; ++i) {
+        tp.org[i] = cam->origin[i];
+        tp.llc[i] = cam->lower_left_corner[i];
+        tp.right[i] = cam->right[i];
+        tp.up[i] = cam->up[i];
+    }
+    tp.w = cam->w;
+    tp.pixlist = c->d_pix;
+    tp.P = P;
+    tp.max_bounce = 1;
+    tp.seed = cfg->seed;
+    tp.counter = c->d_counter;
+    tp.stats = c->d_stats;
+    F.w.T = (uint32_t)T;
+    F.w.fetch8 = ps.wfc;
+    F.rec = ps.q0;
+    const float inv_spp = 1.0f / (float)spp;               // stage3.zig:223
+
+    HIP_TRY(hipMemsetAsync(c->d_stats, 0, 512, c->stream));
+    HIP_TRY(hipEventRecord(c->ev_begin, c->stream));
+    uint32_t launches = 0;
+    // the frustum bounds, under the render's rule (zrt_context_render)
+    if (c->d_sat && !counting && pl.packed && !(cfg->flags & ZRT_FLAG_NO_FRUSTUM) &&
+        ((uint64_t)P * spp >= kFrustumMinSamples || (cfg->flags & ZRT_FLAG_FRUSTUM))) {
+        if ((rc = launch_frustum(c, cam, cfg, nranks, tp)) != ZRT_OK) return rc;
+        ++launches;
+    }
+    for (uint32_t pass = 0; pass < npasses; ++pass) {
+        const uint32_t s0 = (uint32_t)(pass * s_pass);
+        const uint32_t S = (uint32_t)std::min<uint64_t>(s_pass, spp - s0);
+        tp.s0 = s0;
+        tp.total = S * P;
+        tp.S = S;
+        tp.sdiv = div_magic(S);
+        HIP_TRY(hipMemsetAsync(ps.wfc, 0, 4ull * 8 * kCtr, c->stream));
+        hipLaunchKernelGGL(f_walk, dim3(grid), dim3(kTraceThreads), pl.lds_wf, c->stream, F);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(feature_resolve_kernel, dim3((P + kResPix - 1) / kResPix), dim3(kBlock), 0, c->stream,
+                           (const float4*)ps.q0, P, S, c->d_facc, pass == 0 ? 1 : 0, pass + 1 == npasses ? 1 : 0,
+                           inv_spp, planes);
+        HIP_TRY(hipGetLastError());
+        launches += 2;
+    }
+    HIP_TRY(hipEventRecord(c->ev_trace[1], c->stream));
+    if (host) {
+        const float* const b = c->d_fout;
+        const struct { void* dst; const float* src; size_t words; } cp[6] = {
+            {out->base_color, b, 3ull * P},        {out->normal, b + 3ull * P, 3ull * P},
+            {out->emissive, b + 6ull * P, 3ull * P}, {out->depth, b + 9ull * P, P},
+            {out->transparency, b + 10ull * P, P},  {out->hits, b + 11ull * P, P}};
+        for (const auto& k : cp)
+            if (k.dst) HIP_TRY(copy_sync(k.dst, k.src, 4ull * k.words, hipMemcpyDeviceToHost, c->stream));
+    }
+    if ((rc = finish_query(c, !host, launches, st)) != ZRT_OK) return rc;
+    if (host) {                                            // the kernels' time, without the copies
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, c->ev_begin, c->ev_trace[1]));
+        st.trace_kernel_ms = ms;
+    }
+    unsigned long long hs[4];
+    HIP_TRY(copy_sync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+    st.segments = st.samples = (uint64_t)P * spp;
+    st.hits = hs[3];
+    if (counting) {
+        st.cells_visited = hs[1];
+        st.triangle_tests = hs[2];
+    }
+    if (stats) *stats = st;
     return ZRT_OK;
 }
 

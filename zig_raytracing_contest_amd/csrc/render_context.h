@@ -192,6 +192,10 @@ struct zrt_context {
     uint32_t* d_hits = nullptr; size_t hits_cap = 0;
     // zrt_context_surface: a host batch's chunk of records (4 float4 per ray)
     float4* d_surf = nullptr; size_t surf_cap = 0;
+    // zrt_context_features: the sums between passes (3 float4 per pixel) and a
+    // host call's planes (12 words per pixel)
+    float4* d_facc = nullptr; size_t facc_cap = 0;
+    float* d_fout = nullptr; size_t fout_cap = 0;
     // zrt_context_radiance: a chunk's rays with normalised directions (6 floats per ray)
     float* d_nrays = nullptr; size_t nrays_cap = 0;
     std::vector<hipEvent_t> ev_pass;   // per pass: its resolve done

@@ -157,6 +157,16 @@ class TransmittanceBatch(C.Structure):
                 ("t_max_all", C.c_float), ("max_crossings", C.c_uint32)]
 
 
+class FeatureOutputs(C.Structure):
+    _fields_ = [("base_color", C.c_void_p), ("normal", C.c_void_p), ("emissive", C.c_void_p), ("depth", C.c_void_p),
+                ("transparency", C.c_void_p), ("hits", C.c_void_p), ("on_device", C.c_uint32),
+                ("_reserved", C.c_uint32)]
+
+
+# zrt_feature_outputs' planes: (name, floats or counts per pixel)
+FEATURE_PLANES = (("base_color", 3), ("normal", 3), ("emissive", 3), ("depth", 1), ("transparency", 1), ("hits", 1))
+
+
 class RadianceBatch(C.Structure):
     _fields_ = [("num_rays", C.c_uint64), ("rays", C.c_void_p), ("radiance", C.c_void_p), ("rgb", C.c_void_p),
                 ("on_device", C.c_uint32), ("flags", C.c_uint32), ("num_samples", C.c_uint32),
@@ -172,6 +182,7 @@ EXPORTS = [
     "zrt_camera_from_matrix", "zrt_probe", "zrt_timed_kernels", "zrt_context_profile", "zrt_context_trace",
     "zrt_group_create", "zrt_group_create_built", "zrt_group_render", "zrt_group_context", "zrt_group_destroy",
     "zrt_context_radiance", "zrt_context_segments", "zrt_context_surface", "zrt_context_transmittance",
+    "zrt_context_features",
 ]
 
 
@@ -213,6 +224,8 @@ def lib():
     L.zrt_context_segments.argtypes = [C.c_void_p, C.POINTER(SegmentBatch), C.POINTER(Stats)]
     L.zrt_context_surface.argtypes = [C.c_void_p, C.POINTER(SurfaceBatch), C.POINTER(Stats)]
     L.zrt_context_transmittance.argtypes = [C.c_void_p, C.POINTER(TransmittanceBatch), C.POINTER(Stats)]
+    L.zrt_context_features.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderConfig),
+                                       C.POINTER(FeatureOutputs), C.POINTER(Stats)]
     if hasattr(L, "zrt_group_create"):     # ABI 2 (an ABI-1 build: tools/ A/B baselines only)
         L.zrt_group_create.argtypes = [C.POINTER(Scene), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
         L.zrt_group_create_built.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -645,6 +658,58 @@ class Context:
         res = {"transmittance": T, "stats": st}
         if crossings:
             res["crossings"] = cr
+        return res
+
+    def features_raw(self, cam: Camera, spp: int, pointers: dict, on_device: bool, seed: int = 0, rank: int = 0,
+                     num_ranks: int = 1, tile_size: int = 0, flags: int = 0, samples_per_pass: int = 0,
+                     reserved: int = 0):
+        """zrt_context_features on raw pointers: `pointers` maps the names of
+        FEATURE_PLANES to addresses (absent or None: not asked for); returns
+        the stats dict."""
+        cfg = RenderConfig()
+        cfg.num_samples, cfg.seed, cfg.device = int(spp), int(seed), -1
+        cfg.rank, cfg.num_ranks, cfg.tile_size = int(rank), int(num_ranks), int(tile_size)
+        cfg.flags, cfg.samples_per_pass = int(flags), int(samples_per_pass)
+        out = FeatureOutputs(*[pointers.get(name) for name, _ in FEATURE_PLANES], 1 if on_device else 0, int(reserved))
+        st = Stats()
+        check(lib().zrt_context_features(self._h, C.byref(cam), C.byref(cfg), C.byref(out), C.byref(st)),
+              "zrt_context_features")
+        return st.as_dict()
+
+    def features(self, cam: Camera, spp: int, seed: int = 0, rank: int = 0, num_ranks: int = 1, tile_size: int = 0,
+                 flags: int = 0, samples_per_pass: int = 0, planes=None, stats: bool = False):
+        """The auxiliary planes of the frame a render(cam, spp, ..., seed)
+        gives (zrt_context_features): per pixel the base colour, interpolated
+        normal (not normalised), emission, distance and transparency of the
+        first hit, averaged over the render's own `spp` jittered camera
+        samples -- a miss adds nothing -- and the number of samples that hit.
+
+        `planes`: the names wanted, of "base_color", "normal", "emissive"
+        ((n, 3) float32), "depth", "transparency" ((n,) float32), "hits"
+        ((n,) uint32); None: all six.  The arrays are packed in
+        tile_pixels(w, h, tile_size or 64, rank, num_ranks) order, n that
+        call's count.  With num_ranks == 1 the result also holds "images":
+        the same planes scattered into (h, w, C) arrays, C = 3 or 1.  "stats" is filled in
+        every call (segments, samples, hits), the cell and test counters with
+        stats=True."""
+        names = [n for n, _ in FEATURE_PLANES] if planes is None else list(planes)
+        width = dict(FEATURE_PLANES)
+        if not names or any(n not in width for n in names):
+            raise ValueError(f"features: planes must name some of {[n for n, _ in FEATURE_PLANES]}")
+        pix = tile_pixels(cam.w, cam.h, tile_size or 64, rank, num_ranks)
+        n = int(pix.size)
+        res = {k: np.zeros((n, 3) if width[k] == 3 else (n,), np.uint32 if k == "hits" else np.float32)
+               for k in names}
+        st = self.features_raw(cam, spp, {k: v.ctypes.data for k, v in res.items()}, False, seed, rank, num_ranks,
+                               tile_size, int(flags) | (FLAG_COUNT_STATS if stats else 0), samples_per_pass)
+        if num_ranks == 1:
+            images = {}
+            for k in names:
+                img = np.zeros((cam.h * cam.w, width[k]), res[k].dtype)
+                img[pix] = res[k].reshape(n, width[k])
+                images[k] = img.reshape(cam.h, cam.w, width[k])
+            res["images"] = images
+        res["stats"] = st
         return res
 
     def radiance_raw(self,num_rays: int, rays_ptr, radiance_ptr, rgb_ptr, on_device: bool, spp: int,
