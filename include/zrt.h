@@ -600,6 +600,76 @@ typedef struct zrt_feature_outputs {
 int zrt_context_features(zrt_context* ctx, const zrt_camera* camera, const zrt_render_config* cfg,
                          const zrt_feature_outputs* out, zrt_stats* stats_or_null);
 
+/* ---- occlusion queries (ABI 2, added) ----------------------------------- */
+
+/* Hemisphere visibility at each ray's first hit: ambient occlusion, baking,
+ * probe lighting.  The sample directions are the ones the path tracer scatters
+ * along (stage3.zig:214, normalize(normal + randomUnitVector)) and come from
+ * the library's own RNG stream, made on the device: nothing per sample crosses
+ * the bus.  Everything is f32, nothing contracted.  For ray i:
+ *   h = the zrt_context_trace record of ray i (stored to hits[i] if asked)
+ *   r = the zrt_surface of (ray i, h)
+ *   a miss: occluded[i] = 0
+ *   a hit, for s = 0 .. num_samples - 1:
+ *     (a, b, c) = the first three floatNorm draws of the stream
+ *                 (seed, (uint32_t)(index_base + i), s), from the stream's
+ *                 start, nothing dropped: Vec3.randomUnitVector,
+ *                 linalg.zig:140-148
+ *     d_s = normalize(r.normal + normalize((a, b, c))), where normalize(x) is
+ *           x * (1.0f / sqrt((x.x*x.x + x.y*x.y) + x.z*x.z)) with the correctly
+ *           rounded reciprocal, the render's own form; r.normal is used as
+ *           interpolated, not normalised, as the reference does
+ *     sample s is traced iff every component of r.position and of d_s is
+ *           finite and d_s is not all zero (a huge normal makes the squared
+ *           length overflow and the direction +0; a NaN or infinite normal
+ *           makes it NaN); a sample that is not traced counts as unoccluded
+ *     a traced sample is occluded iff the closest-mode zrt_context_segments
+ *           result of (r.position, d_s, radius_i) is a hit: the radius follows
+ *           the t_max rules as they stand -- strict at equality, +inf is open
+ *           sky, <= 0, -inf or NaN is never occluded
+ *   occluded[i]   = the number of occluded samples
+ *   visibility[i] = (float)(num_samples - occluded[i]) / (float)num_samples, by
+ *                   the IEEE division: a miss or a fully open point is exactly
+ *                   1.0f (x * (1 / S) is not, for every S)
+ * For a unit normal the plain average of these samples is the cosine-weighted
+ * visibility: normal + a uniform unit vector, normalised, is cosine-distributed
+ * about the normal. */
+typedef struct zrt_occlusion_batch {
+    uint64_t num_rays;
+    const float* rays;        /* num_rays * 6, as zrt_ray_batch */
+    const float* radius;      /* num_rays, or null: radius_all for every ray */
+    float* visibility;        /* num_rays, or null */
+    uint32_t* occluded;       /* num_rays, or null (visibility and occluded not both null) */
+    zrt_hit* hits;            /* num_rays, or null: the first hits, as zrt_context_trace */
+    uint32_t on_device;       /* as zrt_ray_batch; applies to all five pointers */
+    uint32_t flags;           /* exactly zrt_ray_batch's flags */
+    float radius_all;
+    uint32_t num_samples;     /* 1..65535 */
+    uint64_t seed;
+    uint64_t index_base;      /* stream key of ray 0; keys wrap at 2^32, as zrt_radiance_batch */
+} zrt_occlusion_batch;        /* 80 B */
+
+/* Synchronous, one thread at a time per context; alternates freely with
+ * renders and the other queries (every use writes what it reads first) and
+ * leaves zrt_context_profile's record untouched.  The first hits are traced as
+ * zrt_context_trace traces them, in chunks of at most 2^20 rays; a chunk's
+ * (ray, sample) items run in sub-chunks of at most 2^20 items, made on the
+ * device.  Items that cannot be occluded -- those of a ray that missed, samples
+ * that are not traced -- are never walked.  The samples take the lane walk or,
+ * from 2^16 items in the batch or with ZRT_TRACE_PARK, the park kernel in its
+ * bounded closest mode; the answer is the same.
+ * num_rays == 0 returns ZRT_OK and touches nothing.  ZRT_ERR_INVALID_ARG before
+ * any device work, the outputs untouched: a null context or batch, null rays,
+ * visibility and occluded both null, a flag zrt_context_trace would refuse,
+ * on_device > 1, num_samples outside 1..65535.
+ * stats (may be null), in every call: segments = num_rays + the traced samples,
+ * hits = the sum of occluded, samples = 0, render_ms, trace_kernel_ms and
+ * trace_launches as in zrt_context_trace.  With ZRT_FLAG_COUNT_STATS
+ * cells_visited and triangle_tests: the sum of a counting zrt_context_trace
+ * call over the rays and a counting ZRT_SEGMENT_ANY zrt_context_segments call
+ * over exactly the traced samples; samples that are not traced add nothing. */
+int zrt_context_occlusion(zrt_context* ctx, const zrt_occlusion_batch* batch, zrt_stats* stats_or_null);
+
 /* A device group: one context per entry of `devices` (HIP ordinals, repeats
  * allowed), the scene resident on each, rendered by one call -- Scene.render's
  * spawn + join of its workers (stage3.zig:247-256) across GPUs in one

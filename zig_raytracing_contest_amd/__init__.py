@@ -148,6 +148,14 @@ class RenderScene:
         num_samples, seed=seed) gives: see native.Context.features."""
         return self.context.features(camera, num_samples, seed=seed, **kw)
 
+    def occlusion(self, origins, dirs, spp: int, radius=float("inf"), seed: int = 0, index_base: int = 0,
+                  flags: int = 0, stats: bool = False, hits: bool = False):
+        """Hemisphere visibility at each ray's first hit, `spp` samples of the
+        path tracer's own scatter directions within `radius`: see
+        native.Context.occlusion."""
+        return self.context.occlusion(origins, dirs, spp, radius, seed=seed, index_base=index_base, flags=flags,
+                                      stats=stats, hits=hits)
+
     def radiance(self, origins, dirs, spp: int, max_bounce: int, seed: int = 0, index_base: int = 0,
                  flags: int = 0, rgb: bool = False, stats: bool = False):
         """Scene.traceRayRecursive (stage3.zig:188-220) for a batch of rays,

@@ -2736,6 +2736,215 @@ const TransmitFn kTransmitWalk[5] = {(TransmitFn)transmit_walk_kernel<false, tru
                                      (TransmitFn)transmit_walk_kernel<true, false, false, true>};
 
 // ---------------------------------------------------------------------------
+// Occlusion queries (zrt_context_occlusion): per ray the number of
+// S hemisphere samples at its first hit that meet something within a radius.
+// A sample is the direction the path tracer scatters along (stage3.zig:214,
+// shade_segment's `normalize_rn(add(nrm, normalize_rn(...)))`) from the start of
+// the stream (seed, key, s), as a bounded segment from zrt_surface.position.
+// An item is a (ray, sample) pair; a chunk's items run in sub-chunks of at most
+// kOccItems, item j of a sub-chunk being (ray0 + (s0 + j) / S, (s0 + j) % S).
+// occlusion_gen_kernel makes the segments of the items that can be occluded --
+// the ray hit and the sample is traced (include/zrt.h) -- and leaves the others
+// out, so that no walk, counting or timed, ever sees them:
+//   the park path: an item of the fast domain (ray_fast) is appended to the
+//   region of queue slot j (P = m, S = 1) as (o, j) (d, bound), which
+//   wf_park_kernel's bounded closest mode reads as it stands;
+//   every other live item, and every live item of the lane path, is appended to
+//   a list of plain rays, bounds and item indices that the query_walk_kernel
+//   SEG instantiations walk as a segment call's.
+// The appends are wf_append's: a ballot, one returning atomic per wave (and
+// region), ranks by popcount.  The order inside a region or the list is free:
+// occlusion_reduce_kernel adds an occluded item to its ray's count, and integer
+// sums do not depend on the order.  ctr[4] counts the list, ctr[5] every live
+// item; the host reads both back per sub-chunk (the list launches' size, and
+// zrt_stats.segments).
+struct OcclusionParams {
+    const float* rays;        // this chunk: 6 floats per ray (origin, direction as given)
+    const uint32_t* hits;     // this chunk: the zrt_hit of every ray as 4 u32 (4-byte aligned)
+    const float* radius;      // this chunk: a bound per ray, or null: radius_all
+    float radius_all;
+    uint32_t S;               // samples per ray, 1..65535
+    const float4* tri_data;   // TraceParams::tri_data
+    const DevMat* mats;
+    const float* texels;
+    const double* zig;        // the ziggurat's tables (TraceParams::zig)
+    uint64_t seed;
+    uint32_t key0;            // RNG stream key of the chunk's ray 0; keys wrap at 2^32
+    uint32_t n;               // rays of this chunk
+    uint32_t nl;              // occlusion_reduce_kernel, kOccList: the list's entries
+    uint32_t ray0, s0;        // the sub-chunk's first item: sample s0 of ray ray0
+    uint32_t m;               // items of this sub-chunk (<= kOccItems)
+    uint32_t park;            // occlusion_gen_kernel: items of the fast domain go to the queue
+    uint32_t mode;            // occlusion_reduce_kernel: kOccQueue, kOccList or kOccFinish
+    float4* q;                // the queue (m slots) and its region counts
+    uint32_t* n_in8;
+    const float4* hit;        // the park kernel's hit record per queue slot
+    float* irays;             // the list: 6 floats, a bound and an item index per entry
+    float* ibound;
+    uint32_t* iitem;
+    const uint8_t* occ;       // the lane walk's byte per list entry
+    uint32_t* ctr;            // [4]: entries of the list, [5]: live items
+    uint32_t* occluded;       // this chunk: the occluded samples of every ray so far
+    float* visibility;        // this chunk, or null
+    unsigned long long* stats;   // [kOccStat]: the occluded samples of the call
+};
+constexpr uint32_t kOccItems = 1u << 20;       // items per sub-chunk
+constexpr uint32_t kOccGenItems = 4;           // items per thread of occlusion_gen_kernel
+constexpr uint32_t kOccQueue = 0, kOccList = 1, kOccFinish = 2;
+constexpr uint32_t kOccStat = 16;              // (stats[0..3] are the walk kernels', [0..15] the counting render's)
+
+__device__ __forceinline__ bool finite3(v3 a) {
+    return fabsf(a.x) < kInf && fabsf(a.y) < kInf && fabsf(a.z) < kInf;       // (false for a NaN)
+}
+
+// A block takes kOccGenItems * kBlock consecutive items, a wave 64 consecutive
+// ones at a time (one queue region: region bounds are multiples of 64 or m).
+// The normal and the position are surface_kernel's: surface_gather's `nrm`
+// (the texel loads it does not use fall away) and `add(o, scale(d, t + eps))`.
+__global__ __launch_bounds__(kBlock) void occlusion_gen_kernel(const OcclusionParams r) {
+    __shared__ double s_zig[514];
+    for (uint32_t i = threadIdx.x; i < 514; i += blockDim.x) s_zig[i] = r.zig[i];
+    __syncthreads();
+    const double* zx = s_zig;
+    const double* zf = s_zig + 257;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t below = (1ull << lane) - 1ull;
+    const bool aligned = (reinterpret_cast<uintptr_t>(r.hits) & 15u) == 0u;   // (uniform: the context's own records always are)
+    for (uint32_t k = 0; k < kOccGenItems; ++k) {
+        const uint32_t j = (blockIdx.x * kOccGenItems + k) * kBlock + threadIdx.x;
+        if (__ballot(j < r.m) == 0ull) break;                                   // (wave-uniform)
+        bool live = false;
+        v3 o = mk(0, 0, 0), d = mk(0, 0, 0);
+        float bound = 0.0f;
+        if (j < r.m) {
+            const uint32_t L = j + r.s0, ql = L / r.S;
+            const uint32_t ray = r.ray0 + ql, s = L - ql * r.S;
+            uint4 h = make_uint4(0x7F800000u, 0u, 0u, 0xFFFFFFFFu);
+            if (ray < r.n) {                                                    // (always: m items of n rays)
+                if (aligned) {
+                    h = reinterpret_cast<const uint4*>(r.hits)[ray];
+                } else {
+                    const uint32_t* hq = r.hits + 4ull * ray;
+                    h = make_uint4(hq[0], hq[1], hq[2], hq[3]);
+                }
+            }
+            const float t = __uint_as_float(h.x);
+            if (t != kInf) {                                                    // a hit (query_store)
+                v3 ro, rd;
+                ray_load(r.rays, ray, ro, rd);
+                const SurfaceInputs g = surface_gather(r.tri_data, r.mats, r.texels, __uint_as_float(h.y),
+                                                       __uint_as_float(h.z), h.w);
+                o = add(ro, scale(rd, t + kFltEps));
+                Rng rng;
+                rng.s = path_key(r.seed, r.key0 + ray, s);
+                const float nx = (float)rng_norm64(rng, zx, zf);
+                const float ny = (float)rng_norm64(rng, zx, zf);
+                const float nz = (float)rng_norm64(rng, zx, zf);
+                d = normalize_rn(add(g.nrm, normalize_rn(mk(nx, ny, nz))));
+                live = finite3(o) && finite3(d) && (d.x != 0.0f || d.y != 0.0f || d.z != 0.0f);
+                bound = r.radius ? r.radius[ray] : r.radius_all;
+            }
+        }
+        const bool to_q = live && r.park != 0u && ray_fast(d);
+        const bool to_l = live && !to_q;
+        const uint64_t ma = __ballot(live);
+        if (ma != 0ull && lane == (uint32_t)__builtin_ctzll(ma)) atomicAdd(&r.ctr[5], (uint32_t)__popcll(ma));
+        const uint64_t ml = __ballot(to_l);
+        if (ml != 0ull) {
+            const uint32_t lead = (uint32_t)__builtin_ctzll(ml);
+            uint32_t ob = 0;
+            if (lane == lead) ob = atomicAdd(&r.ctr[4], (uint32_t)__popcll(ml));
+            ob = (uint32_t)__builtin_amdgcn_readlane((int)ob, (int)lead);
+            const uint32_t pos = ob + (uint32_t)__popcll(ml & below);
+            if (to_l && pos < r.m) {                                            // (always: at most m live items)
+                float* q = r.irays + 6ull * pos;
+                q[0] = o.x; q[1] = o.y; q[2] = o.z;
+                q[3] = d.x; q[4] = d.y; q[5] = d.z;
+                r.ibound[pos] = bound;
+                r.iitem[pos] = j;
+            }
+        }
+        // the queue: region g of slot j receives at most the items of its own slots
+        uint32_t g = 0;
+        for (uint32_t x = 1; x < 8u; ++x) g += j >= xcd_q0(r.m, x) ? 1u : 0u;
+        uint64_t pend = __ballot(to_q);
+        while (pend) {
+            const uint32_t lead = (uint32_t)__builtin_ctzll(pend);
+            const uint32_t gl = (uint32_t)__builtin_amdgcn_readlane((int)g, (int)lead);
+            const uint64_t mq = __ballot(to_q && g == gl);
+            uint32_t ob = 0;
+            if (lane == lead) ob = atomicAdd(&r.n_in8[gl * kCtr], (uint32_t)__popcll(mq));
+            ob = (uint32_t)__builtin_amdgcn_readlane((int)ob, (int)lead) + xcd_q0(r.m, gl);
+            if (to_q && g == gl) {
+                const uint32_t pos = ob + (uint32_t)__popcll(mq & below);
+                if (pos < xcd_q0(r.m, gl + 1u)) {                               // (always)
+                    r.q[3ull * pos] = make_float4(o.x, o.y, o.z, __uint_as_float(j));
+                    r.q[3ull * pos + 1] = make_float4(d.x, d.y, d.z, bound);
+                }
+            }
+            pend &= ~mq;
+        }
+    }
+}
+
+// kOccQueue: one thread per queue slot of the sub-chunk, the park kernel's hit
+// record of a live slot (a miss: the ref at 0xFFFFFFFF); kOccList: one thread
+// per list entry, the lane walk's byte.  An occluded item adds one to its ray's
+// count -- with S >= 64 a wave's items are a few rays', and each distinct ray of
+// the wave takes one atomic; below that one per item -- and the block's total
+// goes to stats[kOccStat] with one atomic.  kOccFinish, once per chunk after
+// its last sub-chunk: one thread per ray, visibility = (S - occluded) / S by
+// the IEEE division.
+__global__ __launch_bounds__(kBlock) void occlusion_reduce_kernel(const OcclusionParams r) {
+    __shared__ uint32_t s_n;
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (r.mode == kOccFinish) {
+        if (i < r.n && r.visibility) r.visibility[i] = (float)(r.S - r.occluded[i]) / (float)r.S;
+        return;
+    }
+    if (threadIdx.x == 0) s_n = 0u;
+    __syncthreads();
+    bool hit = false;
+    uint32_t j = 0;
+    if (r.mode == kOccQueue) {
+        uint32_t g;
+        if (queue_slot_live(r.m, r.n_in8, i, g)) {
+            j = __float_as_uint(r.q[3ull * i].w);
+            hit = __float_as_uint(r.hit[i].w) != 0xFFFFFFFFu;
+        }
+    } else if (i < r.nl) {
+        j = r.iitem[i];
+        hit = r.occ[i] != (uint8_t)0;
+    }
+    const uint32_t ray = r.ray0 + (j + r.s0) / r.S;
+    hit = hit && ray < r.n;                                         // (always: no store without it)
+    const uint32_t lane = threadIdx.x & 63u;
+    if (r.S >= 64u) {
+        uint64_t pend = __ballot(hit);
+        while (pend) {
+            const uint32_t lead = (uint32_t)__builtin_ctzll(pend);
+            const uint32_t rl = (uint32_t)__builtin_amdgcn_readlane((int)ray, (int)lead);
+            const uint64_t mr = __ballot(hit && ray == rl);
+            if (lane == lead) atomicAdd(&r.occluded[rl], (uint32_t)__popcll(mr));
+            pend &= ~mr;
+        }
+    } else if (hit) {
+        atomicAdd(&r.occluded[ray], 1u);
+    }
+    const unsigned long long s = wave_sum(hit ? 1u : 0u);
+    if (lane == 0 && s != 0ull) atomicAdd(&s_n, (uint32_t)s);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_n != 0u) atomicAdd(&r.stats[kOccStat], (unsigned long long)s_n);
+}
+// total items (rays x samples) from which a call takes the park path unasked
+// for its samples (ZRT_TRACE_PARK forces it, ZRT_FLAG_LANE_WALK forbids it;
+// the first hits follow zrt_context_trace's kTraceParkMin): 2^16, the smallest
+// size tools/occlusion_bench.py measures; there, at 2^18 and at 2^20 the park
+// path won in both rounds on cfg3 and the Cornell box at both radii, at 2^16 by
+// 26% and by 2-14% (profiles/occlusion_bench.json, samples_lane / samples_park)
+constexpr uint64_t kOccParkMin = kSegParkMin;
+
+// ---------------------------------------------------------------------------
 // Radiance queries (zrt_context_radiance): Scene.traceRayRecursive
 // (stage3.zig:188-220) for caller-given rays, S samples each, through the
 // render's own queues, park, shade and resolve kernels.  A chunk
@@ -4409,6 +4618,242 @@ extern "C" int zrt_context_transmittance(zrt_context* c, const zrt_transmittance
     HIP_TRY(copy_sync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
     st.segments = hs[0];
     st.hits = hs[3];
+    if (counting) {
+        st.cells_visited = hs[1];
+        st.triangle_tests = hs[2];
+    }
+    if (stats) *stats = st;
+    return ZRT_OK;
+}
+
+// Hemisphere occlusion at each ray's first hit: see include/zrt.h, the kernels'
+// comment (OcclusionParams) and DESIGN 5.17.  A sibling of query_rays -- the
+// same plan, chunk loop, staging and stats.  Per chunk of at most kTraceChunk
+// rays, all on the context's stream:
+//   the first hits as zrt_context_trace traces them (trace_first_segments, the
+//   park path from kTraceParkMin rays or as ZRT_TRACE_PARK asks), their records
+//   in `hits` or in the context's staging buffer; the counts zeroed;
+//   per sub-chunk of at most kOccItems items:
+//     occlusion_gen_kernel, then the two live counts read back;
+//     park path:  wf_park_kernel (bounded closest mode, unchanged) over the
+//                 queue the gen kernel appended -> occlusion_reduce_kernel
+//                 (kOccQueue); then, if the list holds any item (outside the
+//                 fast domain), the IEEE-division lane kernel over it (kRaysAll)
+//                 -> occlusion_reduce_kernel (kOccList);
+//     lane path:  the segment call's query_walk_kernel launches over the list
+//                 (kRaysFast then kRaysRest; an mt_exact context, a flag or a
+//                 counting call: kRaysAll, a counting call with the any-hit
+//                 exit) -> occlusion_reduce_kernel (kOccList);
+//   occlusion_reduce_kernel (kOccFinish): the visibilities.
+// The park path is pass set 0's queue, hit records and counters; the list and a
+// host batch's rays and radii lie in d_rays, the hit records, counts,
+// visibilities and the list's bytes in d_hits.  Each use writes what it reads
+// first.
+extern "C" int zrt_context_occlusion(zrt_context* c, const zrt_occlusion_batch* b, zrt_stats* stats) {
+    if (!c || !b) return ZRT_ERR_INVALID_ARG;
+    if ((b->flags & ~kTraceFlags) != 0u || b->on_device > 1u || b->num_samples == 0u || b->num_samples > 65535u)
+        return ZRT_ERR_INVALID_ARG;
+    if (b->num_rays == 0) { if (stats) *stats = zrt_stats{}; return ZRT_OK; }
+    if (!b->rays || (!b->visibility && !b->occluded)) return ZRT_ERR_INVALID_ARG;
+    zrt_stats st{};
+    DeviceGuard g(c->device);
+    const bool counting = (b->flags & ZRT_FLAG_COUNT_STATS) != 0;
+    const uint32_t S = b->num_samples;
+    const bool asked = (b->flags & ZRT_TRACE_PARK) != 0;
+    const bool want_first = asked || b->num_rays >= kTraceParkMin;
+    // (ZRT_OCCLUSION_PARK_MIN in the environment overrides the samples' threshold, for tools/occlusion_bench.py)
+    uint64_t park_min = kOccParkMin;
+    if (const char* e = getenv("ZRT_OCCLUSION_PARK_MIN")) park_min = (uint64_t)std::max(0ll, atoll(e));
+    const bool want_items = asked || b->num_rays * S >= park_min;
+    LaunchPlan pl;
+    int rc;
+    if ((rc = resolve_plan(c, b->flags, counting, want_first || want_items, b->num_rays * S >= kSetsMinSamples, pl)) !=
+        ZRT_OK)
+        return rc;
+    const bool park_first = pl.park_ok && want_first, park_items = pl.park_ok && want_items;
+
+    // chunk size, as query_rays; a sub-chunk's buffers are bounded by kOccItems
+    zrt_context::PassSet& ps = c->set[0];
+    const bool dev = b->on_device != 0;
+    const bool own_hits = !dev || !b->hits, own_occ = !dev || !b->occluded, own_vis = !dev && b->visibility;
+    const uint64_t per_ray = (dev ? 0ull : 28ull) + (own_hits ? 16ull : 0ull) + (own_occ ? 4ull : 0ull) +
+                             (own_vis ? 4ull : 0ull) + (park_first ? 64ull : 0ull);
+    const size_t held = 4ull * (c->rays_cap + c->hits_cap) + 16ull * (ps.q0_cap + ps.hit_cap) + c->bfc_bytes + c->esc_extra;
+    const size_t budget = device_budget(c, held);
+    uint64_t chunk = std::min<uint64_t>(kTraceChunk, b->num_rays);
+    if (per_ray) chunk = std::max<uint64_t>(64, std::min<uint64_t>(chunk, budget / per_ray));
+    const uint64_t M = std::min<uint64_t>(kOccItems, chunk * S);          // items of a sub-chunk
+    // words of d_rays: a host batch's rays and radii, then the list
+    const uint64_t off_list = dev ? 0 : 7 * chunk, rays_words = off_list + 8 * M;
+    // words of d_hits: hit records, counts, visibilities, the list's bytes
+    const uint64_t off_occ = own_hits ? 4 * chunk : 0, off_vis = off_occ + (own_occ ? chunk : 0),
+                   off_bytes = off_vis + (own_vis ? chunk : 0), hits_words = off_bytes + (M + 3) / 4;
+    const uint64_t q_slots = std::max<uint64_t>(park_first ? chunk : 0, park_items ? M : 0);
+    const size_t ctr_words = wfc_words(0);
+    if ((rc = grow(&c->d_rays, &c->rays_cap, rays_words)) != ZRT_OK) return rc;
+    if ((rc = grow(&c->d_hits, &c->hits_cap, hits_words)) != ZRT_OK) return rc;
+    if (q_slots) {
+        if ((rc = grow(&ps.q0, &ps.q0_cap, 3 * q_slots)) != ZRT_OK) return rc;
+        if ((rc = grow(&ps.hit, &ps.hit_cap, q_slots)) != ZRT_OK) return rc;
+        if ((rc = grow(&ps.wfc, &ps.wfc_cap, ctr_words)) != ZRT_OK) return rc;
+    }
+    // capacity guard: every buffer a launch below writes holds a chunk / a sub-chunk
+    if (shortfall("rays, list", c->d_rays, c->rays_cap, rays_words) ||
+        shortfall("hits, counts", c->d_hits, c->hits_cap, hits_words) ||
+        (q_slots && (shortfall("q0", ps.q0, ps.q0_cap, 3 * q_slots) || shortfall("hit records", ps.hit, ps.hit_cap, q_slots) ||
+                     shortfall("counters", ps.wfc, ps.wfc_cap, ctr_words))))
+        return ZRT_ERR_INVALID_ARG;
+    if ((rc = event_pool(c->ev_trace, 2)) != ZRT_OK) return rc;
+
+    RayLaunch rl, ri;                              // the first hits: a trace call's; the items: a segment call's
+    if ((rc = ray_launch(c, pl, counting, park_first, rl, -1)) != ZRT_OK) return rc;
+    if ((rc = ray_launch(c, pl, counting, false, ri, counting ? 1 : 0)) != ZRT_OK) return rc;
+    if (park_items && (rc = resident_blocks(c, (const void*)ri.f_park, pl.park_block, pl.lds_park, &ri.grid_park)) != ZRT_OK)
+        return rc;
+
+    QueryParams R;
+    memset(&R, 0, sizeof R);
+    scene_params(c, R.w.t);
+    R.w.t.max_bounce = 1;
+    R.w.t.counter = c->d_counter;
+    R.w.t.stats = c->d_stats;
+    R.ctr = c->d_counter;
+    if (q_slots) {
+        R.w.q_in = ps.q0;
+        R.w.hit = ps.hit;
+        R.w.fetch8 = ps.wfc;
+        R.w.n_in8 = region_counts(ps, 0);
+        park_params(c, pl, R.w);
+        R.q = ps.q0;
+        R.n_in8 = region_counts(ps, 0);
+    }
+    OcclusionParams O;
+    memset(&O, 0, sizeof O);
+    O.radius_all = b->radius_all;
+    O.S = S;
+    O.tri_data = c->d_data;
+    O.mats = c->d_mats;
+    O.texels = c->d_texels;
+    O.zig = c->d_zig;
+    O.seed = b->seed;
+    O.park = park_items ? 1u : 0u;
+    O.q = ps.q0;
+    O.n_in8 = q_slots ? region_counts(ps, 0) : nullptr;
+    O.hit = ps.hit;
+    O.irays = c->d_rays + off_list;
+    O.ibound = O.irays + 6 * M;
+    O.iitem = reinterpret_cast<uint32_t*>(O.ibound + M);
+    O.occ = reinterpret_cast<const uint8_t*>(c->d_hits + off_bytes);
+    O.ctr = c->d_counter;
+    O.stats = c->d_stats;
+    // the items' walks: the list as a segment call's rays, bounds and bytes
+    QueryParams I = R;
+    I.rays = O.irays;
+    I.t_max = O.ibound;
+    I.occ = reinterpret_cast<uint8_t*>(c->d_hits + off_bytes);
+
+    HIP_TRY(hipMemsetAsync(c->d_stats, 0, 512, c->stream));
+    HIP_TRY(hipEventRecord(c->ev_begin, c->stream));
+    uint32_t launches = 0;
+    uint64_t traced = 0;
+    for (uint64_t off = 0; off < b->num_rays; off += chunk) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, b->num_rays - off);
+        const uint32_t nblk = (n + kBlock - 1) / kBlock;
+        if (dev) {
+            R.rays = b->rays + 6 * off;
+            O.radius = b->radius ? b->radius + off : nullptr;
+        } else {
+            HIP_TRY(hipMemcpyAsync(c->d_rays, b->rays + 6 * off, 24ull * n, hipMemcpyHostToDevice, c->stream));
+            R.rays = c->d_rays;
+            if (b->radius) {
+                HIP_TRY(hipMemcpyAsync(c->d_rays + 6 * chunk, b->radius + off, 4ull * n, hipMemcpyHostToDevice, c->stream));
+                O.radius = c->d_rays + 6 * chunk;
+            }
+            HIP_TRY(hipEventRecord(c->ev_trace[0], c->stream));
+        }
+        R.hits = own_hits ? c->d_hits : reinterpret_cast<uint32_t*>(b->hits + off);
+        O.occluded = own_occ ? c->d_hits + off_occ : b->occluded + off;
+        O.visibility = own_vis ? reinterpret_cast<float*>(c->d_hits + off_vis) : dev && b->visibility ? b->visibility + off
+                                                                                                      : nullptr;
+        HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
+        if (park_first) HIP_TRY(hipMemsetAsync(ps.wfc, 0, 4ull * 16 * kCtr, c->stream));
+        if ((rc = trace_first_segments(c, pl, rl, R, n, true, &launches)) != ZRT_OK) return rc;
+        HIP_TRY(hipMemsetAsync(O.occluded, 0, 4ull * n, c->stream));
+        O.rays = R.rays;
+        O.hits = R.hits;
+        O.n = n;
+        O.key0 = (uint32_t)(b->index_base + off);
+        const uint64_t items = (uint64_t)n * S;
+        for (uint64_t i0 = 0; i0 < items; i0 += kOccItems) {
+            const uint32_t m = (uint32_t)std::min<uint64_t>(kOccItems, items - i0);
+            const uint32_t mblk = (m + kBlock - 1) / kBlock;
+            O.ray0 = (uint32_t)(i0 / S);
+            O.s0 = (uint32_t)(i0 % S);
+            O.m = m;
+            HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
+            // the park kernel's work counters and the region counts the gen kernel adds to
+            if (park_items) HIP_TRY(hipMemsetAsync(ps.wfc, 0, 4ull * 16 * kCtr, c->stream));
+            hipLaunchKernelGGL(occlusion_gen_kernel, dim3((mblk + kOccGenItems - 1) / kOccGenItems), dim3(kBlock), 0,
+                               c->stream, O);
+            ++launches;
+            HIP_TRY(hipGetLastError());
+            uint32_t live[2] = {0, 0};                 // the list's entries, every live item
+            HIP_TRY(copy_sync(live, c->d_counter + 4, sizeof live, hipMemcpyDeviceToHost, c->stream));
+            if (live[0] > m || live[1] > m || live[0] > live[1]) return ZRT_ERR_HIP;   // (never: the kernel's own bounds)
+            traced += live[1];
+            if (park_items && live[1] > live[0]) {
+                I.w.t.P = m;
+                I.w.t.S = 1;
+                I.w.t.total = m;
+                I.w.t.sdiv = div_magic(1);
+                hipLaunchKernelGGL(ri.f_park, dim3(ri.grid_park), dim3(pl.park_block), pl.lds_park, c->stream, I.w);
+                O.mode = kOccQueue;
+                hipLaunchKernelGGL(occlusion_reduce_kernel, dim3(mblk), dim3(kBlock), 0, c->stream, O);
+                launches += 2;
+            }
+            if (live[0] != 0u) {
+                const uint32_t lblk = (live[0] + kBlock - 1) / kBlock;
+                I.n = live[0];
+                auto walk = [&](QueryFn f, uint32_t grid, uint32_t which) {
+                    I.which = which;
+                    hipLaunchKernelGGL(f, dim3(std::min(grid, lblk)), dim3(kTraceThreads), pl.lds_wf, c->stream, I);
+                    ++launches;
+                };
+                if (!park_items && ri.f_fast) {
+                    walk(ri.f_fast, ri.grid_fast, kRaysFast);
+                    walk(ri.f_exact, ri.grid_exact, kRaysRest);
+                } else {
+                    walk(ri.f_exact, ri.grid_exact, kRaysAll);
+                }
+                O.mode = kOccList;
+                O.nl = live[0];
+                hipLaunchKernelGGL(occlusion_reduce_kernel, dim3(lblk), dim3(kBlock), 0, c->stream, O);
+                ++launches;
+            }
+            HIP_TRY(hipGetLastError());
+        }
+        if (O.visibility) {
+            O.mode = kOccFinish;
+            hipLaunchKernelGGL(occlusion_reduce_kernel, dim3(nblk), dim3(kBlock), 0, c->stream, O);
+            ++launches;
+            HIP_TRY(hipGetLastError());
+        }
+        if (!dev) {
+            HIP_TRY(hipEventRecord(c->ev_trace[1], c->stream));
+            if (b->hits) HIP_TRY(copy_sync(b->hits + off, c->d_hits, 16ull * n, hipMemcpyDeviceToHost, c->stream));
+            if (b->occluded) HIP_TRY(copy_sync(b->occluded + off, O.occluded, 4ull * n, hipMemcpyDeviceToHost, c->stream));
+            if (b->visibility)
+                HIP_TRY(copy_sync(b->visibility + off, O.visibility, 4ull * n, hipMemcpyDeviceToHost, c->stream));
+            float t = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&t, c->ev_trace[0], c->ev_trace[1]));
+            st.trace_kernel_ms += t;
+        }
+    }
+    if ((rc = finish_query(c, dev, launches, st)) != ZRT_OK) return rc;
+    unsigned long long hs[kOccStat + 1];
+    HIP_TRY(copy_sync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+    st.segments = b->num_rays + traced;
+    st.hits = hs[kOccStat];
     if (counting) {
         st.cells_visited = hs[1];
         st.triangle_tests = hs[2];

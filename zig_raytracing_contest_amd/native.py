@@ -167,6 +167,13 @@ class FeatureOutputs(C.Structure):
 FEATURE_PLANES = (("base_color", 3), ("normal", 3), ("emissive", 3), ("depth", 1), ("transparency", 1), ("hits", 1))
 
 
+class OcclusionBatch(C.Structure):
+    _fields_ = [("num_rays", C.c_uint64), ("rays", C.c_void_p), ("radius", C.c_void_p), ("visibility", C.c_void_p),
+                ("occluded", C.c_void_p), ("hits", C.c_void_p), ("on_device", C.c_uint32), ("flags", C.c_uint32),
+                ("radius_all", C.c_float), ("num_samples", C.c_uint32), ("seed", C.c_uint64),
+                ("index_base", C.c_uint64)]
+
+
 class RadianceBatch(C.Structure):
     _fields_ = [("num_rays", C.c_uint64), ("rays", C.c_void_p), ("radiance", C.c_void_p), ("rgb", C.c_void_p),
                 ("on_device", C.c_uint32), ("flags", C.c_uint32), ("num_samples", C.c_uint32),
@@ -182,7 +189,7 @@ EXPORTS = [
     "zrt_camera_from_matrix", "zrt_probe", "zrt_timed_kernels", "zrt_context_profile", "zrt_context_trace",
     "zrt_group_create", "zrt_group_create_built", "zrt_group_render", "zrt_group_context", "zrt_group_destroy",
     "zrt_context_radiance", "zrt_context_segments", "zrt_context_surface", "zrt_context_transmittance",
-    "zrt_context_features",
+    "zrt_context_features", "zrt_context_occlusion",
 ]
 
 
@@ -226,6 +233,7 @@ def lib():
     L.zrt_context_transmittance.argtypes = [C.c_void_p, C.POINTER(TransmittanceBatch), C.POINTER(Stats)]
     L.zrt_context_features.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderConfig),
                                        C.POINTER(FeatureOutputs), C.POINTER(Stats)]
+    L.zrt_context_occlusion.argtypes = [C.c_void_p, C.POINTER(OcclusionBatch), C.POINTER(Stats)]
     if hasattr(L, "zrt_group_create"):     # ABI 2 (an ABI-1 build: tools/ A/B baselines only)
         L.zrt_group_create.argtypes = [C.POINTER(Scene), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
         L.zrt_group_create_built.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -710,6 +718,76 @@ class Context:
                 images[k] = img.reshape(cam.h, cam.w, width[k])
             res["images"] = images
         res["stats"] = st
+        return res
+
+    def occlusion_raw(self, num_rays: int, rays_ptr, radius_ptr, visibility_ptr, occluded_ptr, hits_ptr,
+                      on_device: bool, spp: int, radius_all: float = float("inf"), seed: int = 0, index_base: int = 0,
+                      flags: int = 0):
+        """zrt_context_occlusion on raw pointers; returns the stats dict."""
+        batch = OcclusionBatch(int(num_rays), rays_ptr, radius_ptr, visibility_ptr, occluded_ptr, hits_ptr,
+                               1 if on_device else 0, int(flags), float(radius_all), int(spp),
+                               int(seed) & 0xFFFFFFFFFFFFFFFF, int(index_base) & 0xFFFFFFFFFFFFFFFF)
+        st = Stats()
+        check(lib().zrt_context_occlusion(self._h, C.byref(batch), C.byref(st)), "zrt_context_occlusion")
+        return st.as_dict()
+
+    def occlusion(self, origins, dirs, spp: int, radius=float("inf"), seed: int = 0, index_base: int = 0,
+                  flags: int = 0, stats: bool = False, hits: bool = False):
+        """Hemisphere visibility at each ray's first hit (zrt_context_occlusion):
+        `spp` directions normalize(normal + random unit vector) per hit, the
+        path tracer's own scatter directions from the stream (seed, index_base +
+        ray, sample), each traced as a segment of length `radius` -- a scalar
+        for every ray or n values; +inf: open sky -- from the surface.  A miss
+        is fully visible.
+
+        Two (n, 3) float32 numpy arrays give {"visibility": (n,) float32 =
+        (spp - occluded) / spp, "occluded": (n,) uint32, "stats"}, and with
+        hits=True trace()'s "t", "u", "v", "triangle" of the first hits.
+        "stats" holds "segments" (rays + traced samples) and "hits" (the sum of
+        "occluded") in every call, the cell and test counters with stats=True.
+
+        Two (n, 3) float32 CUDA tensors (torch-ROCm) on the context's device
+        (and `radius` a float or an (n,) float32 tensor there) are traced in
+        place, after a sync of torch's current stream: "visibility" an (n,)
+        float32 and "occluded" an (n,) int32 CUDA tensor, with hits=True "hits"
+        as in trace()."""
+        flags = int(flags) | (FLAG_COUNT_STATS if stats else 0)
+        torch, n, rays = self._rays("occlusion", origins, dirs)
+        if torch:
+            rad, rad_all = None, float("inf")
+            if torch.is_tensor(radius) and radius.dim() > 0:
+                if radius.device != origins.device or radius.dtype != torch.float32 or radius.shape != (n,):
+                    raise ValueError("occlusion: radius must be a float or an (n,) float32 tensor on the rays' device")
+                rad = radius.contiguous()
+            else:
+                rad_all = float(radius)
+            vis = torch.empty((n,), dtype=torch.float32, device=origins.device)
+            occ = torch.empty((n,), dtype=torch.int32, device=origins.device)
+            rec = torch.empty((n, 4), dtype=torch.float32, device=origins.device) if hits else None
+            torch.cuda.current_stream(origins.device).synchronize()
+            st = self.occlusion_raw(n, rays.data_ptr() if n else None, rad.data_ptr() if rad is not None and n else None,
+                                    vis.data_ptr() if n else None, occ.data_ptr() if n else None,
+                                    rec.data_ptr() if hits and n else None, True, spp, rad_all, seed, index_base, flags)
+            res = {"visibility": vis, "occluded": occ, "stats": st}
+            if hits:
+                res["hits"] = rec
+            return res
+        rad, rad_all = None, float("inf")
+        if np.ndim(radius) == 0:
+            rad_all = float(radius)
+        else:
+            rad = np.ascontiguousarray(radius, np.float32)
+            if rad.shape != (n,):
+                raise ValueError("occlusion: radius must be a scalar or n values")
+        vis = np.empty(n, np.float32)
+        occ = np.empty(n, np.uint32)
+        rec = np.empty(n, HIT_DTYPE) if hits else None
+        st = self.occlusion_raw(n, rays.ctypes.data if n else None, rad.ctypes.data if rad is not None and n else None,
+                                vis.ctypes.data if n else None, occ.ctypes.data if n else None,
+                                rec.ctypes.data if hits and n else None, False, spp, rad_all, seed, index_base, flags)
+        res = {"visibility": vis, "occluded": occ, "stats": st}
+        if hits:
+            res.update(t=rec["t"].copy(), u=rec["u"].copy(), v=rec["v"].copy(), triangle=rec["triangle"].copy())
         return res
 
     def radiance_raw(self,num_rays: int, rays_ptr, radiance_ptr, rgb_ptr, on_device: bool, spp: int,
