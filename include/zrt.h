@@ -670,6 +670,108 @@ typedef struct zrt_occlusion_batch {
  * over exactly the traced samples; samples that are not traced add nothing. */
 int zrt_context_occlusion(zrt_context* ctx, const zrt_occlusion_batch* batch, zrt_stats* stats_or_null);
 
+/* ---- direct-light queries (ABI 2, added) -------------------------------- */
+
+/* The light of punctual lights at each ray's first hit, shadowed through
+ * transparent hits as the path tracer sees them: what zrt_context_surface and
+ * zrt_context_transmittance were added for, assembled.  The reference scene has
+ * no punctual lights -- only emissive surfaces and the sky -- so the lights are
+ * the caller's, a small host array per call.  The shadow rays are made, culled,
+ * traced and summed on the device: nothing per (ray, light) item crosses the
+ * bus, and the sum's order is fixed.
+ * Everything is f32, nothing is contracted (no FMA), operations run left to
+ * right as written.  dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z; length(a) is
+ * the IEEE sqrt of dot(a, a); normalize_rn(a) = a * (1.0f / length(a)) with the
+ * correctly rounded reciprocal, the render's own form.  For ray i:
+ *   h = the zrt_context_trace record of ray i (stored to hits[i] if asked)
+ *   r = the zrt_surface of (ray i, h)
+ *   a miss: irradiance[i] and radiance[i] are three +0
+ *   a hit: N = normalize_rn(r.normal).  The ray is shaded iff every component
+ *     of r.position and of N is finite (a zero, NaN or infinite interpolated
+ *     normal makes N NaN: not shaded); a ray that is not shaded has no traced
+ *     item and E = +0.  A huge normal, whose squared length overflows, makes
+ *     N = (+0, +0, +0): c = 0 for every light, so it has no traced item and
+ *     E = +0 just the same
+ *   E = (+0, +0, +0); for l = 0 .. num_lights - 1, in this order:
+ *     POINT, SPOT:  v = light.position - r.position;  d2 = dot(v, v)
+ *                   w = normalize_rn(v);  b = length(v)
+ *     DIRECTIONAL:  w = normalize_rn((-dir.x, -dir.y, -dir.z));  b = +inf
+ *     c = dot(N, w).  The item is traced iff c > 0, and for a SPOT also iff
+ *         k > 0 (below).  That one test skips a light behind the surface, a
+ *         light at the hit point (w is NaN) and a light at overflow distance
+ *         (w is 0)
+ *     f = c / d2 by the IEEE division (POINT, SPOT);  f = c (DIRECTIONAL)
+ *     SPOT:  s = -dot(normalize_rn(light.direction), w)
+ *            k = fminf(fmaxf(s * angle_scale + angle_offset, 0.0f), 1.0f) --
+ *                two roundings; a NaN becomes 0
+ *            f = f * (k * k)
+ *     T = the zrt_context_transmittance result of (r.position, w, b,
+ *         max_crossings), its rules as they stand: strict at t == b, and the
+ *         cap is part of the contract.  With ZRT_DIRECT_UNSHADOWED T = 1 and no
+ *         segment is traced
+ *     g = f * T;  E.k = E.k + light.color[k] * g for k = 0, 1, 2
+ *     an item that is not traced adds nothing
+ *   irradiance[i] = E
+ *   radiance[i].k = r.emissive[k] + (r.base_color[k] * E.k) * 0x1.45f306p-2f --
+ *     1 / pi rounded to f32, bits 0x3EA2F983: the Lambertian surface the path
+ *     tracer's diffuse branch stands for.  A transparent first hit is shaded
+ *     like any other, as in zrt_context_surface.  For a hit that is not shaded
+ *     radiance is r.emissive.  A NaN or inf the arithmetic produces is stored
+ *     as it is.
+ * Non-finite light fields are taken as given; the arithmetic above decides. */
+enum { ZRT_LIGHT_POINT = 0, ZRT_LIGHT_DIRECTIONAL = 1, ZRT_LIGHT_SPOT = 2 };
+typedef struct zrt_light {
+    uint32_t type;
+    float position[3];        /* POINT, SPOT */
+    float direction[3];       /* DIRECTIONAL, SPOT: the way the light travels; any length */
+    float color[3];           /* POINT / SPOT: intensity (W/sr, linear RGB); DIRECTIONAL: irradiance on a
+                                 facing surface */
+    float angle_scale;        /* SPOT: 1 / max(0.001, cos_inner - cos_outer) ... */
+    float angle_offset;       /* ... and -cos_outer * angle_scale (the caller computes them) */
+} zrt_light;                  /* 48 B */
+
+#define ZRT_DIRECT_UNSHADOWED 0x80000u   /* zrt_direct_batch.flags only: T = 1 for every traced item, no
+                                            shadow segment */
+
+typedef struct zrt_direct_batch {
+    uint64_t num_rays;
+    const float* rays;        /* num_rays * 6, as zrt_ray_batch */
+    const zrt_light* lights;  /* num_lights, ALWAYS a host pointer (copied per call) */
+    float* irradiance;        /* num_rays * 3, or null */
+    float* radiance;          /* num_rays * 3, or null (irradiance and radiance not both null) */
+    zrt_hit* hits;            /* num_rays, or null: the first hits, as zrt_context_trace */
+    uint32_t on_device;       /* as zrt_ray_batch; applies to rays, irradiance, radiance, hits */
+    uint32_t flags;           /* zrt_ray_batch's flags | ZRT_DIRECT_UNSHADOWED */
+    uint32_t num_lights;      /* 1..65535 */
+    uint32_t max_crossings;   /* 1..256, as zrt_transmittance_batch */
+} zrt_direct_batch;           /* 64 B */
+
+/* Synchronous, one thread at a time per context; alternates freely with
+ * renders and the other queries (every use writes what it reads first) and
+ * leaves zrt_context_profile's record untouched.  The first hits are traced as
+ * zrt_context_trace traces them, in chunks of at most 2^20 rays, under the
+ * trace call's own thresholds; ZRT_TRACE_PARK and the escape, release and cull
+ * flags govern the first hits only.  A chunk's (ray, light) items run in
+ * sub-chunks of at most 2^20 items, made on the device; a ray's lights may
+ * straddle a cut, and its sum still adds in light order.  Items that are not
+ * traced are never walked.  The chains take the transmittance call's lane walk
+ * -- a ray's whole chain in one launch -- at every size: the park-and-step
+ * rounds measured no faster for chains and are not built for
+ * the items.
+ * num_rays == 0 returns ZRT_OK and touches nothing.  ZRT_ERR_INVALID_ARG before
+ * any device work, the outputs untouched: a null context or batch, null rays or
+ * lights, irradiance and radiance both null, num_lights 0 or above 65535, a
+ * light type above 2, max_crossings 0 or above 256, on_device > 1, a flag
+ * zrt_context_trace would refuse.
+ * stats (may be null), in every call: segments = num_rays + the Scene.traceRay
+ * calls of all chains, samples = the traced items, hits = the sum of the
+ * chains' crossings, render_ms, trace_kernel_ms and trace_launches as in
+ * zrt_context_trace.  With ZRT_FLAG_COUNT_STATS cells_visited and
+ * triangle_tests: the sum of a counting zrt_context_trace call over the rays
+ * and a counting zrt_context_transmittance call over exactly the traced items;
+ * items that are not traced add nothing. */
+int zrt_context_direct(zrt_context* ctx, const zrt_direct_batch* batch, zrt_stats* stats_or_null);
+
 /* A device group: one context per entry of `devices` (HIP ordinals, repeats
  * allowed), the scene resident on each, rendered by one call -- Scene.render's
  * spawn + join of its workers (stage3.zig:247-256) across GPUs in one

@@ -156,6 +156,14 @@ class RenderScene:
         return self.context.occlusion(origins, dirs, spp, radius, seed=seed, index_base=index_base, flags=flags,
                                       stats=stats, hits=hits)
 
+    def direct(self, origins, dirs, lights, max_crossings: int = 16, flags: int = 0, unshadowed: bool = False,
+               irradiance: bool = True, radiance: bool = False, hits: bool = False, stats: bool = False):
+        """Direct light of punctual lights (native.Light) at each ray's first
+        hit, shadowed through transparent hits: see native.Context.direct."""
+        return self.context.direct(origins, dirs, lights, max_crossings=max_crossings, flags=flags,
+                                   unshadowed=unshadowed, irradiance=irradiance, radiance=radiance, hits=hits,
+                                   stats=stats)
+
     def radiance(self, origins, dirs, spp: int, max_bounce: int, seed: int = 0, index_base: int = 0,
                  flags: int = 0, rgb: bool = False, stats: bool = False):
         """Scene.traceRayRecursive (stage3.zig:188-220) for a batch of rays,

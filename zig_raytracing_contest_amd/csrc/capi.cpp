@@ -45,6 +45,18 @@ extern "C" int zrt_abi_version(void) { return ZRT_ABI_VERSION; }
 
 namespace zrt {
 
+bool direct_batch_ok(const zrt_direct_batch* b, uint32_t trace_flags) {
+    if (!b) return false;
+    if ((b->flags & ~(trace_flags | ZRT_DIRECT_UNSHADOWED)) != 0u || b->on_device > 1u || b->num_lights == 0u ||
+        b->num_lights > 65535u || b->max_crossings == 0u || b->max_crossings > 256u)
+        return false;
+    if (b->num_rays == 0) return true;
+    if (!b->rays || !b->lights || (!b->irradiance && !b->radiance)) return false;
+    for (uint32_t l = 0; l < b->num_lights; ++l)
+        if (b->lights[l].type > (uint32_t)ZRT_LIGHT_SPOT) return false;
+    return true;
+}
+
 void zig_tables(double zx[257], double zf[257]) {
     static std::once_flag once;
     static double X[257], F[257];

@@ -2244,6 +2244,9 @@ constexpr uint32_t kTraceFlags = ZRT_FLAG_COUNT_STATS | ZRT_FLAG_LANE_WALK | ZRT
                                  ZRT_FLAG_NO_ESCAPE | ZRT_FLAG_RELEASE | ZRT_FLAG_NO_RELEASE | ZRT_FLAG_BFCULL |
                                  ZRT_FLAG_NO_BFCULL | ZRT_FLAG_HOP | ZRT_FLAG_NO_HOP | ZRT_TRACE_PARK;
 static_assert((ZRT_SEGMENT_ANY & (kTraceFlags | ZRT_RADIANCE_PER_SAMPLE | 0xFFFFu)) == 0u, "a bit of its own");
+static_assert((ZRT_DIRECT_UNSHADOWED & (kTraceFlags | ZRT_RADIANCE_PER_SAMPLE | ZRT_SEGMENT_ANY | 0xFFFFu)) == 0u,
+              "a bit of its own");
+static_assert(sizeof(zrt_light) == 48 && sizeof(zrt_direct_batch) == 64, "include/zrt.h");
 
 // batch size from which a segment call takes the park path unasked: 2^16, the
 // smallest size tools/segment_bench.py measures; there and at 2^20 and 2^22 the
@@ -2943,6 +2946,186 @@ __global__ __launch_bounds__(kBlock) void occlusion_reduce_kernel(const Occlusio
 // path won in both rounds on cfg3 and the Cornell box at both radii, at 2^16 by
 // 26% and by 2-14% (profiles/occlusion_bench.json, samples_lane / samples_park)
 constexpr uint64_t kOccParkMin = kSegParkMin;
+
+// ---------------------------------------------------------------------------
+// Direct-light queries (zrt_context_direct): per ray the
+// irradiance of L punctual lights at its first hit, each light shadowed by the
+// transmittance chain of the segment towards it, and the Lambertian radiance
+// that irradiance gives.  An item is a (ray, light) pair; a chunk's items run
+// in sub-chunks of at most kDirItems, item j of a sub-chunk being
+// (ray0 + (l0 + j) / L, (l0 + j) % L).  direct_gen_kernel computes the item's
+// direction w, bound b and factor f (include/zrt.h) and appends the traced
+// items -- the ray hit and is shaded, the light is in front of the surface and,
+// a spot, inside its cone -- to a list of plain rays and bounds that the
+// transmit_walk_kernel instantiations walk as a transmittance call's, T of a
+// list entry landing at its slot; the others are never walked and never
+// counted.  The append is wf_append's: a ballot, one returning atomic per wave,
+// ranks by popcount.  The order inside the list is free: every item keeps its
+// factor and its slot (0xFFFFFFFF: not traced) in two dense rows, and
+// direct_reduce_kernel, one thread per ray, walks the ray's items of the
+// sub-chunk in light order and folds colour * (f * T) into the ray's running E,
+// which waits in the chunk's irradiance row between sub-chunks: a ray whose
+// lights straddle a cut is summed in the same order as any other.  ctr[4]
+// counts the list; the host reads it back per sub-chunk (the walk launches'
+// size, and zrt_stats.samples).
+struct DirectParams {
+    const float* rays;        // this chunk: 6 floats per ray (origin, direction as given)
+    const uint32_t* hits;     // this chunk: the zrt_hit of every ray as 4 u32 (4-byte aligned)
+    const float4* tri_data;   // TraceParams::tri_data
+    const DevMat* mats;
+    const float* texels;
+    const zrt_light* lights;  // L lights, on the device
+    uint32_t L;               // lights per ray, 1..65535
+    uint32_t n;               // rays of this chunk
+    uint32_t ray0, l0;        // the sub-chunk's first item: light l0 of ray ray0
+    uint32_t m;               // items of this sub-chunk (<= kDirItems)
+    uint32_t unshadowed;      // ZRT_DIRECT_UNSHADOWED: no list is written, T = 1
+    uint32_t fold;            // direct_reduce_kernel: the walk launches ran; move their counts
+    float* irays;             // the list: 6 floats and a bound per entry
+    float* ibound;
+    const float* T;           // the walk's transmittance per list entry
+    float* f;                 // the factor of every item of the sub-chunk
+    uint32_t* slot;           //   and its list entry, or 0xFFFFFFFF
+    uint32_t* ctr;            // [4]: entries of the list
+    float* E;                 // this chunk: the irradiance of every ray, 3 floats
+    float* radiance;          // this chunk: 3 floats per ray, or null
+    unsigned long long* stats;   // [kDirStat]: the chains' segments, [kDirStat + 1]: their crossings
+};
+constexpr uint32_t kDirItems = 1u << 20;       // items per sub-chunk
+constexpr uint32_t kDirGenItems = 4;           // items per thread of direct_gen_kernel
+constexpr uint32_t kDirStat = 16;              // (stats[0..3] are the walk kernels', [0..15] the counting render's)
+constexpr float kInvPi = 0x1.45f306p-2f;       // 1 / pi rounded to f32, 0x3EA2F983
+
+__device__ __forceinline__ uint4 hit_load(const uint32_t* hits, bool aligned, uint32_t ray) {
+    if (aligned) return reinterpret_cast<const uint4*>(hits)[ray];
+    const uint32_t* hq = hits + 4ull * ray;
+    return make_uint4(hq[0], hq[1], hq[2], hq[3]);
+}
+
+// A block takes kDirGenItems * kBlock consecutive items, a wave 64 consecutive
+// ones at a time.  The normal and the position are surface_kernel's:
+// surface_gather's `nrm` (the texel loads it does not use fall away) and
+// `add(o, scale(d, t + eps))`.  The divisions and the square root are IEEE's.
+__global__ __launch_bounds__(kBlock) void direct_gen_kernel(const DirectParams r) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t below = (1ull << lane) - 1ull;
+    const bool aligned = (reinterpret_cast<uintptr_t>(r.hits) & 15u) == 0u;   // (uniform: the context's own records always are)
+    for (uint32_t k = 0; k < kDirGenItems; ++k) {
+        const uint32_t j = (blockIdx.x * kDirGenItems + k) * kBlock + threadIdx.x;
+        if (__ballot(j < r.m) == 0ull) break;                                   // (wave-uniform)
+        bool live = false;
+        v3 o = mk(0, 0, 0), w = mk(0, 0, 0);
+        float bound = 0.0f, f = 0.0f;
+        if (j < r.m) {
+            const uint32_t I = j + r.l0, qr = I / r.L;
+            const uint32_t ray = r.ray0 + qr, l = I - qr * r.L;
+            uint4 h = make_uint4(0x7F800000u, 0u, 0u, 0xFFFFFFFFu);
+            if (ray < r.n) h = hit_load(r.hits, aligned, ray);                  // (always: m items of n rays)
+            const float t = __uint_as_float(h.x);
+            if (t != kInf) {                                                    // a hit (query_store)
+                v3 ro, rd;
+                ray_load(r.rays, ray, ro, rd);
+                const SurfaceInputs g = surface_gather(r.tri_data, r.mats, r.texels, __uint_as_float(h.y),
+                                                       __uint_as_float(h.z), h.w);
+                o = add(ro, scale(rd, t + kFltEps));
+                const v3 N = normalize_rn(g.nrm);
+                if (finite3(o) && finite3(N)) {                                 // shaded
+                    const zrt_light& lt = r.lights[l];
+                    float d2 = 1.0f;
+                    if (lt.type == ZRT_LIGHT_DIRECTIONAL) {
+                        w = normalize_rn(mk(-lt.direction[0], -lt.direction[1], -lt.direction[2]));
+                        bound = kInf;
+                    } else {
+                        const v3 v = sub(ld3(lt.position), o);
+                        d2 = dot(v, v);
+                        w = normalize_rn(v);
+                        bound = length(v);
+                    }
+                    const float c = dot(N, w);
+                    live = c > 0.0f;                                            // (false for a NaN)
+                    f = lt.type == ZRT_LIGHT_DIRECTIONAL ? c : c / d2;
+                    if (lt.type == ZRT_LIGHT_SPOT) {
+                        const float s = -dot(normalize_rn(ld3(lt.direction)), w);
+                        const float kk = fminf(fmaxf(s * lt.angle_scale + lt.angle_offset, 0.0f), 1.0f);
+                        f = f * (kk * kk);
+                        live = live && kk > 0.0f;
+                    }
+                }
+            }
+        }
+        const uint64_t ml = __ballot(live);
+        uint32_t pos = 0xFFFFFFFFu;
+        if (ml != 0ull) {
+            const uint32_t lead = (uint32_t)__builtin_ctzll(ml);
+            uint32_t ob = 0;
+            if (lane == lead) ob = atomicAdd(&r.ctr[4], (uint32_t)__popcll(ml));
+            ob = (uint32_t)__builtin_amdgcn_readlane((int)ob, (int)lead);
+            if (live) pos = ob + (uint32_t)__popcll(ml & below);
+            if (pos >= r.m) pos = 0xFFFFFFFFu;                                  // (never: at most m live items)
+            if (pos != 0xFFFFFFFFu && r.unshadowed == 0u) {
+                float* q = r.irays + 6ull * pos;
+                q[0] = o.x; q[1] = o.y; q[2] = o.z;
+                q[3] = w.x; q[4] = w.y; q[5] = w.z;
+                r.ibound[pos] = bound;
+            }
+        }
+        if (j < r.m) {
+            r.f[j] = pos != 0xFFFFFFFFu ? f : 0.0f;
+            r.slot[j] = pos;
+        }
+    }
+}
+
+// One thread per ray of the sub-chunk, ray0 + i: its items [a, e) of the
+// sub-chunk in light order.  E starts at +0 with the ray's light 0 and is read
+// back from the row otherwise; an item that is not traced adds nothing.  With
+// the ray's last light, and `radiance` asked, the surface is gathered once more
+// for its base colour and emission.  Thread 0 moves the walk launches' segment
+// and crossing counts (stats[0], stats[3], which the first hits' kernels also
+// add to and the host cleared after them) to the call's own two.
+__global__ __launch_bounds__(kBlock) void direct_reduce_kernel(const DirectParams r) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i == 0u && r.fold != 0u) {
+        r.stats[kDirStat] += r.stats[0];
+        r.stats[kDirStat + 1] += r.stats[3];
+        r.stats[0] = 0ull;
+        r.stats[3] = 0ull;
+    }
+    const uint32_t end = r.l0 + r.m;                                            // (< 2^21: l0 < L < 2^16)
+    const uint32_t ray = r.ray0 + i;
+    if ((uint64_t)i * r.L >= end || ray >= r.n) return;                         // (ray < n: always)
+    const uint32_t first = i * r.L;
+    const uint32_t a = max(first, r.l0), e = min(first + r.L, end);
+    const bool aligned = (reinterpret_cast<uintptr_t>(r.hits) & 15u) == 0u;
+    const uint4 h = hit_load(r.hits, aligned, ray);
+    const float t = __uint_as_float(h.x);
+    float* const Ep = r.E + 3ull * ray;
+    v3 E = mk(0.0f, 0.0f, 0.0f);
+    if (t != kInf) {
+        if (a != first) E = ld3(Ep);
+        for (uint32_t x = a; x < e; ++x) {
+            const uint32_t j = x - r.l0, s = r.slot[j];
+            if (s == 0xFFFFFFFFu) continue;
+            const float T = r.unshadowed != 0u ? 1.0f : r.T[s];
+            const float g = r.f[j] * T;
+            const zrt_light& lt = r.lights[x - first];
+            E = add(E, scale(ld3(lt.color), g));
+        }
+    }
+    Ep[0] = E.x; Ep[1] = E.y; Ep[2] = E.z;
+    if (e != first + r.L || !r.radiance) return;
+    v3 out = mk(0.0f, 0.0f, 0.0f);
+    if (t != kInf) {
+        v3 ro, rd;
+        ray_load(r.rays, ray, ro, rd);
+        const SurfaceInputs g = surface_gather(r.tri_data, r.mats, r.texels, __uint_as_float(h.y), __uint_as_float(h.z),
+                                               h.w);
+        const bool shaded = finite3(add(ro, scale(rd, t + kFltEps))) && finite3(normalize_rn(g.nrm));
+        out = shaded ? add(g.emissive, scale(mul(g.albedo, E), kInvPi)) : g.emissive;
+    }
+    float* const Rp = r.radiance + 3ull * ray;
+    Rp[0] = out.x; Rp[1] = out.y; Rp[2] = out.z;
+}
 
 // ---------------------------------------------------------------------------
 // Radiance queries (zrt_context_radiance): Scene.traceRayRecursive
@@ -4854,6 +5037,219 @@ extern "C" int zrt_context_occlusion(zrt_context* c, const zrt_occlusion_batch* 
     HIP_TRY(copy_sync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
     st.segments = b->num_rays + traced;
     st.hits = hs[kOccStat];
+    if (counting) {
+        st.cells_visited = hs[1];
+        st.triangle_tests = hs[2];
+    }
+    if (stats) *stats = st;
+    return ZRT_OK;
+}
+
+// Direct light of punctual lights at each ray's first hit: see include/zrt.h,
+// the kernels' comment (DirectParams) and DESIGN 5.18.  A sibling of
+// zrt_context_occlusion -- the same plan, chunk loop, staging and stats.  Per
+// chunk of at most kTraceChunk rays, all on the context's stream:
+//   the first hits as zrt_context_trace traces them (trace_first_segments, the
+//   park path from kTraceParkMin rays or as ZRT_TRACE_PARK asks), their records
+//   in `hits` or in the context's staging buffer; the walk counters those
+//   launches added to (stats[0], stats[3]) cleared;
+//   per sub-chunk of at most kDirItems items:
+//     direct_gen_kernel, then the list's size read back;
+//     the transmittance call's lane launches over the list (kRaysFast then
+//     kRaysRest; an mt_exact context, a flag or a counting call: kRaysAll),
+//     unless the list is empty or ZRT_DIRECT_UNSHADOWED is set;
+//     direct_reduce_kernel.
+// The chains never take the park-and-step rounds (DESIGN 5.15 measured the lane
+// chain as fast or faster).  The lights, a host batch's rays, the list and the
+// item rows lie in d_rays; the hit records and a host batch's (or an unasked)
+// irradiance and radiance in d_hits.  Each use writes what it reads first.
+extern "C" int zrt_context_direct(zrt_context* c, const zrt_direct_batch* b, zrt_stats* stats) {
+    if (!c || !direct_batch_ok(b, kTraceFlags)) return ZRT_ERR_INVALID_ARG;
+    if (b->num_rays == 0) { if (stats) *stats = zrt_stats{}; return ZRT_OK; }
+    zrt_stats st{};
+    DeviceGuard g(c->device);
+    const bool counting = (b->flags & ZRT_FLAG_COUNT_STATS) != 0;
+    const bool unshadowed = (b->flags & ZRT_DIRECT_UNSHADOWED) != 0;
+    const uint32_t flags = b->flags & ~ZRT_DIRECT_UNSHADOWED;
+    const uint32_t L = b->num_lights;
+    const bool want_first = (flags & ZRT_TRACE_PARK) != 0 || b->num_rays >= kTraceParkMin;
+    LaunchPlan pl;
+    int rc;
+    if ((rc = resolve_plan(c, flags, counting, want_first, b->num_rays >= kSetsMinSamples, pl)) != ZRT_OK) return rc;
+    const bool park_first = pl.park_ok && want_first;
+
+    // chunk size, as query_rays; a sub-chunk's buffers are bounded by kDirItems
+    zrt_context::PassSet& ps = c->set[0];
+    const bool dev = b->on_device != 0;
+    const bool own_hits = !dev || !b->hits, own_E = !dev || !b->irradiance, own_rad = !dev && b->radiance;
+    const uint64_t per_ray = (dev ? 0ull : 24ull) + (own_hits ? 16ull : 0ull) + (own_E ? 12ull : 0ull) +
+                             (own_rad ? 12ull : 0ull) + (park_first ? 64ull : 0ull);
+    const size_t held = 4ull * (c->rays_cap + c->hits_cap) + 16ull * (ps.q0_cap + ps.hit_cap) + c->bfc_bytes + c->esc_extra;
+    const size_t budget = device_budget(c, held);
+    uint64_t chunk = std::min<uint64_t>(kTraceChunk, b->num_rays);
+    if (per_ray) chunk = std::max<uint64_t>(64, std::min<uint64_t>(chunk, budget / per_ray));
+    const uint64_t M = std::min<uint64_t>(kDirItems, chunk * L);          // items of a sub-chunk
+    // words of d_rays: a host batch's rays, the lights, the list (rays, bounds), T, f, slots
+    const uint64_t off_lights = dev ? 0 : 6 * chunk, off_list = off_lights + 12ull * L, rays_words = off_list + 10 * M;
+    // words of d_hits: hit records, irradiance, radiance
+    const uint64_t off_E = own_hits ? 4 * chunk : 0, off_rad = off_E + (own_E ? 3 * chunk : 0),
+                   hits_words = off_rad + (own_rad ? 3 * chunk : 0);
+    const size_t ctr_words = wfc_words(0);
+    if ((rc = grow(&c->d_rays, &c->rays_cap, rays_words)) != ZRT_OK) return rc;
+    if (hits_words && (rc = grow(&c->d_hits, &c->hits_cap, hits_words)) != ZRT_OK) return rc;
+    if (park_first) {
+        if ((rc = grow(&ps.q0, &ps.q0_cap, 3 * chunk)) != ZRT_OK) return rc;
+        if ((rc = grow(&ps.hit, &ps.hit_cap, chunk)) != ZRT_OK) return rc;
+        if ((rc = grow(&ps.wfc, &ps.wfc_cap, ctr_words)) != ZRT_OK) return rc;
+    }
+    // capacity guard: every buffer a launch below writes holds a chunk / a sub-chunk
+    if (shortfall("rays, lights, list", c->d_rays, c->rays_cap, rays_words) ||
+        (hits_words && shortfall("hits, irradiance", c->d_hits, c->hits_cap, hits_words)) ||
+        (park_first && (shortfall("q0", ps.q0, ps.q0_cap, 3 * chunk) || shortfall("hit records", ps.hit, ps.hit_cap, chunk) ||
+                        shortfall("counters", ps.wfc, ps.wfc_cap, ctr_words))))
+        return ZRT_ERR_INVALID_ARG;
+    if ((rc = event_pool(c->ev_trace, 2)) != ZRT_OK) return rc;
+
+    RayLaunch rl;                                  // the first hits: a trace call's
+    if ((rc = ray_launch(c, pl, counting, park_first, rl, -1)) != ZRT_OK) return rc;
+    // the chains: a transmittance call's lane kernels and their occupancy-sized persistent grids
+    const TransmitFn f_fast = counting || pl.mtx ? nullptr : kTransmitWalk[pl.packed ? (pl.pbm ? 0 : 1) : 2];
+    const TransmitFn f_exact = kTransmitWalk[counting ? 4 : 3];
+    uint32_t grid_fast = 0, grid_exact = 0;
+    if (!unshadowed) {
+        if (f_fast && (rc = resident_blocks(c, (const void*)f_fast, kTraceThreads, pl.lds_wf, &grid_fast)) != ZRT_OK)
+            return rc;
+        if ((rc = resident_blocks(c, (const void*)f_exact, kTraceThreads, pl.lds_wf, &grid_exact)) != ZRT_OK) return rc;
+    }
+
+    QueryParams R;
+    memset(&R, 0, sizeof R);
+    scene_params(c, R.w.t);
+    R.w.t.max_bounce = 1;
+    R.w.t.counter = c->d_counter;
+    R.w.t.stats = c->d_stats;
+    R.ctr = c->d_counter;
+    if (park_first) {
+        R.w.q_in = ps.q0;
+        R.w.hit = ps.hit;
+        R.w.fetch8 = ps.wfc;
+        R.w.n_in8 = region_counts(ps, 0);
+        park_params(c, pl, R.w);
+        R.q = ps.q0;
+        R.n_in8 = region_counts(ps, 0);
+    }
+    DirectParams D;
+    memset(&D, 0, sizeof D);
+    D.tri_data = c->d_data;
+    D.mats = c->d_mats;
+    D.texels = c->d_texels;
+    D.lights = reinterpret_cast<const zrt_light*>(c->d_rays + off_lights);
+    D.L = L;
+    D.unshadowed = unshadowed ? 1u : 0u;
+    D.irays = c->d_rays + off_list;
+    D.ibound = D.irays + 6 * M;
+    float* const dT = D.ibound + M;
+    D.T = dT;
+    D.f = dT + M;
+    D.slot = reinterpret_cast<uint32_t*>(D.f + M);
+    D.ctr = c->d_counter;
+    D.stats = c->d_stats;
+    // the chains' walks: the list as a transmittance call's rays and bounds
+    TransmitParams I;
+    memset(&I, 0, sizeof I);
+    scene_params(c, I.q.w.t);
+    I.q.w.t.max_bounce = 1;
+    I.q.w.t.counter = c->d_counter;
+    I.q.w.t.stats = c->d_stats;
+    I.q.ctr = c->d_counter;
+    I.q.rays = D.irays;
+    I.q.t_max = D.ibound;
+    I.T = dT;
+    I.max_cross = b->max_crossings;
+    I.q.w.t.S = 1;
+    I.q.w.t.sdiv = div_magic(1);
+
+    HIP_TRY(hipMemsetAsync(c->d_stats, 0, 512, c->stream));
+    HIP_TRY(hipEventRecord(c->ev_begin, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_rays + off_lights, b->lights, sizeof(zrt_light) * (size_t)L, hipMemcpyHostToDevice,
+                           c->stream));
+    uint32_t launches = 0;
+    uint64_t traced = 0;
+    for (uint64_t off = 0; off < b->num_rays; off += chunk) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, b->num_rays - off);
+        if (dev) {
+            R.rays = b->rays + 6 * off;
+        } else {
+            HIP_TRY(hipMemcpyAsync(c->d_rays, b->rays + 6 * off, 24ull * n, hipMemcpyHostToDevice, c->stream));
+            R.rays = c->d_rays;
+            HIP_TRY(hipEventRecord(c->ev_trace[0], c->stream));
+        }
+        R.hits = own_hits ? c->d_hits : reinterpret_cast<uint32_t*>(b->hits + off);
+        D.E = own_E ? reinterpret_cast<float*>(c->d_hits + off_E) : b->irradiance + 3 * off;
+        D.radiance = own_rad ? reinterpret_cast<float*>(c->d_hits + off_rad) : dev && b->radiance ? b->radiance + 3 * off
+                                                                                                 : nullptr;
+        HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
+        if (park_first) HIP_TRY(hipMemsetAsync(ps.wfc, 0, 4ull * 16 * kCtr, c->stream));
+        if ((rc = trace_first_segments(c, pl, rl, R, n, true, &launches)) != ZRT_OK) return rc;
+        // the first hits' segments and hits are not the chains'
+        HIP_TRY(hipMemsetAsync(c->d_stats, 0, 8, c->stream));
+        HIP_TRY(hipMemsetAsync(c->d_stats + 3, 0, 8, c->stream));
+        D.rays = R.rays;
+        D.hits = R.hits;
+        D.n = n;
+        const uint64_t items = (uint64_t)n * L;
+        for (uint64_t i0 = 0; i0 < items; i0 += kDirItems) {
+            const uint32_t m = (uint32_t)std::min<uint64_t>(kDirItems, items - i0);
+            const uint32_t mblk = (m + kBlock - 1) / kBlock;
+            D.ray0 = (uint32_t)(i0 / L);
+            D.l0 = (uint32_t)(i0 % L);
+            D.m = m;
+            HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
+            hipLaunchKernelGGL(direct_gen_kernel, dim3((mblk + kDirGenItems - 1) / kDirGenItems), dim3(kBlock), 0, c->stream,
+                               D);
+            ++launches;
+            HIP_TRY(hipGetLastError());
+            uint32_t live = 0;                         // the list's entries: the traced items
+            HIP_TRY(copy_sync(&live, c->d_counter + 4, sizeof live, hipMemcpyDeviceToHost, c->stream));
+            if (live > m) return ZRT_ERR_HIP;          // (never: the kernel's own bounds)
+            traced += live;
+            D.fold = 0u;
+            if (live != 0u && !unshadowed) {
+                const uint32_t lblk = (live + kBlock - 1) / kBlock;
+                I.q.n = live;
+                I.q.w.t.P = live;
+                I.q.w.t.total = live;
+                auto walk = [&](TransmitFn f, uint32_t grid, uint32_t which) {
+                    I.q.which = which;
+                    hipLaunchKernelGGL(f, dim3(std::min(grid, lblk)), dim3(kTraceThreads), pl.lds_wf, c->stream, I);
+                    ++launches;
+                };
+                if (f_fast) walk(f_fast, grid_fast, kRaysFast);
+                walk(f_exact, grid_exact, f_fast ? kRaysRest : kRaysAll);
+                D.fold = 1u;
+            }
+            const uint32_t nr = (uint32_t)((D.l0 + (uint64_t)m + L - 1) / L);   // rays with an item in the sub-chunk
+            hipLaunchKernelGGL(direct_reduce_kernel, dim3((nr + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, D);
+            ++launches;
+            HIP_TRY(hipGetLastError());
+        }
+        if (!dev) {
+            HIP_TRY(hipEventRecord(c->ev_trace[1], c->stream));
+            if (b->hits) HIP_TRY(copy_sync(b->hits + off, c->d_hits, 16ull * n, hipMemcpyDeviceToHost, c->stream));
+            if (b->irradiance) HIP_TRY(copy_sync(b->irradiance + 3 * off, D.E, 12ull * n, hipMemcpyDeviceToHost, c->stream));
+            if (b->radiance)
+                HIP_TRY(copy_sync(b->radiance + 3 * off, D.radiance, 12ull * n, hipMemcpyDeviceToHost, c->stream));
+            float t = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&t, c->ev_trace[0], c->ev_trace[1]));
+            st.trace_kernel_ms += t;
+        }
+    }
+    if ((rc = finish_query(c, dev, launches, st)) != ZRT_OK) return rc;
+    unsigned long long hs[kDirStat + 2];
+    HIP_TRY(copy_sync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+    st.segments = b->num_rays + hs[kDirStat];
+    st.samples = traced;
+    st.hits = hs[kDirStat + 1];
     if (counting) {
         st.cells_visited = hs[1];
         st.triangle_tests = hs[2];

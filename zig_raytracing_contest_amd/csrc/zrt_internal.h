@@ -83,6 +83,11 @@ inline bool occx_usable(uint64_t bricks, uint64_t occupied, uint64_t lds_bytes, 
 int tile_pixels(uint32_t w, uint32_t h, uint32_t tile, uint32_t rank, uint32_t nranks,
                 uint32_t* out, uint32_t* count);
 
+// zrt_context_direct's argument checks, which need no device (capi.cpp): the
+// batch's scalar fields, then -- num_rays != 0 -- its pointers and the lights'
+// types.  `trace_flags`: the flags zrt_context_trace accepts.
+bool direct_batch_ok(const zrt_direct_batch* b, uint32_t trace_flags);
+
 // The packed RGB8 of a context's last render (device memory on its device,
 // 3 * pixels bytes in its rank's zrt_tile_pixels order): what a device group
 // gathers (group.hip).

@@ -30,6 +30,8 @@ FLAG_HOP, FLAG_NO_HOP = 0x8000, 0x8
 TRACE_PARK = 0x10000       # ZRT_TRACE_PARK (zrt_ray_batch / zrt_radiance_batch flags only)
 RADIANCE_PER_SAMPLE = 0x20000   # ZRT_RADIANCE_PER_SAMPLE (zrt_radiance_batch.flags only)
 SEGMENT_ANY = 0x40000      # ZRT_SEGMENT_ANY (zrt_segment_batch.flags only)
+DIRECT_UNSHADOWED = 0x80000   # ZRT_DIRECT_UNSHADOWED (zrt_direct_batch.flags only)
+LIGHT_POINT, LIGHT_DIRECTIONAL, LIGHT_SPOT = 0, 1, 2
 MISS = 0xFFFFFFFF          # zrt_hit.triangle of a ray that hit nothing
 # zrt_kernel_profile classes (include/zrt.h)
 KERNEL_CLASSES = ("primary", "park", "shade", "bounce", "resolve", "count")
@@ -174,6 +176,36 @@ class OcclusionBatch(C.Structure):
                 ("index_base", C.c_uint64)]
 
 
+class Light(C.Structure):
+    """zrt_light.  Light.point / .directional / .spot build one; a spot's
+    angle_scale and angle_offset come from its cone angles in float32:
+    1 / max(0.001, cos_inner - cos_outer) and -cos_outer * angle_scale."""
+    _fields_ = [("type", C.c_uint32), ("position", C.c_float * 3), ("direction", C.c_float * 3),
+                ("color", C.c_float * 3), ("angle_scale", C.c_float), ("angle_offset", C.c_float)]
+
+    @classmethod
+    def point(cls, position, color):
+        return cls(LIGHT_POINT, (C.c_float * 3)(*position), (C.c_float * 3)(), (C.c_float * 3)(*color), 0.0, 0.0)
+
+    @classmethod
+    def directional(cls, direction, color):
+        return cls(LIGHT_DIRECTIONAL, (C.c_float * 3)(), (C.c_float * 3)(*direction), (C.c_float * 3)(*color), 0.0, 0.0)
+
+    @classmethod
+    def spot(cls, position, direction, color, inner_angle, outer_angle):
+        """Cone angles in radians from the axis (KHR_lights_punctual's)."""
+        ci, co = np.float32(np.cos(inner_angle)), np.float32(np.cos(outer_angle))
+        scale = np.float32(1.0) / max(np.float32(0.001), np.float32(ci - co))
+        return cls(LIGHT_SPOT, (C.c_float * 3)(*position), (C.c_float * 3)(*direction), (C.c_float * 3)(*color),
+                   float(scale), float(np.float32(-co * scale)))
+
+
+class DirectBatch(C.Structure):
+    _fields_ = [("num_rays", C.c_uint64), ("rays", C.c_void_p), ("lights", C.c_void_p), ("irradiance", C.c_void_p),
+                ("radiance", C.c_void_p), ("hits", C.c_void_p), ("on_device", C.c_uint32), ("flags", C.c_uint32),
+                ("num_lights", C.c_uint32), ("max_crossings", C.c_uint32)]
+
+
 class RadianceBatch(C.Structure):
     _fields_ = [("num_rays", C.c_uint64), ("rays", C.c_void_p), ("radiance", C.c_void_p), ("rgb", C.c_void_p),
                 ("on_device", C.c_uint32), ("flags", C.c_uint32), ("num_samples", C.c_uint32),
@@ -189,7 +221,7 @@ EXPORTS = [
     "zrt_camera_from_matrix", "zrt_probe", "zrt_timed_kernels", "zrt_context_profile", "zrt_context_trace",
     "zrt_group_create", "zrt_group_create_built", "zrt_group_render", "zrt_group_context", "zrt_group_destroy",
     "zrt_context_radiance", "zrt_context_segments", "zrt_context_surface", "zrt_context_transmittance",
-    "zrt_context_features", "zrt_context_occlusion",
+    "zrt_context_features", "zrt_context_occlusion", "zrt_context_direct",
 ]
 
 
@@ -234,6 +266,8 @@ def lib():
     L.zrt_context_features.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderConfig),
                                        C.POINTER(FeatureOutputs), C.POINTER(Stats)]
     L.zrt_context_occlusion.argtypes = [C.c_void_p, C.POINTER(OcclusionBatch), C.POINTER(Stats)]
+    if hasattr(L, "zrt_context_direct"):   # (a build from before this query: tools/ A/B baselines only)
+        L.zrt_context_direct.argtypes = [C.c_void_p, C.POINTER(DirectBatch), C.POINTER(Stats)]
     if hasattr(L, "zrt_group_create"):     # ABI 2 (an ABI-1 build: tools/ A/B baselines only)
         L.zrt_group_create.argtypes = [C.POINTER(Scene), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
         L.zrt_group_create_built.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -787,6 +821,69 @@ class Context:
                                 rec.ctypes.data if hits and n else None, False, spp, rad_all, seed, index_base, flags)
         res = {"visibility": vis, "occluded": occ, "stats": st}
         if hits:
+            res.update(t=rec["t"].copy(), u=rec["u"].copy(), v=rec["v"].copy(), triangle=rec["triangle"].copy())
+        return res
+
+    def direct_raw(self, num_rays: int, rays_ptr, lights, irradiance_ptr, radiance_ptr, hits_ptr, on_device: bool,
+                   max_crossings: int = 16, flags: int = 0):
+        """zrt_context_direct on raw pointers; `lights`: a sequence of Light
+        (always host memory).  Returns the stats dict."""
+        arr = (Light * len(lights))(*lights)
+        batch = DirectBatch(int(num_rays), rays_ptr, C.cast(arr, C.c_void_p) if len(lights) else None, irradiance_ptr,
+                            radiance_ptr, hits_ptr, 1 if on_device else 0, int(flags), len(lights), int(max_crossings))
+        st = Stats()
+        check(lib().zrt_context_direct(self._h, C.byref(batch), C.byref(st)), "zrt_context_direct")
+        return st.as_dict()
+
+    def direct(self, origins, dirs, lights, max_crossings: int = 16, flags: int = 0, unshadowed: bool = False,
+               irradiance: bool = True, radiance: bool = False, hits: bool = False, stats: bool = False):
+        """Direct light of punctual lights at each ray's first hit
+        (zrt_context_direct): per ray the irradiance E = sum over `lights` (a
+        sequence of Light, in order) of colour * falloff * T, T the
+        transmittance of the segment to the light through at most
+        `max_crossings` transparent hits (unshadowed=True: T = 1, nothing
+        traced), and the Lambertian radiance emissive + base_color * E / pi.
+        A miss is zero in both.
+
+        Two (n, 3) float32 numpy arrays give {"irradiance": (n, 3) float32,
+        "radiance": (n, 3) float32 (each only when asked), "stats"}, and with
+        hits=True trace()'s "t", "u", "v", "triangle" of the first hits.
+        "stats" holds "segments" (rays + the chains' segments), "samples" (the
+        traced (ray, light) items) and "hits" (the chains' crossings) in every
+        call, the cell and test counters with stats=True.
+
+        Two (n, 3) float32 CUDA tensors (torch-ROCm) on the context's device
+        are traced in place, after a sync of torch's current stream: the
+        outputs are (n, 3) float32 CUDA tensors, with hits=True "hits" as in
+        trace()."""
+        if not (irradiance or radiance):
+            raise ValueError("direct: irradiance or radiance must be asked for")
+        flags = int(flags) | (FLAG_COUNT_STATS if stats else 0) | (DIRECT_UNSHADOWED if unshadowed else 0)
+        lights = list(lights)
+        torch, n, rays = self._rays("direct", origins, dirs)
+        if torch:
+            irr = torch.empty((n, 3), dtype=torch.float32, device=origins.device) if irradiance else None
+            rad = torch.empty((n, 3), dtype=torch.float32, device=origins.device) if radiance else None
+            rec = torch.empty((n, 4), dtype=torch.float32, device=origins.device) if hits else None
+            torch.cuda.current_stream(origins.device).synchronize()
+            ptr = lambda x: x.data_ptr() if x is not None and n else None
+        else:
+            irr = np.empty((n, 3), np.float32) if irradiance else None
+            rad = np.empty((n, 3), np.float32) if radiance else None
+            rec = np.empty(n, HIT_DTYPE) if hits else None
+            ptr = lambda x: x.ctypes.data if x is not None and n else None
+        if n == 0:                                 # (an empty batch: any non-null output pointer passes the checks)
+            st = self.direct_raw(0, None, lights, None, None, None, bool(torch), max_crossings, flags)
+        else:
+            st = self.direct_raw(n, ptr(rays), lights, ptr(irr), ptr(rad), ptr(rec), bool(torch), max_crossings, flags)
+        res = {"stats": st}
+        if irradiance:
+            res["irradiance"] = irr
+        if radiance:
+            res["radiance"] = rad
+        if hits and torch:
+            res["hits"] = rec
+        elif hits:
             res.update(t=rec["t"].copy(), u=rec["u"].copy(), v=rec["v"].copy(), triangle=rec["triangle"].copy())
         return res
 
