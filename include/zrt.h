@@ -772,6 +772,90 @@ typedef struct zrt_direct_batch {
  * items that are not traced add nothing. */
 int zrt_context_direct(zrt_context* ctx, const zrt_direct_batch* batch, zrt_stats* stats_or_null);
 
+/* ---- light-probe queries (ABI 2, added) --------------------------------- */
+
+/* The light arriving at a point from all directions: per probe position the
+ * order-2 spherical-harmonics projection of the path-traced radiance field,
+ * the first-hit distance moments and the hit count -- zrt_context_radiance's
+ * first use, with the directions drawn, traced, projected and summed on the
+ * device.  Nothing per (probe, direction) item crosses the bus unless the
+ * caller asks for the raw directions or radiance, and the sum's order is fixed.
+ * Everything is f32, nothing is contracted (no FMA), operations run left to
+ * right as written.  normalize_rn(a) = a * (1.0f / sqrt((a.x*a.x + a.y*a.y) +
+ * a.z*a.z)) with the IEEE square root and the correctly rounded reciprocal, the
+ * render's own form.  For probe p at x_p = positions[p] and direction
+ * j = 0 .. D - 1 (D = num_directions), in this order:
+ *   key  = (uint32_t)(index_base + p * D + j), the product taken in 64 bits
+ *   d_j  = normalize_rn((a, b, c)): a, b, c the first three floatNorm draws of
+ *          the stream (seed, key, sample 65535) taken from its start
+ *          (Vec3.randomUnitVector, linalg.zig:140-148).  Sample index 65535 is
+ *          never a path's: a call's paths use samples 0 .. num_samples - 1 <=
+ *          65534 and the stream key gives the sample 16 bits, so the directions
+ *          are independent of every path stream under the same seed and key
+ *   L_j  = the radiance[i] zrt_context_radiance specifies for the ray (x_p, d_j)
+ *          with stream key `key`, num_samples, max_bounce and seed, bit for bit.
+ *          That call adds +0 twice to d_j and normalises it again: u_j.  The
+ *          first segment is traced once per direction, as there
+ *   h_j  = the zrt_context_trace record of (x_p, u_j)
+ *   the basis on d_j (not u_j), (x, y, z) = d_j, the constants f32 literals:
+ *     C0 = 0x1.20dd76p-2f (0x3E906EBB)   C1 = 0x1.f45438p-2f (0x3EFA2A1C)
+ *     C2 = 0x1.17b142p+0f (0x3F8BD8A1)   C3 = 0x1.42f602p-2f (0x3EA17B01)
+ *     C4 = 0x1.17b142p-1f (0x3F0BD8A1)
+ *     Y0 = C0          Y1 = C1*y        Y2 = C1*z        Y3 = C1*x
+ *     Y4 = (C2*x)*y    Y5 = (C2*y)*z    Y6 = C3*((3.0f*(z*z)) - 1.0f)
+ *     Y7 = (C2*x)*z    Y8 = C4*((x*x) - (y*y))
+ *   the sums, from +0 and 0, in direction order:
+ *     A[k][c] = A[k][c] + L_j[c] * Y_k          k = 0..8, c = 0..2
+ *     a hit (h_j.t != +inf):  T1 += h_j.t;  T2 += h_j.t * h_j.t;  n += 1
+ *     a miss adds nothing to T1, T2 or n
+ * and then
+ *   sh[p][k][c]  = A[k][c] * w,  w = 0x1.921fb6p+3f / (float)D -- 4 pi rounded
+ *                  to f32 (0x41490FDB), by the IEEE division
+ *   distance[p]  = (T1 * r, T2 * r),  r = 1.0f / (float)D
+ *   hits[p]      = n
+ *   directions[p * D + j] = d_j,  radiance[p * D + j] = L_j
+ * A NaN or inf the arithmetic produces is stored as it is.  A non-finite
+ * position or a NaN direction gives an unspecified result; the call still
+ * returns. */
+typedef struct zrt_light_probe_batch {
+    uint64_t num_probes;
+    const float* positions;   /* num_probes * 3 */
+    float* sh;                /* num_probes * 27: [k][c], k = 0..8, c = RGB; or null */
+    float* distance;          /* num_probes * 2: mean t, mean t*t of the first hits; or null */
+    uint32_t* hits;           /* num_probes: directions whose first segment hit; or null */
+    float* directions;        /* num_probes * num_directions * 3: d_j as generated; or null */
+    float* radiance;          /* num_probes * num_directions * 3: L_j; or null */
+    uint32_t on_device;       /* as zrt_ray_batch; applies to positions and all five outputs */
+    uint32_t flags;           /* zrt_radiance_batch's flags without ZRT_RADIANCE_PER_SAMPLE */
+    uint32_t num_directions;  /* D, 1..65535 */
+    uint32_t num_samples;     /* S, 1..65535 paths per direction */
+    uint32_t max_bounce;      /* 1..32 */
+    uint32_t _reserved;       /* 0 */
+    uint64_t seed;
+    uint64_t index_base;      /* stream key of probe 0's direction 0; keys wrap at 2^32 */
+} zrt_light_probe_batch;      /* 96 B; offsets 0 8 16 24 32 40 48 56 60 64 68 72 76 80 88 */
+
+/* Synchronous, one thread at a time per context; alternates freely with
+ * renders and the other queries (every use writes what it reads first) and
+ * leaves zrt_context_profile's record untouched.  The (probe, direction) items
+ * run through the radiance call's launches in chunks of at most 2^20 items,
+ * fewer where num_samples paths per item would not fit the memory budget of a
+ * render's pass.  The summation order is part of the contract: a probe's
+ * directions may straddle a cut and still add in direction order, so the result
+ * is the same bits for any chunking.
+ * num_probes == 0 returns ZRT_OK and touches nothing.  ZRT_ERR_INVALID_ARG
+ * before any device work, the outputs untouched: a null context or batch, null
+ * positions, all five outputs null, on_device > 1, a non-zero _reserved,
+ * num_directions or num_samples outside 1..65535, num_probes above 2^47 (the
+ * item count num_probes * num_directions stays below 2^63), max_bounce == 0,
+ * any flag outside the accepted set (ZRT_RADIANCE_PER_SAMPLE and
+ * ZRT_FLAG_COUNT_STATS included).  max_bounce > 32 is ZRT_ERR_UNSUPPORTED, as in the radiance call.
+ * stats (may be null), in every call: segments = what a zrt_context_radiance
+ * call over the same num_probes * D rays reports, samples = num_probes * D * S,
+ * hits = the sum of the hits plane whether or not `hits` was asked for,
+ * render_ms, trace_kernel_ms and trace_launches as in zrt_context_trace. */
+int zrt_context_light_probes(zrt_context* ctx, const zrt_light_probe_batch* batch, zrt_stats* stats_or_null);
+
 /* A device group: one context per entry of `devices` (HIP ordinals, repeats
  * allowed), the scene resident on each, rendered by one call -- Scene.render's
  * spawn + join of its workers (stage3.zig:247-256) across GPUs in one

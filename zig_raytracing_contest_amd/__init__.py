@@ -164,6 +164,16 @@ class RenderScene:
                                    unshadowed=unshadowed, irradiance=irradiance, radiance=radiance, hits=hits,
                                    stats=stats)
 
+    def light_probes(self, positions, num_directions: int, spp: int, max_bounce: int, seed: int = 0,
+                     index_base: int = 0, flags: int = 0, sh: bool = True, distance: bool = False, hits: bool = False,
+                     directions: bool = False, radiance: bool = False):
+        """Order-2 SH radiance, first-hit distance moments and hit counts at
+        points, from `num_directions` device-made directions of `spp` paths
+        each: see native.Context.light_probes."""
+        return self.context.light_probes(positions, num_directions, spp, max_bounce, seed=seed, index_base=index_base,
+                                         flags=flags, sh=sh, distance=distance, hits=hits, directions=directions,
+                                         radiance=radiance)
+
     def radiance(self, origins, dirs, spp: int, max_bounce: int, seed: int = 0, index_base: int = 0,
                  flags: int = 0, rgb: bool = False, stats: bool = False):
         """Scene.traceRayRecursive (stage3.zig:188-220) for a batch of rays,

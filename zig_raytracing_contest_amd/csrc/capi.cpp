@@ -57,6 +57,16 @@ bool direct_batch_ok(const zrt_direct_batch* b, uint32_t trace_flags) {
     return true;
 }
 
+bool light_probe_batch_ok(const zrt_light_probe_batch* b, uint32_t probe_flags) {
+    if (!b) return false;
+    if ((b->flags & ~probe_flags) != 0u || b->on_device > 1u || b->_reserved != 0u || b->num_directions == 0u ||
+        b->num_directions > 65535u || b->num_samples == 0u || b->num_samples > 65535u || b->max_bounce == 0u)
+        return false;
+    if (b->num_probes == 0) return true;
+    if (b->num_probes > (1ull << 47)) return false;     // (num_probes * num_directions stays below 2^63)
+    return b->positions && (b->sh || b->distance || b->hits || b->directions || b->radiance);
+}
+
 void zig_tables(double zx[257], double zf[257]) {
     static std::once_flag once;
     static double X[257], F[257];

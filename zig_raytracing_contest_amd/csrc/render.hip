@@ -3267,6 +3267,192 @@ __global__ __launch_bounds__(kTraceBlock, 1) void rad_fanout_kernel(const RadPar
     if (lane == 0) atomicAdd(&p.stats[0], s0);
 }
 
+// ---------------------------------------------------------------------------
+// Light-probe queries (zrt_context_light_probes): per probe
+// position the order-2 SH projection of the radiance zrt_context_radiance
+// computes along D directions made on the device, the first hits' distance
+// moments and their count.  An item is a (probe, direction) pair; a chunk's n
+// items are the radiance call's n rays: item i of a chunk that starts at
+// direction j0 of probe p0 is (p0 + (j0 + i) / D, (j0 + i) % D), its stream key
+// key0 + i.  light_probe_gen_kernel writes the chunk's ray row, which
+// rad_pack_kernel, the first segments, rad_fanout_kernel, the bounce launches
+// and wf_resolve_kernel then run over as they stand.
+// light_probe_reduce_kernel has two modes:
+//   kLpTake, right after the fan-out (the first segments' records in w.hit are
+//   valid until bounce launch 1's park kernel reuses the array): t of every
+//   item copied to a 4-byte row, kLpTakeItems items per thread, and the hits of
+//   the call counted with one atomic per block (one per wave of 64 items took
+//   0.2 ms of a 2^20-item chunk on one address);
+//   kLpFold, after the resolve: 32 lanes per probe of the chunk, lane 3 * k + c
+//   the sum A[k][c], lane 27 T1, lane 28 T2, lane 29 n; every lane walks its
+//   probe's items of the chunk in direction order, 32 at a time: the half-wave
+//   loads a tile of L_j, d_j and t into LDS, one item per lane, and every lane
+//   reads the items from there.  A sum starts at +0 where the probe's direction 0
+//   lies in this chunk and is read back from the carry row `carry_in` otherwise
+//   -- only a chunk's first probe can have begun before it; only its last can
+//   go on after it, and leaves its sums in `carry_out`.  The two are different
+//   rows, which the host swaps from chunk to chunk: in a chunk whose first
+//   probe reads and whose last probe writes, the two half-waves run in no order.
+//   A probe whose last direction was added is scaled and stored.  So a probe
+//   whose directions straddle a cut, or many cuts, is summed in the same order
+//   as any other.
+struct LightProbeParams {
+    const float* pos;         // 3 floats per probe, from the chunk's first probe p0 on
+    float* rays;              // the chunk's ray row: 6 floats per item (x_p, d_j)
+    float* dirs;              // this chunk: d_j, 3 floats per item, or null
+    const double* zig;        // the ziggurat's tables (TraceParams::zig)
+    uint64_t seed;
+    uint32_t key0;            // RNG stream key of the chunk's item 0; keys wrap at 2^32
+    uint32_t D;               // directions per probe, 1..65535
+    uint32_t j0;              // the chunk's item 0 is direction j0 of probe p0
+    uint32_t n;               // items of this chunk (<= kTraceChunk)
+    uint32_t np;              // probes with an item in this chunk
+    uint32_t mode;            // light_probe_reduce_kernel: kLpTake or kLpFold
+    const float4* hit;        // kLpTake: the first segments' records, one per item
+    float* t;                 // the chunk's first-hit distances, one per item (+inf: a miss)
+    const float* lin;         // kLpFold: L_j, 3 floats per item (wf_resolve_kernel's linear row)
+    const float* carry_in;    // 32 words: the sums of the probe the previous chunk left unfinished
+    float* carry_out;         // 32 words, another row: the sums of a probe that goes on in the next chunk
+    float* sh;                // from probe p0 on: 27 floats per probe, or null
+    float* dist;              //   2 floats per probe, or null
+    uint32_t* hits;           //   a count per probe, or null
+    unsigned long long* stats;   // [kLpStat]: the hits of the call
+};
+constexpr uint32_t kLpGenItems = 4;            // items per thread of light_probe_gen_kernel
+constexpr uint32_t kLpTakeItems = 8;           // items per thread of light_probe_reduce_kernel, kLpTake
+constexpr uint32_t kLpTake = 0, kLpFold = 1;
+constexpr uint32_t kLpStat = 16;               // (stats[0..3] are the walk kernels', [0..15] the counting render's)
+constexpr uint32_t kLpDirSample = 65535;       // the sample index of a direction's stream: never a path's
+constexpr float kLpFourPi = 0x1.921fb6p+3f;    // 4 pi rounded to f32, 0x41490FDB
+constexpr float kShC0 = 0x1.20dd76p-2f, kShC1 = 0x1.f45438p-2f, kShC2 = 0x1.17b142p+0f, kShC3 = 0x1.42f602p-2f,
+                kShC4 = 0x1.17b142p-1f;
+
+// A block takes kLpGenItems * kBlock consecutive items.  The direction is
+// Vec3.randomUnitVector from the start of the stream (seed, key, 65535), as
+// occlusion_gen_kernel draws a sample's.
+__global__ __launch_bounds__(kBlock) void light_probe_gen_kernel(const LightProbeParams r) {
+    __shared__ double s_zig[514];
+    for (uint32_t i = threadIdx.x; i < 514; i += blockDim.x) s_zig[i] = r.zig[i];
+    __syncthreads();
+    const double* zx = s_zig;
+    const double* zf = s_zig + 257;
+    for (uint32_t k = 0; k < kLpGenItems; ++k) {
+        const uint32_t i = (blockIdx.x * kLpGenItems + k) * kBlock + threadIdx.x;
+        if (i >= r.n) break;
+        const uint32_t q = (i + r.j0) / r.D;                                    // (i + j0 < 2^20 + 2^16)
+        if (q >= r.np) break;                                                   // (never: n items of np probes)
+        const float* x = r.pos + 3ull * q;
+        Rng rng;
+        rng.s = path_key(r.seed, r.key0 + i, kLpDirSample);
+        const float nx = (float)rng_norm64(rng, zx, zf);
+        const float ny = (float)rng_norm64(rng, zx, zf);
+        const float nz = (float)rng_norm64(rng, zx, zf);
+        const v3 d = normalize_rn(mk(nx, ny, nz));
+        float* o = r.rays + 6ull * i;
+        o[0] = x[0]; o[1] = x[1]; o[2] = x[2];
+        o[3] = d.x; o[4] = d.y; o[5] = d.z;
+        if (r.dirs) {
+            float* w = r.dirs + 3ull * i;
+            w[0] = d.x; w[1] = d.y; w[2] = d.z;
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void light_probe_reduce_kernel(const LightProbeParams r) {
+    __shared__ uint32_t s_n;
+    __shared__ __attribute__((aligned(16))) float s_tile[kBlock / 32][32][8];
+    const uint32_t lane = threadIdx.x & 63u;
+    if (r.mode == kLpTake) {
+        if (threadIdx.x == 0) s_n = 0u;
+        __syncthreads();
+        uint32_t n_hit = 0;
+        for (uint32_t k = 0; k < kLpTakeItems; ++k) {
+            const uint32_t i = (blockIdx.x * kLpTakeItems + k) * kBlock + threadIdx.x;
+            if (i >= r.n) break;
+            const float t = r.hit[i].x;
+            r.t[i] = t;
+            n_hit += t != kInf ? 1u : 0u;
+        }
+        const unsigned long long s = wave_sum(n_hit);
+        if (lane == 0 && s != 0ull) atomicAdd(&s_n, (uint32_t)s);
+        __syncthreads();
+        if (threadIdx.x == 0 && s_n != 0u) atomicAdd(&r.stats[kLpStat], (unsigned long long)s_n);
+        return;
+    }
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t q = i >> 5, l = i & 31u;
+    if (q >= r.np) return;                                                      // (a whole half-wave)
+    const uint32_t first = q * r.D, end = r.j0 + r.n;                           // (q * D <= j0 + n < 2^21)
+    const uint32_t a = max(first, r.j0), e = min(first + r.D, end);
+    const uint32_t kk = l / 3u, c = min(l - 3u * kk, 2u);
+    const bool is_sh = l < 27u;
+    float acc = 0.0f;
+    uint32_t cnt = 0u;
+    if (a != first && l < 30u) {
+        acc = r.carry_in[l];
+        cnt = __float_as_uint(acc);
+    }
+    // a tile of 32 items: lane l of the half-wave loads item x0 + l (coalesced
+    // rows) and lays it into the half-wave's LDS tile as (d, t) (L, -); then
+    // every lane takes the tile's items in order, every read one address or
+    // three per half-wave.  The next tile's loads are in flight meanwhile.  The
+    // lanes of a half-wave run in lockstep (one wave, one control flow): a
+    // tile's writes are done before its reads, its reads before the next writes.
+    float(*const tile)[8] = s_tile[threadIdx.x >> 5];
+    struct Item { float4 dt, L; };
+    auto load = [&](uint32_t x0) {
+        Item m = {make_float4(0.0f, 0.0f, 0.0f, kInf), make_float4(0.0f, 0.0f, 0.0f, 0.0f)};
+        const uint32_t x = x0 + l;
+        if (x < e) {
+            const uint32_t it = x - r.j0;
+            const float* dp = r.rays + 6ull * it + 3;
+            const float* lp = r.lin + 3ull * it;
+            m.dt = make_float4(dp[0], dp[1], dp[2], r.t[it]);
+            m.L = make_float4(lp[0], lp[1], lp[2], 0.0f);
+        }
+        return m;
+    };
+    Item cur = load(a);
+    for (uint32_t x0 = a; x0 < e; x0 += 32u) {
+        *reinterpret_cast<float4*>(&tile[l][0]) = cur.dt;
+        *reinterpret_cast<float4*>(&tile[l][4]) = cur.L;
+        __builtin_amdgcn_wave_barrier();
+        cur = load(x0 + 32u);
+        const uint32_t m = min(32u, e - x0);
+#pragma unroll 4
+        for (uint32_t s = 0; s < m; ++s) {
+            const float4 dt = *reinterpret_cast<const float4*>(&tile[s][0]);
+            const float Lc = tile[s][4 + c];
+            const float dx = dt.x, dy = dt.y, dz = dt.z, t = dt.w;
+            // all nine, then the lane's own: selects, no branch
+            const float y1 = kShC1 * dy, y2 = kShC1 * dz, y3 = kShC1 * dx;
+            const float y4 = (kShC2 * dx) * dy, y5 = (kShC2 * dy) * dz, y7 = (kShC2 * dx) * dz;
+            const float y6 = kShC3 * ((3.0f * (dz * dz)) - 1.0f);
+            const float y8 = kShC4 * ((dx * dx) - (dy * dy));
+            float Y = kk == 0u ? kShC0 : kk == 1u ? y1 : kk == 2u ? y2 : kk == 3u ? y3 : y4;
+            Y = kk == 5u ? y5 : kk == 6u ? y6 : kk == 7u ? y7 : kk == 8u ? y8 : Y;
+            const float term = is_sh ? Lc * Y : l == 27u ? t : t * t;
+            const bool hit = t != kInf;
+            acc = is_sh || hit ? acc + term : acc;
+            cnt += hit ? 1u : 0u;
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (l >= 30u) return;
+    if (e != first + r.D) {                                                     // goes on in the next chunk
+        r.carry_out[l] = l == 29u ? __uint_as_float(cnt) : acc;
+        return;
+    }
+    const float fD = (float)r.D;
+    if (l < 27u) {
+        if (r.sh) r.sh[27ull * q + l] = acc * (kLpFourPi / fD);
+    } else if (l < 29u) {
+        if (r.dist) r.dist[2ull * q + (l - 27u)] = acc * (1.0f / fD);
+    } else if (r.hits) {
+        r.hits[q] = cnt;
+    }
+}
+
 using RadFn = void (*)(const RadParams);
 constexpr uint32_t kRadianceFlags = ZRT_FLAG_LANE_WALK | ZRT_FLAG_MT_EXACT | ZRT_FLAG_ESCAPE | ZRT_FLAG_NO_ESCAPE |
                                     ZRT_FLAG_RELEASE | ZRT_FLAG_NO_RELEASE | ZRT_FLAG_BFCULL | ZRT_FLAG_NO_BFCULL |
@@ -5258,6 +5444,177 @@ extern "C" int zrt_context_direct(zrt_context* c, const zrt_direct_batch* b, zrt
     return ZRT_OK;
 }
 
+// What zrt_context_radiance and zrt_context_light_probes settle alike before
+// their chunk loops (rad_plan) and launch alike per chunk (rad_chunk_first,
+// rad_chunk_rest): the plan, the chunk size, pass set 0's buffers, the grids
+// and the launch parameters of a call of S samples per ray and max_bounce mb.
+struct RadCall {
+    uint32_t S, mb, nb;
+    bool per_sample, park_first, park_next, park_any;
+    LaunchPlan pl;
+    BounceGrids grids;
+    RayLaunch rl;
+    RadFn f_fan;
+    uint32_t grid_fan;
+    uint64_t chunk;           // rays per chunk
+    float inv_spp;
+    RadParams R;
+};
+
+// `stage_per_ray`: the bytes per ray of a chunk the caller stages beyond the
+// radiance launches' own; `stage_held`: the bytes of grow-only buffers it
+// stages them in (device_budget's `held`).  The caller grows those after this
+// returns: the budget is read before any buffer grows.
+static int rad_plan(zrt_context* c, uint32_t flags, uint64_t num_rays, uint32_t S, uint32_t mb, uint64_t seed,
+                    uint64_t stage_per_ray, size_t stage_held, RadCall& k) {
+    const uint32_t nb = std::max<uint32_t>(mb, 1);
+    k.S = S;
+    k.mb = mb;
+    k.nb = nb;
+    k.per_sample = (flags & ZRT_RADIANCE_PER_SAMPLE) != 0;
+    const bool per_sample = k.per_sample;
+    const uint64_t first_n = per_sample ? num_rays * S : num_rays;
+    const bool want_first = (flags & ZRT_TRACE_PARK) || first_n >= kTraceParkMin;
+    LaunchPlan& pl = k.pl;
+    int rc;
+    if ((rc = resolve_plan(c, flags, false, want_first || nb > 1, num_rays * S >= kSetsMinSamples, pl)) != ZRT_OK)
+        return rc;
+    k.park_next = pl.park_ok;
+    k.park_first = pl.park_ok && want_first;
+    k.park_any = pl.park;
+    const bool lmats = c->nmat <= kLdsMats;
+    k.f_fan = nb == 1 ? (lmats ? (RadFn)rad_fanout_kernel<true, true> : (RadFn)rad_fanout_kernel<false, true>)
+                      : (lmats ? (RadFn)rad_fanout_kernel<true, false> : (RadFn)rad_fanout_kernel<false, false>);
+
+    // chunk size: at most kTraceChunk rays, its n * S items below 2^31 and
+    // within the memory budget of a render's pass (its per-item bytes,
+    // device_budget); S <= 65535 always fits at 64 rays
+    zrt_context::PassSet& ps = c->set[0];
+    const uint64_t per_item = 96ull + 16ull + 16ull + 32ull * nb;
+    const uint64_t per_ray = per_item * S + 24ull + 15ull + stage_per_ray;
+    const size_t held = stage_held + 4ull * (c->nrays_cap + c->lin_cap) + c->rgb_cap + c->bfc_bytes + c->esc_extra + held_bytes(ps);
+    const size_t budget = device_budget(c, held);
+    uint64_t chunk = std::min<uint64_t>(kTraceChunk, 0x7FFFFF00ull / S);
+    chunk = std::max<uint64_t>(64, std::min<uint64_t>(chunk, budget / per_ray));
+    chunk = std::min<uint64_t>(chunk, num_rays);
+    k.chunk = chunk;
+    const uint64_t T = chunk * S;                  // items of the largest chunk
+    const uint64_t hit_need = std::max<uint64_t>(k.park_any ? T : 0, per_sample ? 0 : chunk);
+    if (!per_sample && (rc = grow(&c->d_nrays, &c->nrays_cap, 6 * chunk)) != ZRT_OK) return rc;
+    if ((rc = grow(&c->d_lin, &c->lin_cap, 3 * chunk)) != ZRT_OK) return rc;
+    if ((rc = grow(&c->d_rgb, &c->rgb_cap, 3 * chunk)) != ZRT_OK) return rc;
+    if ((rc = grow_pass_set(ps, T, nb, mb, hit_need)) != ZRT_OK) return rc;
+    // capacity guard of the rest: every buffer a launch below writes holds
+    // what a chunk's launches write; a chunk's items fit 31 bits
+    if ((!per_sample && shortfall("unit rays", c->d_nrays, c->nrays_cap, 6 * chunk)) ||
+        shortfall("linear", c->d_lin, c->lin_cap, 3 * chunk) || shortfall("rgb", c->d_rgb, c->rgb_cap, 3 * chunk) ||
+        chunk == 0 || chunk > kTraceChunk || T > 0x7FFFFF00ull)
+        return ZRT_ERR_INVALID_ARG;
+    if ((rc = event_pool(c->ev_trace, 2)) != ZRT_OK) return rc;
+
+    // occupancy-sized persistent grids
+    if ((rc = bounce_grids(c, pl, k.park_any, (!k.park_next && nb > 1) || (per_sample && !k.park_first), k.grids)) !=
+        ZRT_OK)
+        return rc;
+    k.rl = RayLaunch{};
+    k.grid_fan = 0;
+    if (!per_sample) {
+        if ((rc = ray_launch(c, pl, false, k.park_first, k.rl)) != ZRT_OK) return rc;
+        if ((rc = resident_blocks(c, (const void*)k.f_fan, kTraceThreads, pl.lds_shade, &k.grid_fan)) != ZRT_OK)
+            return rc;
+    }
+
+    RadParams& R = k.R;
+    memset(&R, 0, sizeof R);
+    WfParams& W = R.w;
+    scene_params(c, W.t);
+    W.t.max_bounce = mb;
+    W.t.seed = seed;
+    W.t.counter = c->d_counter;
+    W.t.stats = c->d_stats;
+    W.stk4 = ps.stk4;
+    W.stk2 = ps.stk2;
+    W.term = ps.term;
+    W.hit = ps.hit;
+    park_params(c, pl, W);
+    R.ctr = c->d_counter;
+    R.nrays = c->d_nrays;
+    R.q = ps.q1;                                   // launch 0 reads q1 (bounce_params)
+    R.n_in8 = region_counts(ps, 0);
+    // stage3.zig:223 inv_num_samples = ones / splat(spp)  (f32 division)
+    k.inv_spp = 1.0f / (float)S;
+    return ZRT_OK;
+}
+
+// A chunk of n rays (on the device, 6 floats each) up to the paths entering
+// launch 1: the pack kernel, the shared first segments (their records in
+// ps.hit[ray] until launch 1 reuses the array) and the fan-out; with
+// ZRT_RADIANCE_PER_SAMPLE the per-sample pack kernel alone.
+static int rad_chunk_first(zrt_context* c, RadCall& k, const float* rays, uint32_t n, uint32_t key0, uint32_t* launches) {
+    zrt_context::PassSet& ps = c->set[0];
+    RadParams& R = k.R;
+    WfParams& W = R.w;
+    const uint32_t items = n * k.S;                // <= T < 2^31
+    int rc;
+    R.rays = rays;
+    R.n = n;
+    R.key0 = key0;
+    // the counters of every launch (wfc_words); the pack kernels write launch 0's region counts
+    HIP_TRY(hipMemsetAsync(ps.wfc, 0, 4ull * wfc_words(k.mb), c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
+    W.t.P = n;
+    W.t.S = k.S;
+    W.t.total = items;
+    W.t.sdiv = div_magic(k.S);
+    W.T = items;
+    bounce_params(W, ps, 0, k.mb);
+    if (k.per_sample) {
+        hipLaunchKernelGGL(rad_pack_samples_kernel, dim3((items + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, R);
+        ++*launches;
+        HIP_TRY(hipGetLastError());
+        return ZRT_OK;
+    }
+    hipLaunchKernelGGL(rad_pack_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, R);
+    ++*launches;
+    // the first segments: one per ray, launch 0's queue as the identity queue
+    QueryParams Q;
+    memset(&Q, 0, sizeof Q);
+    Q.w = W;
+    Q.w.t.max_bounce = 1;
+    Q.rays = c->d_nrays;
+    Q.hits = reinterpret_cast<uint32_t*>(ps.hit);
+    Q.ctr = c->d_counter;
+    if ((rc = trace_first_segments(c, k.pl, k.rl, Q, n, false, launches)) != ZRT_OK) return rc;
+    // the fan-out: items fetched like a primary launch's, on launch 0's
+    // shade counter, appended to launch 1's queue
+    W.fetch8 = W.fetch8s;
+    hipLaunchKernelGGL(k.f_fan, dim3(k.grid_fan), dim3(kTraceThreads), k.pl.lds_shade, c->stream, R);
+    ++*launches;
+    HIP_TRY(hipGetLastError());
+    return ZRT_OK;
+}
+
+// The rest of the chunk: launch k as a render runs a bounce launch (launch 0
+// of the per-sample records by the first segment's rule), then
+// wf_resolve_kernel (P = n, one pass) into d_lin / d_rgb.
+static int rad_chunk_rest(zrt_context* c, RadCall& k, uint32_t n, uint32_t* launches) {
+    zrt_context::PassSet& ps = c->set[0];
+    WfParams& W = k.R.w;
+    const uint32_t items = n * k.S;
+    int rc;
+    for (uint32_t i = k.per_sample ? 0u : 1u; i < k.nb; ++i) {
+        const bool park = i == 0 ? k.park_first : k.park_next;
+        bounce_params(W, ps, i, k.mb);
+        if ((rc = launch_bounce(k.pl, k.grids, W, c->stream, park, i + 1 == k.nb, nullptr)) != ZRT_OK) return rc;
+        *launches += park ? 2 : 1;
+    }
+    hipLaunchKernelGGL(wf_resolve_kernel, dim3((n + kResPix - 1) / kResPix), dim3(kBlock), 0, c->stream, ps.term,
+                       ps.stk4, ps.stk2, items, n, k.S, k.mb, c->d_acc, 1, 1, k.inv_spp, c->d_rgb, c->d_lin);
+    ++*launches;
+    HIP_TRY(hipGetLastError());
+    return ZRT_OK;
+}
+
 // Scene.traceRayRecursive (stage3.zig:188-220) for a batch of rays: see
 // include/zrt.h, the kernels' comment (RadParams) and DESIGN 5.12.  The launch
 // plan is the one a render resolves (resolve_plan); the first segment takes
@@ -5284,7 +5641,7 @@ extern "C" int zrt_context_radiance(zrt_context* c, const zrt_radiance_batch* b,
     if (!b->rays || !b->radiance) return ZRT_ERR_INVALID_ARG;
     DeviceGuard g(c->device);
 
-    const uint32_t S = b->num_samples, mb = b->max_bounce, nb = std::max<uint32_t>(mb, 1);
+    const uint32_t S = b->num_samples, mb = b->max_bounce;
     st.samples = b->num_rays * S;
     if (mb == 0) {
         // traceRayRecursive at depth 0 returns 0: the sum of S zeros times 1 / S, and toRGB(0) = 0
@@ -5300,134 +5657,30 @@ extern "C" int zrt_context_radiance(zrt_context* c, const zrt_radiance_batch* b,
         return ZRT_OK;
     }
 
-    const bool per_sample = (b->flags & ZRT_RADIANCE_PER_SAMPLE) != 0;
-    const uint64_t first_n = per_sample ? b->num_rays * S : b->num_rays;
-    const bool want_first = (b->flags & ZRT_TRACE_PARK) || first_n >= kTraceParkMin;
-    LaunchPlan pl;
+    RadCall k;
     int rc;
-    if ((rc = resolve_plan(c, b->flags, false, want_first || nb > 1, b->num_rays * S >= kSetsMinSamples, pl)) != ZRT_OK)
+    if ((rc = rad_plan(c, b->flags, b->num_rays, S, mb, b->seed, b->on_device ? 0ull : 24ull, 4ull * c->rays_cap, k)) !=
+        ZRT_OK)
         return rc;
-    const bool park_next = pl.park_ok, park_first = pl.park_ok && want_first, park_any = pl.park;
-    const bool lmats = c->nmat <= kLdsMats;
-    const RadFn f_fan = nb == 1 ? (lmats ? (RadFn)rad_fanout_kernel<true, true> : (RadFn)rad_fanout_kernel<false, true>)
-                                : (lmats ? (RadFn)rad_fanout_kernel<true, false> : (RadFn)rad_fanout_kernel<false, false>);
-
-    // chunk size: at most kTraceChunk rays, its n * S items below 2^31 and
-    // within the memory budget of a render's pass (its per-item bytes,
-    // device_budget); S <= 65535 always fits at 64 rays
-    zrt_context::PassSet& ps = c->set[0];
-    const uint64_t per_item = 96ull + 16ull + 16ull + 32ull * nb;
-    const uint64_t per_ray = per_item * S + 24ull + 15ull + (b->on_device ? 0ull : 24ull);
-    const size_t held = 4ull * (c->rays_cap + c->nrays_cap + c->lin_cap) + c->rgb_cap + c->bfc_bytes + c->esc_extra + held_bytes(ps);
-    const size_t budget = device_budget(c, held);
-    uint64_t chunk = std::min<uint64_t>(kTraceChunk, 0x7FFFFF00ull / S);
-    chunk = std::max<uint64_t>(64, std::min<uint64_t>(chunk, budget / per_ray));
-    chunk = std::min<uint64_t>(chunk, b->num_rays);
-    const uint64_t T = chunk * S;                  // items of the largest chunk
-    const uint64_t hit_need = std::max<uint64_t>(park_any ? T : 0, per_sample ? 0 : chunk);
-    if (!b->on_device && (rc = grow(&c->d_rays, &c->rays_cap, 6 * chunk)) != ZRT_OK) return rc;
-    if (!per_sample && (rc = grow(&c->d_nrays, &c->nrays_cap, 6 * chunk)) != ZRT_OK) return rc;
-    if ((rc = grow(&c->d_lin, &c->lin_cap, 3 * chunk)) != ZRT_OK) return rc;
-    if ((rc = grow(&c->d_rgb, &c->rgb_cap, 3 * chunk)) != ZRT_OK) return rc;
-    if ((rc = grow_pass_set(ps, T, nb, mb, hit_need)) != ZRT_OK) return rc;
-    // capacity guard of the rest: every buffer a launch below writes holds
-    // what a chunk's launches write; a chunk's items fit 31 bits
-    if ((!b->on_device && shortfall("rays", c->d_rays, c->rays_cap, 6 * chunk)) ||
-        (!per_sample && shortfall("unit rays", c->d_nrays, c->nrays_cap, 6 * chunk)) ||
-        shortfall("linear", c->d_lin, c->lin_cap, 3 * chunk) || shortfall("rgb", c->d_rgb, c->rgb_cap, 3 * chunk) ||
-        chunk == 0 || chunk > kTraceChunk || T > 0x7FFFFF00ull)
-        return ZRT_ERR_INVALID_ARG;
-    if ((rc = event_pool(c->ev_trace, 2)) != ZRT_OK) return rc;
-
-    // occupancy-sized persistent grids
-    BounceGrids grids;
-    if ((rc = bounce_grids(c, pl, park_any, (!park_next && nb > 1) || (per_sample && !park_first), grids)) != ZRT_OK)
-        return rc;
-    RayLaunch rl{};
-    uint32_t grid_fan = 0;
-    if (!per_sample) {
-        if ((rc = ray_launch(c, pl, false, park_first, rl)) != ZRT_OK) return rc;
-        if ((rc = resident_blocks(c, (const void*)f_fan, kTraceThreads, pl.lds_shade, &grid_fan)) != ZRT_OK) return rc;
+    const uint64_t chunk = k.chunk;
+    if (!b->on_device) {
+        if ((rc = grow(&c->d_rays, &c->rays_cap, 6 * chunk)) != ZRT_OK) return rc;
+        if (shortfall("rays", c->d_rays, c->rays_cap, 6 * chunk)) return ZRT_ERR_INVALID_ARG;
     }
-
-    RadParams R;
-    memset(&R, 0, sizeof R);
-    WfParams& W = R.w;
-    scene_params(c, W.t);
-    W.t.max_bounce = mb;
-    W.t.seed = b->seed;
-    W.t.counter = c->d_counter;
-    W.t.stats = c->d_stats;
-    W.stk4 = ps.stk4;
-    W.stk2 = ps.stk2;
-    W.term = ps.term;
-    W.hit = ps.hit;
-    park_params(c, pl, W);
-    R.ctr = c->d_counter;
-    R.nrays = c->d_nrays;
-    R.q = ps.q1;                                   // launch 0 reads q1 (bounce_params)
-    R.n_in8 = region_counts(ps, 0);
-    // stage3.zig:223 inv_num_samples = ones / splat(spp)  (f32 division)
-    const float inv_spp = 1.0f / (float)S;
 
     HIP_TRY(hipMemsetAsync(c->d_stats, 0, 512, c->stream));
     HIP_TRY(hipEventRecord(c->ev_begin, c->stream));
     uint32_t launches = 0;
     for (uint64_t off = 0; off < b->num_rays; off += chunk) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, b->num_rays - off);
-        const uint32_t items = n * S;              // <= T < 2^31
-        if (b->on_device) {
-            R.rays = b->rays + 6 * off;
-        } else {
+        const float* rays = b->rays + 6 * off;
+        if (!b->on_device) {
             HIP_TRY(hipMemcpyAsync(c->d_rays, b->rays + 6 * off, 24ull * n, hipMemcpyHostToDevice, c->stream));
-            R.rays = c->d_rays;
+            rays = c->d_rays;
             HIP_TRY(hipEventRecord(c->ev_trace[0], c->stream));
         }
-        R.n = n;
-        R.key0 = (uint32_t)(b->index_base + off);
-        // the counters of every launch (wfc_words); the pack kernels write launch 0's region counts
-        HIP_TRY(hipMemsetAsync(ps.wfc, 0, 4ull * wfc_words(mb), c->stream));
-        HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
-        W.t.P = n;
-        W.t.S = S;
-        W.t.total = items;
-        W.t.sdiv = div_magic(S);
-        W.T = items;
-        bounce_params(W, ps, 0, mb);
-        if (per_sample) {
-            hipLaunchKernelGGL(rad_pack_samples_kernel, dim3((items + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, R);
-            ++launches;
-            HIP_TRY(hipGetLastError());
-        } else {
-            hipLaunchKernelGGL(rad_pack_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, R);
-            ++launches;
-            // the first segments: one per ray, launch 0's queue as the identity queue
-            QueryParams Q;
-            memset(&Q, 0, sizeof Q);
-            Q.w = W;
-            Q.w.t.max_bounce = 1;
-            Q.rays = c->d_nrays;
-            Q.hits = reinterpret_cast<uint32_t*>(ps.hit);
-            Q.ctr = c->d_counter;
-            if ((rc = trace_first_segments(c, pl, rl, Q, n, false, &launches)) != ZRT_OK) return rc;
-            // the fan-out: items fetched like a primary launch's, on launch 0's
-            // shade counter, appended to launch 1's queue
-            W.fetch8 = W.fetch8s;
-            hipLaunchKernelGGL(f_fan, dim3(grid_fan), dim3(kTraceThreads), pl.lds_shade, c->stream, R);
-            ++launches;
-            HIP_TRY(hipGetLastError());
-        }
-        // launch k as a render runs a bounce launch; launch 0 of the per-sample records by the first segment's rule
-        for (uint32_t k = per_sample ? 0u : 1u; k < nb; ++k) {
-            const bool park = k == 0 ? park_first : park_next;
-            bounce_params(W, ps, k, mb);
-            if ((rc = launch_bounce(pl, grids, W, c->stream, park, k + 1 == nb, nullptr)) != ZRT_OK) return rc;
-            launches += park ? 2 : 1;
-        }
-        hipLaunchKernelGGL(wf_resolve_kernel, dim3((n + kResPix - 1) / kResPix), dim3(kBlock), 0, c->stream, ps.term,
-                           ps.stk4, ps.stk2, items, n, S, mb, c->d_acc, 1, 1, inv_spp, c->d_rgb, c->d_lin);
-        ++launches;
-        HIP_TRY(hipGetLastError());
+        if ((rc = rad_chunk_first(c, k, rays, n, (uint32_t)(b->index_base + off), &launches)) != ZRT_OK) return rc;
+        if ((rc = rad_chunk_rest(c, k, n, &launches)) != ZRT_OK) return rc;
         if (b->on_device) {
             HIP_TRY(hipMemcpyAsync(b->radiance + 3 * off, c->d_lin, 12ull * n, hipMemcpyDeviceToDevice, c->stream));
             if (b->rgb)
@@ -5445,7 +5698,152 @@ extern "C" int zrt_context_radiance(zrt_context* c, const zrt_radiance_batch* b,
     unsigned long long hs[1];
     HIP_TRY(copy_sync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
     // the reference traces a shared first segment once per sample
-    st.segments = hs[0] + (per_sample ? 0ull : b->num_rays * (uint64_t)(S - 1));
+    st.segments = hs[0] + (k.per_sample ? 0ull : b->num_rays * (uint64_t)(S - 1));
+    if (stats) *stats = st;
+    return ZRT_OK;
+}
+
+// Light probes: see include/zrt.h, the kernels' comment (LightProbeParams) and
+// DESIGN 5.19.  The N * D (probe, direction) items are a radiance call's rays,
+// made on the device; per chunk of n items, all on the context's stream and
+// pass set 0:
+//   light_probe_gen_kernel -> the chunk's ray row in d_rays;
+//   rad_chunk_first (rad_pack_kernel, the first segments, rad_fanout_kernel);
+//   light_probe_reduce_kernel, kLpTake: t of the first hits, before launch 1
+//   reuses their records;
+//   rad_chunk_rest (the bounce launches, wf_resolve_kernel);
+//   light_probe_reduce_kernel, kLpFold: the chunk's items into the sums of its
+//   probes; the probes that end in the chunk are stored.
+// d_rays holds the ray row and a host batch's positions of the chunk's probes;
+// d_hits the t row, the two carry rows and a host batch's output rows (sh, distance,
+// hits of the chunk's probes, the directions of its items); a device batch's
+// outputs are written in place.  Each use writes what it reads first.
+extern "C" int zrt_context_light_probes(zrt_context* c, const zrt_light_probe_batch* b, zrt_stats* stats) {
+    if (!c || !light_probe_batch_ok(b, kRadianceFlags & ~ZRT_RADIANCE_PER_SAMPLE)) return ZRT_ERR_INVALID_ARG;
+    // the scatter mask holds one bit per bounce slot, the queue 16 bits of depth
+    if (b->max_bounce > 32) return ZRT_ERR_UNSUPPORTED;
+    zrt_stats st{};
+    if (b->num_probes == 0) { if (stats) *stats = st; return ZRT_OK; }
+    DeviceGuard g(c->device);
+
+    const uint32_t D = b->num_directions, S = b->num_samples, mb = b->max_bounce;
+    const uint64_t N = b->num_probes, total = N * D;
+    const bool dev = b->on_device != 0;
+    st.samples = total * S;
+    // bytes per item beyond a device radiance call's: the ray row and t; a host
+    // batch's directions; with D = 1 an item is a probe: its position and rows
+    const uint64_t stage = 24ull + 4ull + (dev ? 0ull : 12ull + (12ull + 120ull + D - 1) / D);
+    RadCall k;
+    int rc;
+    if ((rc = rad_plan(c, b->flags, total, S, mb, b->seed, stage, 4ull * (c->rays_cap + c->hits_cap), k)) != ZRT_OK)
+        return rc;
+    const uint64_t chunk = k.chunk;
+    const uint64_t npmax = std::min<uint64_t>(N, (chunk + D - 1) / D + 1);   // probes with an item in one chunk
+    // words of d_rays: the ray row, a host batch's positions
+    const uint64_t off_pos = 6 * chunk, rays_words = off_pos + (dev ? 0 : 3 * npmax);
+    // words of d_hits: t, the two carry rows, a host batch's sh, distance, hits and directions
+    const uint64_t off_carry = chunk, off_sh = off_carry + 64, off_dist = off_sh + (!dev && b->sh ? 27 * npmax : 0),
+                   off_hits = off_dist + (!dev && b->distance ? 2 * npmax : 0),
+                   off_dirs = off_hits + (!dev && b->hits ? npmax : 0),
+                   hits_words = off_dirs + (!dev && b->directions ? 3 * chunk : 0);
+    if ((rc = grow(&c->d_rays, &c->rays_cap, rays_words)) != ZRT_OK) return rc;
+    if ((rc = grow(&c->d_hits, &c->hits_cap, hits_words)) != ZRT_OK) return rc;
+    // capacity guard: every buffer a launch below writes holds a chunk
+    if (shortfall("rays, positions", c->d_rays, c->rays_cap, rays_words) ||
+        shortfall("t, carry, rows", c->d_hits, c->hits_cap, hits_words))
+        return ZRT_ERR_INVALID_ARG;
+
+    LightProbeParams P;
+    memset(&P, 0, sizeof P);
+    P.rays = c->d_rays;
+    P.zig = c->d_zig;
+    P.seed = b->seed;
+    P.D = D;
+    P.hit = c->set[0].hit;
+    P.t = reinterpret_cast<float*>(c->d_hits);
+    P.lin = c->d_lin;
+    P.stats = c->d_stats;
+    float* const s_pos = c->d_rays + off_pos;
+    float* const s_sh = reinterpret_cast<float*>(c->d_hits + off_sh);
+    float* const s_dist = reinterpret_cast<float*>(c->d_hits + off_dist);
+    uint32_t* const s_hits = c->d_hits + off_hits;
+    float* const s_dirs = reinterpret_cast<float*>(c->d_hits + off_dirs);
+
+    HIP_TRY(hipMemsetAsync(c->d_stats, 0, 512, c->stream));
+    HIP_TRY(hipEventRecord(c->ev_begin, c->stream));
+    uint32_t launches = 0, parity = 0;
+    for (uint64_t off = 0; off < total; off += chunk) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, total - off);
+        const uint64_t p0 = off / D, p1 = (off + n - 1) / D;
+        const uint32_t np = (uint32_t)(p1 - p0 + 1);                  // <= npmax
+        const uint32_t done = np - ((p1 + 1) * D <= off + n ? 0u : 1u);   // probes p0 .. that end in this chunk
+        if (np > npmax) return ZRT_ERR_INVALID_ARG;                   // (never)
+        if (dev) {
+            P.pos = b->positions + 3 * p0;
+            P.dirs = b->directions ? b->directions + 3 * off : nullptr;
+            P.sh = b->sh ? b->sh + 27 * p0 : nullptr;
+            P.dist = b->distance ? b->distance + 2 * p0 : nullptr;
+            P.hits = b->hits ? b->hits + p0 : nullptr;
+        } else {
+            HIP_TRY(hipMemcpyAsync(s_pos, b->positions + 3 * p0, 12ull * np, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(hipEventRecord(c->ev_trace[0], c->stream));
+            P.pos = s_pos;
+            P.dirs = b->directions ? s_dirs : nullptr;
+            P.sh = b->sh ? s_sh : nullptr;
+            P.dist = b->distance ? s_dist : nullptr;
+            P.hits = b->hits ? s_hits : nullptr;
+        }
+        P.key0 = (uint32_t)(b->index_base + off);
+        P.j0 = (uint32_t)(off - p0 * D);
+        P.n = n;
+        P.np = np;
+        // the carry rows alternate: the fold's first probe reads what the previous chunk's last one left,
+        // its last probe writes the other row -- two half-waves of one launch, in no order
+        P.carry_in = reinterpret_cast<const float*>(c->d_hits + off_carry + 32 * (parity ^ 1u));
+        P.carry_out = reinterpret_cast<float*>(c->d_hits + off_carry + 32 * parity);
+        parity ^= 1u;
+        const uint32_t nblk = (n + kBlock - 1) / kBlock;
+        hipLaunchKernelGGL(light_probe_gen_kernel, dim3((nblk + kLpGenItems - 1) / kLpGenItems), dim3(kBlock), 0, c->stream,
+                           P);
+        ++launches;
+        HIP_TRY(hipGetLastError());
+        if ((rc = rad_chunk_first(c, k, c->d_rays, n, P.key0, &launches)) != ZRT_OK) return rc;
+        P.mode = kLpTake;
+        hipLaunchKernelGGL(light_probe_reduce_kernel, dim3((nblk + kLpTakeItems - 1) / kLpTakeItems), dim3(kBlock), 0,
+                           c->stream, P);
+        ++launches;
+        HIP_TRY(hipGetLastError());
+        if ((rc = rad_chunk_rest(c, k, n, &launches)) != ZRT_OK) return rc;
+        P.mode = kLpFold;
+        hipLaunchKernelGGL(light_probe_reduce_kernel, dim3((32u * np + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, P);
+        ++launches;
+        HIP_TRY(hipGetLastError());
+        if (dev) {
+            if (b->radiance)
+                HIP_TRY(hipMemcpyAsync(b->radiance + 3 * off, c->d_lin, 12ull * n, hipMemcpyDeviceToDevice, c->stream));
+        } else {
+            HIP_TRY(hipEventRecord(c->ev_trace[1], c->stream));
+            if (b->radiance) HIP_TRY(copy_sync(b->radiance + 3 * off, c->d_lin, 12ull * n, hipMemcpyDeviceToHost, c->stream));
+            if (b->directions)
+                HIP_TRY(copy_sync(b->directions + 3 * off, s_dirs, 12ull * n, hipMemcpyDeviceToHost, c->stream));
+            if (done != 0u) {
+                if (b->sh) HIP_TRY(copy_sync(b->sh + 27 * p0, s_sh, 108ull * done, hipMemcpyDeviceToHost, c->stream));
+                if (b->distance)
+                    HIP_TRY(copy_sync(b->distance + 2 * p0, s_dist, 8ull * done, hipMemcpyDeviceToHost, c->stream));
+                if (b->hits) HIP_TRY(copy_sync(b->hits + p0, s_hits, 4ull * done, hipMemcpyDeviceToHost, c->stream));
+            }
+            HIP_TRY(hipStreamSynchronize(c->stream));   // (a chunk that copied nothing back: the events)
+            float t = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&t, c->ev_trace[0], c->ev_trace[1]));
+            st.trace_kernel_ms += t;
+        }
+    }
+    if ((rc = finish_query(c, dev, launches, st)) != ZRT_OK) return rc;
+    unsigned long long hs[kLpStat + 1];
+    HIP_TRY(copy_sync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+    // the reference traces a shared first segment once per sample
+    st.segments = hs[0] + total * (uint64_t)(S - 1);
+    st.hits = hs[kLpStat];
     if (stats) *stats = st;
     return ZRT_OK;
 }

@@ -88,6 +88,14 @@ int tile_pixels(uint32_t w, uint32_t h, uint32_t tile, uint32_t rank, uint32_t n
 // types.  `trace_flags`: the flags zrt_context_trace accepts.
 bool direct_batch_ok(const zrt_direct_batch* b, uint32_t trace_flags);
 
+// zrt_context_light_probes' argument checks, which need no device (capi.cpp):
+// the batch's scalar fields, then -- num_probes != 0 -- its size (at most 2^47
+// probes) and its pointers.
+// `probe_flags`: the flags the call accepts (zrt_context_radiance's without
+// ZRT_RADIANCE_PER_SAMPLE).  max_bounce > 32 is not refused here: it is
+// ZRT_ERR_UNSUPPORTED, the caller's to tell apart.
+bool light_probe_batch_ok(const zrt_light_probe_batch* b, uint32_t probe_flags);
+
 // The packed RGB8 of a context's last render (device memory on its device,
 // 3 * pixels bytes in its rank's zrt_tile_pixels order): what a device group
 // gathers (group.hip).

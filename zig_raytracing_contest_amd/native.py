@@ -206,6 +206,14 @@ class DirectBatch(C.Structure):
                 ("num_lights", C.c_uint32), ("max_crossings", C.c_uint32)]
 
 
+class LightProbeBatch(C.Structure):
+    _fields_ = [("num_probes", C.c_uint64), ("positions", C.c_void_p), ("sh", C.c_void_p), ("distance", C.c_void_p),
+                ("hits", C.c_void_p), ("directions", C.c_void_p), ("radiance", C.c_void_p), ("on_device", C.c_uint32),
+                ("flags", C.c_uint32), ("num_directions", C.c_uint32), ("num_samples", C.c_uint32),
+                ("max_bounce", C.c_uint32), ("_reserved", C.c_uint32), ("seed", C.c_uint64),
+                ("index_base", C.c_uint64)]
+
+
 class RadianceBatch(C.Structure):
     _fields_ = [("num_rays", C.c_uint64), ("rays", C.c_void_p), ("radiance", C.c_void_p), ("rgb", C.c_void_p),
                 ("on_device", C.c_uint32), ("flags", C.c_uint32), ("num_samples", C.c_uint32),
@@ -222,6 +230,7 @@ EXPORTS = [
     "zrt_group_create", "zrt_group_create_built", "zrt_group_render", "zrt_group_context", "zrt_group_destroy",
     "zrt_context_radiance", "zrt_context_segments", "zrt_context_surface", "zrt_context_transmittance",
     "zrt_context_features", "zrt_context_occlusion", "zrt_context_direct",
+    "zrt_context_light_probes",
 ]
 
 
@@ -268,6 +277,8 @@ def lib():
     L.zrt_context_occlusion.argtypes = [C.c_void_p, C.POINTER(OcclusionBatch), C.POINTER(Stats)]
     if hasattr(L, "zrt_context_direct"):   # (a build from before this query: tools/ A/B baselines only)
         L.zrt_context_direct.argtypes = [C.c_void_p, C.POINTER(DirectBatch), C.POINTER(Stats)]
+    if hasattr(L, "zrt_context_light_probes"):   # (likewise)
+        L.zrt_context_light_probes.argtypes = [C.c_void_p, C.POINTER(LightProbeBatch), C.POINTER(Stats)]
     if hasattr(L, "zrt_group_create"):     # ABI 2 (an ABI-1 build: tools/ A/B baselines only)
         L.zrt_group_create.argtypes = [C.POINTER(Scene), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
         L.zrt_group_create_built.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -885,6 +896,72 @@ class Context:
             res["hits"] = rec
         elif hits:
             res.update(t=rec["t"].copy(), u=rec["u"].copy(), v=rec["v"].copy(), triangle=rec["triangle"].copy())
+        return res
+
+    def light_probes_raw(self, num_probes: int, positions_ptr, sh_ptr, distance_ptr, hits_ptr, directions_ptr,
+                         radiance_ptr, on_device: bool, num_directions: int, spp: int, max_bounce: int, seed: int = 0,
+                         index_base: int = 0, flags: int = 0, reserved: int = 0):
+        """zrt_context_light_probes on raw pointers; returns the stats dict."""
+        batch = LightProbeBatch(int(num_probes), positions_ptr, sh_ptr, distance_ptr, hits_ptr, directions_ptr,
+                                radiance_ptr, 1 if on_device else 0, int(flags), int(num_directions), int(spp),
+                                int(max_bounce), int(reserved), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                int(index_base) & 0xFFFFFFFFFFFFFFFF)
+        st = Stats()
+        check(lib().zrt_context_light_probes(self._h, C.byref(batch), C.byref(st)), "zrt_context_light_probes")
+        return st.as_dict()
+
+    def light_probes(self, positions, num_directions: int, spp: int, max_bounce: int, seed: int = 0,
+                     index_base: int = 0, flags: int = 0, sh: bool = True, distance: bool = False, hits: bool = False,
+                     directions: bool = False, radiance: bool = False):
+        """The light arriving at each of n points (zrt_context_light_probes):
+        `num_directions` random unit vectors per point, made on the device from
+        the stream (seed, index_base + point * num_directions + j, sample
+        65535), the path tracer's radiance along each (`spp` paths of at most
+        `max_bounce` segments, as radiance()), projected onto the nine order-2
+        real spherical harmonics and summed in direction order.
+
+        An (n, 3) float32 numpy array gives, each only when asked, {"sh":
+        (n, 9, 3) float32 -- coefficient k, RGB --, "distance": (n, 2) float32,
+        the mean t and t * t of the first hits over all directions, "hits":
+        (n,) uint32, the directions that hit, "directions" and "radiance":
+        (n, num_directions, 3) float32, "stats"}.  "stats" holds "segments",
+        "samples" and "hits" (the sum of the hits plane) in every call.
+
+        An (n, 3) float32 CUDA tensor (torch-ROCm) on the context's device is
+        read in place, after a sync of torch's current stream: the outputs are
+        CUDA tensors of the same shapes ("hits" int32)."""
+        if not (sh or distance or hits or directions or radiance):
+            raise ValueError("light_probes: one output at least must be asked for")
+        D = int(num_directions)
+        torch = None
+        if hasattr(positions, "is_cuda"):
+            import torch
+            if not positions.is_cuda or positions.dtype != torch.float32 or positions.dim() != 2 or \
+                    positions.shape[1] != 3:
+                raise ValueError("light_probes: an (n, 3) float32 CUDA tensor expected")
+            pos = positions.contiguous()
+            n = int(pos.shape[0])
+            new = lambda shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=pos.device)
+            i32 = torch.int32
+            ptr = lambda x: x.data_ptr() if x is not None and n else None
+        else:
+            pos = np.ascontiguousarray(positions, np.float32)
+            if pos.ndim != 2 or pos.shape[1] != 3:
+                raise ValueError("light_probes: an (n, 3) array expected")
+            n = pos.shape[0]
+            new = lambda shape, dt=np.float32: np.empty(shape, dt)
+            i32 = np.uint32
+            ptr = lambda x: x.ctypes.data if x is not None and n else None
+        out = {"sh": new((n, 9, 3)) if sh else None, "distance": new((n, 2)) if distance else None,
+               "hits": new((n,), i32) if hits else None, "directions": new((n, D, 3)) if directions else None,
+               "radiance": new((n, D, 3)) if radiance else None}
+        if torch:
+            torch.cuda.current_stream(pos.device).synchronize()
+        st = self.light_probes_raw(n, ptr(pos), ptr(out["sh"]), ptr(out["distance"]), ptr(out["hits"]),
+                                   ptr(out["directions"]), ptr(out["radiance"]), bool(torch), D, spp, max_bounce, seed,
+                                   index_base, flags)
+        res = {k: v for k, v in out.items() if v is not None}
+        res["stats"] = st
         return res
 
     def radiance_raw(self,num_rays: int, rays_ptr, radiance_ptr, rgb_ptr, on_device: bool, spp: int,
