@@ -607,11 +607,33 @@ __global__ __launch_bounds__(kBlock) void esc_sat_fill_kernel(const uint2* __res
         sat[(uint64_t)(z + 1) * n01 + (uint64_t)(y + 1) * n0 + x + 1] = c.x < c.y ? 1u : 0u;
     }
 }
-// prefix sums along one axis of the (n0 x n1 x n2) volume: one thread per line
+// The same for a batch of per-direction occupancies (escape.h
+// esc_dir_occupied): volume k of the batch is cull bin cb0 + k's.
+__global__ __launch_bounds__(kBlock) void esc_dir_fill_kernel(const uint2* __restrict__ cells,
+                                                              const float* __restrict__ pos, uint32_t r0, uint32_t r1,
+                                                              uint32_t ncells, uint32_t n0, uint32_t n01, uint64_t vol,
+                                                              uint32_t cb0, uint32_t ncb, uint32_t* __restrict__ sat) {
+    const uint64_t total = (uint64_t)ncells * ncb;
+    for (uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (uint64_t)gridDim.x * kBlock) {
+        const uint32_t k = (uint32_t)(i / ncells), ci = (uint32_t)(i - (uint64_t)k * ncells);
+        const uint2 c = cells[ci];
+        const uint32_t x = ci % r0, y = (ci / r0) % r1, z = ci / r0 / r1;
+        const bool occ = esc_dir_occupied(c.x, c.y, [&](uint32_t r, float* e1, float* e2) {
+            for (uint32_t j = 0; j < 3; ++j) {
+                e1[j] = __uint_as_float(tri_word(pos, r, 3 + j));
+                e2[j] = __uint_as_float(tri_word(pos, r, 6 + j));
+            }
+        }, cb0 + k);
+        sat[k * vol + (uint64_t)(z + 1) * n01 + (uint64_t)(y + 1) * n0 + x + 1] = occ ? 1u : 0u;
+    }
+}
+// prefix sums along one axis of the (n0 x n1 x n2) volume: one thread per
+// line; blockIdx.y: the volume of a batch
 __global__ __launch_bounds__(kBlock) void esc_sat_scan_kernel(uint32_t* __restrict__ sat, uint32_t n0, uint32_t n1,
                                                               uint32_t n2, uint32_t axis) {
     const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
     const uint64_t n01 = (uint64_t)n0 * n1;
+    sat += (uint64_t)blockIdx.y * n01 * n2;
     uint64_t base, stride;
     uint32_t len;
     if (axis == 0) {
@@ -642,6 +664,28 @@ __global__ __launch_bounds__(kBlock) void esc_build_kernel(const uint32_t* __res
     const uint32_t res[3] = {r0, r1, r2};
     const float cs[3] = {cs0, cs1, cs2};
     const EscSat S{sat, r0 + 1u, (r0 + 1u) * (r1 + 1u)};
+    if (esc_compute_region(S, res, cs, sh, br % nb0, (br / nb0) % nb1, br / (nb0 * nb1), sub, bin))
+        atomicOr(&esc[(uint64_t)rg * kEscWords + (bin >> 5)], 1u << (bin & 31u));
+}
+// The direction-aware table (escape.h): one thread per (cull bin of the
+// batch, region, escape bin of the cull bin), cull bin outermost so that
+// neighbouring threads read the same summed-area table.
+__global__ __launch_bounds__(kBlock) void esc_build_dir_kernel(const uint32_t* __restrict__ sat, uint64_t vol,
+                                                               uint32_t cb0, uint32_t ncb, uint32_t r0, uint32_t r1,
+                                                               uint32_t r2, float cs0, float cs1, float cs2,
+                                                               uint32_t nb0, uint32_t nb1, uint32_t nbr, EscShape sh,
+                                                               uint32_t* __restrict__ esc) {
+    const uint64_t t = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t lg = esc_regions_lg(sh);
+    const uint64_t per = ((uint64_t)nbr << lg) * kEscPerCull;
+    if (t >= per * ncb) return;
+    const uint32_t k = (uint32_t)(t / per);
+    const uint64_t rem = t - (uint64_t)k * per;
+    const uint32_t rg = (uint32_t)(rem / kEscPerCull), bin = esc_bin_of_cull(cb0 + k, (uint32_t)(rem % kEscPerCull));
+    const uint32_t br = rg >> lg, sub = rg & ((1u << lg) - 1u);
+    const uint32_t res[3] = {r0, r1, r2};
+    const float cs[3] = {cs0, cs1, cs2};
+    const EscSat S{sat + k * vol, r0 + 1u, (r0 + 1u) * (r1 + 1u)};
     if (esc_compute_region(S, res, cs, sh, br % nb0, (br / nb0) % nb1, br / (nb0 * nb1), sub, bin))
         atomicOr(&esc[(uint64_t)rg * kEscWords + (bin >> 5)], 1u << (bin & 31u));
 }
@@ -722,17 +766,79 @@ int context_escape(zrt_context* c, bool forced) {
                       hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes <= free_b / 4 && bytes < (1ull << 32) &&
                       ((nbr << lg) * kEscNBin) / kBlock < (1ull << 31);
     if (fits) {
+        // Direction-aware (escape.h): one occupancy and summed-area table per
+        // cull bin, transient, in batches of as many volumes as fit a quarter
+        // of the memory that is free beside the table itself; if not even one
+        // fits, the plain region table as before.  ZRT_ESC_PLAIN=1 keeps the
+        // plain one too (tools/ A/B runs and the tests).
+        const uint64_t n0 = r[0] + 1ull, n1 = r[1] + 1ull, n2 = r[2] + 1ull, vol = n0 * n1 * n2;
+        uint32_t batch = 0;
+        if (!getenv("ZRT_ESC_PLAIN") && c->d_pos && free_b >= bytes)
+            batch = (uint32_t)std::min<uint64_t>(kBfcNBin, (free_b - bytes) / 4 / (4ull * vol));
+        // (a launch's 2^31 blocks)
+        while (batch && ((nbr << lg) * kEscPerCull * batch) / kBlock >= (1ull << 31)) batch /= 2;
         uint32_t* fine = nullptr;
-        if ((rc = build(sh, &fine)) != ZRT_OK) {
-            (void)hipFree(fine);
-            return rc;
+        struct Volumes {
+            uint32_t* p = nullptr;
+            ~Volumes() {
+                if (p) (void)hipFree(p);
+            }
+        } tmp;
+        if (batch && hipMalloc((void**)&tmp.p, 4ull * vol * batch) != hipSuccess) {
+            (void)hipGetLastError();
+            tmp.p = nullptr;
+            batch = 0;
+        }
+        if (!batch) {
+            if ((rc = build(sh, &fine)) != ZRT_OK) {
+                (void)hipFree(fine);
+                return rc;
+            }
+        } else {
+            hipError_t e = hipMalloc((void**)&fine, bytes);
+            if (e == hipSuccess) e = hipMemsetAsync(fine, 0, bytes, c->stream);
+            const uint64_t lines[3] = {n1 * n2, n0 * n2, n0 * n1};
+            for (uint32_t cb0 = 0; e == hipSuccess && cb0 < kBfcNBin; cb0 += batch) {
+                const uint32_t ncb = std::min<uint32_t>(batch, kBfcNBin - cb0);
+                e = hipMemsetAsync(tmp.p, 0, 4ull * vol * ncb, c->stream);
+                if (e != hipSuccess) break;
+                hipLaunchKernelGGL(esc_dir_fill_kernel, dim3(16384), dim3(kBlock), 0, c->stream, c->d_cells,
+                                   (const float*)c->d_pos, r[0], r[1], c->ncells, (uint32_t)n0, (uint32_t)(n0 * n1), vol,
+                                   cb0, ncb, tmp.p);
+                sc.mark(c, "escape table (per-direction occupancies)");
+                for (uint32_t a = 0; a < 3; ++a)
+                    hipLaunchKernelGGL(esc_sat_scan_kernel, dim3((uint32_t)((lines[a] + kBlock - 1) / kBlock), ncb),
+                                       dim3(kBlock), 0, c->stream, tmp.p, (uint32_t)n0, (uint32_t)n1, (uint32_t)n2, a);
+                sc.mark(c, "escape table (their prefix sums)");
+                const uint64_t nthr = (nbr << lg) * kEscPerCull * ncb;
+                hipLaunchKernelGGL(esc_build_dir_kernel, dim3((uint32_t)((nthr + kBlock - 1) / kBlock)), dim3(kBlock), 0,
+                                   c->stream, (const uint32_t*)tmp.p, vol, cb0, ncb, r[0], r[1], r[2],
+                                   c->grid.cell_size[0], c->grid.cell_size[1], c->grid.cell_size[2], c->occx_nb[0],
+                                   c->occx_nb[1], (uint32_t)nbr, sh, fine);
+                e = hipGetLastError();
+            }
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess) {
+                (void)hipFree(fine);
+                HIP_TRY(e);
+            }
         }
         HIP_TRY(hipStreamSynchronize(c->stream));
         (void)hipFree(c->d_esc);
         c->d_esc = fine;
         c->esc_extra = bytes - 4ull * kEscWords * nbr;
         c->esc_key = esc_walk_key(sh);
-        sc.mark(c, "escape table (regions)");
+        c->esc_dir = batch != 0;
+        sc.mark(c, c->esc_dir ? "escape table (regions, per direction bin)" : "escape table (regions)");
+        if (getenv("ZRT_WF_DEBUG")) {
+            std::vector<uint32_t> hf(bytes / 4);
+            HIP_TRY(hipMemcpy(hf.data(), fine, bytes, hipMemcpyDeviceToHost));
+            uint64_t nset = 0;
+            for (uint32_t x : hf) nset += (uint64_t)__builtin_popcount(x);
+            fprintf(stderr, "{\"zrt_escape\": {\"bytes\": %llu, \"per_direction\": %d, \"batch\": %u, "
+                    "\"brick_density\": %.4f, \"region_density\": %.4f}}\n", (unsigned long long)bytes,
+                    c->esc_dir ? 1 : 0, batch, c->esc_density, (double)nset / ((double)(nbr << lg) * kEscNBin));
+        }
     }
     return ZRT_OK;
 }

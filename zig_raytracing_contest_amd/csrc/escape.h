@@ -450,4 +450,57 @@ ZHD bool bfc_cull(const float e1[3], const float e2[3], uint32_t bin, double mar
     return true;
 }
 
+// ---------------------------------------------------------------------------
+// The direction-aware escape table (context.hip context_escape; host check
+// tests/cpp/escape_dir_check.cpp).
+//
+// The table above ends a walk only when no later cell HOLDS a ref.  But a ref
+// that bfc_cull rejects for a bin's whole cone cannot pass tri_ray for any ray
+// of that bin: a cell whose every ref is rejected that way cannot change
+// `nearest`, a tie or the break test, so for that bin it is an empty cell.
+// The region table is therefore built from one occupancy per cull bin
+// (kBfcNBin of them, each serving its (kEscBins / kBfcBins)^2 escape bins,
+// whose cones lie inside the cull bin's): a cell is occupied for the bin iff
+// it holds at least one ref that bfc_cull cannot reject (esc_dir_occupied; no
+// 32-ref limit, refs with non-finite edges or S > 2^120 are never rejected).
+// esc_compute_box runs unchanged on that occupancy's summed-area table.
+// Soundness is the header's argument with one more line: every cell the ray
+// visits from its start region on lies in the swept region, and every cell
+// there is empty or holds only refs with det_f32 < 1e-8 for every direction
+// of the cone, so no test there can pass and the hit so far stands.  Unlike
+// the plain table's, the start region itself may hold such refs, so a bit can
+// be set for a ray that starts on a surface and leaves it.  The cone argument
+// needs the direction inside bfc_cull's domain: a ray with !bfc_dir_ok(d)
+// never uses a bit (the park kernel's emask).  Plain occupancy is the union
+// over bins, every bound is monotone in the occupancy, so every bit of the
+// plain table is set in this one.
+// The brick-level table, its density statistic and the gate stay plain.
+// Cull bins, not the 384 escape bins' own narrower cones: a quarter of the
+// transient volumes and prefix passes; on the contest stand-in the cull bins
+// already reject 37% of the (ref, bin) pairs (tools/escape_sim.cpp).
+//
+// Whether a ray may use the table at all: Dda.neg without bit 3 (the header's
+// -inf / NaN crossing sequences) and a direction inside bfc_cull's domain.
+ZHD bool esc_ray_usable(uint32_t neg, v3 d) { return neg < 8u && bfc_dir_ok(d); }
+// Whether the cell with refs [rb, re) is occupied for cull bin `cb`;
+// edges(r, e1, e2) gives ref r's edges as tri_ray reads them.
+template <class Edges>
+ZHD bool esc_dir_occupied(uint32_t rb, uint32_t re, Edges edges, uint32_t cb, double margin = kBfcMargin,
+                          double eps = kEscEps) {
+    for (uint32_t r = rb; r < re; ++r) {
+        float e1[3], e2[3];
+        edges(r, e1, e2);
+        if (!bfc_cull(e1, e2, cb, margin, eps)) return true;
+    }
+    return false;
+}
+// The q-th escape bin served by cull bin `cb`, q < (kEscBins / kBfcBins)^2
+// (bfc_bin_of's inverse).
+constexpr uint32_t kEscPerCull = (kEscBins / kBfcBins) * (kEscBins / kBfcBins);
+ZHD uint32_t esc_bin_of_cull(uint32_t cb, uint32_t q) {
+    constexpr uint32_t m = kEscBins / kBfcBins;
+    const uint32_t f = cb / (kBfcBins * kBfcBins), cu = (cb / kBfcBins) % kBfcBins, cv = cb % kBfcBins;
+    return (f * kEscBins + cu * m + q / m) * kEscBins + cv * m + q % m;
+}
+
 }  // namespace zrt

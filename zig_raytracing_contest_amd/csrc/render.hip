@@ -1362,7 +1362,10 @@ __global__ __launch_bounds__(kParkBlock) ZRT_PARK_ATTR void wf_park_kernel(const
                                     // refill); the parity suite renders every scene
                                     // with the table forced on)
                                     eoff = (bin >> 5) * 4u;
-                                    emask = w.esc && s0.neg < 8u ? 1u << (bin & 31u) : 0u;
+                                    // (a direction outside bfc_cull's domain never
+                                    // uses a bit: the direction-aware table's cone
+                                    // argument, escape.h)
+                                    emask = w.esc && esc_ray_usable(s0.neg, d) ? 1u << (bin & 31u) : 0u;
                                     eb = ~0u;
                                     esc_slot[lane] = 0u;
                                 }

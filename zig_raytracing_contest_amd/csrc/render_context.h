@@ -150,6 +150,7 @@ struct zrt_context {
     bool esc_tried = false;         // context_escape ran (at the first render that can use it)
     double esc_density = 0.0;       // fraction of its (brick, bin) bits set
     uint32_t esc_key = 0;           // the table's shape for the walk (escape.h esc_walk_key; 0: brick-level)
+    bool esc_dir = false;           // ... built from one occupancy per cull bin (escape.h, the direction-aware table)
     size_t esc_extra = 0;           // its bytes beyond the brick-level table's (counted as held)
     // back-face cull masks (escape.h, context_bfcull): built at the first
     // render that can use them, if they fit kBfcBudget / mem_share
