@@ -856,6 +856,88 @@ typedef struct zrt_light_probe_batch {
  * render_ms, trace_kernel_ms and trace_launches as in zrt_context_trace. */
 int zrt_context_light_probes(zrt_context* ctx, const zrt_light_probe_batch* batch, zrt_stats* stats_or_null);
 
+/* ---- films: progressive renders (ABI 2, added) -------------------------- */
+
+/* A film keeps a frame's per-pixel sample sums between calls, so that a frame
+ * can be shown after a few samples and refined, rendered until a deadline,
+ * stopped and resumed, or given more samples without paying for the first ones
+ * again.  It is renderWorker's `pixel` of every pixel (stage3.zig:222-245: the
+ * `pixel = pixel.add(...)` chain over the samples, then `inv_num_samples`),
+ * stopped after any sample and picked up again.
+ *
+ * A film is the accumulator of one rank's share of a w x h frame: one f32 RGB
+ * sum per pixel of zrt_tile_pixels(w, h, tile_size, rank, num_ranks), in that
+ * order, and the number of samples summed so far (0 after create and reset).
+ * tile_size 0 = 64, num_ranks 0 = 1, as in zrt_render_config.  It lives on its
+ * context's device: destroy it before that context (zrt_film_destroy itself
+ * does not touch the context).  zrt_film_create refuses what zrt_tile_pixels
+ * refuses and a frame of more than 2^32 - 1 pixels. */
+typedef struct zrt_film zrt_film;
+int zrt_film_create(zrt_context* ctx, uint32_t w, uint32_t h, uint32_t tile_size, uint32_t rank,
+                    uint32_t num_ranks, zrt_film** out);
+/* samples = 0.  The sums are not cleared: the next call starts from +0 and
+ * never reads them. */
+int zrt_film_reset(zrt_film* film);
+/* Either pointer may be null. */
+int zrt_film_info(const zrt_film* film, uint32_t* n_owned, uint32_t* samples);
+/* Checkpoint and resume: host arrays of n_owned * 3 floats, the sums as they
+ * are stored (no division), bit for bit.  A film read after s samples and
+ * written into another film of the same shape -- of this or another context
+ * of the same scene -- continues exactly as the first would have.  Reading an
+ * empty film gives +0 everywhere.  zrt_film_write with samples 0 is a reset
+ * (sums may be null); samples > 65535 is ZRT_ERR_INVALID_ARG, the film
+ * untouched.  Both are synchronous on the context's stream. */
+int zrt_film_read(zrt_film* film, float* sums, uint32_t* samples_or_null);
+int zrt_film_write(zrt_film* film, const float* sums, uint32_t samples);
+void zrt_film_destroy(zrt_film* film);
+
+/* zrt_context_render for the next cfg->num_samples samples of a film.  With
+ * b = the film's samples and n = cfg->num_samples, for every owned pixel:
+ *   - the call traces the paths of samples b .. b + n - 1: exactly the paths a
+ *     zrt_context_render of the same camera, seed and max_bounce traces for
+ *     those sample indices, with the stream (seed, pixel, s);
+ *   - it adds their radiances to the pixel's sum in sample order
+ *     (stage3.zig:236-241), starting from the stored sum, or from +0 when
+ *     b == 0 (the stored bits are ignored then);
+ *   - it stores the sum and sets the film's samples to b + n;
+ *   - the outputs, if asked, are linear = sum * (1.0f / (float)(b + n))
+ *     (stage3.zig:223, :242 inv_num_samples) and rgb = toRGB(linear).  All four
+ *     zrt_outputs fields mean what they mean in a render; outputs may be null,
+ *     and a call that asks for none writes none on the device either.
+ * Consequence: after calls with counts n_1 .. n_k and one camera, seed and
+ * max_bounce, the outputs of the last call are, bit for bit, those of one
+ * zrt_context_render with num_samples = n_1 + .. + n_k -- in every kernel mode
+ * (cfg->flags) and for any samples_per_pass in any call, which may differ from
+ * call to call.
+ * The film stores nothing of the camera: a caller who changes it between calls
+ * gets the sum over the cameras (motion blur, lens sampling).  The same holds
+ * for seed and max_bounce.
+ * cfg: every field and flag means what it means in zrt_context_render,
+ * ZRT_FLAG_COUNT_STATS and ZRT_FLAG_KERNEL_TIMES included; num_devices and
+ * devices are ignored.  The kernels are chosen from this call's own
+ * n_owned * n (the 2^23-sample thresholds of the two pass sets and of the
+ * frustum bounds), and the tables a first big render builds are built as there.
+ * ZRT_ERR_INVALID_ARG before any device work, film and outputs untouched: a
+ * null context, film, camera or cfg; a film of another context; n == 0 or
+ * b + n > 65535 (the stream key gives the sample index 16 bits); camera->w or
+ * camera->h, cfg->tile_size, cfg->rank or cfg->num_ranks (after their defaults)
+ * that differ from the film's; whatever zrt_context_render refuses.
+ * max_bounce > 32 is ZRT_ERR_UNSUPPORTED, likewise.  A rank that owns no pixel
+ * returns ZRT_OK, and its film's samples still advance.  If a HIP call fails
+ * midway the film's contents are unspecified until zrt_film_reset or
+ * zrt_film_write.
+ * stats (may be null): of this call alone, as a render of n samples reports
+ * them -- samples = n_owned * n; segments, and with ZRT_FLAG_COUNT_STATS
+ * cells_visited, triangle_tests and hits, those of the paths of samples
+ * b .. b + n - 1, so that over a sequence of calls they add up to the one
+ * render's.  zrt_context_profile records the call as it records a render.
+ * Synchronous, one thread at a time per context; alternates freely with
+ * renders, every query and other films of the same context (the sums live in
+ * the film, not in the context's buffers). */
+int zrt_context_accumulate(zrt_context* ctx, zrt_film* film, const zrt_camera* camera,
+                           const zrt_render_config* cfg, const zrt_outputs* outputs_or_null,
+                           zrt_stats* stats_or_null);
+
 /* A device group: one context per entry of `devices` (HIP ordinals, repeats
  * allowed), the scene resident on each, rendered by one call -- Scene.render's
  * spawn + join of its workers (stage3.zig:247-256) across GPUs in one
@@ -892,7 +974,7 @@ enum {
     ZRT_KERNEL_PARK = 1,      /* wf_park_kernel, bounce trace */
     ZRT_KERNEL_SHADE = 2,     /* wf_shade_kernel, bounce shading */
     ZRT_KERNEL_BOUNCE = 3,    /* wf_kernel, bounce launch (lane walk / no OccX) */
-    ZRT_KERNEL_RESOLVE = 4,   /* wf_resolve_kernel / resolve_kernel */
+    ZRT_KERNEL_RESOLVE = 4,   /* wf_resolve_kernel / resolve_kernel (a film's call: their film forms) */
     ZRT_KERNEL_COUNT = 5,     /* trace_kernel (counting build) */
     ZRT_KERNEL_CLASSES = 8
 };

@@ -2,6 +2,7 @@
 // ziggurat tables, the per-rank tile order of the packed image.
 #include <sched.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -91,6 +92,10 @@ int tile_pixels(uint32_t w, uint32_t h, uint32_t tile, uint32_t rank, uint32_t n
     uint64_t n = 0;
     for (uint64_t t = rank; t < (uint64_t)tx * ty; t += nranks) {
         const uint32_t x0 = (uint32_t)(t % tx) * tile, y0 = (uint32_t)(t / tx) * tile;
+        if (!out) {                  // the count alone: the tile clipped to the image
+            n += (uint64_t)std::min(tile, w - x0) * std::min(tile, h - y0);
+            continue;
+        }
         for (uint32_t by = 0; by < tile; by += 8)
             for (uint32_t bx = 0; bx < tile; bx += 8)
                 for (uint32_t py = 0; py < 8; ++py)

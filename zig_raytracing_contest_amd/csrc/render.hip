@@ -21,6 +21,8 @@
 //     SAMPLE ORDER (renderWorker's `pixel = pixel.add(ray_color)`), scales by
 //     the f32 reciprocal of spp and quantizes with toRGB: the image is
 //     bit-identical to the recursion's for any scheduling.
+#include <new>
+
 #include "render_context.h"
 #include "escape.h"
 
@@ -1909,6 +1911,101 @@ __global__ __launch_bounds__(kBlock) void resolve_kernel(const float4* __restric
     rgb[3 * (size_t)q + 0] = c[0];
     rgb[3 * (size_t)q + 1] = c[1];
     rgb[3 * (size_t)q + 2] = c[2];
+    if (lin) { lin[3 * (size_t)q] = l.x; lin[3 * (size_t)q + 1] = l.y; lin[3 * (size_t)q + 2] = l.z; }
+}
+
+// The resolves of zrt_context_accumulate (a film): the two
+// kernels above with the sum kept AND shown.  `film` is the film's row of
+// per-pixel sums where those read and write d_acc; `first`: the film holds no
+// sample yet (the stored bits are not read); every pass stores the sum back,
+// and the call's last pass then also writes the image so far, sum * inv_spp
+// with inv_spp = 1 / (samples in the film after this call), into whichever of
+// rgb / lin is not null (a call that asked for no output stores 16 B per pixel
+// and nothing else).  wf_film_resolve_kernel's fold and its ordered per-pixel
+// add are wf_resolve_kernel's, statement for statement: the bit contract
+// (any split of N samples over calls == one render of N) rests on the same
+// f32 operations in the same order, so the two are kept apart rather than
+// templated into one body whose code for the render could shift.
+__global__ __launch_bounds__(kBlock) void wf_film_resolve_kernel(const float4* __restrict__ term,
+                                                                 const float4* __restrict__ stk4,
+                                                                 const float2* __restrict__ stk2, uint32_t T,
+                                                                 uint32_t P, uint32_t S, uint32_t max_bounce,
+                                                                 float4* film, int first, int last,
+                                                                 float inv_spp, uint8_t* rgb, float* lin) {
+    __shared__ float s_l[kResPix * kResRow];
+    const uint32_t q0 = blockIdx.x * kResPix;
+    const uint32_t np = min(kResPix, P - q0);
+    const uint32_t tid = threadIdx.x;
+    const uint32_t q = q0 + tid;
+    v3 px = mk(0, 0, 0);
+    if (tid < np && !first) { const float4 a = film[q]; px = mk(a.x, a.y, a.z); }
+    for (uint32_t c = 0; c < S; c += kResSmp) {
+        const uint32_t ns = min(kResSmp, S - c);
+        for (uint32_t m = tid; m < kResPix * kResSmp; m += kBlock) {
+            const uint32_t i = m / kResSmp, k = m % kResSmp;   // the block's pixel i, sample c + k
+            if (i < np && k < ns) {
+                const uint32_t item = (q0 + i) * S + c + k;
+                const float4 tm = term[item];
+                v3 L = mk(tm.x, tm.y, tm.z);
+                const uint32_t mask = __float_as_uint(tm.w);
+                for (int slot = (int)max_bounce - 1; slot >= 0; --slot) {
+                    if ((mask >> slot) & 1u) {
+                        const float4 a = stk4[(uint64_t)slot * T + item];
+                        v3 e = mk(0.0f, 0.0f, 0.0f);
+                        if (__float_as_uint(a.w) != 0u) {
+                            const float4 ee = reinterpret_cast<const float4*>(stk2)[(uint64_t)slot * T + item];
+                            e = mk(ee.x, ee.y, ee.z);
+                        }
+                        L = add(e, mul(mk(a.x, a.y, a.z), L));
+                    }
+                }
+                float* dst = s_l + i * kResRow + 3u * k;
+                dst[0] = L.x; dst[1] = L.y; dst[2] = L.z;
+            }
+        }
+        __syncthreads();
+        if (tid < np) {
+            const float* src = s_l + tid * kResRow;
+            for (uint32_t k = 0; k < ns; ++k) px = add(px, mk(src[3 * k], src[3 * k + 1], src[3 * k + 2]));
+        }
+        __syncthreads();
+    }
+    if (tid >= np) return;
+    film[q] = make_float4(px.x, px.y, px.z, 0.0f);
+    if (!last || (!rgb && !lin)) return;
+    const v3 l = mul(px, mk(inv_spp, inv_spp, inv_spp));
+    if (rgb) {
+        uint8_t c[3];
+        to_rgb(l, c);
+        rgb[3 * (size_t)q + 0] = c[0];
+        rgb[3 * (size_t)q + 1] = c[1];
+        rgb[3 * (size_t)q + 2] = c[2];
+    }
+    if (lin) { lin[3 * (size_t)q] = l.x; lin[3 * (size_t)q + 1] = l.y; lin[3 * (size_t)q + 2] = l.z; }
+}
+
+// ... and resolve_kernel's, for the counting megakernel.
+__global__ __launch_bounds__(kBlock) void film_resolve_kernel(const float4* __restrict__ out, uint32_t P,
+                                                              uint32_t S, float4* film, int first, int last,
+                                                              float inv_spp, uint8_t* rgb, float* lin) {
+    const uint32_t q = blockIdx.x * kBlock + threadIdx.x;
+    if (q >= P) return;
+    v3 px = mk(0, 0, 0);
+    if (!first) { const float4 a = film[q]; px = mk(a.x, a.y, a.z); }
+    for (uint32_t s = 0; s < S; ++s) {
+        const float4 c = out[(size_t)q * S + s];          // pixel-major items
+        px = add(px, mk(c.x, c.y, c.z));
+    }
+    film[q] = make_float4(px.x, px.y, px.z, 0.0f);
+    if (!last || (!rgb && !lin)) return;
+    const v3 l = mul(px, mk(inv_spp, inv_spp, inv_spp));
+    if (rgb) {
+        uint8_t c[3];
+        to_rgb(l, c);
+        rgb[3 * (size_t)q + 0] = c[0];
+        rgb[3 * (size_t)q + 1] = c[1];
+        rgb[3 * (size_t)q + 2] = c[2];
+    }
     if (lin) { lin[3 * (size_t)q] = l.x; lin[3 * (size_t)q + 1] = l.y; lin[3 * (size_t)q + 2] = l.z; }
 }
 
@@ -4206,10 +4303,20 @@ static int finish_render(zrt_context* c, const zrt_outputs* outs, KernelTimes& k
     return ZRT_OK;
 }
 
-extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const zrt_render_config* cfg,
-                                  const zrt_outputs* outs, zrt_stats* stats) {
+// zrt_context_render and zrt_context_accumulate: samples base .. base +
+// cfg->num_samples - 1 of every owned pixel (the stream key's sample index;
+// the passes split the call's own num_samples).  Without a film, base is 0 and
+// the sums live in d_acc between the passes of a frame of several; with one
+// they are read from (base > 0) and left in the film, the film's resolve
+// kernels take the places of wf_resolve_kernel / resolve_kernel with
+// 1 / (base + num_samples) as inv_spp, and d_rgb / d_lin are written only if
+// the call asked for them.  Everything else -- the split, the plan, the launch
+// sequence, the stats -- is the render's.
+static int render_samples(zrt_context* c, const zrt_camera* cam, const zrt_render_config* cfg,
+                          const zrt_outputs* outs, zrt_stats* stats, uint32_t base, zrt_film* film) {
     if (!c || !cam || !cfg) return ZRT_ERR_INVALID_ARG;
-    if (cfg->num_samples == 0 || cfg->num_samples > 65535) return ZRT_ERR_INVALID_ARG;
+    // (the stream key gives the sample index 16 bits)
+    if (cfg->num_samples == 0 || (uint64_t)base + cfg->num_samples > 65535) return ZRT_ERR_INVALID_ARG;
     if (cam->w == 0 || cam->h == 0 || (uint64_t)cam->w * cam->h > 0xFFFFFFFFull) return ZRT_ERR_INVALID_ARG;
     const uint32_t nranks = cfg->num_ranks ? cfg->num_ranks : 1;
     if (cfg->rank >= nranks) return ZRT_ERR_INVALID_ARG;
@@ -4224,7 +4331,12 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
     if ((rc = rank_pixels(c, cam, cfg, nranks)) != ZRT_OK) return rc;
     const uint32_t P = (uint32_t)c->pix.size();
     zrt_stats st{};
-    if (P == 0) { if (stats) *stats = st; return ZRT_OK; }
+    if (film && film->n_owned != P) return ZRT_ERR_INVALID_ARG;
+    if (P == 0) {
+        if (film) film->samples = base + cfg->num_samples;
+        if (stats) *stats = st;
+        return ZRT_OK;
+    }
 
     const uint32_t spp = cfg->num_samples;
     const uint32_t mb = cfg->max_bounce;
@@ -4277,8 +4389,15 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
         if (!c->ev_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
         if ((rc = event_pool(c->ev_pass, npasses, hipEventDisableTiming)) != ZRT_OK) return rc;
     }
-    if (npasses > 1 && (rc = grow(&c->d_acc, &c->acc_cap, P)) != ZRT_OK) return rc;
-    if ((rc = grow(&c->d_rgb, &c->rgb_cap, 3ull * P)) != ZRT_OK) return rc;
+    // a film's sums live in the film, not in d_acc, which a render of several
+    // passes between two of its calls overwrites
+    const bool use_acc = !film && npasses > 1;
+    if (use_acc && (rc = grow(&c->d_acc, &c->acc_cap, P)) != ZRT_OK) return rc;
+    float4* const acc = film ? film->d_sum : c->d_acc;
+    // a render always leaves its image in d_rgb (a group gathers it from
+    // there); a film's call only when it asked for an RGB8 output
+    const bool want_rgb = !film || (outs && (outs->rgb_image || outs->rgb_packed || outs->device_rgb_packed));
+    if (want_rgb && (rc = grow(&c->d_rgb, &c->rgb_cap, 3ull * P)) != ZRT_OK) return rc;
     const bool want_lin = outs && outs->linear_packed;
     if (want_lin && (rc = grow(&c->d_lin, &c->lin_cap, 3ull * P)) != ZRT_OK) return rc;
     const uint32_t launches_per_pass = counting ? 1 : nb;
@@ -4294,8 +4413,9 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
     // frame's buffers, the counting output 1 per item, the other sets'
     // streams, and every pass's items S * P <= T
     {
-        bool bad = shortfall("pixel list", c->d_pix, c->pix_cap, P) || shortfall("rgb", c->d_rgb, c->rgb_cap, 3ull * P) ||
-                   (npasses > 1 && shortfall("accumulator", c->d_acc, c->acc_cap, P)) ||
+        bool bad = shortfall("pixel list", c->d_pix, c->pix_cap, P) ||
+                   (want_rgb && shortfall("rgb", c->d_rgb, c->rgb_cap, 3ull * P)) ||
+                   (use_acc && shortfall("accumulator", c->d_acc, c->acc_cap, P)) || (film && !film->d_sum) ||
                    (want_lin && shortfall("linear", c->d_lin, c->lin_cap, 3ull * P)) ||
                    (counting && shortfall("counting output", c->d_out, c->out_cap, T));
         for (uint32_t k = 1; k < nsets && !counting && !bad; ++k) bad = !c->set[k].stream || !c->set[k].ev_join;
@@ -4330,8 +4450,12 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
     tp.out = c->d_out;
     tp.counter = c->d_counter;
     tp.stats = c->d_stats;
-    // stage3.zig:223 inv_num_samples = ones / splat(spp)  (f32 division)
-    const float inv_spp = 1.0f / (float)spp;
+    // stage3.zig:223 inv_num_samples = ones / splat(spp)  (f32 division); a
+    // film's image so far: over the samples it holds after this call
+    const float inv_spp = 1.0f / (float)(base + spp);
+    uint8_t* const rgb_dst = want_rgb ? c->d_rgb : nullptr;
+    const auto wf_res = film ? wf_film_resolve_kernel : wf_resolve_kernel;
+    const auto count_res = film ? film_resolve_kernel : resolve_kernel;
 
     HIP_TRY(hipMemsetAsync(c->d_stats, 0, 512, c->stream));
     HIP_TRY(hipEventRecord(c->ev_begin, c->stream));
@@ -4354,11 +4478,16 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
         hipStream_t sm = counting ? c->stream : ps.stream;
         const uint32_t s0 = pass_first(sp, pass);
         const uint32_t S = pass_count(sp, pass);
-        tp.s0 = s0;
+        tp.s0 = base + s0;
         tp.total = S * P;
         tp.S = S;
         tp.sdiv = div_magic(S);
-        const int first = pass == 0 ? 1 : 0, last = pass + 1 == npasses ? 1 : 0;
+        // first: nothing summed yet.  Pass 0 of a continuing call (base > 0)
+        // reads the film's sums, which the previous call -- synchronous, it
+        // returned after its streams were waited for -- left complete, so that
+        // resolve waits for nothing but its own stream, as pass 0 always did;
+        // the later passes chain through ev_pass below, film or not.
+        const int first = pass == 0 && base == 0 ? 1 : 0, last = pass + 1 == npasses ? 1 : 0;
         if (!counting) {
             HIP_TRY(hipMemsetAsync(ps.wfc, 0, 4ull * wfc_words(mb), sm));
             WfParams W;
@@ -4387,9 +4516,9 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
             // the passes' sums into acc stay in pass order (stage3.zig:236-242)
             if (nsets > 1 && pass > 0) HIP_TRY(hipStreamWaitEvent(sm, c->ev_pass[pass - 1], 0));
             if ((rc = kt.begin(ZRT_KERNEL_RESOLVE, sm)) != ZRT_OK) return rc;
-            hipLaunchKernelGGL(wf_resolve_kernel, dim3((P + kResPix - 1) / kResPix), dim3(kBlock), 0, sm,
-                               ps.term, ps.stk4, ps.stk2, (uint32_t)T, P, S, mb, c->d_acc, first, last, inv_spp,
-                               c->d_rgb, want_lin ? c->d_lin : nullptr);
+            hipLaunchKernelGGL(wf_res, dim3((P + kResPix - 1) / kResPix), dim3(kBlock), 0, sm,
+                               ps.term, ps.stk4, ps.stk2, (uint32_t)T, P, S, mb, acc, first, last, inv_spp,
+                               rgb_dst, want_lin ? c->d_lin : nullptr);
             if ((rc = kt.end(sm)) != ZRT_OK) return rc;
             if (nsets > 1) HIP_TRY(hipEventRecord(c->ev_pass[pass], sm));
         } else {
@@ -4402,8 +4531,8 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
             ++launches;
             HIP_TRY(hipEventRecord(c->ev_trace[ne++], c->stream));
             if ((rc = kt.begin(ZRT_KERNEL_RESOLVE, c->stream)) != ZRT_OK) return rc;
-            hipLaunchKernelGGL(resolve_kernel, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream,
-                               c->d_out, P, S, c->d_acc, first, last, inv_spp, c->d_rgb,
+            hipLaunchKernelGGL(count_res, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream,
+                               c->d_out, P, S, acc, first, last, inv_spp, rgb_dst,
                                want_lin ? c->d_lin : nullptr);
             if ((rc = kt.end(c->stream)) != ZRT_OK) return rc;
         }
@@ -4420,8 +4549,101 @@ extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const z
     HIP_TRY(hipStreamSynchronize(c->stream));
 
     if ((rc = finish_render(c, outs, kt, sp, P, counting, park_next, ne, launches, st)) != ZRT_OK) return rc;
+    if (film) film->samples = base + spp;
     if (stats) *stats = st;
     return ZRT_OK;
+}
+
+extern "C" int zrt_context_render(zrt_context* c, const zrt_camera* cam, const zrt_render_config* cfg,
+                                  const zrt_outputs* outs, zrt_stats* stats) {
+    return render_samples(c, cam, cfg, outs, stats, 0u, nullptr);
+}
+
+// ---------------------------------------------------------------------------
+// Films (include/zrt.h): a frame's per-pixel sums kept between
+// calls, so that zrt_context_accumulate continues them where a render would
+// start at sample 0 and forget them.
+extern "C" int zrt_film_create(zrt_context* c, uint32_t w, uint32_t h, uint32_t tile_size, uint32_t rank,
+                               uint32_t num_ranks, zrt_film** out) {
+    if (!c || !out) return ZRT_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (w == 0 || h == 0 || (uint64_t)w * h > 0xFFFFFFFFull) return ZRT_ERR_INVALID_ARG;
+    const uint32_t nranks = num_ranks ? num_ranks : 1, tile = tile_size ? tile_size : 64;
+    uint32_t n = 0;
+    int rc = tile_pixels(w, h, tile, rank, nranks, nullptr, &n);       // (refuses rank >= nranks, tile % 8)
+    if (rc != ZRT_OK) return rc;
+    DeviceGuard g(c->device);
+    zrt_film* f = new (std::nothrow) zrt_film;
+    if (!f) return ZRT_ERR_OUT_OF_MEMORY;
+    size_t cap = 0;
+    if ((rc = grow(&f->d_sum, &cap, std::max<size_t>(n, 1))) != ZRT_OK) { delete f; return rc; }
+    f->ctx = c;
+    f->device = c->device;
+    f->w = w; f->h = h; f->tile = tile; f->rank = rank; f->nranks = nranks;
+    f->n_owned = n;
+    *out = f;
+    return ZRT_OK;
+}
+
+extern "C" int zrt_film_reset(zrt_film* f) {
+    if (!f) return ZRT_ERR_INVALID_ARG;
+    f->samples = 0;               // the next call starts from +0 (first): the sums need no clearing
+    return ZRT_OK;
+}
+
+extern "C" int zrt_film_info(const zrt_film* f, uint32_t* n_owned, uint32_t* samples) {
+    if (!f) return ZRT_ERR_INVALID_ARG;
+    if (n_owned) *n_owned = f->n_owned;
+    if (samples) *samples = f->samples;
+    return ZRT_OK;
+}
+
+// The sums as stored (float4 rows on the device, 3 floats per pixel for the
+// caller), no division: a checkpoint written back continues bit for bit.
+extern "C" int zrt_film_read(zrt_film* f, float* sums, uint32_t* samples) {
+    if (!f || (!sums && f->n_owned)) return ZRT_ERR_INVALID_ARG;
+    DeviceGuard g(f->device);
+    if (f->n_owned && f->samples) {
+        std::vector<float4> tmp(f->n_owned);
+        HIP_TRY(copy_sync(tmp.data(), f->d_sum, tmp.size() * sizeof(float4), hipMemcpyDeviceToHost, f->ctx->stream));
+        for (uint32_t q = 0; q < f->n_owned; ++q) {
+            sums[3ull * q] = tmp[q].x; sums[3ull * q + 1] = tmp[q].y; sums[3ull * q + 2] = tmp[q].z;
+        }
+    } else {
+        // an empty film: the stored bits are never read; +0 is what the next call starts from
+        for (uint64_t k = 0; k < 3ull * f->n_owned; ++k) sums[k] = 0.0f;
+    }
+    if (samples) *samples = f->samples;
+    return ZRT_OK;
+}
+
+extern "C" int zrt_film_write(zrt_film* f, const float* sums, uint32_t samples) {
+    if (!f || samples > 65535 || (!sums && f->n_owned && samples)) return ZRT_ERR_INVALID_ARG;
+    DeviceGuard g(f->device);
+    if (f->n_owned && samples) {
+        std::vector<float4> tmp(f->n_owned);
+        for (uint32_t q = 0; q < f->n_owned; ++q)
+            tmp[q] = make_float4(sums[3ull * q], sums[3ull * q + 1], sums[3ull * q + 2], 0.0f);
+        HIP_TRY(copy_sync(f->d_sum, tmp.data(), tmp.size() * sizeof(float4), hipMemcpyHostToDevice, f->ctx->stream));
+    }
+    f->samples = samples;
+    return ZRT_OK;
+}
+
+extern "C" void zrt_film_destroy(zrt_film* f) {
+    if (!f) return;
+    DeviceGuard g(f->device);
+    if (f->d_sum) (void)hipFree(f->d_sum);
+    delete f;
+}
+
+extern "C" int zrt_context_accumulate(zrt_context* c, zrt_film* f, const zrt_camera* cam, const zrt_render_config* cfg,
+                                      const zrt_outputs* outs, zrt_stats* stats) {
+    if (!c || !f || !cam || !cfg || f->ctx != c) return ZRT_ERR_INVALID_ARG;
+    if (cam->w != f->w || cam->h != f->h || (cfg->tile_size ? cfg->tile_size : 64u) != f->tile ||
+        cfg->rank != f->rank || (cfg->num_ranks ? cfg->num_ranks : 1u) != f->nranks)
+        return ZRT_ERR_INVALID_ARG;
+    return render_samples(c, cam, cfg, outs, stats, f->samples, f);
 }
 
 extern "C" int zrt_context_profile(const zrt_context* c, zrt_kernel_profile* out) {

@@ -214,6 +214,17 @@ struct zrt_context {
     bool pix_valid = false;
 };
 
+// The accumulator of one rank's share of a frame (zrt_film_*):
+// what d_acc is between the passes of one render, kept between calls.
+struct zrt_film {
+    zrt_context* ctx = nullptr;
+    int device = 0;                    // ctx's (zrt_film_destroy does not touch ctx)
+    uint32_t w = 0, h = 0, tile = 0, rank = 0, nranks = 0;   // tile, nranks: after their defaults
+    uint32_t n_owned = 0;              // pixels of zrt_tile_pixels(w, h, tile, rank, nranks)
+    uint32_t samples = 0;              // samples summed so far; 0: d_sum's bits are not read
+    float4* d_sum = nullptr;           // n_owned (x, y, z: the f32 sums; w: 0)
+};
+
 // A copy on the context's stream, waited for: the product path never uses
 // HIP's null stream, whose first use in a process creates its hardware
 // queue (~10 ms of the CLI's start-up, r06d)

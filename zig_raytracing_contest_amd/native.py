@@ -231,6 +231,8 @@ EXPORTS = [
     "zrt_context_radiance", "zrt_context_segments", "zrt_context_surface", "zrt_context_transmittance",
     "zrt_context_features", "zrt_context_occlusion", "zrt_context_direct",
     "zrt_context_light_probes",
+    "zrt_film_create", "zrt_film_reset", "zrt_film_info", "zrt_film_read", "zrt_film_write", "zrt_film_destroy",
+    "zrt_context_accumulate",
 ]
 
 
@@ -279,6 +281,17 @@ def lib():
         L.zrt_context_direct.argtypes = [C.c_void_p, C.POINTER(DirectBatch), C.POINTER(Stats)]
     if hasattr(L, "zrt_context_light_probes"):   # (likewise)
         L.zrt_context_light_probes.argtypes = [C.c_void_p, C.POINTER(LightProbeBatch), C.POINTER(Stats)]
+    if hasattr(L, "zrt_context_accumulate"):   # (likewise)
+        L.zrt_film_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                      C.POINTER(C.c_void_p)]
+        L.zrt_film_reset.argtypes = [C.c_void_p]
+        L.zrt_film_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.zrt_film_read.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+        L.zrt_film_write.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.zrt_film_destroy.argtypes = [C.c_void_p]
+        L.zrt_film_destroy.restype = None
+        L.zrt_context_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Camera), C.POINTER(RenderConfig),
+                                             C.POINTER(Outputs), C.POINTER(Stats)]
     if hasattr(L, "zrt_group_create"):     # ABI 2 (an ABI-1 build: tools/ A/B baselines only)
         L.zrt_group_create.argtypes = [C.POINTER(Scene), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
         L.zrt_group_create_built.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -411,6 +424,55 @@ def attach_materials(scene: Scene, tex_desc: np.ndarray, texels: np.ndarray, kee
     scene.num_texel_floats = tx.size
 
 
+class Film:
+    """zrt_film: the per-pixel sample sums of one rank's share of a w x h
+    frame, kept between Context.accumulate calls (progressive renders,
+    checkpoint and resume).  Close it before its context."""
+
+    def __init__(self, context: "Context", w: int, h: int, tile: int = 64, rank: int = 0, num_ranks: int = 1):
+        h_ = C.c_void_p()
+        check(lib().zrt_film_create(context._h, w, h, tile, rank, num_ranks, C.byref(h_)), "zrt_film_create")
+        self._h = h_
+        self._context = context          # (keeps the context alive as long as the film)
+        self.w, self.h, self.tile, self.rank, self.num_ranks = w, h, tile or 64, rank, num_ranks or 1
+        self.n_owned = self.info()[0]
+
+    def info(self):
+        """(pixels owned, samples summed so far)."""
+        n, s = C.c_uint32(0), C.c_uint32(0)
+        check(lib().zrt_film_info(self._h, C.byref(n), C.byref(s)), "zrt_film_info")
+        return int(n.value), int(s.value)
+
+    @property
+    def samples(self) -> int:
+        return self.info()[1]
+
+    def reset(self):
+        check(lib().zrt_film_reset(self._h), "zrt_film_reset")
+
+    def read(self):
+        """(sums (n_owned, 3) float32 as stored -- no division --, samples): a checkpoint."""
+        sums = np.zeros((self.n_owned, 3), np.float32)
+        s = C.c_uint32(0)
+        check(lib().zrt_film_read(self._h, sums.ctypes.data, C.byref(s)), "zrt_film_read")
+        return sums, int(s.value)
+
+    def write(self, sums, samples: int):
+        """Resume from a checkpoint: the sums of `samples` samples (0: a reset)."""
+        a = np.ascontiguousarray(sums, np.float32)
+        if a.size != 3 * self.n_owned:
+            raise ValueError(f"zrt_film_write: {self.n_owned} x 3 sums expected")
+        check(lib().zrt_film_write(self._h, a.ctypes.data, int(samples)), "zrt_film_write")
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and _lib is not None:
+            _lib.zrt_film_destroy(self._h)       # (frees its device memory; does not touch the context)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
 class Context:
     """Device-resident scene (zrt_context): upload once, render many times."""
 
@@ -484,6 +546,48 @@ class Context:
         check(lib().zrt_context_render(self._h, C.byref(cam), C.byref(cfg), C.byref(out),
                                        C.byref(st)), "zrt_context_render")
         res["stats"] = st.as_dict()
+        return res
+
+    def film(self, w: int, h: int, tile: int = 64, rank: int = 0, num_ranks: int = 1) -> "Film":
+        """A Film of this context for this rank's share of a w x h frame."""
+        return Film(self, w, h, tile, rank, num_ranks)
+
+    def accumulate(self, film: "Film", cam: Camera, spp: int, max_bounce: int, seed: int = 0,
+                   stats: bool = False, image=None, packed=False, linear=False, device_ptr=None,
+                   samples_per_pass=0, flags=0, want_linear=None):
+        """zrt_context_accumulate: the next `spp` samples of every pixel of
+        `film` (samples film.samples .. film.samples + spp - 1 of the stream a
+        render of the same camera, seed and max_bounce draws), added to its
+        sums in sample order.  The outputs asked for, as in render (image,
+        packed, linear -- want_linear is its other name -- and device_ptr), show
+        the frame so far: after any split of N samples over calls they are, bit
+        for bit, one render's of N.  rank, num_ranks and tile are the film's.
+        With no output asked the call only accumulates."""
+        cfg = RenderConfig()
+        cfg.num_samples, cfg.max_bounce, cfg.seed = spp, max_bounce, seed
+        cfg.device, cfg.rank, cfg.num_ranks, cfg.tile_size = -1, film.rank, film.num_ranks, film.tile
+        cfg.flags = (FLAG_COUNT_STATS if stats else 0) | flags
+        cfg.samples_per_pass = samples_per_pass
+        if want_linear is not None:
+            linear = want_linear
+        out = Outputs()
+        res = {}
+        if image is not None:
+            out.rgb_image = image.ctypes.data
+        if packed:
+            res["packed"] = np.zeros((film.n_owned, 3), np.uint8)
+            out.rgb_packed = res["packed"].ctypes.data
+        if linear:
+            res["linear"] = np.zeros((film.n_owned, 3), np.float32)
+            out.linear_packed = res["linear"].ctypes.data
+        if device_ptr is not None:
+            out.device_rgb_packed = device_ptr
+        asked = image is not None or packed or linear or device_ptr is not None
+        st = Stats()
+        check(lib().zrt_context_accumulate(self._h, film._h, C.byref(cam), C.byref(cfg),
+                                           C.byref(out) if asked else None, C.byref(st)), "zrt_context_accumulate")
+        res["stats"] = st.as_dict()
+        res["samples"] = film.samples
         return res
 
     @staticmethod
