@@ -938,6 +938,72 @@ int zrt_context_accumulate(zrt_context* ctx, zrt_film* film, const zrt_camera* c
                            const zrt_render_config* cfg, const zrt_outputs* outputs_or_null,
                            zrt_stats* stats_or_null);
 
+/* ---- adaptive films: sample only unconverged pixels (ABI 2, added) ------- */
+
+/* zrt_context_refine is zrt_context_accumulate for the pixels of a film whose
+ * image is still changing.  Beside its sums the film keeps, from its first
+ * refine call on: per pixel a frozen flag and the count n[q] it was frozen at;
+ * per pixel the checkpoint, its linear value when the previous refine call
+ * started tracing; and the checkpoint's sample count c (0: none).  A pixel that
+ * is not frozen holds the film's samples.
+ *
+ * A call does, in this order, with b = the film's samples and
+ * n = cfg->num_samples (all f32, nothing contracted, left to right as written,
+ * sqrt and / IEEE-rounded):
+ * 1. Decide.  If c == 0 or b < min_samples nothing changes.  Otherwise, for
+ *    every pixel q that is not frozen:
+ *      cur = sum[q] * (1.0f / (float)b)        the image a film shows at b
+ *      p   = checkpoint[q]                     the image it showed at c
+ *      d   = (|cur.x - p.x| + |cur.y - p.y|) + |cur.z - p.z|
+ *      m   = (cur.x + cur.y) + cur.z
+ *      k   = (float)b / (float)(b - c)         "last batch's mean vs the mean before it"
+ *      err = (d * k) / sqrt(fmaxf(m, 0x1p-10f))
+ *    and the pixel is frozen iff !(err > threshold) (a NaN error freezes).  A
+ *    frozen pixel keeps n[q] = b and its sum and is not traced again until
+ *    zrt_film_reset / zrt_film_write.
+ * 2. Compact.  The active pixels in zrt_tile_pixels order are the call's pixel
+ *    list; A is their number, *active_or_null = A.
+ * 3. Trace.  If A == 0 nothing is traced and the film's samples, c and the
+ *    checkpoints stay.  Otherwise, for every active pixel, checkpoint[q] = cur
+ *    (not when b == 0), c = b, and samples b .. b + n - 1 -- the paths a
+ *    zrt_context_render of this camera, seed and max_bounce traces for that
+ *    pixel and those indices -- are added to sum[q] in sample order (from +0
+ *    when b == 0); the film's samples become b + n.
+ * 4. Present.  For EVERY owned pixel linear = sum[q] * (1.0f / (float)N) with
+ *    N = n[q] if frozen, else the film's samples, and rgb = toRGB(linear), into
+ *    whichever zrt_outputs fields are set (they mean what they mean in a
+ *    render); sample_counts[q] = N.  A call that asks for none of them runs no
+ *    present pass.
+ * So every pixel's outputs are, bit for bit, the one-shot render's pixel at N
+ * samples, in every kernel mode and for any samples_per_pass; and while nothing
+ * is frozen (min_samples above the frame's final count) the calls are
+ * zrt_context_accumulate's, outputs and stats.
+ * The kernels are chosen as a render of A pixels and n samples chooses them
+ * (A * n against the 2^23-sample thresholds).  stats are those of the traced
+ * paths only: samples = A * n, segments and the counting build's counters of
+ * samples b .. b + n - 1 of the active pixels, trace_launches of a render of A
+ * pixels; A == 0 gives all zero.  zrt_context_profile records the trace as a
+ * render.
+ * ZRT_ERR_INVALID_ARG (max_bounce > 32: ZRT_ERR_UNSUPPORTED) before any device
+ * work, film and outputs untouched: what zrt_context_accumulate refuses, a null
+ * refine, a NaN threshold, b + n > 65535.
+ * zrt_context_accumulate on a film with a frozen pixel is ZRT_ERR_INVALID_ARG;
+ * on a film without one it leaves c and the checkpoints alone.  zrt_film_reset
+ * and zrt_film_write clear the frozen flags and c.  zrt_film_read returns the
+ * sums as stored; zrt_film_counts says how many samples each holds. */
+typedef struct zrt_refine_config {
+    uint32_t* sample_counts;  /* host, n_owned, or null: every owned pixel's count after the call */
+    float threshold;          /* a pixel stays active iff err > threshold; NaN: ZRT_ERR_INVALID_ARG */
+    uint32_t min_samples;     /* no pixel is frozen while the film holds fewer samples than this */
+} zrt_refine_config;          /* 16 B */
+
+int zrt_context_refine(zrt_context* ctx, zrt_film* film, const zrt_camera* camera,
+                       const zrt_render_config* cfg, const zrt_refine_config* refine,
+                       const zrt_outputs* outputs_or_null, zrt_stats* stats_or_null,
+                       uint32_t* active_or_null);
+/* counts: host n_owned or null; active: pixels not frozen, or null */
+int zrt_film_counts(zrt_film* film, uint32_t* counts, uint32_t* active);
+
 /* A device group: one context per entry of `devices` (HIP ordinals, repeats
  * allowed), the scene resident on each, rendered by one call -- Scene.render's
  * spawn + join of its workers (stage3.zig:247-256) across GPUs in one

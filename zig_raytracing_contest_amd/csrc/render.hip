@@ -2009,6 +2009,200 @@ __global__ __launch_bounds__(kBlock) void film_resolve_kernel(const float4* __re
     if (lin) { lin[3 * (size_t)q] = l.x; lin[3 * (size_t)q + 1] = l.y; lin[3 * (size_t)q + 2] = l.z; }
 }
 
+// The resolves of zrt_context_refine on a sparse pixel list: the
+// two film resolves above for the A active pixels of a film.  Item pixel q < A
+// is the list's q-th pixel and its sums are the film's row slot[q]; the image
+// is written by film_present_kernel for every owned pixel afterwards, so these
+// take no outputs.  Separate kernels with the fold and the per-pixel add
+// statement for statement, for the reason given above.
+__global__ __launch_bounds__(kBlock) void wf_film_sparse_resolve_kernel(const float4* __restrict__ term,
+                                                                        const float4* __restrict__ stk4,
+                                                                        const float2* __restrict__ stk2, uint32_t T,
+                                                                        uint32_t P, uint32_t S, uint32_t max_bounce,
+                                                                        float4* film,
+                                                                        const uint32_t* __restrict__ slots,
+                                                                        int first) {
+    __shared__ float s_l[kResPix * kResRow];
+    const uint32_t q0 = blockIdx.x * kResPix;
+    const uint32_t np = min(kResPix, P - q0);
+    const uint32_t tid = threadIdx.x;
+    const uint32_t row = tid < np ? slots[q0 + tid] : 0u;
+    v3 px = mk(0, 0, 0);
+    if (tid < np && !first) { const float4 a = film[row]; px = mk(a.x, a.y, a.z); }
+    for (uint32_t c = 0; c < S; c += kResSmp) {
+        const uint32_t ns = min(kResSmp, S - c);
+        for (uint32_t m = tid; m < kResPix * kResSmp; m += kBlock) {
+            const uint32_t i = m / kResSmp, k = m % kResSmp;   // the block's pixel i, sample c + k
+            if (i < np && k < ns) {
+                const uint32_t item = (q0 + i) * S + c + k;
+                const float4 tm = term[item];
+                v3 L = mk(tm.x, tm.y, tm.z);
+                const uint32_t mask = __float_as_uint(tm.w);
+                for (int slot = (int)max_bounce - 1; slot >= 0; --slot) {
+                    if ((mask >> slot) & 1u) {
+                        const float4 a = stk4[(uint64_t)slot * T + item];
+                        v3 e = mk(0.0f, 0.0f, 0.0f);
+                        if (__float_as_uint(a.w) != 0u) {
+                            const float4 ee = reinterpret_cast<const float4*>(stk2)[(uint64_t)slot * T + item];
+                            e = mk(ee.x, ee.y, ee.z);
+                        }
+                        L = add(e, mul(mk(a.x, a.y, a.z), L));
+                    }
+                }
+                float* dst = s_l + i * kResRow + 3u * k;
+                dst[0] = L.x; dst[1] = L.y; dst[2] = L.z;
+            }
+        }
+        __syncthreads();
+        if (tid < np) {
+            const float* src = s_l + tid * kResRow;
+            for (uint32_t k = 0; k < ns; ++k) px = add(px, mk(src[3 * k], src[3 * k + 1], src[3 * k + 2]));
+        }
+        __syncthreads();
+    }
+    if (tid >= np) return;
+    film[row] = make_float4(px.x, px.y, px.z, 0.0f);
+}
+
+__global__ __launch_bounds__(kBlock) void film_sparse_resolve_kernel(const float4* __restrict__ out, uint32_t P,
+                                                                     uint32_t S, float4* film,
+                                                                     const uint32_t* __restrict__ slots, int first) {
+    const uint32_t q = blockIdx.x * kBlock + threadIdx.x;
+    if (q >= P) return;
+    const uint32_t row = slots[q];
+    v3 px = mk(0, 0, 0);
+    if (!first) { const float4 a = film[row]; px = mk(a.x, a.y, a.z); }
+    for (uint32_t s = 0; s < S; ++s) {
+        const float4 c = out[(size_t)q * S + s];          // pixel-major items
+        px = add(px, mk(c.x, c.y, c.z));
+    }
+    film[row] = make_float4(px.x, px.y, px.z, 0.0f);
+}
+
+// zrt_context_refine's decision (include/zrt.h), one thread per
+// owned pixel.  An active pixel's image at b samples, cur = sum * (1 / b), is
+// compared with its checkpoint, the image it showed at c samples; with
+// `decide`, a pixel whose error is not above the threshold is frozen at b
+// samples (a NaN error freezes).  A pixel that stays active takes cur as its
+// new checkpoint.  blk[block] = the block's active pixels, for the scan.
+// Everything f32, left to right as the header writes it; / and sqrtf are
+// IEEE-rounded and nothing contracts (the build's flags).
+__global__ __launch_bounds__(kBlock) void film_decide_kernel(const float4* __restrict__ sum, float4* state, uint32_t n,
+                                                             uint32_t b, uint32_t c, float threshold, int decide,
+                                                             uint32_t* __restrict__ blk) {
+    __shared__ uint32_t s_w[kBlock / 64];
+    const uint32_t q = blockIdx.x * kBlock + threadIdx.x;
+    bool act = false;
+    if (q < n) {
+        const float4 st = state[q];
+        act = (__float_as_uint(st.w) & kFilmFrozen) == 0u;
+        if (act) {
+            const float4 s = sum[q];
+            const float inv = 1.0f / (float)b;
+            const v3 cur = mul(mk(s.x, s.y, s.z), mk(inv, inv, inv));
+            if (decide) {
+                const float d = (fabsf(cur.x - st.x) + fabsf(cur.y - st.y)) + fabsf(cur.z - st.z);
+                const float m = (cur.x + cur.y) + cur.z;
+                const float k = (float)b / (float)(b - c);
+                const float err = (d * k) / sqrtf(fmaxf(m, 0x1p-10f));
+                act = err > threshold;
+            }
+            state[q] = act ? make_float4(cur.x, cur.y, cur.z, 0.0f)
+                           : make_float4(st.x, st.y, st.z, __uint_as_float(kFilmFrozen | b));
+        }
+    }
+    const uint64_t bal = __ballot(act);
+    if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (uint32_t v = 0; v < kBlock / 64; ++v) t += s_w[v];
+        blk[blockIdx.x] = t;
+    }
+}
+
+// The blocks' counts into their exclusive bases, in place, and the total A
+// into blk[nblk]: one workgroup walks the counts kBlock at a time (a 1080p
+// rank has 8100), so no block ever waits for another.
+__global__ __launch_bounds__(kBlock) void film_scan_kernel(uint32_t* blk, uint32_t nblk) {
+    __shared__ uint32_t s_v[kBlock];
+    __shared__ uint32_t s_carry;
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) s_carry = 0;
+    __syncthreads();
+    for (uint32_t i0 = 0; i0 < nblk; i0 += kBlock) {
+        const uint32_t i = i0 + tid;
+        const uint32_t v = i < nblk ? blk[i] : 0u;
+        s_v[tid] = v;
+        __syncthreads();
+        for (uint32_t off = 1; off < kBlock; off <<= 1) {       // inclusive scan of the chunk
+            const uint32_t a = tid >= off ? s_v[tid - off] : 0u;
+            __syncthreads();
+            s_v[tid] += a;
+            __syncthreads();
+        }
+        const uint32_t carry = s_carry;
+        if (i < nblk) blk[i] = carry + s_v[tid] - v;
+        __syncthreads();
+        if (tid == kBlock - 1) s_carry = carry + s_v[tid];
+        __syncthreads();
+    }
+    if (tid == 0) blk[nblk] = s_carry;
+}
+
+// The active pixels in packed order: pixel q's place is its block's base, the
+// active pixels of the block's waves before its own, and its rank among its
+// wave's (ballot and mbcnt).  list: the image pixel (a call's pixlist), slot:
+// the film row.  base + rank < A <= n: the flags are those the counts were
+// taken from.
+__global__ __launch_bounds__(kBlock) void film_scatter_kernel(const float4* __restrict__ state,
+                                                              const uint32_t* __restrict__ pix, uint32_t n,
+                                                              const uint32_t* __restrict__ blk,
+                                                              uint32_t* __restrict__ list,
+                                                              uint32_t* __restrict__ slot) {
+    __shared__ uint32_t s_w[kBlock / 64];
+    const uint32_t q = blockIdx.x * kBlock + threadIdx.x;
+    const bool act = q < n && (__float_as_uint(state[q].w) & kFilmFrozen) == 0u;
+    const uint64_t bal = __ballot(act);
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0u) s_w[wave] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    if (!act) return;
+    uint32_t at = blk[blockIdx.x] + rank;
+    for (uint32_t v = 0; v < wave; ++v) at += s_w[v];
+    if (at >= n) return;                   // (cannot happen; a list of n entries is what was allocated)
+    list[at] = pix[q];
+    slot[at] = q;
+}
+
+// The frame a film shows, every owned pixel at its own sample count: N = the
+// count a frozen pixel was frozen at, else the film's samples; linear = sum *
+// (1 / N), rgb = toRGB(linear).  state null: no pixel is frozen.  Null outputs
+// are skipped; cnt: N itself.
+__global__ __launch_bounds__(kBlock) void film_present_kernel(const float4* __restrict__ sum,
+                                                              const float4* __restrict__ state, uint32_t n,
+                                                              uint32_t samples, uint8_t* rgb, float* lin,
+                                                              uint32_t* cnt) {
+    const uint32_t q = blockIdx.x * kBlock + threadIdx.x;
+    if (q >= n) return;
+    const uint32_t w = state ? __float_as_uint(state[q].w) : 0u;
+    const uint32_t N = (w & kFilmFrozen) ? (w & ~kFilmFrozen) : samples;
+    if (cnt) cnt[q] = N;
+    if (!rgb && !lin) return;
+    const float4 a = sum[q];
+    const float inv = 1.0f / (float)N;
+    const v3 l = mul(mk(a.x, a.y, a.z), mk(inv, inv, inv));
+    if (rgb) {
+        uint8_t c[3];
+        to_rgb(l, c);
+        rgb[3 * (size_t)q + 0] = c[0];
+        rgb[3 * (size_t)q + 1] = c[1];
+        rgb[3 * (size_t)q + 2] = c[2];
+    }
+    if (lin) { lin[3 * (size_t)q] = l.x; lin[3 * (size_t)q + 1] = l.y; lin[3 * (size_t)q + 2] = l.z; }
+}
+
 using TraceFn = void (*)(const TraceParams);
 using WfFn = void (*)(const WfParams);
 
@@ -4312,8 +4506,20 @@ static int finish_render(zrt_context* c, const zrt_outputs* outs, KernelTimes& k
 // 1 / (base + num_samples) as inv_spp, and d_rgb / d_lin are written only if
 // the call asked for them.  Everything else -- the split, the plan, the launch
 // sequence, the stats -- is the render's.
-static int render_samples(zrt_context* c, const zrt_camera* cam, const zrt_render_config* cfg,
-                          const zrt_outputs* outs, zrt_stats* stats, uint32_t base, zrt_film* film) {
+//
+// zrt_context_refine traces a film's active pixels only: `sparse`
+// names A of the rank's pixels (image indices, the kernels' pixlist) and their
+// rows in the film.  The call is then a render of those A pixels -- P = A in
+// the split, the plan, the thresholds and the stats -- whose resolves are the
+// sparse film resolves; it writes no outputs (the caller presents the film).
+struct SparsePixels {
+    const uint32_t* list;    // device, A image pixels in packed order
+    const uint32_t* slot;    // device, their rows in the film
+    uint32_t A;              // 0 < A <= the rank's pixels
+};
+
+// What a render refuses before any device work.
+static int render_args(const zrt_context* c, const zrt_camera* cam, const zrt_render_config* cfg, uint32_t base) {
     if (!c || !cam || !cfg) return ZRT_ERR_INVALID_ARG;
     // (the stream key gives the sample index 16 bits)
     if (cfg->num_samples == 0 || (uint64_t)base + cfg->num_samples > 65535) return ZRT_ERR_INVALID_ARG;
@@ -4322,16 +4528,27 @@ static int render_samples(zrt_context* c, const zrt_camera* cam, const zrt_rende
     if (cfg->rank >= nranks) return ZRT_ERR_INVALID_ARG;
     // the scatter mask holds one bit per bounce slot, the queue 16 bits of depth
     if (cfg->max_bounce > 32) return ZRT_ERR_UNSUPPORTED;
+    if ((cfg->flags & ZRT_FLAG_COUNT_STATS) != 0 && !count_fn(cfg->max_bounce)) return ZRT_ERR_UNSUPPORTED;
+    return ZRT_OK;
+}
+
+static int render_samples(zrt_context* c, const zrt_camera* cam, const zrt_render_config* cfg,
+                          const zrt_outputs* outs, zrt_stats* stats, uint32_t base, zrt_film* film,
+                          const SparsePixels* sparse = nullptr) {
+    int rc;
+    if ((rc = render_args(c, cam, cfg, base)) != ZRT_OK) return rc;
+    const uint32_t nranks = cfg->num_ranks ? cfg->num_ranks : 1;
     const bool counting = (cfg->flags & ZRT_FLAG_COUNT_STATS) != 0;
     const TraceFn cfn = count_fn(cfg->max_bounce);
-    if (counting && !cfn) return ZRT_ERR_UNSUPPORTED;
     DeviceGuard g(c->device);
 
-    int rc;
     if ((rc = rank_pixels(c, cam, cfg, nranks)) != ZRT_OK) return rc;
-    const uint32_t P = (uint32_t)c->pix.size();
+    const uint32_t owned = (uint32_t)c->pix.size();
     zrt_stats st{};
-    if (film && film->n_owned != P) return ZRT_ERR_INVALID_ARG;
+    if (film && film->n_owned != owned) return ZRT_ERR_INVALID_ARG;
+    if (sparse && (!film || outs || sparse->A == 0 || sparse->A > owned || !sparse->list || !sparse->slot))
+        return ZRT_ERR_INVALID_ARG;
+    const uint32_t P = sparse ? sparse->A : owned;
     if (P == 0) {
         if (film) film->samples = base + cfg->num_samples;
         if (stats) *stats = st;
@@ -4443,7 +4660,7 @@ static int render_samples(zrt_context* c, const zrt_camera* cam, const zrt_rende
         tp.up[i] = cam->up[i];
     }
     tp.w = cam->w;
-    tp.pixlist = c->d_pix;
+    tp.pixlist = sparse ? sparse->list : c->d_pix;
     tp.P = P;
     tp.max_bounce = mb;
     tp.seed = cfg->seed;
@@ -4516,9 +4733,13 @@ static int render_samples(zrt_context* c, const zrt_camera* cam, const zrt_rende
             // the passes' sums into acc stay in pass order (stage3.zig:236-242)
             if (nsets > 1 && pass > 0) HIP_TRY(hipStreamWaitEvent(sm, c->ev_pass[pass - 1], 0));
             if ((rc = kt.begin(ZRT_KERNEL_RESOLVE, sm)) != ZRT_OK) return rc;
-            hipLaunchKernelGGL(wf_res, dim3((P + kResPix - 1) / kResPix), dim3(kBlock), 0, sm,
-                               ps.term, ps.stk4, ps.stk2, (uint32_t)T, P, S, mb, acc, first, last, inv_spp,
-                               rgb_dst, want_lin ? c->d_lin : nullptr);
+            if (sparse)
+                hipLaunchKernelGGL(wf_film_sparse_resolve_kernel, dim3((P + kResPix - 1) / kResPix), dim3(kBlock), 0,
+                                   sm, ps.term, ps.stk4, ps.stk2, (uint32_t)T, P, S, mb, acc, sparse->slot, first);
+            else
+                hipLaunchKernelGGL(wf_res, dim3((P + kResPix - 1) / kResPix), dim3(kBlock), 0, sm,
+                                   ps.term, ps.stk4, ps.stk2, (uint32_t)T, P, S, mb, acc, first, last, inv_spp,
+                                   rgb_dst, want_lin ? c->d_lin : nullptr);
             if ((rc = kt.end(sm)) != ZRT_OK) return rc;
             if (nsets > 1) HIP_TRY(hipEventRecord(c->ev_pass[pass], sm));
         } else {
@@ -4531,9 +4752,13 @@ static int render_samples(zrt_context* c, const zrt_camera* cam, const zrt_rende
             ++launches;
             HIP_TRY(hipEventRecord(c->ev_trace[ne++], c->stream));
             if ((rc = kt.begin(ZRT_KERNEL_RESOLVE, c->stream)) != ZRT_OK) return rc;
-            hipLaunchKernelGGL(count_res, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream,
-                               c->d_out, P, S, acc, first, last, inv_spp, rgb_dst,
-                               want_lin ? c->d_lin : nullptr);
+            if (sparse)
+                hipLaunchKernelGGL(film_sparse_resolve_kernel, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0,
+                                   c->stream, c->d_out, P, S, acc, sparse->slot, first);
+            else
+                hipLaunchKernelGGL(count_res, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream,
+                                   c->d_out, P, S, acc, first, last, inv_spp, rgb_dst,
+                                   want_lin ? c->d_lin : nullptr);
             if ((rc = kt.end(c->stream)) != ZRT_OK) return rc;
         }
         HIP_TRY(hipGetLastError());
@@ -4580,14 +4805,24 @@ extern "C" int zrt_film_create(zrt_context* c, uint32_t w, uint32_t h, uint32_t 
     f->ctx = c;
     f->device = c->device;
     f->w = w; f->h = h; f->tile = tile; f->rank = rank; f->nranks = nranks;
-    f->n_owned = n;
+    f->n_owned = f->active = n;
     *out = f;
     return ZRT_OK;
+}
+
+// No pixel frozen, no checkpoint (reset, write): the next refine call clears
+// the flags on the device before it reads them.
+static void film_thaw(zrt_film* f) {
+    f->checkpoint = 0;
+    f->active = f->n_owned;
+    f->state_stale = true;
+    f->list_valid = false;
 }
 
 extern "C" int zrt_film_reset(zrt_film* f) {
     if (!f) return ZRT_ERR_INVALID_ARG;
     f->samples = 0;               // the next call starts from +0 (first): the sums need no clearing
+    film_thaw(f);
     return ZRT_OK;
 }
 
@@ -4627,6 +4862,7 @@ extern "C" int zrt_film_write(zrt_film* f, const float* sums, uint32_t samples) 
         HIP_TRY(copy_sync(f->d_sum, tmp.data(), tmp.size() * sizeof(float4), hipMemcpyHostToDevice, f->ctx->stream));
     }
     f->samples = samples;
+    film_thaw(f);
     return ZRT_OK;
 }
 
@@ -4634,6 +4870,11 @@ extern "C" void zrt_film_destroy(zrt_film* f) {
     if (!f) return;
     DeviceGuard g(f->device);
     if (f->d_sum) (void)hipFree(f->d_sum);
+    if (f->d_state) (void)hipFree(f->d_state);
+    if (f->d_list) (void)hipFree(f->d_list);
+    if (f->d_slot) (void)hipFree(f->d_slot);
+    if (f->d_blk) (void)hipFree(f->d_blk);
+    if (f->d_cnt) (void)hipFree(f->d_cnt);
     delete f;
 }
 
@@ -4643,7 +4884,142 @@ extern "C" int zrt_context_accumulate(zrt_context* c, zrt_film* f, const zrt_cam
     if (cam->w != f->w || cam->h != f->h || (cfg->tile_size ? cfg->tile_size : 64u) != f->tile ||
         cfg->rank != f->rank || (cfg->num_ranks ? cfg->num_ranks : 1u) != f->nranks)
         return ZRT_ERR_INVALID_ARG;
+    // a frozen pixel holds fewer samples than the film: only refine continues such a film
+    if (f->active != f->n_owned) return ZRT_ERR_INVALID_ARG;
     return render_samples(c, cam, cfg, outs, stats, f->samples, f);
+}
+
+// ---------------------------------------------------------------------------
+// Adaptive films (include/zrt.h): zrt_context_refine freezes the
+// pixels whose image stopped changing and traces the rest.
+
+// The adaptive state of a film, allocated by its first refine call, and all
+// flags cleared where a reset or a write made them stale.
+static int film_state(zrt_film* f) {
+    int rc;
+    const size_t n = std::max<size_t>(f->n_owned, 1), nblk = (n + kBlock - 1) / kBlock;
+    if (!f->d_state) {
+        size_t cap = 0;
+        if ((rc = grow(&f->d_state, &cap, n)) != ZRT_OK) return rc;
+        cap = 0;
+        if ((rc = grow(&f->d_list, &cap, n)) != ZRT_OK) return rc;
+        cap = 0;
+        if ((rc = grow(&f->d_slot, &cap, n)) != ZRT_OK) return rc;
+        cap = 0;
+        if ((rc = grow(&f->d_blk, &cap, nblk + 1)) != ZRT_OK) return rc;
+        f->state_stale = true;
+    }
+    if (f->state_stale) {
+        HIP_TRY(hipMemsetAsync(f->d_state, 0, n * sizeof(float4), f->ctx->stream));
+        f->state_stale = false;
+        f->list_valid = false;
+        f->active = f->n_owned;
+        f->checkpoint = 0;
+    }
+    return ZRT_OK;
+}
+
+// Every owned pixel at its own count into the context's output buffers and on
+// to the caller (what finish_render does with a render's), and the counts.
+static int film_present(zrt_context* c, zrt_film* f, const zrt_outputs* outs, uint32_t* counts) {
+    const uint32_t n = f->n_owned;
+    const bool want_rgb = outs && (outs->rgb_image || outs->rgb_packed || outs->device_rgb_packed);
+    const bool want_lin = outs && outs->linear_packed;
+    if (n == 0 || (!want_rgb && !want_lin && !counts)) return ZRT_OK;
+    int rc;
+    if (want_rgb && (rc = grow(&c->d_rgb, &c->rgb_cap, 3ull * n)) != ZRT_OK) return rc;
+    if (want_lin && (rc = grow(&c->d_lin, &c->lin_cap, 3ull * n)) != ZRT_OK) return rc;
+    if (counts && (rc = grow(&f->d_cnt, &f->cnt_cap, n)) != ZRT_OK) return rc;
+    if ((want_rgb && shortfall("rgb", c->d_rgb, c->rgb_cap, 3ull * n)) ||
+        (want_lin && shortfall("linear", c->d_lin, c->lin_cap, 3ull * n)) ||
+        (counts && shortfall("counts", f->d_cnt, f->cnt_cap, n)) || !f->d_sum)
+        return ZRT_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(film_present_kernel, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, f->d_sum,
+                       f->d_state, n, f->samples, want_rgb ? c->d_rgb : nullptr, want_lin ? c->d_lin : nullptr,
+                       counts ? f->d_cnt : nullptr);
+    HIP_TRY(hipGetLastError());
+    if (outs && outs->device_rgb_packed)
+        HIP_TRY(hipMemcpyAsync(outs->device_rgb_packed, c->d_rgb, 3ull * n, hipMemcpyDeviceToDevice, c->stream));
+    if (outs && (outs->rgb_packed || outs->rgb_image)) {
+        std::vector<uint8_t> tmp;
+        uint8_t* dst = outs->rgb_packed;
+        if (!dst) { tmp.resize(3ull * n); dst = tmp.data(); }
+        HIP_TRY(copy_sync(dst, c->d_rgb, 3ull * n, hipMemcpyDeviceToHost, c->stream));
+        if (outs->rgb_image)
+            for (uint32_t q = 0; q < n; ++q) memcpy(outs->rgb_image + 3ull * c->pix[q], dst + 3ull * q, 3);
+    }
+    if (want_lin)
+        HIP_TRY(copy_sync(outs->linear_packed, c->d_lin, 3ull * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (counts) HIP_TRY(copy_sync(counts, f->d_cnt, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return ZRT_OK;
+}
+
+extern "C" int zrt_context_refine(zrt_context* c, zrt_film* f, const zrt_camera* cam, const zrt_render_config* cfg,
+                                  const zrt_refine_config* rf, const zrt_outputs* outs, zrt_stats* stats,
+                                  uint32_t* active) {
+    if (!c || !f || !cam || !cfg || !rf || f->ctx != c) return ZRT_ERR_INVALID_ARG;
+    if (cam->w != f->w || cam->h != f->h || (cfg->tile_size ? cfg->tile_size : 64u) != f->tile ||
+        cfg->rank != f->rank || (cfg->num_ranks ? cfg->num_ranks : 1u) != f->nranks)
+        return ZRT_ERR_INVALID_ARG;
+    if (rf->threshold != rf->threshold) return ZRT_ERR_INVALID_ARG;       // NaN
+    int rc;
+    const uint32_t b = f->samples, n = f->n_owned;
+    if ((rc = render_args(c, cam, cfg, b)) != ZRT_OK) return rc;
+    DeviceGuard g(c->device);
+    if ((rc = rank_pixels(c, cam, cfg, f->nranks)) != ZRT_OK) return rc;
+    if (c->pix.size() != n) return ZRT_ERR_INVALID_ARG;
+    zrt_stats st{};
+    if ((rc = film_state(f)) != ZRT_OK) return rc;
+
+    // 1. decide, 2. compact.  Without a decision the flags, A and the lists
+    // stay what the previous call left; the kernel then only takes the
+    // checkpoints (there is none to take of an empty film).
+    const bool decide = f->checkpoint != 0 && b >= rf->min_samples;
+    const uint32_t nblk = (n + kBlock - 1) / kBlock;
+    uint32_t A = f->active;
+    if (b != 0 && A != 0) {
+        if (shortfall("pixel list", c->d_pix, c->pix_cap, n) || !f->d_state || !f->d_list || !f->d_slot || !f->d_blk)
+            return ZRT_ERR_INVALID_ARG;
+        hipLaunchKernelGGL(film_decide_kernel, dim3(nblk), dim3(kBlock), 0, c->stream, f->d_sum, f->d_state, n, b,
+                           f->checkpoint, rf->threshold, decide ? 1 : 0, f->d_blk);
+        HIP_TRY(hipGetLastError());
+        if (decide) {
+            hipLaunchKernelGGL(film_scan_kernel, dim3(1), dim3(kBlock), 0, c->stream, f->d_blk, nblk);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(film_scatter_kernel, dim3(nblk), dim3(kBlock), 0, c->stream, f->d_state, c->d_pix, n,
+                               f->d_blk, f->d_list, f->d_slot);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(copy_sync(&A, f->d_blk + nblk, sizeof A, hipMemcpyDeviceToHost, c->stream));
+            if (A > f->active) return ZRT_ERR_HIP;                        // (a frozen pixel never thaws)
+            f->active = A;
+            f->list_valid = true;
+        }
+    }
+    // 3. trace: a render of the A active pixels' next samples into the film
+    if (A != 0) {
+        if (A != n && !f->list_valid) return ZRT_ERR_INVALID_ARG;
+        const SparsePixels sparse{f->d_list, f->d_slot, A};
+        f->checkpoint = b;
+        if ((rc = render_samples(c, cam, cfg, nullptr, &st, b, f, A != n ? &sparse : nullptr)) != ZRT_OK) return rc;
+    }
+    // 4. present
+    if ((rc = film_present(c, f, outs, rf->sample_counts)) != ZRT_OK) return rc;
+    if (stats) *stats = st;
+    if (active) *active = A;
+    return ZRT_OK;
+}
+
+extern "C" int zrt_film_counts(zrt_film* f, uint32_t* counts, uint32_t* active) {
+    if (!f) return ZRT_ERR_INVALID_ARG;
+    if (active) *active = f->active;
+    if (!counts || f->n_owned == 0) return ZRT_OK;
+    if (!f->d_state || f->state_stale || f->active == f->n_owned) {        // no pixel frozen
+        for (uint32_t q = 0; q < f->n_owned; ++q) counts[q] = f->samples;
+        return ZRT_OK;
+    }
+    DeviceGuard g(f->device);
+    return film_present(f->ctx, f, nullptr, counts);
 }
 
 extern "C" int zrt_context_profile(const zrt_context* c, zrt_kernel_profile* out) {

@@ -223,7 +223,22 @@ struct zrt_film {
     uint32_t n_owned = 0;              // pixels of zrt_tile_pixels(w, h, tile, rank, nranks)
     uint32_t samples = 0;              // samples summed so far; 0: d_sum's bits are not read
     float4* d_sum = nullptr;           // n_owned (x, y, z: the f32 sums; w: 0)
+    // Adaptive state (zrt_context_refine), allocated by the first
+    // refine call.  d_state[q]: x, y, z the checkpoint (the pixel's linear value
+    // when the previous refine call started tracing), w the bits kFilmFrozen |
+    // n[q] of a frozen pixel, 0 of an active one.
+    float4* d_state = nullptr;         // n_owned
+    uint32_t* d_list = nullptr;        // the active pixels' image indices, packed order (a call's pixlist)
+    uint32_t* d_slot = nullptr;        // ... and their rows in d_sum / d_state
+    uint32_t* d_blk = nullptr;         // per compaction block: its active count, then its base; [nblk]: A
+    uint32_t* d_cnt = nullptr;         // n_owned sample counts, when a caller asks for them
+    size_t cnt_cap = 0;
+    uint32_t checkpoint = 0;          // c: the samples the checkpoints were taken at (0: none)
+    uint32_t active = 0;               // pixels not frozen (n_owned without state)
+    bool state_stale = false;          // d_state holds flags of before a reset / write
+    bool list_valid = false;           // d_list / d_slot are the compaction of d_state's flags as they are
 };
+constexpr uint32_t kFilmFrozen = 0x80000000u;
 
 // A copy on the context's stream, waited for: the product path never uses
 // HIP's null stream, whose first use in a process creates its hardware

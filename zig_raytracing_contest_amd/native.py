@@ -119,6 +119,10 @@ class Outputs(C.Structure):
                 ("linear_packed", C.c_void_p), ("device_rgb_packed", C.c_void_p)]
 
 
+class RefineConfig(C.Structure):
+    _fields_ = [("sample_counts", C.c_void_p), ("threshold", C.c_float), ("min_samples", C.c_uint32)]
+
+
 class Hit(C.Structure):
     _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("triangle", C.c_uint32)]
 
@@ -233,6 +237,7 @@ EXPORTS = [
     "zrt_context_light_probes",
     "zrt_film_create", "zrt_film_reset", "zrt_film_info", "zrt_film_read", "zrt_film_write", "zrt_film_destroy",
     "zrt_context_accumulate",
+    "zrt_context_refine", "zrt_film_counts",
 ]
 
 
@@ -292,6 +297,11 @@ def lib():
         L.zrt_film_destroy.restype = None
         L.zrt_context_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Camera), C.POINTER(RenderConfig),
                                              C.POINTER(Outputs), C.POINTER(Stats)]
+    if hasattr(L, "zrt_context_refine"):   # (likewise)
+        L.zrt_context_refine.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(Camera), C.POINTER(RenderConfig),
+                                         C.POINTER(RefineConfig), C.POINTER(Outputs), C.POINTER(Stats),
+                                         C.POINTER(C.c_uint32)]
+        L.zrt_film_counts.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
     if hasattr(L, "zrt_group_create"):     # ABI 2 (an ABI-1 build: tools/ A/B baselines only)
         L.zrt_group_create.argtypes = [C.POINTER(Scene), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
         L.zrt_group_create_built.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -447,6 +457,14 @@ class Film:
     def samples(self) -> int:
         return self.info()[1]
 
+    def counts(self):
+        """(samples each owned pixel holds (n_owned,) uint32, pixels not frozen):
+        zrt_film_counts.  They differ between pixels after Context.refine."""
+        n = np.zeros(self.n_owned, np.uint32)
+        a = C.c_uint32(0)
+        check(lib().zrt_film_counts(self._h, n.ctypes.data, C.byref(a)), "zrt_film_counts")
+        return n, int(a.value)
+
     def reset(self):
         check(lib().zrt_film_reset(self._h), "zrt_film_reset")
 
@@ -588,6 +606,52 @@ class Context:
                                            C.byref(out) if asked else None, C.byref(st)), "zrt_context_accumulate")
         res["stats"] = st.as_dict()
         res["samples"] = film.samples
+        return res
+
+    def refine(self, film: "Film", cam: Camera, spp: int, max_bounce: int, threshold: float, min_samples: int = 0,
+               seed: int = 0, stats: bool = False, image=None, packed=False, linear=False, device_ptr=None,
+               samples_per_pass=0, flags=0, want_linear=None, counts=False):
+        """zrt_context_refine: accumulate for the pixels of `film` that have not
+        converged.  A pixel whose image changed by no more than `threshold`
+        (relative, see include/zrt.h) since the previous refine call is frozen
+        at the samples it holds, once the film holds `min_samples`; the others
+        get the next `spp` samples.  The outputs show every pixel at its own
+        count -- bit for bit a render's pixel of that many samples.
+        res["active"]: pixels traced; res["counts"] (with counts=True): samples
+        per owned pixel; res["stats"]: of the traced paths only."""
+        cfg = RenderConfig()
+        cfg.num_samples, cfg.max_bounce, cfg.seed = spp, max_bounce, seed
+        cfg.device, cfg.rank, cfg.num_ranks, cfg.tile_size = -1, film.rank, film.num_ranks, film.tile
+        cfg.flags = (FLAG_COUNT_STATS if stats else 0) | flags
+        cfg.samples_per_pass = samples_per_pass
+        if want_linear is not None:
+            linear = want_linear
+        rf = RefineConfig()
+        rf.threshold, rf.min_samples = threshold, min_samples
+        out = Outputs()
+        res = {}
+        if counts:
+            res["counts"] = np.zeros(film.n_owned, np.uint32)
+            rf.sample_counts = res["counts"].ctypes.data
+        if image is not None:
+            out.rgb_image = image.ctypes.data
+        if packed:
+            res["packed"] = np.zeros((film.n_owned, 3), np.uint8)
+            out.rgb_packed = res["packed"].ctypes.data
+        if linear:
+            res["linear"] = np.zeros((film.n_owned, 3), np.float32)
+            out.linear_packed = res["linear"].ctypes.data
+        if device_ptr is not None:
+            out.device_rgb_packed = device_ptr
+        asked = image is not None or packed or linear or device_ptr is not None
+        st = Stats()
+        act = C.c_uint32(0)
+        check(lib().zrt_context_refine(self._h, film._h, C.byref(cam), C.byref(cfg), C.byref(rf),
+                                       C.byref(out) if asked else None, C.byref(st), C.byref(act)),
+              "zrt_context_refine")
+        res["stats"] = st.as_dict()
+        res["samples"] = film.samples
+        res["active"] = int(act.value)
         return res
 
     @staticmethod
