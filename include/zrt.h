@@ -1004,6 +1004,100 @@ int zrt_context_refine(zrt_context* ctx, zrt_film* film, const zrt_camera* camer
 /* counts: host n_owned or null; active: pixels not frozen, or null */
 int zrt_film_counts(zrt_film* film, uint32_t* counts, uint32_t* active);
 
+/* ---- denoise: edge-avoiding a-trous filter (ABI 2, added) ---------------- */
+
+/* The last stage of a progressive frame: a colour frame of a few samples --
+ * a plane, or a film's sums -- smoothed under the guidance of the feature
+ * planes zrt_context_features gives, on the device, into an image one can look
+ * at.  It is the edge-avoiding a-trous wavelet filter (Dammertz et al. 2010):
+ * `iterations` levels of a 5x5 B3-spline kernel with holes, each tap weighted
+ * by how far its colour, normal, depth and albedo are from the centre pixel's.
+ * The weights are compact polynomials, not exp: every operation is an IEEE f32
+ * + - * /, fmaxf or a comparison, left to right as written, nothing contracted
+ * (no FMA); `/` is the IEEE division and fmaxf is C's (a NaN operand gives the
+ * other operand).  So the result is the same bits everywhere.
+ *
+ * P = w * h.  All planes, in and out, are in zrt_tile_pixels(w, h, tile_size,
+ * 0, 1) order -- the order zrt_context_features and a film of rank 0 of 1 use;
+ * with ZRT_DENOISE_ROW_MAJOR they are in row-major image order and tile_size
+ * is ignored (a caller who gathered several ranks' tiles).  The filter needs
+ * every pixel's neighbours: one call covers one whole frame, there is no rank.
+ *
+ * Colour source: exactly one of `color` and `film`.  A film must belong to
+ * ctx, have the same w, h and tile_size (after defaults), be rank 0 of 1 and
+ * hold at least one sample; ZRT_DENOISE_ROW_MAJOR with a film is refused.  The
+ * colour of the film's pixel q is step 4 of zrt_context_refine:
+ * sum[q] * (1.0f / (float)N), N = the pixel's frozen count if it is frozen,
+ * else the film's samples.  The film is read, never written.
+ *
+ * With c_0 the colour frame and h = (1/16, 1/4, 3/8, 1/4, 1/16), for level
+ * i = 0 .. iterations - 1, step = 1 << i:
+ *   s_i = sigma_color * 2^-i (exact);  kc = 1.0f / (s_i * s_i)
+ *   kn = 1.0f / (sigma_normal * sigma_normal);  kz, ka likewise from
+ *   sigma_depth, sigma_albedo
+ *   for every pixel p = (x, y):
+ *     iz = 1.0f / fmaxf(depth[p], 0x1p-20f)      the depth guide is relative
+ *     S = (+0, +0, +0), W = +0
+ *     for dy = -2 .. 2 (outer), dx = -2 .. 2 (inner), q = (x + dx * step,
+ *     y + dy * step), in this order:
+ *       a tap outside the image is skipped
+ *       k  = h[dx + 2] * h[dy + 2]                (exact)
+ *       dc = c_i[p] - c_i[q] per component
+ *       xc = ((dc.x * dc.x + dc.y * dc.y) + dc.z * dc.z) * kc
+ *       wc = fmaxf(1.0f - xc, 0.0f);  wc = wc * wc
+ *       wn likewise from normal[p] - normal[q] and kn
+ *       wa likewise from albedo[p] - albedo[q] and ka
+ *       r  = (depth[p] - depth[q]) * iz;  xz = (r * r) * kz
+ *       wz = fmaxf(1.0f - xz, 0.0f);  wz = wz * wz
+ *       wt = (((k * wc) * wn) * wz) * wa -- an absent guide's factor is left
+ *            out, not multiplied as 1.0f
+ *       if !(wt > 0) the tap is skipped: a NaN anywhere in a tap's guides or
+ *       colour difference drops that tap and does not poison the sum; a NaN
+ *       centre pixel drops every tap
+ *       S.k = S.k + c_i[q].k * wt for k = 0, 1, 2;  W = W + wt
+ *     c_{i+1}[p] = (S.x / W, S.y / W, S.z / W) if W > 0, else c_i[p] bit for bit
+ * The guides are the same at every level; only the colour is filtered.
+ * linear = c_iterations, rgb = toRGB(linear) with the render's own toRGB.  An
+ * inf the arithmetic produces is stored as it is.  A sigma of +inf is allowed:
+ * its k is 0 and the guide drops only taps whose difference is not finite. */
+#define ZRT_DENOISE_ROW_MAJOR 0x100000u  /* zrt_denoise_batch.flags only: planes in row-major image order */
+
+typedef struct zrt_denoise_batch {
+    uint32_t w, h, tile_size; /* the frame; tile_size 0 = 64 */
+    uint32_t iterations;      /* 1..8 */
+    float sigma_color, sigma_normal, sigma_depth, sigma_albedo;   /* > 0, +inf allowed; an absent guide's
+                                                                     is not read */
+    const float* color;       /* P * 3 linear, or null when `film` is given */
+    zrt_film* film;           /* or null */
+    const float* normal;      /* P * 3, or null: that guide's weight is 1 */
+    const float* depth;       /* P, or null */
+    const float* albedo;      /* P * 3, or null */
+    float* linear;            /* P * 3, or null */
+    uint8_t* rgb;             /* P * 3, or null (linear and rgb not both null) */
+    uint32_t on_device;       /* as zrt_ray_batch; applies to color, normal, depth, albedo, linear, rgb
+                                 (4-byte aligned, rgb 1-byte) */
+    uint32_t flags;           /* ZRT_DENOISE_ROW_MAJOR; any other bit is ZRT_ERR_INVALID_ARG */
+    uint32_t _reserved;       /* 0 */
+} zrt_denoise_batch;          /* 104 B; offsets 0 4 8 12 16 20 24 28 32 40 48 56 64 72 80 88 92 96 */
+
+/* Synchronous, one thread at a time per context; alternates freely with
+ * renders, films and every query (the work buffers are its own: four 16-byte
+ * records per pixel, grow-only, freed with the context) and leaves
+ * zrt_context_profile's record untouched.
+ * ZRT_ERR_INVALID_ARG before any device work, the outputs untouched: a null
+ * context or batch; w or h of 0, or P above 2^31; a tile_size zrt_tile_pixels
+ * refuses (not with ZRT_DENOISE_ROW_MAJOR, which ignores it); iterations 0 or
+ * above 8; sigma_color, or the sigma of a present guide, that is NaN, zero or
+ * negative; color and film both set or both null; a film that breaks the rules
+ * above; linear and rgb both null; on_device > 1; a non-zero _reserved; any
+ * other flag bit.
+ * stats (may be null): samples = P; segments = cells_visited = triangle_tests =
+ * hits = 0; render_ms the device time of the call, trace_kernel_ms that of its
+ * kernels (the same for device pointers; a host call's render_ms includes the
+ * staging copies); trace_launches = iterations + 2: one gather, one launch per
+ * level, one present. */
+int zrt_context_denoise(zrt_context* ctx, const zrt_denoise_batch* batch, zrt_stats* stats_or_null);
+
 /* A device group: one context per entry of `devices` (HIP ordinals, repeats
  * allowed), the scene resident on each, rendered by one call -- Scene.render's
  * spawn + join of its workers (stage3.zig:247-256) across GPUs in one

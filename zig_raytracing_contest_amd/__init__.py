@@ -148,6 +148,11 @@ class RenderScene:
         num_samples, seed=seed) gives: see native.Context.features."""
         return self.context.features(camera, num_samples, seed=seed, **kw)
 
+    def denoise(self, w: int, h: int, **kw):
+        """The edge-avoiding a-trous filter over a colour frame or a film's
+        frame so far, guided by the feature planes: see native.Context.denoise."""
+        return self.context.denoise(w, h, **kw)
+
     def occlusion(self, origins, dirs, spp: int, radius=float("inf"), seed: int = 0, index_base: int = 0,
                   flags: int = 0, stats: bool = False, hits: bool = False):
         """Hemisphere visibility at each ray's first hit, `spp` samples of the

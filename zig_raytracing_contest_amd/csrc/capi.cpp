@@ -68,6 +68,21 @@ bool light_probe_batch_ok(const zrt_light_probe_batch* b, uint32_t probe_flags) 
     return b->positions && (b->sh || b->distance || b->hits || b->directions || b->radiance);
 }
 
+bool denoise_batch_ok(const zrt_denoise_batch* b) {
+    if (!b) return false;
+    if ((b->flags & ~ZRT_DENOISE_ROW_MAJOR) != 0u || b->on_device > 1u || b->_reserved != 0u) return false;
+    if (b->w == 0u || b->h == 0u || (uint64_t)b->w * b->h > (1ull << 31)) return false;
+    const bool row_major = (b->flags & ZRT_DENOISE_ROW_MAJOR) != 0u;
+    if (!row_major && (b->tile_size ? b->tile_size : 64u) % 8u != 0u) return false;   // (tile_pixels' rule)
+    if (b->iterations == 0u || b->iterations > 8u) return false;
+    // !(s > 0): NaN, zero and negative; +inf passes
+    if (!(b->sigma_color > 0.0f) || (b->normal && !(b->sigma_normal > 0.0f)) ||
+        (b->depth && !(b->sigma_depth > 0.0f)) || (b->albedo && !(b->sigma_albedo > 0.0f)))
+        return false;
+    if ((b->color != nullptr) == (b->film != nullptr) || (b->film && row_major)) return false;
+    return b->linear || b->rgb;
+}
+
 void zig_tables(double zx[257], double zf[257]) {
     static std::once_flag once;
     static double X[257], F[257];

@@ -4239,7 +4239,7 @@ static uint64_t pass_samples(const zrt_context* c, const zrt_render_config* cfg,
 
 // The packed pixel order of this rank (tile_pixels) in c->pix and d_pix,
 // cached across calls.
-static int rank_pixels(zrt_context* c, const zrt_camera* cam, const zrt_render_config* cfg, uint32_t nranks) {
+int rank_pixels(zrt_context* c, const zrt_camera* cam, const zrt_render_config* cfg, uint32_t nranks) {
     const uint32_t key[5] = {cam->w, cam->h, cfg->tile_size ? cfg->tile_size : 64, cfg->rank, nranks};
     if (c->pix_valid && memcmp(key, c->pix_key, sizeof key) == 0) return ZRT_OK;
     uint32_t n = 0;

@@ -197,6 +197,11 @@ struct zrt_context {
     // host call's planes (12 words per pixel)
     float4* d_facc = nullptr; size_t facc_cap = 0;
     float* d_fout = nullptr; size_t fout_cap = 0;
+    // zrt_context_denoise: the filter's records (4 float4 per pixel: colour +
+    // depth twice, ping-pong; normal + 1/depth; albedo) and a host call's
+    // planes in and out (10 words per pixel)
+    float4* d_dn = nullptr; size_t dn_cap = 0;
+    float* d_dnio = nullptr; size_t dnio_cap = 0;
     // zrt_context_radiance: a chunk's rays with normalised directions (6 floats per ray)
     float* d_nrays = nullptr; size_t nrays_cap = 0;
     std::vector<hipEvent_t> ev_pass;   // per pass: its resolve done
@@ -248,8 +253,10 @@ static hipError_t copy_sync(void* dst, const void* src, size_t n, hipMemcpyKind 
     return e != hipSuccess ? e : hipStreamSynchronize(st);
 }
 
-// context.hip's for resolve_plan, render.hip's for zrt_device_warmup (hidden: not part of libzrt.so's interface)
+// context.hip's for resolve_plan, render.hip's for zrt_device_warmup and for
+// denoise.hip's pixel list (hidden: not part of libzrt.so's interface)
 #pragma GCC visibility push(hidden)
+int rank_pixels(zrt_context* c, const zrt_camera* cam, const zrt_render_config* cfg, uint32_t nranks);
 int context_escape(zrt_context* c, bool forced);
 int context_bfcull(zrt_context* c, bool forced);
 int render_warmup();

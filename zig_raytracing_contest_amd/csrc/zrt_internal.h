@@ -96,6 +96,10 @@ bool direct_batch_ok(const zrt_direct_batch* b, uint32_t trace_flags);
 // ZRT_ERR_UNSUPPORTED, the caller's to tell apart.
 bool light_probe_batch_ok(const zrt_light_probe_batch* b, uint32_t probe_flags);
 
+// zrt_context_denoise's argument checks, which need no device (capi.cpp): every
+// refusal of the header but those that read the film.
+bool denoise_batch_ok(const zrt_denoise_batch* b);
+
 // The packed RGB8 of a context's last render (device memory on its device,
 // 3 * pixels bytes in its rank's zrt_tile_pixels order): what a device group
 // gathers (group.hip).

@@ -31,6 +31,11 @@ TRACE_PARK = 0x10000       # ZRT_TRACE_PARK (zrt_ray_batch / zrt_radiance_batch 
 RADIANCE_PER_SAMPLE = 0x20000   # ZRT_RADIANCE_PER_SAMPLE (zrt_radiance_batch.flags only)
 SEGMENT_ANY = 0x40000      # ZRT_SEGMENT_ANY (zrt_segment_batch.flags only)
 DIRECT_UNSHADOWED = 0x80000   # ZRT_DIRECT_UNSHADOWED (zrt_direct_batch.flags only)
+DENOISE_ROW_MAJOR = 0x100000  # ZRT_DENOISE_ROW_MAJOR (zrt_denoise_batch.flags only)
+# Context.denoise's default sigmas (colour, normal, depth, albedo): the C interface has none.  Chosen on the
+# CPU reference over oracle frames: every finite sigma_color tried lowers the error of a
+# 4-sample frame; these lower it most on the larger frames without blurring the textured scene
+DENOISE_SIGMAS = (4.0, 0.5, 0.1, 0.25)
 LIGHT_POINT, LIGHT_DIRECTIONAL, LIGHT_SPOT = 0, 1, 2
 MISS = 0xFFFFFFFF          # zrt_hit.triangle of a ray that hit nothing
 # zrt_kernel_profile classes (include/zrt.h)
@@ -218,6 +223,14 @@ class LightProbeBatch(C.Structure):
                 ("index_base", C.c_uint64)]
 
 
+class DenoiseBatch(C.Structure):
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("tile_size", C.c_uint32), ("iterations", C.c_uint32),
+                ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("sigma_albedo", C.c_float), ("color", C.c_void_p), ("film", C.c_void_p), ("normal", C.c_void_p),
+                ("depth", C.c_void_p), ("albedo", C.c_void_p), ("linear", C.c_void_p), ("rgb", C.c_void_p),
+                ("on_device", C.c_uint32), ("flags", C.c_uint32), ("_reserved", C.c_uint32)]
+
+
 class RadianceBatch(C.Structure):
     _fields_ = [("num_rays", C.c_uint64), ("rays", C.c_void_p), ("radiance", C.c_void_p), ("rgb", C.c_void_p),
                 ("on_device", C.c_uint32), ("flags", C.c_uint32), ("num_samples", C.c_uint32),
@@ -238,6 +251,7 @@ EXPORTS = [
     "zrt_film_create", "zrt_film_reset", "zrt_film_info", "zrt_film_read", "zrt_film_write", "zrt_film_destroy",
     "zrt_context_accumulate",
     "zrt_context_refine", "zrt_film_counts",
+    "zrt_context_denoise",
 ]
 
 
@@ -302,6 +316,8 @@ def lib():
                                          C.POINTER(RefineConfig), C.POINTER(Outputs), C.POINTER(Stats),
                                          C.POINTER(C.c_uint32)]
         L.zrt_film_counts.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+    if hasattr(L, "zrt_context_denoise"):   # (likewise)
+        L.zrt_context_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseBatch), C.POINTER(Stats)]
     if hasattr(L, "zrt_group_create"):     # ABI 2 (an ABI-1 build: tools/ A/B baselines only)
         L.zrt_group_create.argtypes = [C.POINTER(Scene), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
         L.zrt_group_create_built.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -481,6 +497,11 @@ class Film:
         if a.size != 3 * self.n_owned:
             raise ValueError(f"zrt_film_write: {self.n_owned} x 3 sums expected")
         check(lib().zrt_film_write(self._h, a.ctypes.data, int(samples)), "zrt_film_write")
+
+    def denoise(self, **kw):
+        """Context.denoise(w, h, film=self, tile=self.tile, ...) of the film's
+        context: the frame the film shows, filtered (a film of rank 0 of 1)."""
+        return self._context.denoise(self.w, self.h, film=self, tile=self.tile, **kw)
 
     def close(self):
         if getattr(self, "_h", None) is not None and _lib is not None:
@@ -929,6 +950,99 @@ class Context:
                 img = np.zeros((cam.h * cam.w, width[k]), res[k].dtype)
                 img[pix] = res[k].reshape(n, width[k])
                 images[k] = img.reshape(cam.h, cam.w, width[k])
+            res["images"] = images
+        res["stats"] = st
+        return res
+
+    def denoise_raw(self, w: int, h: int, color_ptr, film, normal_ptr, depth_ptr, albedo_ptr, linear_ptr, rgb_ptr,
+                    on_device: bool, iterations: int, sigma_color: float, sigma_normal: float = 0.0,
+                    sigma_depth: float = 0.0, sigma_albedo: float = 0.0, tile_size: int = 0, flags: int = 0,
+                    reserved: int = 0):
+        """zrt_context_denoise on raw pointers (`film`: a Film or None); returns
+        the stats dict."""
+        batch = DenoiseBatch(int(w), int(h), int(tile_size), int(iterations), sigma_color, sigma_normal, sigma_depth,
+                             sigma_albedo, color_ptr, film._h if film is not None else None, normal_ptr, depth_ptr,
+                             albedo_ptr, linear_ptr, rgb_ptr, 1 if on_device else 0, int(flags), int(reserved))
+        st = Stats()
+        check(lib().zrt_context_denoise(self._h, C.byref(batch), C.byref(st)), "zrt_context_denoise")
+        return st.as_dict()
+
+    def denoise(self, w: int, h: int, color=None, film=None, normal=None, depth=None, albedo=None,
+                iterations: int = 5, sigma_color: float = DENOISE_SIGMAS[0], sigma_normal: float = DENOISE_SIGMAS[1],
+                sigma_depth: float = DENOISE_SIGMAS[2], sigma_albedo: float = DENOISE_SIGMAS[3], tile: int = 64,
+                row_major: bool = False, linear: bool = True, rgb: bool = False, stats: bool = False):
+        """The edge-avoiding a-trous filter over a w x h colour frame
+        (zrt_context_denoise): `iterations` levels of a 5x5 B3 kernel with
+        holes, each tap weighted by how far its colour and its guides -- the
+        planes Context.features gives: `normal`, `depth`, `albedo` (its
+        "base_color"); each may be None -- are from the centre pixel's.
+
+        The colour is `color`, (P, 3) float32 with P = w * h, or `film`, a Film
+        of this context of rank 0 of 1, whose frame so far is filtered (every
+        pixel at its own sample count).  All planes, in and out, are in
+        tile_pixels(w, h, tile) order, as Context.features and the film's
+        outputs are; with row_major=True in image order (not with a film).
+
+        numpy arrays give {"linear": (P, 3) float32, "rgb": (P, 3) uint8} --
+        those asked for -- in the planes' order, "images": the same as
+        (h, w, 3) arrays, and "stats".  CUDA tensors (torch-ROCm) on the
+        context's device -- every plane given must be one -- are filtered in
+        place after a sync of torch's current stream and give "linear" and
+        "rgb" as CUDA tensors, complete when the call returns, and no "images"
+        (a film without a guide plane gives numpy arrays).  `stats` is accepted
+        for symmetry: the stats are filled in every call."""
+        P = int(w) * int(h)
+        if (color is None) == (film is None):
+            raise ValueError("denoise: exactly one of color and film")
+        if not (linear or rgb):
+            raise ValueError("denoise: linear or rgb (or both) must be asked for")
+        given = {"color": (color, 3), "normal": (normal, 3), "depth": (depth, 1), "albedo": (albedo, 3)}
+        planes = {k: v for k, (v, _) in given.items() if v is not None}
+        on_torch = [type(v).__module__.split(".")[0] == "torch" for v in planes.values()]
+        flags = DENOISE_ROW_MAJOR if row_major else 0
+        sig = (float(sigma_color), float(sigma_normal), float(sigma_depth), float(sigma_albedo))
+        res = {}
+        if planes and all(on_torch):
+            import torch
+            dev = next(iter(planes.values())).device
+            for k, v in planes.items():
+                if not v.is_cuda or v.device != dev or v.dtype != torch.float32 or v.numel() != P * given[k][1]:
+                    raise ValueError(f"denoise: {k}: a float32 CUDA tensor of {P} x {given[k][1]} on one device expected")
+            planes = {k: v.contiguous() for k, v in planes.items()}
+            if linear:
+                res["linear"] = torch.empty((P, 3), dtype=torch.float32, device=dev)
+            if rgb:
+                res["rgb"] = torch.empty((P, 3), dtype=torch.uint8, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            ptr = {k: v.data_ptr() for k, v in planes.items()}
+            out = {k: v.data_ptr() for k, v in res.items()}
+            on_device = True
+        elif any(on_torch):
+            raise ValueError("denoise: the planes must be all numpy arrays or all CUDA tensors")
+        else:
+            for k in planes:
+                planes[k] = np.ascontiguousarray(planes[k], np.float32)
+                if planes[k].size != P * given[k][1]:
+                    raise ValueError(f"denoise: {k}: {P} x {given[k][1]} floats expected")
+            if linear:
+                res["linear"] = np.zeros((P, 3), np.float32)
+            if rgb:
+                res["rgb"] = np.zeros((P, 3), np.uint8)
+            ptr = {k: v.ctypes.data for k, v in planes.items()}
+            out = {k: v.ctypes.data for k, v in res.items()}
+            on_device = False
+        st = self.denoise_raw(w, h, ptr.get("color"), film, ptr.get("normal"), ptr.get("depth"), ptr.get("albedo"),
+                              out.get("linear"), out.get("rgb"), on_device, iterations, *sig, tile_size=tile,
+                              flags=flags)
+        if not on_device:
+            pix = None if row_major else tile_pixels(w, h, tile or 64)
+            images = {}
+            for k in list(res):
+                img = res[k]
+                if pix is not None:
+                    img = np.zeros_like(res[k])
+                    img[pix] = res[k]
+                images[k] = img.reshape(h, w, 3)
             res["images"] = images
         res["stats"] = st
         return res
