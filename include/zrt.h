@@ -1098,6 +1098,127 @@ typedef struct zrt_denoise_batch {
  * level, one present. */
 int zrt_context_denoise(zrt_context* ctx, const zrt_denoise_batch* batch, zrt_stats* stats_or_null);
 
+/* ---- reproject: carry a frame's history across a camera change (ABI 2, added) */
+
+/* The stage between the film and the denoiser when the camera moves: the
+ * previous frame's colour is fetched where each pixel of the current frame was
+ * seen from the previous camera, and blended with the current colour by
+ * 1 / history length.  The materials are diffuse, transparent or emissive and
+ * the sky depends on direction only, so the radiance leaving a surface point
+ * does not depend on the view: reprojected history is unbiased except at
+ * disocclusions and over the bilinear footprint.  For every pixel: the world
+ * point it sees from the current depth plane and camera; that point projected
+ * into the previous camera; the previous colour there from four bilinear taps,
+ * a tap counting only if the previous depth (and normal, if given) agrees.
+ * Every operation is an IEEE f32 + - * /, sqrt, floorf, fabsf or a comparison,
+ * left to right as written, nothing contracted (no FMA): the same bits
+ * everywhere.
+ *
+ * w, h come from `camera`; P = w * h.  All planes, in and out, are in
+ * zrt_tile_pixels(w, h, tile_size, 0, 1) order; with ZRT_REPROJECT_ROW_MAJOR
+ * they are row-major and tile_size is ignored.  One call covers a whole
+ * frame: there is no rank.
+ *   dot(a, b)   = (a.x*b.x + a.y*b.y) + a.z*b.z
+ *   cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x)
+ *
+ * Colour source: exactly one of `color` and `film`.  The film's rules and its
+ * presented value are zrt_context_denoise's: it must belong to ctx, have the
+ * same w, h and tile_size (after defaults), be rank 0 of 1 and hold at least
+ * one sample; ZRT_REPROJECT_ROW_MAJOR with a film is refused; its colour is
+ * sum * (1.0f / (float)N) at the pixel's own count N; it is read, never
+ * written.
+ *
+ * Per-call constants, computed once in f32 as written.  O, L, R, U are the
+ * current camera's origin, lower_left_corner, right and up; primes are the
+ * previous camera's:
+ *   A = cross(U', L'), B = cross(L', R'), Cv = cross(R', U'), D = dot(L', Cv)
+ *   if D < 0: A, B and Cv are negated (exact)
+ *   if D is zero or NaN no pixel has a projection
+ *   tn2 = normal_tolerance * normal_tolerance
+ *
+ * Projection.  For pixel p = (x, y) with packed index k, c its current colour
+ * and z = depth[k], the projection is defined iff z > 0 and z < +inf, D is
+ * usable and g > 0 below:
+ *   v  = (L + R * ((float)x + 0.5f)) + U * ((float)y + 0.5f)    the render's getRay order, at the pixel centre
+ *   d  = v * (1.0f / sqrt((v.x*v.x + v.y*v.y) + v.z*v.z))        the render's normalisation
+ *   X  = O + d * z;   q = X - O'
+ *   g  = dot(q, Cv);  a = dot(q, A) / g;  b = dot(q, B) / g;  zq = sqrt(dot(q, q))
+ * (a, b) are the previous camera's continuous pixel coordinates of X and zq
+ * the depth the previous frame should hold there.
+ * motion[k] = (a - ((float)x + 0.5f), b - ((float)y + 0.5f)); without a
+ * projection motion[k] is two 0x7FC00000.
+ *
+ * History needs a projection.  fx = a - 0.5f, fy = b - 0.5f, and all four of
+ * fx > -1.0f, fx < (float)w, fy > -1.0f, fy < (float)h (a NaN fails).
+ * x0 = (int)floorf(fx), tx = fx - (float)x0; y0 and ty likewise.
+ * S = (+0, +0, +0), W = +0, M = 0xFFFFFFFF; for j = 0, 1 (outer), i = 0, 1
+ * (inner), in this order, tap t = (x0 + i, y0 + j):
+ *   a tap outside the image is skipped
+ *   bw = (i ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty);            skipped if !(bw > 0)
+ *   zp = prev_depth[t];                                           skipped if !(zp > 0)
+ *   skipped if !(fabsf(zp - zq) <= depth_tolerance * zq)
+ *   if normal and prev_normal are both given:
+ *     dn = normal[p] - prev_normal[t];   skipped if !(((dn.x*dn.x + dn.y*dn.y) + dn.z*dn.z) <= tn2)
+ *   cp = prev_color[t];                                           skipped if a component is NaN or infinite
+ *   lp = prev_length ? prev_length[t] : 1;                        skipped if lp == 0
+ *   S.k = S.k + cp.k * bw (k = 0, 1, 2);  W = W + bw;  M = min(M, lp)
+ *
+ * Blend.  If W > 0: hist = (S.x / W, S.y / W, S.z / W), N = min(M,
+ * max_history - 1) + 1, alpha = 1.0f / (float)N, out = (hist * (1.0f - alpha))
+ * + (c * alpha) per component -- when N == 1, out is c bit for bit.  Else
+ * out = c bit for bit and N = 1.  color_out[k] = out, length_out[k] = N.  A
+ * NaN or inf the arithmetic produces is stored as it is; it heals at the next
+ * call, because such a tap is skipped.
+ *
+ * Aliasing: the call reads the previous planes completely before it writes
+ * anything.  color_out may be the same pointer as prev_color or as color, and
+ * length_out the same pointer as prev_length; any other overlap is
+ * unspecified.  So a caller keeps one history buffer and passes this frame's
+ * depth and normal planes as the next call's prev_*. */
+#define ZRT_REPROJECT_ROW_MAJOR 0x200000u   /* zrt_reproject_batch.flags only: planes in row-major image order */
+
+typedef struct zrt_reproject_batch {
+    uint32_t tile_size;          /* 0 = 64 */
+    uint32_t max_history;        /* 1..65535: N never exceeds it, so alpha >= 1 / max_history */
+    float depth_tolerance;       /* >= 0, +inf allowed; relative */
+    float normal_tolerance;      /* >= 0, +inf allowed; not read unless both normal planes are given */
+    uint32_t on_device;          /* applies to every plane pointer; the cameras are always host */
+    uint32_t flags;              /* ZRT_REPROJECT_ROW_MAJOR; any other bit is ZRT_ERR_INVALID_ARG */
+    const zrt_camera* camera;        /* current */
+    const zrt_camera* prev_camera;   /* same w, h */
+    const float* color;          /* P * 3, or null when film is given */
+    zrt_film* film;              /* or null */
+    const float* depth;          /* P */
+    const float* normal;         /* P * 3 or null */
+    const float* prev_color;     /* P * 3 */
+    const float* prev_depth;     /* P */
+    const float* prev_normal;    /* P * 3 or null */
+    const uint32_t* prev_length; /* P or null: 1 everywhere */
+    float* color_out;            /* P * 3 */
+    uint32_t* length_out;        /* P or null */
+    float* motion;               /* P * 2 or null */
+    uint64_t _reserved;          /* 0 */
+} zrt_reproject_batch;           /* 136 B; offsets 0 4 8 12 16 20 24 32 40 48 56 64 72 80 88 96 104 112 120 128 */
+
+/* Synchronous, one thread at a time per context; alternates freely with every
+ * other call (the work buffers are its own: two 16-byte records per pixel,
+ * grow-only, freed with the context) and leaves zrt_context_profile's record
+ * untouched.
+ * ZRT_ERR_INVALID_ARG before any device work, the outputs untouched: a null
+ * context or batch, or either camera null; w or h of 0, P above 2^31, or a
+ * previous camera of another size; a tile_size zrt_tile_pixels refuses (not
+ * with ZRT_REPROJECT_ROW_MAJOR); max_history of 0 or above 65535; a tolerance
+ * that is NaN or negative (normal_tolerance only when both normals are given);
+ * color and film both set or both null; a film that breaks the rules above;
+ * null depth, prev_color, prev_depth or color_out; on_device > 1; a non-zero
+ * _reserved; any other flag bit.
+ * stats (may be null): samples = P; hits = the pixels with W > 0; segments =
+ * cells_visited = triangle_tests = 0; render_ms the device time of the call,
+ * trace_kernel_ms that of its kernels (the same for device pointers; a host
+ * call's render_ms includes the staging copies); trace_launches = 2: the
+ * gather of the previous planes into row-major records, and the reprojection. */
+int zrt_context_reproject(zrt_context* ctx, const zrt_reproject_batch* batch, zrt_stats* stats_or_null);
+
 /* A device group: one context per entry of `devices` (HIP ordinals, repeats
  * allowed), the scene resident on each, rendered by one call -- Scene.render's
  * spawn + join of its workers (stage3.zig:247-256) across GPUs in one

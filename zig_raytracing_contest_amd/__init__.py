@@ -153,6 +153,16 @@ class RenderScene:
         frame so far, guided by the feature planes: see native.Context.denoise."""
         return self.context.denoise(w, h, **kw)
 
+    def reproject(self, camera: native.Camera, prev_camera: native.Camera, **kw):
+        """The previous frame's history carried across a camera change and
+        blended with the current colour: see native.Context.reproject."""
+        return self.context.reproject(camera, prev_camera, **kw)
+
+    def history(self, w: int, h: int, **kw):
+        """A native.History of this scene's context: the buffers of a preview
+        under a moving camera."""
+        return native.History(self.context, w, h, **kw)
+
     def occlusion(self, origins, dirs, spp: int, radius=float("inf"), seed: int = 0, index_base: int = 0,
                   flags: int = 0, stats: bool = False, hits: bool = False):
         """Hemisphere visibility at each ray's first hit, `spp` samples of the

@@ -83,6 +83,22 @@ bool denoise_batch_ok(const zrt_denoise_batch* b) {
     return b->linear || b->rgb;
 }
 
+bool reproject_batch_ok(const zrt_reproject_batch* b) {
+    if (!b || !b->camera || !b->prev_camera) return false;
+    if ((b->flags & ~ZRT_REPROJECT_ROW_MAJOR) != 0u || b->on_device > 1u || b->_reserved != 0u) return false;
+    const uint32_t w = b->camera->w, h = b->camera->h;
+    if (w == 0u || h == 0u || (uint64_t)w * h > (1ull << 31)) return false;
+    if (b->prev_camera->w != w || b->prev_camera->h != h) return false;
+    const bool row_major = (b->flags & ZRT_REPROJECT_ROW_MAJOR) != 0u;
+    if (!row_major && (b->tile_size ? b->tile_size : 64u) % 8u != 0u) return false;   // (tile_pixels' rule)
+    if (b->max_history == 0u || b->max_history > 65535u) return false;
+    // !(t >= 0): NaN and negative; +inf passes
+    if (!(b->depth_tolerance >= 0.0f) || (b->normal && b->prev_normal && !(b->normal_tolerance >= 0.0f)))
+        return false;
+    if ((b->color != nullptr) == (b->film != nullptr) || (b->film && row_major)) return false;
+    return b->depth && b->prev_color && b->prev_depth && b->color_out;
+}
+
 void zig_tables(double zx[257], double zf[257]) {
     static std::once_flag once;
     static double X[257], F[257];

@@ -217,6 +217,11 @@ struct zrt_context {
     std::vector<uint32_t> pix;
     uint32_t pix_key[5] = {0, 0, 0, 0, 0};
     bool pix_valid = false;
+    // zrt_context_reproject: the previous frame's records (2 float4 per pixel:
+    // colour + depth; normal + length) and 8 KB of counters of the pixels with
+    // history, and a host call's planes in and out (21 words per pixel)
+    float4* d_rp = nullptr; size_t rp_cap = 0;
+    float* d_rpio = nullptr; size_t rpio_cap = 0;
 };
 
 // The accumulator of one rank's share of a frame (zrt_film_*):

@@ -100,6 +100,9 @@ bool light_probe_batch_ok(const zrt_light_probe_batch* b, uint32_t probe_flags);
 // refusal of the header but those that read the film.
 bool denoise_batch_ok(const zrt_denoise_batch* b);
 
+// zrt_context_reproject's, likewise.
+bool reproject_batch_ok(const zrt_reproject_batch* b);
+
 // The packed RGB8 of a context's last render (device memory on its device,
 // 3 * pixels bytes in its rank's zrt_tile_pixels order): what a device group
 // gathers (group.hip).

@@ -36,6 +36,10 @@ DENOISE_ROW_MAJOR = 0x100000  # ZRT_DENOISE_ROW_MAJOR (zrt_denoise_batch.flags o
 # CPU reference over oracle frames: every finite sigma_color tried lowers the error of a
 # 4-sample frame; these lower it most on the larger frames without blurring the textured scene
 DENOISE_SIGMAS = (4.0, 0.5, 0.1, 0.25)
+REPROJECT_ROW_MAJOR = 0x200000  # ZRT_REPROJECT_ROW_MAJOR (zrt_reproject_batch.flags only)
+# Context.reproject's and History's defaults (max_history, depth_tolerance, normal_tolerance): the C interface
+# has none.  The values the quality condition of tests/test_reproject_host.py is stated for
+REPROJECT_DEFAULTS = (32, 0.05, 0.5)
 LIGHT_POINT, LIGHT_DIRECTIONAL, LIGHT_SPOT = 0, 1, 2
 MISS = 0xFFFFFFFF          # zrt_hit.triangle of a ray that hit nothing
 # zrt_kernel_profile classes (include/zrt.h)
@@ -231,6 +235,15 @@ class DenoiseBatch(C.Structure):
                 ("on_device", C.c_uint32), ("flags", C.c_uint32), ("_reserved", C.c_uint32)]
 
 
+class ReprojectBatch(C.Structure):
+    _fields_ = [("tile_size", C.c_uint32), ("max_history", C.c_uint32), ("depth_tolerance", C.c_float),
+                ("normal_tolerance", C.c_float), ("on_device", C.c_uint32), ("flags", C.c_uint32),
+                ("camera", C.c_void_p), ("prev_camera", C.c_void_p), ("color", C.c_void_p), ("film", C.c_void_p),
+                ("depth", C.c_void_p), ("normal", C.c_void_p), ("prev_color", C.c_void_p), ("prev_depth", C.c_void_p),
+                ("prev_normal", C.c_void_p), ("prev_length", C.c_void_p), ("color_out", C.c_void_p),
+                ("length_out", C.c_void_p), ("motion", C.c_void_p), ("_reserved", C.c_uint64)]
+
+
 class RadianceBatch(C.Structure):
     _fields_ = [("num_rays", C.c_uint64), ("rays", C.c_void_p), ("radiance", C.c_void_p), ("rgb", C.c_void_p),
                 ("on_device", C.c_uint32), ("flags", C.c_uint32), ("num_samples", C.c_uint32),
@@ -252,6 +265,7 @@ EXPORTS = [
     "zrt_context_accumulate",
     "zrt_context_refine", "zrt_film_counts",
     "zrt_context_denoise",
+    "zrt_context_reproject",
 ]
 
 
@@ -318,6 +332,8 @@ def lib():
         L.zrt_film_counts.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
     if hasattr(L, "zrt_context_denoise"):   # (likewise)
         L.zrt_context_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseBatch), C.POINTER(Stats)]
+    if hasattr(L, "zrt_context_reproject"):   # (likewise)
+        L.zrt_context_reproject.argtypes = [C.c_void_p, C.POINTER(ReprojectBatch), C.POINTER(Stats)]
     if hasattr(L, "zrt_group_create"):     # ABI 2 (an ABI-1 build: tools/ A/B baselines only)
         L.zrt_group_create.argtypes = [C.POINTER(Scene), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
         L.zrt_group_create_built.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -502,6 +518,12 @@ class Film:
         """Context.denoise(w, h, film=self, tile=self.tile, ...) of the film's
         context: the frame the film shows, filtered (a film of rank 0 of 1)."""
         return self._context.denoise(self.w, self.h, film=self, tile=self.tile, **kw)
+
+    def reproject(self, camera, prev_camera, **kw):
+        """Context.reproject(camera, prev_camera, film=self, tile=self.tile, ...)
+        of the film's context: the frame the film shows, blended with the
+        previous frame's history (a film of rank 0 of 1)."""
+        return self._context.reproject(camera, prev_camera, film=self, tile=self.tile, **kw)
 
     def close(self):
         if getattr(self, "_h", None) is not None and _lib is not None:
@@ -1047,6 +1069,107 @@ class Context:
         res["stats"] = st
         return res
 
+    def reproject_raw(self, camera: Camera, prev_camera: Camera, color_ptr, film, depth_ptr, normal_ptr, prev_color_ptr,
+                      prev_depth_ptr, prev_normal_ptr, prev_length_ptr, color_out_ptr, length_out_ptr, motion_ptr,
+                      on_device: bool, max_history: int = REPROJECT_DEFAULTS[0],
+                      depth_tolerance: float = REPROJECT_DEFAULTS[1], normal_tolerance: float = REPROJECT_DEFAULTS[2],
+                      tile_size: int = 0, flags: int = 0, reserved: int = 0):
+        """zrt_context_reproject on raw pointers (`film`: a Film or None);
+        returns the stats dict."""
+        batch = ReprojectBatch(int(tile_size), int(max_history), depth_tolerance, normal_tolerance,
+                               1 if on_device else 0, int(flags), C.addressof(camera), C.addressof(prev_camera),
+                               color_ptr, film._h if film is not None else None, depth_ptr, normal_ptr, prev_color_ptr,
+                               prev_depth_ptr, prev_normal_ptr, prev_length_ptr, color_out_ptr, length_out_ptr,
+                               motion_ptr, int(reserved))
+        st = Stats()
+        check(lib().zrt_context_reproject(self._h, C.byref(batch), C.byref(st)), "zrt_context_reproject")
+        return st.as_dict()
+
+    def reproject(self, camera: Camera, prev_camera: Camera, color=None, film=None, depth=None, normal=None,
+                  prev_color=None, prev_depth=None, prev_normal=None, prev_length=None,
+                  max_history: int = REPROJECT_DEFAULTS[0], depth_tolerance: float = REPROJECT_DEFAULTS[1],
+                  normal_tolerance: float = REPROJECT_DEFAULTS[2], tile: int = 64, row_major: bool = False,
+                  motion: bool = False, out=None, length_out=None):
+        """The previous frame's history carried to the current camera and
+        blended with the current colour (zrt_context_reproject): each pixel's
+        world point, from `depth` and `camera`, is projected into
+        `prev_camera`; `prev_color` is fetched there with four bilinear taps,
+        a tap counting only if `prev_depth` (and `prev_normal` against
+        `normal`, when both are given) agrees; the result is
+        hist * (1 - 1 / N) + colour / N with N = min(least tap length,
+        max_history - 1) + 1, or the colour itself and N = 1 without history.
+
+        The colour is `color`, (P, 3) float32 with P = w * h of the cameras,
+        or `film`, a Film of this context of rank 0 of 1.  `depth`,
+        `prev_color` and `prev_depth` are required; `prev_length` (P,) uint32
+        or None: 1 everywhere.  All planes are in tile_pixels(w, h, tile)
+        order, as Context.features and the film's outputs are; with
+        row_major=True in image order (not with a film).
+
+        numpy arrays give {"color": (P, 3) float32, "length": (P,) uint32,
+        "motion": (P, 2) float32 with motion=True, "stats"}.  CUDA tensors
+        (torch-ROCm) on the context's device -- every plane given must be one;
+        lengths are int32 tensors holding the uint32 bits -- are read in place
+        after a sync of torch's current stream and give CUDA tensors, complete
+        when the call returns.  `out` / `length_out`: tensors to write instead
+        of new ones; `out` may be `prev_color` or `color`, `length_out` may be
+        `prev_length` (the call reads the previous planes before it writes)."""
+        w, h = int(camera.w), int(camera.h)
+        P = w * h
+        if (color is None) == (film is None):
+            raise ValueError("reproject: exactly one of color and film")
+        given = {"color": (color, 3), "depth": (depth, 1), "normal": (normal, 3), "prev_color": (prev_color, 3),
+                 "prev_depth": (prev_depth, 1), "prev_normal": (prev_normal, 3), "prev_length": (prev_length, 1)}
+        for k in ("depth", "prev_color", "prev_depth"):
+            if given[k][0] is None:
+                raise ValueError(f"reproject: {k} is required")
+        planes = {k: v for k, (v, _) in given.items() if v is not None}
+        on_torch = [type(v).__module__.split(".")[0] == "torch" for v in planes.values()]
+        flags = REPROJECT_ROW_MAJOR if row_major else 0
+        res = {}
+        if all(on_torch):
+            import torch
+            dev = planes["depth"].device
+            for k, v in planes.items():
+                want = torch.int32 if k == "prev_length" else torch.float32
+                if not v.is_cuda or v.device != dev or v.dtype != want or v.numel() != P * given[k][1]:
+                    raise ValueError(f"reproject: {k}: a {want} CUDA tensor of {P} x {given[k][1]} on one device expected")
+            planes = {k: (v if v.is_contiguous() else v.contiguous()) for k, v in planes.items()}
+            res["color"] = torch.empty((P, 3), dtype=torch.float32, device=dev) if out is None else out
+            res["length"] = torch.empty((P,), dtype=torch.int32, device=dev) if length_out is None else length_out
+            if motion:
+                res["motion"] = torch.empty((P, 2), dtype=torch.float32, device=dev)
+            for k, want, n in (("color", torch.float32, 3 * P), ("length", torch.int32, P)):
+                v = res[k]
+                if not v.is_cuda or v.device != dev or v.dtype != want or v.numel() != n or not v.is_contiguous():
+                    raise ValueError(f"reproject: the {k} output: a contiguous {want} CUDA tensor of {n} expected")
+            torch.cuda.current_stream(dev).synchronize()
+            ptr = {k: v.data_ptr() for k, v in planes.items()}
+            outp = {k: v.data_ptr() for k, v in res.items()}
+            on_device = True
+        elif any(on_torch):
+            raise ValueError("reproject: the planes must be all numpy arrays or all CUDA tensors")
+        else:
+            if out is not None or length_out is not None:
+                raise ValueError("reproject: out and length_out are for CUDA tensors")
+            for k in planes:
+                planes[k] = np.ascontiguousarray(planes[k], np.uint32 if k == "prev_length" else np.float32)
+                if planes[k].size != P * given[k][1]:
+                    raise ValueError(f"reproject: {k}: {P} x {given[k][1]} values expected")
+            res["color"] = np.zeros((P, 3), np.float32)
+            res["length"] = np.zeros(P, np.uint32)
+            if motion:
+                res["motion"] = np.zeros((P, 2), np.float32)
+            ptr = {k: v.ctypes.data for k, v in planes.items()}
+            outp = {k: v.ctypes.data for k, v in res.items()}
+            on_device = False
+        res["stats"] = self.reproject_raw(camera, prev_camera, ptr.get("color"), film, ptr["depth"], ptr.get("normal"),
+                                          ptr["prev_color"], ptr["prev_depth"], ptr.get("prev_normal"),
+                                          ptr.get("prev_length"), outp["color"], outp["length"], outp.get("motion"),
+                                          on_device, max_history, float(depth_tolerance), float(normal_tolerance),
+                                          tile_size=tile, flags=flags)
+        return res
+
     def occlusion_raw(self, num_rays: int, rays_ptr, radius_ptr, visibility_ptr, occluded_ptr, hits_ptr,
                       on_device: bool, spp: int, radius_all: float = float("inf"), seed: int = 0, index_base: int = 0,
                       flags: int = 0):
@@ -1292,6 +1415,62 @@ class Context:
         if rgb:
             res["rgb"] = out8
         return res
+
+
+class History:
+    """The history of an interactive preview under a moving camera: the
+    colour, history-length, depth and normal (and base-colour) planes of one
+    frame size, on the context's device as torch tensors in tile_pixels(w, h,
+    tile) order.  update() after each frame's Context.accumulate; its result
+    goes to Context.denoise."""
+
+    def __init__(self, context: "Context", w: int, h: int, tile: int = 64, max_history: int = REPROJECT_DEFAULTS[0],
+                 depth_tolerance: float = REPROJECT_DEFAULTS[1], normal_tolerance: float = REPROJECT_DEFAULTS[2],
+                 device=None):
+        import torch
+        self._context = context
+        self.w, self.h, self.tile = int(w), int(h), int(tile) or 64
+        self.max_history, self.depth_tolerance, self.normal_tolerance = max_history, depth_tolerance, normal_tolerance
+        P = self.w * self.h
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self.color = torch.zeros((P, 3), dtype=torch.float32, device=dev)
+        self.length = torch.zeros((P,), dtype=torch.int32, device=dev)
+        # the guides of the current frame and of the previous one, swapped by every update
+        self._guides = [{"base_color": torch.zeros((P, 3), dtype=torch.float32, device=dev),
+                         "normal": torch.zeros((P, 3), dtype=torch.float32, device=dev),
+                         "depth": torch.zeros((P,), dtype=torch.float32, device=dev)} for _ in range(2)]
+        self.camera = None               # the previous update's; None: no history yet
+        self.stats = None                # the last update's reproject stats
+        torch.cuda.synchronize(dev)
+
+    def reset(self):
+        """Forget the history: the next update yields the film's frame, lengths 1."""
+        self.camera = None
+
+    def update(self, film: "Film", camera: Camera, seed: int = 0, num_samples: int = 4, **features_kw):
+        """One frame: Context.features(camera, num_samples, seed) into the
+        history's own planes, then the film's frame so far reprojected in
+        place against the previous update's guides and camera.  The first
+        update (or the first after reset()) has no history: the film's frame,
+        lengths 1.  Returns {"color", "normal", "depth", "albedo"}: what
+        Context.denoise(w, h, tile=history.tile, **result) takes; the lengths
+        are in .length, the call's stats in .stats."""
+        if (film.w, film.h, film.tile) != (self.w, self.h, self.tile) or camera.w != self.w or camera.h != self.h:
+            raise ValueError("History.update: the film and the camera must have the history's w, h and tile")
+        cur, prev = self._guides
+        self._context.features_raw(camera, num_samples, {k: v.data_ptr() for k, v in cur.items()}, True, seed,
+                                   tile_size=self.tile, **features_kw)
+        first = self.camera is None
+        # (no history: the frame against itself with max_history 1 is the film's colour bit for bit, lengths 1)
+        self.stats = self._context.reproject(
+            camera, camera if first else self.camera, film=film, depth=cur["depth"], normal=cur["normal"],
+            prev_color=self.color, prev_depth=cur["depth"] if first else prev["depth"],
+            prev_normal=cur["normal"] if first else prev["normal"], prev_length=None if first else self.length,
+            max_history=1 if first else self.max_history, depth_tolerance=self.depth_tolerance,
+            normal_tolerance=self.normal_tolerance, tile=self.tile, out=self.color, length_out=self.length)["stats"]
+        self.camera = Camera.from_buffer_copy(camera)
+        self._guides = [prev, cur]
+        return {"color": self.color, "normal": cur["normal"], "depth": cur["depth"], "albedo": cur["base_color"]}
 
 
 def render_oneshot(scene: Scene, cam: Camera, spp: int, max_bounce: int, seed: int = 0,
