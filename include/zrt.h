@@ -1219,6 +1219,170 @@ typedef struct zrt_reproject_batch {
  * gather of the previous planes into row-major records, and the reprojection. */
 int zrt_context_reproject(zrt_context* ctx, const zrt_reproject_batch* batch, zrt_stats* stats_or_null);
 
+/* ---- svgf: luminance moments and a variance-guided a-trous filter (ABI 2, added) */
+
+/* zrt_context_denoise weighs colour by one absolute sigma for the whole frame;
+ * it does not know how noisy a pixel is.  These two calls add what it lacks
+ * (SVGF, Schied et al. 2017): the colour is divided by the first-hit albedo so
+ * that texture is not filtered, the first two moments of its luminance are
+ * kept beside it, and the filter's luminance weight is scaled by each pixel's
+ * own standard deviation -- estimated from the moments' history where it is
+ * long enough, from the pixel's 7x7 neighbourhood where not -- and the
+ * variance is filtered along with the colour, so that later levels narrow as
+ * the image cleans up.  The temporal half needs no call of its own:
+ * zrt_context_reproject blends any 3-channel plane by 1 / N, the moments
+ * plane (l, l*l, 0) included.  One frame of a preview:
+ *   zrt_context_features -> zrt_context_illumination (film, albedo) ->
+ *   zrt_context_reproject (illumination) -> zrt_context_reproject (moments,
+ *   same previous guides, camera and lengths) -> zrt_context_svgf.
+ * Every operation is an IEEE f32 + - * /, sqrt, fmaxf, fabsf or a comparison,
+ * left to right as written, nothing contracted (no FMA); fmaxf is C's (a NaN
+ * operand gives the other operand): the same bits everywhere.
+ *
+ *   lum(c)  = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z
+ *   dmod(a) = fmaxf(a, 0x1p-4f) per component; a NaN albedo gives 0x1p-4f
+ *
+ * P = w * h.  All planes, in and out, are in zrt_tile_pixels(w, h, tile_size,
+ * 0, 1) order; with ZRT_SVGF_ROW_MAJOR they are in row-major image order and
+ * tile_size is ignored.  One call covers one whole frame: there is no rank.
+ *
+ * zrt_context_illumination.  Colour source: exactly one of `color` and
+ * `film`.  The film's rules and its presented value are zrt_context_denoise's:
+ * it must belong to ctx, have the same w, h and tile_size (after defaults), be
+ * rank 0 of 1 and hold at least one sample; ZRT_SVGF_ROW_MAJOR with a film is
+ * refused; its colour is sum * (1.0f / (float)N) at the pixel's own count N;
+ * it is read, never written.  For every pixel, c its colour:
+ *   I.k = c.k / dmod(albedo.k) for k = 0, 1, 2; without an albedo I is c bit
+ *   for bit
+ *   l = lum(I);  illumination = I;  moments = (l, l * l, +0)
+ * The moments take three channels so that the plane goes through
+ * zrt_context_reproject as a colour plane. */
+#define ZRT_SVGF_ROW_MAJOR 0x400000u   /* zrt_illumination_batch.flags and zrt_svgf_batch.flags only: planes in
+                                          row-major image order */
+
+typedef struct zrt_illumination_batch {
+    uint32_t w, h, tile_size; /* the frame; tile_size 0 = 64 */
+    const float* color;       /* P * 3 linear, or null when `film` is given */
+    zrt_film* film;           /* or null */
+    const float* albedo;      /* P * 3, or null: no demodulation */
+    float* illumination;      /* P * 3, or null */
+    float* moments;           /* P * 3, or null (illumination and moments not both null) */
+    uint32_t on_device;       /* as zrt_ray_batch; applies to color, albedo, illumination, moments */
+    uint32_t flags;           /* ZRT_SVGF_ROW_MAJOR; any other bit is ZRT_ERR_INVALID_ARG */
+    uint32_t _reserved;       /* 0 */
+} zrt_illumination_batch;     /* 72 B; offsets 0 4 8 16 24 32 40 48 56 60 64 */
+
+/* Synchronous, one thread at a time per context; alternates freely with every
+ * other call (a host call's planes are staged in the svgf work buffer,
+ * grow-only, freed with the context) and leaves zrt_context_profile's record
+ * untouched.
+ * ZRT_ERR_INVALID_ARG before any device work, the outputs untouched: a null
+ * context or batch; w or h of 0, or P above 2^31; a tile_size zrt_tile_pixels
+ * refuses (not with ZRT_SVGF_ROW_MAJOR, which ignores it); color and film both
+ * set or both null; a film that breaks the rules above; illumination and
+ * moments both null; on_device > 1; a non-zero _reserved; any other flag bit.
+ * stats (may be null): samples = P; segments = cells_visited = triangle_tests =
+ * hits = 0; render_ms the device time of the call, trace_kernel_ms that of its
+ * kernel (the same for device pointers; a host call's render_ms includes the
+ * staging copies); trace_launches = 1. */
+int zrt_context_illumination(zrt_context* ctx, const zrt_illumination_batch* batch, zrt_stats* stats_or_null);
+
+/* zrt_context_svgf.  `color` is the illumination, normally after
+ * reprojection; `moments` the reprojected moments (component 2 is ignored) and
+ * `length` the history lengths zrt_context_reproject wrote (null: 1
+ * everywhere).  `normal` and `depth` are the guides; `albedo` is not a guide:
+ * the output is remodulated by it.  With h = (1/16, 1/4, 3/8, 1/4, 1/16),
+ * kn = 1.0f / (sigma_normal * sigma_normal), kz likewise from sigma_depth, and
+ * for a centre p and a tap q, exactly as zrt_context_denoise defines them:
+ *   iz = 1.0f / fmaxf(depth[p], 0x1p-20f)
+ *   dn = normal[p] - normal[q];  xn = ((dn.x*dn.x + dn.y*dn.y) + dn.z*dn.z) * kn
+ *   wn = fmaxf(1.0f - xn, 0.0f);  wn = wn * wn
+ *   r  = (depth[p] - depth[q]) * iz;  xz = (r * r) * kz
+ *   wz = fmaxf(1.0f - xz, 0.0f);  wz = wz * wz
+ *
+ * Variance estimate v_0[p].  N = length[p], or 1 when length is null;
+ * m = moments[p].
+ *   if moments is given and N >= 4:  v_0 = fmaxf(m.y - m.x * m.x, 0.0f)
+ *     (the sign of a zero v_0 is unspecified when m.y is -0)
+ *   otherwise the spatial estimate:  S1 = S2 = W = +0
+ *     for dy = -3 .. 3 (outer), dx = -3 .. 3 (inner), q = (x + dx, y + dy):
+ *       a tap outside the image is skipped
+ *       wt = wn * wz -- an absent guide's factor is left out; with both absent
+ *            wt = 1.0f
+ *       lq = lum(color[q])
+ *       the tap is skipped if !(wt > 0) or !(fabsf(lq) < +inf)
+ *       S1 = S1 + lq * wt;  S2 = S2 + (lq * lq) * wt;  W = W + wt
+ *     if W > 0:  m1 = S1 / W;  m2 = S2 / W
+ *                v_0 = fmaxf(m2 - m1 * m1, 0.0f) * (4.0f / (float)min(max(N, 1), 4))
+ *     else       v_0 = +0
+ * A short history widens the spatial estimate: it saw few samples.
+ *
+ * Level i = 0 .. iterations - 1, step = 1 << i, for every pixel p = (x, y):
+ *   g = the 3x3 Gaussian of v_i around p at step 1:  Sg = Wg = +0
+ *     for dy = -1 .. 1 (outer), dx = -1 .. 1 (inner), q = (x + dx, y + dy):
+ *       kk = {1/16, 1/8, 1/16; 1/8, 1/4, 1/8; 1/16, 1/8, 1/16}[dy + 1][dx + 1]
+ *       a tap outside the image is skipped
+ *       Sg = Sg + v_i[q] * kk;  Wg = Wg + kk
+ *     g = Sg / Wg
+ *   den = sigma_luminance * sqrt(g) + 0x1p-16f;  kl = 1.0f / (den * den)
+ *   S = (+0, +0, +0), W = +0, V = +0
+ *   for dy = -2 .. 2 (outer), dx = -2 .. 2 (inner), q = (x + dx * step,
+ *   y + dy * step), zrt_context_denoise's order:
+ *     a tap outside the image is skipped
+ *     k  = h[dx + 2] * h[dy + 2]                  (exact)
+ *     dl = lum(c_i[p]) - lum(c_i[q]);  xl = (dl * dl) * kl
+ *     wl = fmaxf(1.0f - xl, 0.0f);  wl = wl * wl
+ *     wt = ((k * wl) * wn) * wz -- an absent guide's factor is left out
+ *     the tap is skipped if !(wt > 0)
+ *     S.k = S.k + c_i[q].k * wt for k = 0, 1, 2;  W = W + wt
+ *     V = V + v_i[q] * (wt * wt)
+ *   if W > 0:  c_{i+1}[p] = (S.x / W, S.y / W, S.z / W);  v_{i+1}[p] = V / (W * W)
+ *   else both keep their input bits
+ * What follows from the rules: a NaN centre colour makes every wl 0, drops
+ * every tap and returns its bits; a NaN in g makes kl NaN, so that pixel
+ * passes through for that level; a NaN tap colour drops that tap only.  A NaN
+ * tap variance does not drop the tap: it reaches V.
+ *
+ * Present.  f = c_iterations[p]; with albedo f.k = f.k * dmod(albedo.k);
+ * linear = f, rgb = toRGB(f) with the render's own toRGB, variance =
+ * v_iterations[p] (of the illumination: it is not remodulated).  A NaN or inf
+ * the arithmetic produces is stored as it is.  A sigma of +inf is allowed. */
+typedef struct zrt_svgf_batch {
+    uint32_t w, h, tile_size; /* the frame; tile_size 0 = 64 */
+    uint32_t iterations;      /* 1..8 */
+    float sigma_luminance, sigma_normal, sigma_depth;   /* > 0, +inf allowed; an absent guide's is not read */
+    const float* color;       /* P * 3: the illumination */
+    const float* moments;     /* P * 3, or null: the spatial estimate everywhere */
+    const uint32_t* length;   /* P, or null: 1 everywhere */
+    const float* normal;      /* P * 3, or null: that guide's weight is left out */
+    const float* depth;       /* P, or null */
+    const float* albedo;      /* P * 3, or null: no remodulation */
+    float* linear;            /* P * 3, or null */
+    uint8_t* rgb;             /* P * 3, or null (linear and rgb not both null) */
+    float* variance;          /* P, or null */
+    uint32_t on_device;       /* as zrt_ray_batch; applies to every plane pointer (4-byte aligned, rgb 1-byte) */
+    uint32_t flags;           /* ZRT_SVGF_ROW_MAJOR; any other bit is ZRT_ERR_INVALID_ARG */
+    uint32_t _reserved;       /* 0 */
+} zrt_svgf_batch;             /* 120 B; offsets 0 4 8 12 16 20 24 32 40 48 56 64 72 80 88 96 104 108 112 */
+
+/* Synchronous, one thread at a time per context; alternates freely with every
+ * other call (the work buffers are its own: three 16-byte records per pixel
+ * and 8 KB of counters, grow-only, freed with the context) and leaves
+ * zrt_context_profile's record untouched.
+ * ZRT_ERR_INVALID_ARG before any device work, the outputs untouched: a null
+ * context or batch; w or h of 0, or P above 2^31; a tile_size zrt_tile_pixels
+ * refuses (not with ZRT_SVGF_ROW_MAJOR, which ignores it); iterations 0 or
+ * above 8; sigma_luminance, or the sigma of a present guide, that is NaN, zero
+ * or negative; a null color; linear and rgb both null; on_device > 1; a
+ * non-zero _reserved; any other flag bit.
+ * stats (may be null): samples = P; hits = the pixels whose v_0 came from the
+ * moments; segments = cells_visited = triangle_tests = 0; render_ms the device
+ * time of the call, trace_kernel_ms that of its kernels (the same for device
+ * pointers; a host call's render_ms includes the staging copies);
+ * trace_launches = iterations + 3: one gather, the variance estimate, one
+ * launch per level, one present. */
+int zrt_context_svgf(zrt_context* ctx, const zrt_svgf_batch* batch, zrt_stats* stats_or_null);
+
 /* A device group: one context per entry of `devices` (HIP ordinals, repeats
  * allowed), the scene resident on each, rendered by one call -- Scene.render's
  * spawn + join of its workers (stage3.zig:247-256) across GPUs in one

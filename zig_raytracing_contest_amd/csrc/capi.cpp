@@ -99,6 +99,31 @@ bool reproject_batch_ok(const zrt_reproject_batch* b) {
     return b->depth && b->prev_color && b->prev_depth && b->color_out;
 }
 
+bool illumination_batch_ok(const zrt_illumination_batch* b) {
+    if (!b) return false;
+    if ((b->flags & ~ZRT_SVGF_ROW_MAJOR) != 0u || b->on_device > 1u || b->_reserved != 0u) return false;
+    if (b->w == 0u || b->h == 0u || (uint64_t)b->w * b->h > (1ull << 31)) return false;
+    const bool row_major = (b->flags & ZRT_SVGF_ROW_MAJOR) != 0u;
+    if (!row_major && (b->tile_size ? b->tile_size : 64u) % 8u != 0u) return false;   // (tile_pixels' rule)
+    if ((b->color != nullptr) == (b->film != nullptr) || (b->film && row_major)) return false;
+    return b->illumination || b->moments;
+}
+
+bool svgf_batch_ok(const zrt_svgf_batch* b) {
+    if (!b) return false;
+    if ((b->flags & ~ZRT_SVGF_ROW_MAJOR) != 0u || b->on_device > 1u || b->_reserved != 0u) return false;
+    if (b->w == 0u || b->h == 0u || (uint64_t)b->w * b->h > (1ull << 31)) return false;
+    const bool row_major = (b->flags & ZRT_SVGF_ROW_MAJOR) != 0u;
+    if (!row_major && (b->tile_size ? b->tile_size : 64u) % 8u != 0u) return false;   // (tile_pixels' rule)
+    if (b->iterations == 0u || b->iterations > 8u) return false;
+    // !(s > 0): NaN, zero and negative; +inf passes
+    if (!(b->sigma_luminance > 0.0f) || (b->normal && !(b->sigma_normal > 0.0f)) ||
+        (b->depth && !(b->sigma_depth > 0.0f)))
+        return false;
+    if (!b->color) return false;
+    return b->linear || b->rgb;
+}
+
 void zig_tables(double zx[257], double zf[257]) {
     static std::once_flag once;
     static double X[257], F[257];

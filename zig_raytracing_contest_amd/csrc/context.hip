@@ -95,7 +95,8 @@ extern "C" void zrt_context_destroy(zrt_context* c) {
     void* bufs[] = {c->d_cells, c->d_pos, c->d_data, c->d_mats, c->d_texels, c->d_zig, c->d_occ, c->d_occx, c->d_esc,
                     c->d_bfc, c->d_bmask, c->d_sat, c->d_tlo,
                     c->d_pix, c->d_out, c->d_acc, c->d_rgb, c->d_lin, c->d_rays, c->d_hits, c->d_surf, c->d_nrays, c->d_counter,
-                    c->d_stats, c->d_facc, c->d_fout, c->d_dn, c->d_dnio, c->d_rp, c->d_rpio};
+                    c->d_stats, c->d_facc, c->d_fout, c->d_dn, c->d_dnio, c->d_rp, c->d_rpio,
+                    c->d_sv, c->d_svio};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     for (zrt_context::PassSet& ps : c->set) {

@@ -222,6 +222,12 @@ struct zrt_context {
     // history, and a host call's planes in and out (21 words per pixel)
     float4* d_rp = nullptr; size_t rp_cap = 0;
     float* d_rpio = nullptr; size_t rpio_cap = 0;
+    // zrt_context_svgf: the filter's records (3 float4 per pixel: colour +
+    // variance twice, ping-pong; normal + depth) and 8 KB of counters of the
+    // pixels with a temporal variance, and a host call's planes in and out
+    // (19 words per pixel; zrt_context_illumination's 12)
+    float4* d_sv = nullptr; size_t sv_cap = 0;
+    float* d_svio = nullptr; size_t svio_cap = 0;
 };
 
 // The accumulator of one rank's share of a frame (zrt_film_*):

@@ -103,6 +103,10 @@ bool denoise_batch_ok(const zrt_denoise_batch* b);
 // zrt_context_reproject's, likewise.
 bool reproject_batch_ok(const zrt_reproject_batch* b);
 
+// zrt_context_illumination's and zrt_context_svgf's, likewise.
+bool illumination_batch_ok(const zrt_illumination_batch* b);
+bool svgf_batch_ok(const zrt_svgf_batch* b);
+
 // The packed RGB8 of a context's last render (device memory on its device,
 // 3 * pixels bytes in its rank's zrt_tile_pixels order): what a device group
 // gathers (group.hip).

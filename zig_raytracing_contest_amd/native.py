@@ -40,6 +40,10 @@ REPROJECT_ROW_MAJOR = 0x200000  # ZRT_REPROJECT_ROW_MAJOR (zrt_reproject_batch.f
 # Context.reproject's and History's defaults (max_history, depth_tolerance, normal_tolerance): the C interface
 # has none.  The values the quality condition of tests/test_reproject_host.py is stated for
 REPROJECT_DEFAULTS = (32, 0.05, 0.5)
+SVGF_ROW_MAJOR = 0x400000  # ZRT_SVGF_ROW_MAJOR (zrt_illumination_batch.flags and zrt_svgf_batch.flags only)
+# Context.svgf's default sigmas (luminance, in standard deviations; normal; depth): the C interface has none.
+# The values the quality condition of tests/test_svgf_host.py is stated for
+SVGF_SIGMAS = (4.0, 0.5, 0.1)
 LIGHT_POINT, LIGHT_DIRECTIONAL, LIGHT_SPOT = 0, 1, 2
 MISS = 0xFFFFFFFF          # zrt_hit.triangle of a ray that hit nothing
 # zrt_kernel_profile classes (include/zrt.h)
@@ -244,6 +248,20 @@ class ReprojectBatch(C.Structure):
                 ("length_out", C.c_void_p), ("motion", C.c_void_p), ("_reserved", C.c_uint64)]
 
 
+class IlluminationBatch(C.Structure):
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("tile_size", C.c_uint32), ("color", C.c_void_p),
+                ("film", C.c_void_p), ("albedo", C.c_void_p), ("illumination", C.c_void_p), ("moments", C.c_void_p),
+                ("on_device", C.c_uint32), ("flags", C.c_uint32), ("_reserved", C.c_uint32)]
+
+
+class SvgfBatch(C.Structure):
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("tile_size", C.c_uint32), ("iterations", C.c_uint32),
+                ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("color", C.c_void_p), ("moments", C.c_void_p), ("length", C.c_void_p), ("normal", C.c_void_p),
+                ("depth", C.c_void_p), ("albedo", C.c_void_p), ("linear", C.c_void_p), ("rgb", C.c_void_p),
+                ("variance", C.c_void_p), ("on_device", C.c_uint32), ("flags", C.c_uint32), ("_reserved", C.c_uint32)]
+
+
 class RadianceBatch(C.Structure):
     _fields_ = [("num_rays", C.c_uint64), ("rays", C.c_void_p), ("radiance", C.c_void_p), ("rgb", C.c_void_p),
                 ("on_device", C.c_uint32), ("flags", C.c_uint32), ("num_samples", C.c_uint32),
@@ -266,6 +284,7 @@ EXPORTS = [
     "zrt_context_refine", "zrt_film_counts",
     "zrt_context_denoise",
     "zrt_context_reproject",
+    "zrt_context_illumination", "zrt_context_svgf",
 ]
 
 
@@ -334,6 +353,9 @@ def lib():
         L.zrt_context_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseBatch), C.POINTER(Stats)]
     if hasattr(L, "zrt_context_reproject"):   # (likewise)
         L.zrt_context_reproject.argtypes = [C.c_void_p, C.POINTER(ReprojectBatch), C.POINTER(Stats)]
+    if hasattr(L, "zrt_context_svgf"):   # (likewise)
+        L.zrt_context_illumination.argtypes = [C.c_void_p, C.POINTER(IlluminationBatch), C.POINTER(Stats)]
+        L.zrt_context_svgf.argtypes = [C.c_void_p, C.POINTER(SvgfBatch), C.POINTER(Stats)]
     if hasattr(L, "zrt_group_create"):     # ABI 2 (an ABI-1 build: tools/ A/B baselines only)
         L.zrt_group_create.argtypes = [C.POINTER(Scene), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
         L.zrt_group_create_built.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -524,6 +546,11 @@ class Film:
         of the film's context: the frame the film shows, blended with the
         previous frame's history (a film of rank 0 of 1)."""
         return self._context.reproject(camera, prev_camera, film=self, tile=self.tile, **kw)
+
+    def illumination(self, albedo=None, **kw):
+        """Context.illumination(w, h, film=self, albedo=albedo, tile=self.tile,
+        ...) of the film's frame so far (rank 0 of 1)."""
+        return self._context.illumination(self.w, self.h, film=self, albedo=albedo, tile=self.tile, **kw)
 
     def close(self):
         if getattr(self, "_h", None) is not None and _lib is not None:
@@ -1170,6 +1197,170 @@ class Context:
                                           tile_size=tile, flags=flags)
         return res
 
+    @staticmethod
+    def _planes(what, P, given, ints=()):
+        """The planes of a whole-frame call that are not None: (planes, on_device, torch device or None), checked
+        to be all float32 (`ints`: int32 tensors / uint32 arrays) numpy arrays or all CUDA tensors of P x channels."""
+        planes = {k: v for k, (v, _) in given.items() if v is not None}
+        on_torch = [type(v).__module__.split(".")[0] == "torch" for v in planes.values()]
+        if planes and all(on_torch):
+            import torch
+            dev = next(iter(planes.values())).device
+            for k, v in planes.items():
+                want = torch.int32 if k in ints else torch.float32
+                if not v.is_cuda or v.device != dev or v.dtype != want or v.numel() != P * given[k][1]:
+                    raise ValueError(f"{what}: {k}: a {want} CUDA tensor of {P} x {given[k][1]} on one device expected")
+            return {k: (v if v.is_contiguous() else v.contiguous()) for k, v in planes.items()}, True, dev
+        if any(on_torch):
+            raise ValueError(f"{what}: the planes must be all numpy arrays or all CUDA tensors")
+        for k in planes:
+            planes[k] = np.ascontiguousarray(planes[k], np.uint32 if k in ints else np.float32)
+            if planes[k].size != P * given[k][1]:
+                raise ValueError(f"{what}: {k}: {P} x {given[k][1]} values expected")
+        return planes, False, None
+
+    def illumination_raw(self, w: int, h: int, color_ptr, film, albedo_ptr, illumination_ptr, moments_ptr,
+                         on_device: bool, tile_size: int = 0, flags: int = 0, reserved: int = 0):
+        """zrt_context_illumination on raw pointers (`film`: a Film or None);
+        returns the stats dict."""
+        batch = IlluminationBatch(int(w), int(h), int(tile_size), color_ptr, film._h if film is not None else None,
+                                  albedo_ptr, illumination_ptr, moments_ptr, 1 if on_device else 0, int(flags),
+                                  int(reserved))
+        st = Stats()
+        check(lib().zrt_context_illumination(self._h, C.byref(batch), C.byref(st)), "zrt_context_illumination")
+        return st.as_dict()
+
+    def illumination(self, w: int, h: int, color=None, film=None, albedo=None, tile: int = 64, row_major: bool = False,
+                     illumination: bool = True, moments: bool = True, out=None, moments_out=None):
+        """The colour frame divided by max(albedo, 1/16) per component -- what
+        Context.svgf filters, so that texture is not smoothed -- and the moments
+        plane (l, l * l, 0) of its luminance l (zrt_context_illumination), which
+        goes through Context.reproject as a colour plane.
+
+        The colour is `color`, (P, 3) float32 with P = w * h, or `film`, a Film
+        of this context of rank 0 of 1.  `albedo`: Context.features'
+        "base_color", or None: the illumination is the colour bit for bit.
+        Planes are in tile_pixels(w, h, tile) order; with row_major=True in
+        image order (not with a film).
+
+        numpy arrays give {"illumination": (P, 3), "moments": (P, 3) float32}
+        -- those asked for -- and "stats".  CUDA tensors (torch-ROCm) on the
+        context's device are read in place after a sync of torch's current
+        stream and give CUDA tensors, complete when the call returns; `out` /
+        `moments_out`: tensors to write instead of new ones (a film without an
+        albedo plane gives numpy arrays unless one of them is given)."""
+        P = int(w) * int(h)
+        if (color is None) == (film is None):
+            raise ValueError("illumination: exactly one of color and film")
+        given = {"color": (color, 3), "albedo": (albedo, 3), "out": (out, 3), "moments_out": (moments_out, 3)}
+        planes, on_device, dev = self._planes("illumination", P, given)
+        illumination = illumination or out is not None
+        moments = moments or moments_out is not None
+        if not (illumination or moments):
+            raise ValueError("illumination: illumination or moments (or both) must be asked for")
+        res = {}
+        if on_device:
+            import torch
+            if illumination:
+                res["illumination"] = planes.get("out", None)
+                if res["illumination"] is None:
+                    res["illumination"] = torch.empty((P, 3), dtype=torch.float32, device=dev)
+            if moments:
+                res["moments"] = planes.get("moments_out", None)
+                if res["moments"] is None:
+                    res["moments"] = torch.empty((P, 3), dtype=torch.float32, device=dev)
+            if (out is not None and res["illumination"] is not out) or \
+                    (moments_out is not None and res["moments"] is not moments_out):
+                raise ValueError("illumination: out and moments_out must be contiguous")
+            torch.cuda.current_stream(dev).synchronize()
+            ptr = {k: v.data_ptr() for k, v in planes.items()}
+            outp = {k: v.data_ptr() for k, v in res.items()}
+        else:
+            if out is not None or moments_out is not None:
+                raise ValueError("illumination: out and moments_out are for CUDA tensors")
+            if illumination:
+                res["illumination"] = np.zeros((P, 3), np.float32)
+            if moments:
+                res["moments"] = np.zeros((P, 3), np.float32)
+            ptr = {k: v.ctypes.data for k, v in planes.items()}
+            outp = {k: v.ctypes.data for k, v in res.items()}
+        res["stats"] = self.illumination_raw(w, h, ptr.get("color"), film, ptr.get("albedo"), outp.get("illumination"),
+                                             outp.get("moments"), on_device, tile_size=tile,
+                                             flags=SVGF_ROW_MAJOR if row_major else 0)
+        return res
+
+    def svgf_raw(self, w: int, h: int, color_ptr, moments_ptr, length_ptr, normal_ptr, depth_ptr, albedo_ptr,
+                 linear_ptr, rgb_ptr, variance_ptr, on_device: bool, iterations: int,
+                 sigma_luminance: float = SVGF_SIGMAS[0], sigma_normal: float = 0.0, sigma_depth: float = 0.0,
+                 tile_size: int = 0, flags: int = 0, reserved: int = 0):
+        """zrt_context_svgf on raw pointers; returns the stats dict."""
+        batch = SvgfBatch(int(w), int(h), int(tile_size), int(iterations), sigma_luminance, sigma_normal, sigma_depth,
+                          color_ptr, moments_ptr, length_ptr, normal_ptr, depth_ptr, albedo_ptr, linear_ptr, rgb_ptr,
+                          variance_ptr, 1 if on_device else 0, int(flags), int(reserved))
+        st = Stats()
+        check(lib().zrt_context_svgf(self._h, C.byref(batch), C.byref(st)), "zrt_context_svgf")
+        return st.as_dict()
+
+    def svgf(self, w: int, h: int, color=None, moments=None, length=None, normal=None, depth=None, albedo=None,
+             iterations: int = 5, sigma_luminance: float = SVGF_SIGMAS[0], sigma_normal: float = SVGF_SIGMAS[1],
+             sigma_depth: float = SVGF_SIGMAS[2], tile: int = 64, row_major: bool = False, linear: bool = True,
+             rgb: bool = False, variance: bool = False, stats: bool = False):
+        """The variance-guided a-trous filter (zrt_context_svgf) over a w x h
+        illumination frame `color` (Context.illumination's, normally after
+        Context.reproject): each pixel's variance is taken from `moments`
+        where its history `length` is 4 or more, from its 7 x 7 neighbourhood
+        otherwise; `iterations` levels of the 5x5 B3 kernel with holes follow,
+        the luminance weight `sigma_luminance` local standard deviations wide,
+        `normal` and `depth` the guides as in Context.denoise, the variance
+        filtered along; the result is multiplied by max(albedo, 1/16).
+
+        All planes are in tile_pixels(w, h, tile) order, or in image order
+        with row_major=True.  numpy arrays give {"linear": (P, 3) float32,
+        "rgb": (P, 3) uint8, "variance": (P,) float32} -- those asked for --
+        "images" and "stats" (stats["hits"]: the pixels with a temporal
+        variance).  CUDA tensors (torch-ROCm; lengths int32 holding the uint32
+        bits) give CUDA tensors and no "images".  `stats` is accepted for
+        symmetry: the stats are filled in every call."""
+        P = int(w) * int(h)
+        if color is None:
+            raise ValueError("svgf: color is required")
+        if not (linear or rgb):
+            raise ValueError("svgf: linear or rgb (or both) must be asked for")
+        given = {"color": (color, 3), "moments": (moments, 3), "length": (length, 1), "normal": (normal, 3),
+                 "depth": (depth, 1), "albedo": (albedo, 3)}
+        planes, on_device, dev = self._planes("svgf", P, given, ints=("length",))
+        asked = [(k, n, f) for k, n, f, on in (("linear", 3, "float32", linear), ("rgb", 3, "uint8", rgb),
+                                               ("variance", 1, "float32", variance)) if on]
+        res = {}
+        if on_device:
+            import torch
+            for k, n, f in asked:
+                res[k] = torch.empty((P, n) if n > 1 else (P,), dtype=getattr(torch, f), device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            ptr = {k: v.data_ptr() for k, v in planes.items()}
+            out = {k: v.data_ptr() for k, v in res.items()}
+        else:
+            for k, n, f in asked:
+                res[k] = np.zeros((P, n) if n > 1 else (P,), getattr(np, f))
+            ptr = {k: v.ctypes.data for k, v in planes.items()}
+            out = {k: v.ctypes.data for k, v in res.items()}
+        st = self.svgf_raw(w, h, ptr["color"], ptr.get("moments"), ptr.get("length"), ptr.get("normal"),
+                           ptr.get("depth"), ptr.get("albedo"), out.get("linear"), out.get("rgb"), out.get("variance"),
+                           on_device, iterations, float(sigma_luminance), float(sigma_normal), float(sigma_depth),
+                           tile_size=tile, flags=SVGF_ROW_MAJOR if row_major else 0)
+        if not on_device:
+            pix = None if row_major else tile_pixels(w, h, tile or 64)
+            images = {}
+            for k in list(res):
+                img = res[k]
+                if pix is not None:
+                    img = np.zeros_like(res[k])
+                    img[pix] = res[k]
+                images[k] = img.reshape((h, w, 3) if img.ndim == 2 else (h, w))
+            res["images"] = images
+        res["stats"] = st
+        return res
+
     def occlusion_raw(self, num_rays: int, rays_ptr, radius_ptr, visibility_ptr, occluded_ptr, hits_ptr,
                       on_device: bool, spp: int, radius_all: float = float("inf"), seed: int = 0, index_base: int = 0,
                       flags: int = 0):
@@ -1471,6 +1662,79 @@ class History:
         self.camera = Camera.from_buffer_copy(camera)
         self._guides = [prev, cur]
         return {"color": self.color, "normal": cur["normal"], "depth": cur["depth"], "albedo": cur["base_color"]}
+
+
+class SvgfHistory:
+    """History's counterpart for Context.svgf: the illumination (the colour
+    divided by the first-hit albedo), the luminance-moments and the
+    history-length planes of one frame size beside the two guide sets, on the
+    context's device as torch tensors in tile_pixels(w, h, tile) order.
+    update() after each frame's Context.accumulate; its result goes to
+    Context.svgf."""
+
+    def __init__(self, context: "Context", w: int, h: int, tile: int = 64, max_history: int = REPROJECT_DEFAULTS[0],
+                 depth_tolerance: float = REPROJECT_DEFAULTS[1], normal_tolerance: float = REPROJECT_DEFAULTS[2],
+                 device=None):
+        import torch
+        self._context = context
+        self.w, self.h, self.tile = int(w), int(h), int(tile) or 64
+        self.max_history, self.depth_tolerance, self.normal_tolerance = max_history, depth_tolerance, normal_tolerance
+        P = self.w * self.h
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self.color = torch.zeros((P, 3), dtype=torch.float32, device=dev)       # the illumination's history
+        self.moments = torch.zeros((P, 3), dtype=torch.float32, device=dev)
+        self.length = torch.zeros((P,), dtype=torch.int32, device=dev)
+        # both reprojections of a frame read .length; they write this plane, which then takes its place
+        self._length_next = torch.zeros((P,), dtype=torch.int32, device=dev)
+        # this frame's illumination and moments before they are blended into the histories
+        self._frame = [torch.zeros((P, 3), dtype=torch.float32, device=dev) for _ in range(2)]
+        # the guides of the current frame and of the previous one, swapped by every update
+        self._guides = [{"base_color": torch.zeros((P, 3), dtype=torch.float32, device=dev),
+                         "normal": torch.zeros((P, 3), dtype=torch.float32, device=dev),
+                         "depth": torch.zeros((P,), dtype=torch.float32, device=dev)} for _ in range(2)]
+        self.camera = None               # the previous update's; None: no history yet
+        self.stats = None                # the last update's reproject stats: (illumination's, moments')
+        torch.cuda.synchronize(dev)
+
+    def reset(self):
+        """Forget the history: the next update yields the film's frame, lengths 1."""
+        self.camera = None
+
+    def update(self, film: "Film", camera: Camera, seed: int = 0, num_samples: int = 4, **features_kw):
+        """One frame: Context.features(camera, num_samples, seed) into the
+        history's own planes, the film's frame so far demodulated by the new
+        base colour (Context.illumination), then the illumination and its
+        moments each reprojected in place against the previous update's
+        guides, camera and lengths.  The lengths are written once, after both
+        calls have read the previous ones.  The first update (or the first
+        after reset()) has no history: the frame itself, lengths 1.  Returns
+        {"color", "moments", "length", "normal", "depth", "albedo"}: what
+        Context.svgf(w, h, tile=history.tile, **result) takes; the calls'
+        stats are in .stats."""
+        if (film.w, film.h, film.tile) != (self.w, self.h, self.tile) or camera.w != self.w or camera.h != self.h:
+            raise ValueError("SvgfHistory.update: the film and the camera must have the history's w, h and tile")
+        cur, prev = self._guides
+        self._context.features_raw(camera, num_samples, {k: v.data_ptr() for k, v in cur.items()}, True, seed,
+                                   tile_size=self.tile, **features_kw)
+        illum, mom = self._frame
+        self._context.illumination(self.w, self.h, film=film, albedo=cur["base_color"], tile=self.tile, out=illum,
+                                   moments_out=mom)
+        first = self.camera is None
+        # (no history: the frame against itself with max_history 1 is the frame bit for bit, lengths 1)
+        common = dict(depth=cur["depth"], normal=cur["normal"], prev_depth=cur["depth"] if first else prev["depth"],
+                      prev_normal=cur["normal"] if first else prev["normal"],
+                      prev_length=None if first else self.length, max_history=1 if first else self.max_history,
+                      depth_tolerance=self.depth_tolerance, normal_tolerance=self.normal_tolerance, tile=self.tile,
+                      length_out=self._length_next)
+        prev_camera = camera if first else self.camera
+        self.stats = tuple(self._context.reproject(camera, prev_camera, color=now, prev_color=hist, out=hist,
+                                                   **common)["stats"]
+                           for now, hist in ((illum, self.color), (mom, self.moments)))
+        self.length, self._length_next = self._length_next, self.length
+        self.camera = Camera.from_buffer_copy(camera)
+        self._guides = [prev, cur]
+        return {"color": self.color, "moments": self.moments, "length": self.length, "normal": cur["normal"],
+                "depth": cur["depth"], "albedo": cur["base_color"]}
 
 
 def render_oneshot(scene: Scene, cam: Camera, spp: int, max_bounce: int, seed: int = 0,
