@@ -772,6 +772,145 @@ typedef struct zrt_direct_batch {
  * items that are not traced add nothing. */
 int zrt_context_direct(zrt_context* ctx, const zrt_direct_batch* batch, zrt_stats* stats_or_null);
 
+/* ---- area-light queries (ABI 2, added) ---------------------------------- */
+
+/* Direct light from the scene's own lights: its emissive triangles, sampled by
+ * next-event estimation and shadowed through transparent hits as the path
+ * tracer sees them.  Two pieces: an emitter set, built once on the device from
+ * the caller's source triangles and the context's materials, and the call,
+ * zrt_context_direct's sibling.  Nothing per (ray, sample) item crosses the
+ * bus, and both are specified bit for bit.
+ *
+ * The emitter set.  The input is the caller's source triangle soup, the arrays
+ * zrt_context_create_built takes, as HOST pointers: positions n * 9 floats
+ * (v0, v1, v2), texcoords n * 6 floats or null for zeros, material n entries
+ * indexing the context's materials (an index at or above their number is
+ * ZRT_ERR_INVALID_ARG).  It is NOT the context's baked refs: those are
+ * duplicated per grid cell and carry no source id.  A triangle that appears
+ * twice in the soup counts as two lights.  Everything below runs on the device
+ * from the context's own material table and texel pool, in f32, nothing
+ * contracted, left to right:
+ *   per material  m = the fmaxf fold, starting from +0, over every component of
+ *                 every texel of its emissive texture (a maximum is order-free;
+ *                 NaN and negative texels fall away, +inf stays)
+ *   per triangle  e1 = v1 - v0;  e2 = v2 - v0;  n = cross(e1, e2) (linalg.zig:173)
+ *                 a = 0.5f * length(n);  w = a * m
+ *                 an emitter iff w > 0 and w is finite
+ * Emitters keep source-triangle order.  Over them:
+ *   wmax = the maximum w
+ *   q_k  = max(1, (uint32_t)((w_k / wmax) * 0x1p24f)) -- the IEEE division, the
+ *          conversion truncating
+ *   C_k  = the exclusive prefix sum of q as uint64_t;  Q = their total
+ * The distribution is made of integers on purpose: integer sums are
+ * associative, so the device's parallel scans agree with a serial sum bit for
+ * bit.  More than 2^28 emitters is ZRT_ERR_UNSUPPORTED: Q stays below 2^52 and
+ * (float)Q has one rounding however it is computed.  A set with zero emitters
+ * is valid (Q = 0). */
+typedef struct zrt_emitters zrt_emitters;
+typedef struct zrt_emitter {
+    float v0[3];              /* the source triangle's first vertex */
+    float a;                  /* its area, as above */
+    float e1[3];
+    uint32_t q;
+    float e2[3];
+    uint32_t material;
+    float texcoords[6];       /* of v0, v1, v2 */
+    uint32_t triangle;        /* index into the caller's soup */
+    uint32_t _reserved;       /* 0 */
+} zrt_emitter;                /* 80 B */
+
+/* Synchronous, on the context's stream, one thread at a time per context.  The
+ * set belongs to the context it was made on and must be destroyed before it;
+ * it holds no reference to the caller's arrays and is not changed by renders
+ * or queries.  ZRT_ERR_INVALID_ARG before any device work: a null context, out
+ * or material, null positions with num_triangles > 0, a material index out of
+ * range.  num_triangles == 0 gives the empty set. */
+int zrt_emitters_create(zrt_context* ctx, const float* positions, const float* texcoords, const uint32_t* material,
+                        uint32_t num_triangles, zrt_emitters** out);
+/* Any of the three outputs may be null. */
+int zrt_emitters_info(const zrt_emitters* set, uint32_t* num_emitters, uint64_t* total_q, uint32_t* num_triangles);
+/* records: num_emitters zrt_emitter, prefix: num_emitters uint64_t (C); host
+ * pointers, either may be null. */
+int zrt_emitters_read(const zrt_emitters* set, zrt_emitter* records, uint64_t* prefix);
+void zrt_emitters_destroy(zrt_emitters* set);
+
+/* The call.  dot, length and normalize_rn as in zrt_context_direct; all
+ * arithmetic f32, nothing contracted, left to right.  For ray i:
+ *   h = the zrt_context_trace record of ray i (stored to hits[i] if asked)
+ *   r = the zrt_surface of (ray i, h)
+ *   a miss: irradiance[i] and radiance[i] are three +0
+ *   a hit: N = normalize_rn(r.normal); the ray is shaded iff every component of
+ *     r.position and of N is finite, as in zrt_context_direct; a ray that is
+ *     not shaded has no traced item, E = +0 and radiance = r.emissive
+ *   E = (+0, +0, +0); for s = 0 .. num_samples - 1, in this order:
+ *     x0, x1, x2 = the first three raw 64-bit outputs of the stream (seed,
+ *       (uint32_t)(index_base + i), s) -- the render's SplitMix64 stream, whole
+ *       words, so that no float draw's word count enters
+ *     rsel = the high 64 bits of the 128-bit product x0 * Q
+ *     k = the emitter with C_k <= rsel < C_k + q_k
+ *     bu = (float)(x1 >> 40) * 0x1p-24f;  bv = (float)(x2 >> 40) * 0x1p-24f
+ *     if bu + bv > 1: bu = 1 - bu; bv = 1 - bv            (the fold: no square root)
+ *     y = (v0 + e1 * bu) + e2 * bv
+ *     texcoord = zrt_surface's interpolation with (u, v) = (bu, bv): weights
+ *       w0 = (1 - bu) - bv, (tc0 * w0 + tc1 * bu) + tc2 * bv per component
+ *     Le, alpha = the emitter's material's emissive and transparency textures
+ *       sampled there.  The path tracer scatters off a surface -- and so sees
+ *       its emission -- when `U > transparency` fails (stage3.zig:207): an
+ *       emitter shows alpha * Le, the rest passes through
+ *     v = y - r.position;  d2 = dot(v, v);  wdir = normalize_rn(v)
+ *     c = dot(N, wdir);  cl = -dot(normalize_rn(cross(e1, e2)), wdir) --
+ *       emitters are one-sided: the reference culls back faces
+ *     the item is traced iff c > 0 and cl > 0 (a NaN fails both)
+ *     g = ((c * cl) / d2) * (((float)Q / (float)q_k) * a_k)
+ *     T = the zrt_context_transmittance result of (r.position, wdir, b,
+ *       max_crossings) with b = length(v) * 0x1.ff8p-1f (1 - 2^-10).  The
+ *       emitter itself lies at t ~ length(v) and a traced item always faces its
+ *       front, so an unshortened bound would let rounding decide whether the
+ *       lamp shadows itself.  The price: an occluder within 0.1% of the
+ *       distance in front of the lamp is not seen.  With ZRT_AREA_UNSHADOWED
+ *       T = 1 and nothing is traced
+ *     E.j = E.j + ((Le.j * alpha) * g) * T  for j = 0, 1, 2
+ *     an item that is not traced adds nothing
+ *   irradiance[i].j = E.j / (float)num_samples -- the IEEE division
+ *   radiance[i].j = r.emissive[j] + (r.base_color[j] * irradiance[i].j) * 0x1.45f306p-2f
+ * A NaN or inf the arithmetic produces is stored as it is.  An empty set
+ * stores +0 irradiance (radiance = r.emissive + (base_color * 0) / pi as
+ * above) and traces nothing. */
+#define ZRT_AREA_UNSHADOWED 0x800000u    /* zrt_area_light_batch.flags only: T = 1 for every traced item, no
+                                            shadow segment */
+
+typedef struct zrt_area_light_batch {
+    uint64_t num_rays;
+    const float* rays;        /* num_rays * 6, as zrt_ray_batch */
+    const zrt_emitters* emitters;
+    float* irradiance;        /* num_rays * 3, or null */
+    float* radiance;          /* num_rays * 3, or null (irradiance and radiance not both null) */
+    zrt_hit* hits;            /* num_rays, or null: the first hits, as zrt_context_trace */
+    uint32_t on_device;       /* as zrt_ray_batch; applies to rays, irradiance, radiance, hits */
+    uint32_t flags;           /* zrt_ray_batch's flags | ZRT_AREA_UNSHADOWED */
+    uint32_t num_samples;     /* 1..65535 */
+    uint32_t max_crossings;   /* 1..256, as zrt_transmittance_batch */
+    uint64_t seed;
+    uint64_t index_base;      /* stream key of ray 0; keys wrap at 2^32 */
+} zrt_area_light_batch;       /* 80 B */
+
+/* Synchronous, one thread at a time per context; alternates freely with
+ * renders and the other queries and leaves zrt_context_profile's record
+ * untouched.  First hits, chunks, sub-chunks of at most 2^20 (ray, sample)
+ * items (a ray's samples may straddle a cut and still add in sample order) and
+ * the chains' lane walk are zrt_context_direct's.
+ * num_rays == 0 returns ZRT_OK and touches nothing.  ZRT_ERR_INVALID_ARG before
+ * any device work, the outputs untouched: a null context or batch, null rays or
+ * emitters, a set made on another context, irradiance and radiance both null,
+ * num_samples 0 or above 65535, max_crossings 0 or above 256, on_device > 1, a
+ * flag zrt_context_trace would refuse.
+ * stats (may be null), in every call: segments = num_rays + the chains'
+ * segments, samples = the traced items, hits = the chains' crossings; with
+ * ZRT_FLAG_COUNT_STATS cells_visited and triangle_tests: the sum of a counting
+ * zrt_context_trace call over the rays and a counting
+ * zrt_context_transmittance call over exactly the traced items. */
+int zrt_context_area_lights(zrt_context* ctx, const zrt_area_light_batch* batch, zrt_stats* stats_or_null);
+
 /* ---- light-probe queries (ABI 2, added) --------------------------------- */
 
 /* The light arriving at a point from all directions: per probe position the

@@ -87,6 +87,9 @@ class RenderScene:
         self.context = native.Context(self.geometry.scene, device)
 
     def close(self):
+        if getattr(self, "_emitters", None) is not None:
+            self._emitters.close()
+            self._emitters = None
         self.context.close()
 
     def render(self, camera: native.Camera, img: Optional[np.ndarray] = None, num_samples: int = 3,
@@ -178,6 +181,20 @@ class RenderScene:
         return self.context.direct(origins, dirs, lights, max_crossings=max_crossings, flags=flags,
                                    unshadowed=unshadowed, irradiance=irradiance, radiance=radiance, hits=hits,
                                    stats=stats)
+
+    def emitters(self):
+        """The native.Emitters of this scene's own emissive triangles (its soup
+        and the context's materials), built on first use and kept."""
+        if getattr(self, "_emitters", None) is None:
+            self._emitters = native.Emitters(self.context, np.asarray(self.soup.pos, np.float32).reshape(-1, 9),
+                                             np.asarray(self.soup.uv, np.float32).reshape(-1, 6), self.soup.mat)
+        return self._emitters
+
+    def area_lights(self, origins, dirs, spp: int, emitters=None, **kw):
+        """Direct light of the scene's emissive triangles at each ray's first
+        hit, `spp` next-event samples per ray (emitters: a native.Emitters,
+        by default this scene's own): see native.Context.area_lights."""
+        return self.context.area_lights(origins, dirs, self.emitters() if emitters is None else emitters, spp, **kw)
 
     def light_probes(self, positions, num_directions: int, spp: int, max_bounce: int, seed: int = 0,
                      index_base: int = 0, flags: int = 0, sh: bool = True, distance: bool = False, hits: bool = False,

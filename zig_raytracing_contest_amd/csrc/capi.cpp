@@ -58,6 +58,16 @@ bool direct_batch_ok(const zrt_direct_batch* b, uint32_t trace_flags) {
     return true;
 }
 
+bool area_light_batch_ok(const zrt_context* c, const zrt_area_light_batch* b, uint32_t trace_flags) {
+    if (!b) return false;
+    if ((b->flags & ~(trace_flags | ZRT_AREA_UNSHADOWED)) != 0u || b->on_device > 1u || b->num_samples == 0u ||
+        b->num_samples > 65535u || b->max_crossings == 0u || b->max_crossings > 256u)
+        return false;
+    if (b->num_rays == 0) return true;
+    if (!b->rays || !b->emitters || (!b->irradiance && !b->radiance)) return false;
+    return b->emitters->ctx == c;
+}
+
 bool light_probe_batch_ok(const zrt_light_probe_batch* b, uint32_t probe_flags) {
     if (!b) return false;
     if ((b->flags & ~probe_flags) != 0u || b->on_device > 1u || b->_reserved != 0u || b->num_directions == 0u ||

@@ -24,13 +24,13 @@
 #include <new>
 
 #include "render_context.h"
+#include "emitters.h"
 #include "escape.h"
 
 using namespace zrt;
 
 namespace {
 
-constexpr float kFltEps = 1.1920928955078125e-07f;   // std.math.floatEps(f32)
 constexpr int kTraceBlock = 512;                     // launch bound of wf_kernel / trace_kernel
 constexpr int kTraceThreads = 256;                   // threads per wf_kernel / trace_kernel block
 // (r03ze, full spp: 1 -1.3 / -0.6 / -1.5%, 3 -0.6 / -0.2 / -0.6% on cfg3 /
@@ -2323,11 +2323,6 @@ __device__ __forceinline__ bool ray_fast(v3 d) {
     const float n2 = dot(d, d);
     return n2 >= 0.5f && n2 <= 1.5f;
 }
-__device__ __forceinline__ void ray_load(const float* rays, uint32_t i, v3& o, v3& d) {
-    const float* q = rays + 6ull * i;
-    o = mk(q[0], q[1], q[2]);
-    d = mk(q[3], q[4], q[5]);
-}
 __device__ __forceinline__ float query_bound(const QueryParams& q, uint32_t i) { return q.t_max ? q.t_max[i] : q.t_max_all; }
 // The zrt_hit of a ray and / or its byte (a lane's own plain store:
 // global_store_byte); a miss is (+inf, 0, 0, 0xFFFFFFFF), which the reference
@@ -2567,37 +2562,7 @@ struct SurfaceParams {
     const float* texels;
     uint32_t n;               // rays of this chunk
 };
-// The shading inputs of a hit, stage3.zig:199-206: the arithmetic is
-// shade_segment's (its lines "stage3.zig:199-206" to `nrm`), restated here
-// because shade_segment is welded to the RNG draw and the queue append: keep
-// the two in step.  surface_kernel and feature_walk_kernel share this one.  The
-// four Data loads of a hit lane are issued together before any texel load
-// (tri_rec's reason).  The materials are read from global memory whatever
-// their number: a copy in LDS for up to kLdsMats of them, the shade kernel's
-// LMATS, was built and measured beside surface_kernel and did not win in every
-// round, so one path serves both sides of that limit.
-struct SurfaceInputs {
-    v3 nrm, albedo, emissive;
-    float transparency, tc0, tc1;
-    float mat;                // Data.material_idx, the bits of d3.w
-};
-__device__ __forceinline__ SurfaceInputs surface_gather(const float4* tri_data, const DevMat* mats, const float* texels,
-                                                        float hu, float hv, uint32_t ref) {
-    const float4* tdp = tri_data + 4ull * ref;
-    const float4 d0 = tdp[0], d1 = tdp[1], d2 = tdp[2], d3 = tdp[3];   // stage3.zig:199-206
-    SurfaceInputs g;
-    const float w0 = 1.0f - hu - hv;
-    g.tc0 = (d2.y * w0 + d2.w * hu) + d3.y * hv;
-    g.tc1 = (d2.z * w0 + d3.x * hu) + d3.z * hv;
-    const DevMat& m = mats[__float_as_uint(d3.w)];
-    g.albedo = sample3(texels, m.tex[0], g.tc0, g.tc1);
-    g.emissive = sample3(texels, m.tex[1], g.tc0, g.tc1);
-    g.transparency = sample1(texels, m.tex[2], g.tc0, g.tc1);
-    g.nrm = add(add(scale(mk(d0.x, d0.y, d0.z), w0), scale(mk(d0.w, d1.x, d1.y), hu)),
-                scale(mk(d1.z, d1.w, d2.x), hv));
-    g.mat = d3.w;
-    return g;
-}
+// The shading inputs of a hit (SurfaceInputs, surface_gather): emitters.h, shared with emitters.hip.
 // One lane per ray; a miss lane loads nothing after its hit record and ray.
 __global__ __launch_bounds__(kBlock) void surface_kernel(const SurfaceParams r) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
@@ -3090,10 +3055,6 @@ constexpr uint32_t kOccGenItems = 4;           // items per thread of occlusion_
 constexpr uint32_t kOccQueue = 0, kOccList = 1, kOccFinish = 2;
 constexpr uint32_t kOccStat = 16;              // (stats[0..3] are the walk kernels', [0..15] the counting render's)
 
-__device__ __forceinline__ bool finite3(v3 a) {
-    return fabsf(a.x) < kInf && fabsf(a.y) < kInf && fabsf(a.z) < kInf;       // (false for a NaN)
-}
-
 // A block takes kOccGenItems * kBlock consecutive items, a wave 64 consecutive
 // ones at a time (one queue region: region bounds are multiples of 64 or m).
 // The normal and the position are surface_kernel's: surface_gather's `nrm`
@@ -3288,13 +3249,6 @@ struct DirectParams {
 constexpr uint32_t kDirItems = 1u << 20;       // items per sub-chunk
 constexpr uint32_t kDirGenItems = 4;           // items per thread of direct_gen_kernel
 constexpr uint32_t kDirStat = 16;              // (stats[0..3] are the walk kernels', [0..15] the counting render's)
-constexpr float kInvPi = 0x1.45f306p-2f;       // 1 / pi rounded to f32, 0x3EA2F983
-
-__device__ __forceinline__ uint4 hit_load(const uint32_t* hits, bool aligned, uint32_t ray) {
-    if (aligned) return reinterpret_cast<const uint4*>(hits)[ray];
-    const uint32_t* hq = hits + 4ull * ray;
-    return make_uint4(hq[0], hq[1], hq[2], hq[3]);
-}
 
 // A block takes kDirGenItems * kBlock consecutive items, a wave 64 consecutive
 // ones at a time.  The normal and the position are surface_kernel's:
@@ -6037,6 +5991,217 @@ extern "C" int zrt_context_direct(zrt_context* c, const zrt_direct_batch* b, zrt
     st.segments = b->num_rays + hs[kDirStat];
     st.samples = traced;
     st.hits = hs[kDirStat + 1];
+    if (counting) {
+        st.cells_visited = hs[1];
+        st.triangle_tests = hs[2];
+    }
+    if (stats) *stats = st;
+    return ZRT_OK;
+}
+
+// zrt_context_area_lights (include/zrt.h): next-event estimation over an
+// emitter set; the (ray, sample) items, the set and the two item kernels are
+// emitters.hip's (emitters.h).  zrt_context_direct's plan, chunk
+// loop, staging, chains and stats with the lights' row replaced by the set,
+// which lives in memory of its own: per chunk the first hits, then per
+// sub-chunk of at most kAreaItems items area_gen_kernel, the list's size read
+// back, the transmittance call's lane launches over the list and
+// area_reduce_kernel.  A host batch's rays, the list and the item rows lie in
+// d_rays; the hit records and a host batch's (or an unasked) irradiance and
+// radiance in d_hits.  Each use writes what it reads first.
+static_assert((ZRT_AREA_UNSHADOWED & (kTraceFlags | ZRT_RADIANCE_PER_SAMPLE | ZRT_SEGMENT_ANY | ZRT_DIRECT_UNSHADOWED |
+                                      ZRT_DENOISE_ROW_MAJOR | ZRT_REPROJECT_ROW_MAJOR | ZRT_SVGF_ROW_MAJOR | 0xFFFFu)) == 0u,
+              "a bit of its own");
+static_assert(sizeof(zrt_emitter) == 80 && sizeof(zrt_area_light_batch) == 80, "include/zrt.h");
+extern "C" int zrt_context_area_lights(zrt_context* c, const zrt_area_light_batch* b, zrt_stats* stats) {
+    if (!c || !area_light_batch_ok(c, b, kTraceFlags)) return ZRT_ERR_INVALID_ARG;
+    if (b->num_rays == 0) { if (stats) *stats = zrt_stats{}; return ZRT_OK; }
+    zrt_stats st{};
+    DeviceGuard g(c->device);
+    const zrt_emitters* const es = b->emitters;
+    const bool counting = (b->flags & ZRT_FLAG_COUNT_STATS) != 0;
+    const bool unshadowed = (b->flags & ZRT_AREA_UNSHADOWED) != 0;
+    const uint32_t flags = b->flags & ~ZRT_AREA_UNSHADOWED;
+    const uint32_t S = b->num_samples;
+    const bool want_first = (flags & ZRT_TRACE_PARK) != 0 || b->num_rays >= kTraceParkMin;
+    LaunchPlan pl;
+    int rc;
+    if ((rc = resolve_plan(c, flags, counting, want_first, b->num_rays >= kSetsMinSamples, pl)) != ZRT_OK) return rc;
+    const bool park_first = pl.park_ok && want_first;
+
+    // chunk size, as query_rays; a sub-chunk's buffers are bounded by kAreaItems
+    zrt_context::PassSet& ps = c->set[0];
+    const bool dev = b->on_device != 0;
+    const bool own_hits = !dev || !b->hits, own_E = !dev || !b->irradiance, own_rad = !dev && b->radiance;
+    const uint64_t per_ray = (dev ? 0ull : 24ull) + (own_hits ? 16ull : 0ull) + (own_E ? 12ull : 0ull) +
+                             (own_rad ? 12ull : 0ull) + (park_first ? 64ull : 0ull);
+    const size_t held = 4ull * (c->rays_cap + c->hits_cap) + 16ull * (ps.q0_cap + ps.hit_cap) + c->bfc_bytes + c->esc_extra;
+    const size_t budget = device_budget(c, held);
+    uint64_t chunk = std::min<uint64_t>(kTraceChunk, b->num_rays);
+    if (per_ray) chunk = std::max<uint64_t>(64, std::min<uint64_t>(chunk, budget / per_ray));
+    const uint64_t M = std::min<uint64_t>(kAreaItems, chunk * S);         // items of a sub-chunk
+    // words of d_rays: a host batch's rays, (16-byte aligned) the contributions, the list (rays, bounds), T, slots
+    const uint64_t off_con = ((dev ? 0 : 6 * chunk) + 3) & ~3ull, off_list = off_con + 4 * M, rays_words = off_list + 9 * M;
+    // words of d_hits: hit records, irradiance, radiance
+    const uint64_t off_E = own_hits ? 4 * chunk : 0, off_rad = off_E + (own_E ? 3 * chunk : 0),
+                   hits_words = off_rad + (own_rad ? 3 * chunk : 0);
+    const size_t ctr_words = wfc_words(0);
+    if ((rc = grow(&c->d_rays, &c->rays_cap, rays_words)) != ZRT_OK) return rc;
+    if (hits_words && (rc = grow(&c->d_hits, &c->hits_cap, hits_words)) != ZRT_OK) return rc;
+    if (park_first) {
+        if ((rc = grow(&ps.q0, &ps.q0_cap, 3 * chunk)) != ZRT_OK) return rc;
+        if ((rc = grow(&ps.hit, &ps.hit_cap, chunk)) != ZRT_OK) return rc;
+        if ((rc = grow(&ps.wfc, &ps.wfc_cap, ctr_words)) != ZRT_OK) return rc;
+    }
+    // capacity guard: every buffer a launch below writes holds a chunk / a sub-chunk
+    if (shortfall("rays, items, list", c->d_rays, c->rays_cap, rays_words) ||
+        (hits_words && shortfall("hits, irradiance", c->d_hits, c->hits_cap, hits_words)) ||
+        (park_first && (shortfall("q0", ps.q0, ps.q0_cap, 3 * chunk) || shortfall("hit records", ps.hit, ps.hit_cap, chunk) ||
+                        shortfall("counters", ps.wfc, ps.wfc_cap, ctr_words))))
+        return ZRT_ERR_INVALID_ARG;
+    if ((rc = event_pool(c->ev_trace, 2)) != ZRT_OK) return rc;
+
+    RayLaunch rl;                                  // the first hits: a trace call's
+    if ((rc = ray_launch(c, pl, counting, park_first, rl, -1)) != ZRT_OK) return rc;
+    // the chains: a transmittance call's lane kernels and their occupancy-sized persistent grids
+    const TransmitFn f_fast = counting || pl.mtx ? nullptr : kTransmitWalk[pl.packed ? (pl.pbm ? 0 : 1) : 2];
+    const TransmitFn f_exact = kTransmitWalk[counting ? 4 : 3];
+    uint32_t grid_fast = 0, grid_exact = 0;
+    if (!unshadowed && es->count != 0u) {
+        if (f_fast && (rc = resident_blocks(c, (const void*)f_fast, kTraceThreads, pl.lds_wf, &grid_fast)) != ZRT_OK)
+            return rc;
+        if ((rc = resident_blocks(c, (const void*)f_exact, kTraceThreads, pl.lds_wf, &grid_exact)) != ZRT_OK) return rc;
+    }
+
+    QueryParams R;
+    memset(&R, 0, sizeof R);
+    scene_params(c, R.w.t);
+    R.w.t.max_bounce = 1;
+    R.w.t.counter = c->d_counter;
+    R.w.t.stats = c->d_stats;
+    R.ctr = c->d_counter;
+    if (park_first) {
+        R.w.q_in = ps.q0;
+        R.w.hit = ps.hit;
+        R.w.fetch8 = ps.wfc;
+        R.w.n_in8 = region_counts(ps, 0);
+        park_params(c, pl, R.w);
+        R.q = ps.q0;
+        R.n_in8 = region_counts(ps, 0);
+    }
+    AreaParams D;
+    memset(&D, 0, sizeof D);
+    D.tri_data = c->d_data;
+    D.mats = c->d_mats;
+    D.texels = c->d_texels;
+    D.rec = reinterpret_cast<const float4*>(es->d_rec);
+    D.C = es->d_C;
+    D.Q = es->Q;
+    D.Qf = (float)es->Q;
+    D.count = es->count;
+    while ((1ull << D.steps) <= es->count) ++D.steps;
+    D.seed = b->seed;
+    D.S = S;
+    D.unshadowed = unshadowed ? 1u : 0u;
+    D.contrib = reinterpret_cast<float4*>(c->d_rays + off_con);
+    D.irays = c->d_rays + off_list;
+    D.ibound = D.irays + 6 * M;
+    float* const dT = D.ibound + M;
+    D.T = dT;
+    D.slot = reinterpret_cast<uint32_t*>(dT + M);
+    D.ctr = c->d_counter;
+    D.stats = c->d_stats;
+    // the chains' walks: the list as a transmittance call's rays and bounds
+    TransmitParams I;
+    memset(&I, 0, sizeof I);
+    scene_params(c, I.q.w.t);
+    I.q.w.t.max_bounce = 1;
+    I.q.w.t.counter = c->d_counter;
+    I.q.w.t.stats = c->d_stats;
+    I.q.ctr = c->d_counter;
+    I.q.rays = D.irays;
+    I.q.t_max = D.ibound;
+    I.T = dT;
+    I.max_cross = b->max_crossings;
+    I.q.w.t.S = 1;
+    I.q.w.t.sdiv = div_magic(1);
+
+    HIP_TRY(hipMemsetAsync(c->d_stats, 0, 512, c->stream));
+    HIP_TRY(hipEventRecord(c->ev_begin, c->stream));
+    uint32_t launches = 0;
+    uint64_t traced = 0;
+    for (uint64_t off = 0; off < b->num_rays; off += chunk) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, b->num_rays - off);
+        if (dev) {
+            R.rays = b->rays + 6 * off;
+        } else {
+            HIP_TRY(hipMemcpyAsync(c->d_rays, b->rays + 6 * off, 24ull * n, hipMemcpyHostToDevice, c->stream));
+            R.rays = c->d_rays;
+            HIP_TRY(hipEventRecord(c->ev_trace[0], c->stream));
+        }
+        R.hits = own_hits ? c->d_hits : reinterpret_cast<uint32_t*>(b->hits + off);
+        D.E = own_E ? reinterpret_cast<float*>(c->d_hits + off_E) : b->irradiance + 3 * off;
+        D.radiance = own_rad ? reinterpret_cast<float*>(c->d_hits + off_rad) : dev && b->radiance ? b->radiance + 3 * off
+                                                                                                 : nullptr;
+        HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
+        if (park_first) HIP_TRY(hipMemsetAsync(ps.wfc, 0, 4ull * 16 * kCtr, c->stream));
+        if ((rc = trace_first_segments(c, pl, rl, R, n, true, &launches)) != ZRT_OK) return rc;
+        // the first hits' segments and hits are not the chains'
+        HIP_TRY(hipMemsetAsync(c->d_stats, 0, 8, c->stream));
+        HIP_TRY(hipMemsetAsync(c->d_stats + 3, 0, 8, c->stream));
+        D.rays = R.rays;
+        D.hits = R.hits;
+        D.n = n;
+        D.key0 = (uint32_t)(b->index_base + off);
+        const uint64_t items = (uint64_t)n * S;
+        for (uint64_t i0 = 0; i0 < items; i0 += kAreaItems) {
+            const uint32_t m = (uint32_t)std::min<uint64_t>(kAreaItems, items - i0);
+            D.ray0 = (uint32_t)(i0 / S);
+            D.s0 = (uint32_t)(i0 % S);
+            D.m = m;
+            HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
+            if ((rc = area_gen_launch(D, c->stream)) != ZRT_OK) return rc;
+            ++launches;
+            uint32_t live = 0;                         // the list's entries: the traced items
+            HIP_TRY(copy_sync(&live, c->d_counter + 4, sizeof live, hipMemcpyDeviceToHost, c->stream));
+            if (live > m) return ZRT_ERR_HIP;          // (never: the kernel's own bounds)
+            traced += live;
+            D.fold = 0u;
+            if (live != 0u && !unshadowed) {
+                const uint32_t lblk = (live + kBlock - 1) / kBlock;
+                I.q.n = live;
+                I.q.w.t.P = live;
+                I.q.w.t.total = live;
+                auto walk = [&](TransmitFn f, uint32_t grid, uint32_t which) {
+                    I.q.which = which;
+                    hipLaunchKernelGGL(f, dim3(std::min(grid, lblk)), dim3(kTraceThreads), pl.lds_wf, c->stream, I);
+                    ++launches;
+                };
+                if (f_fast) walk(f_fast, grid_fast, kRaysFast);
+                walk(f_exact, grid_exact, f_fast ? kRaysRest : kRaysAll);
+                D.fold = 1u;
+            }
+            const uint32_t nr = (uint32_t)((D.s0 + (uint64_t)m + S - 1) / S);   // rays with an item in the sub-chunk
+            if ((rc = area_reduce_launch(D, nr, c->stream)) != ZRT_OK) return rc;
+            ++launches;
+        }
+        if (!dev) {
+            HIP_TRY(hipEventRecord(c->ev_trace[1], c->stream));
+            if (b->hits) HIP_TRY(copy_sync(b->hits + off, c->d_hits, 16ull * n, hipMemcpyDeviceToHost, c->stream));
+            if (b->irradiance) HIP_TRY(copy_sync(b->irradiance + 3 * off, D.E, 12ull * n, hipMemcpyDeviceToHost, c->stream));
+            if (b->radiance)
+                HIP_TRY(copy_sync(b->radiance + 3 * off, D.radiance, 12ull * n, hipMemcpyDeviceToHost, c->stream));
+            float t = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&t, c->ev_trace[0], c->ev_trace[1]));
+            st.trace_kernel_ms += t;
+        }
+    }
+    if ((rc = finish_query(c, dev, launches, st)) != ZRT_OK) return rc;
+    unsigned long long hs[kAreaStat + 2];
+    HIP_TRY(copy_sync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+    st.segments = b->num_rays + hs[kAreaStat];
+    st.samples = traced;
+    st.hits = hs[kAreaStat + 1];
     if (counting) {
         st.cells_visited = hs[1];
         st.triangle_tests = hs[2];

@@ -5,6 +5,18 @@
 #include "../../include/zrt.h"
 #include "zrt_math.h"
 
+// An emitter set (zrt_emitters_*, emitters.hip): device memory on
+// its context's device, read-only once built.
+struct zrt_emitters {
+    zrt_context* ctx = nullptr;
+    int device = 0;                    // ctx's (zrt_emitters_destroy does not touch ctx)
+    uint32_t num_triangles = 0;        // of the source soup
+    uint32_t count = 0;                // emitters
+    uint64_t Q = 0;                    // the total of q
+    float* d_rec = nullptr;            // count zrt_emitter records (16-byte aligned)
+    unsigned long long* d_C = nullptr; // count exclusive prefix sums of q
+};
+
 namespace zrt {
 
 // Device texture descriptor (stage3.zig:82-92): offset in floats into the
@@ -87,6 +99,10 @@ int tile_pixels(uint32_t w, uint32_t h, uint32_t tile, uint32_t rank, uint32_t n
 // batch's scalar fields, then -- num_rays != 0 -- its pointers and the lights'
 // types.  `trace_flags`: the flags zrt_context_trace accepts.
 bool direct_batch_ok(const zrt_direct_batch* b, uint32_t trace_flags);
+
+// zrt_context_area_lights', likewise: the batch's scalar fields, then --
+// num_rays != 0 -- its pointers and whether the set was made on `c`.
+bool area_light_batch_ok(const zrt_context* c, const zrt_area_light_batch* b, uint32_t trace_flags);
 
 // zrt_context_light_probes' argument checks, which need no device (capi.cpp):
 // the batch's scalar fields, then -- num_probes != 0 -- its size (at most 2^47

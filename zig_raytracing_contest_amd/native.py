@@ -31,6 +31,7 @@ TRACE_PARK = 0x10000       # ZRT_TRACE_PARK (zrt_ray_batch / zrt_radiance_batch 
 RADIANCE_PER_SAMPLE = 0x20000   # ZRT_RADIANCE_PER_SAMPLE (zrt_radiance_batch.flags only)
 SEGMENT_ANY = 0x40000      # ZRT_SEGMENT_ANY (zrt_segment_batch.flags only)
 DIRECT_UNSHADOWED = 0x80000   # ZRT_DIRECT_UNSHADOWED (zrt_direct_batch.flags only)
+AREA_UNSHADOWED = 0x800000    # ZRT_AREA_UNSHADOWED (zrt_area_light_batch.flags only)
 DENOISE_ROW_MAJOR = 0x100000  # ZRT_DENOISE_ROW_MAJOR (zrt_denoise_batch.flags only)
 # Context.denoise's default sigmas (colour, normal, depth, albedo): the C interface has none.  Chosen on the
 # CPU reference over oracle frames: every finite sigma_color tried lowers the error of a
@@ -223,6 +224,19 @@ class DirectBatch(C.Structure):
                 ("num_lights", C.c_uint32), ("max_crossings", C.c_uint32)]
 
 
+class AreaLightBatch(C.Structure):
+    _fields_ = [("num_rays", C.c_uint64), ("rays", C.c_void_p), ("emitters", C.c_void_p), ("irradiance", C.c_void_p),
+                ("radiance", C.c_void_p), ("hits", C.c_void_p), ("on_device", C.c_uint32), ("flags", C.c_uint32),
+                ("num_samples", C.c_uint32), ("max_crossings", C.c_uint32), ("seed", C.c_uint64),
+                ("index_base", C.c_uint64)]
+
+
+# zrt_emitter, 80 bytes
+EMITTER_DTYPE = np.dtype([("v0", np.float32, 3), ("a", np.float32), ("e1", np.float32, 3), ("q", np.uint32),
+                          ("e2", np.float32, 3), ("material", np.uint32), ("texcoords", np.float32, 6),
+                          ("triangle", np.uint32), ("_reserved", np.uint32)])
+
+
 class LightProbeBatch(C.Structure):
     _fields_ = [("num_probes", C.c_uint64), ("positions", C.c_void_p), ("sh", C.c_void_p), ("distance", C.c_void_p),
                 ("hits", C.c_void_p), ("directions", C.c_void_p), ("radiance", C.c_void_p), ("on_device", C.c_uint32),
@@ -285,6 +299,8 @@ EXPORTS = [
     "zrt_context_denoise",
     "zrt_context_reproject",
     "zrt_context_illumination", "zrt_context_svgf",
+    "zrt_emitters_create", "zrt_emitters_info", "zrt_emitters_read", "zrt_emitters_destroy",
+    "zrt_context_area_lights",
 ]
 
 
@@ -356,6 +372,15 @@ def lib():
     if hasattr(L, "zrt_context_svgf"):   # (likewise)
         L.zrt_context_illumination.argtypes = [C.c_void_p, C.POINTER(IlluminationBatch), C.POINTER(Stats)]
         L.zrt_context_svgf.argtypes = [C.c_void_p, C.POINTER(SvgfBatch), C.POINTER(Stats)]
+    if hasattr(L, "zrt_context_area_lights"):   # (likewise)
+        L.zrt_emitters_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                          C.POINTER(C.c_void_p)]
+        L.zrt_emitters_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                        C.POINTER(C.c_uint32)]
+        L.zrt_emitters_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.zrt_emitters_destroy.argtypes = [C.c_void_p]
+        L.zrt_emitters_destroy.restype = None
+        L.zrt_context_area_lights.argtypes = [C.c_void_p, C.POINTER(AreaLightBatch), C.POINTER(Stats)]
     if hasattr(L, "zrt_group_create"):     # ABI 2 (an ABI-1 build: tools/ A/B baselines only)
         L.zrt_group_create.argtypes = [C.POINTER(Scene), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
         L.zrt_group_create_built.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -555,6 +580,55 @@ class Film:
     def close(self):
         if getattr(self, "_h", None) is not None and _lib is not None:
             _lib.zrt_film_destroy(self._h)       # (frees its device memory; does not touch the context)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+class Emitters:
+    """zrt_emitters: the emissive triangles of a source soup as a sampling
+    distribution on the context's device, built once (positions (n, 9),
+    texcoords (n, 6) or None for zeros, material (n,) indices into the
+    context's materials) and read by Context.area_lights.  Close it before its
+    context."""
+
+    def __init__(self, context: "Context", positions, texcoords, material):
+        pos = np.ascontiguousarray(positions, np.float32).reshape(-1)
+        mat = np.ascontiguousarray(material, np.uint32).reshape(-1)
+        uv = None if texcoords is None else np.ascontiguousarray(texcoords, np.float32).reshape(-1)
+        n = mat.size
+        if pos.size != 9 * n or (uv is not None and uv.size != 6 * n):
+            raise ValueError("Emitters: (n, 9) positions, (n, 6) texcoords or None and (n,) materials expected")
+        h_ = C.c_void_p()
+        check(lib().zrt_emitters_create(context._h, pos.ctypes.data if n else None,
+                                        uv.ctypes.data if uv is not None and n else None,
+                                        mat.ctypes.data if n else C.cast(C.pointer(C.c_uint32(0)), C.c_void_p),
+                                        n, C.byref(h_)), "zrt_emitters_create")
+        self._h = h_
+        self._context = context          # (keeps the context alive as long as the set)
+
+    def info(self):
+        """(emitters, Q: the total of their integer weights, source triangles)."""
+        n, q, t = C.c_uint32(0), C.c_uint64(0), C.c_uint32(0)
+        check(lib().zrt_emitters_info(self._h, C.byref(n), C.byref(q), C.byref(t)), "zrt_emitters_info")
+        return int(n.value), int(q.value), int(t.value)
+
+    @property
+    def count(self) -> int:
+        return self.info()[0]
+
+    def read(self):
+        """(records: (count,) EMITTER_DTYPE, C: (count,) uint64 exclusive prefix sums of q)."""
+        n = self.count
+        rec, pre = np.zeros(n, EMITTER_DTYPE), np.zeros(n, np.uint64)
+        check(lib().zrt_emitters_read(self._h, rec.ctypes.data if n else None, pre.ctypes.data if n else None),
+              "zrt_emitters_read")
+        return rec, pre
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and _lib is not None:
+            _lib.zrt_emitters_destroy(self._h)   # (frees its device memory; does not touch the context)
             self._h = None
 
     def __del__(self):
@@ -1483,6 +1557,60 @@ class Context:
             st = self.direct_raw(0, None, lights, None, None, None, bool(torch), max_crossings, flags)
         else:
             st = self.direct_raw(n, ptr(rays), lights, ptr(irr), ptr(rad), ptr(rec), bool(torch), max_crossings, flags)
+        res = {"stats": st}
+        if irradiance:
+            res["irradiance"] = irr
+        if radiance:
+            res["radiance"] = rad
+        if hits and torch:
+            res["hits"] = rec
+        elif hits:
+            res.update(t=rec["t"].copy(), u=rec["u"].copy(), v=rec["v"].copy(), triangle=rec["triangle"].copy())
+        return res
+
+    def area_lights_raw(self, num_rays: int, rays_ptr, emitters, irradiance_ptr, radiance_ptr, hits_ptr,
+                        on_device: bool, spp: int, max_crossings: int = 16, seed: int = 0, index_base: int = 0,
+                        flags: int = 0):
+        """zrt_context_area_lights on raw pointers; `emitters`: an Emitters (or
+        None).  Returns the stats dict."""
+        batch = AreaLightBatch(int(num_rays), rays_ptr, emitters._h if emitters is not None else None, irradiance_ptr,
+                               radiance_ptr, hits_ptr, 1 if on_device else 0, int(flags), int(spp), int(max_crossings),
+                               int(seed) & (2 ** 64 - 1), int(index_base) & (2 ** 64 - 1))
+        st = Stats()
+        check(lib().zrt_context_area_lights(self._h, C.byref(batch), C.byref(st)), "zrt_context_area_lights")
+        return st.as_dict()
+
+    def area_lights(self, origins, dirs, emitters, spp: int, max_crossings: int = 16, seed: int = 0,
+                    index_base: int = 0, flags: int = 0, unshadowed: bool = False, irradiance: bool = True,
+                    radiance: bool = False, hits: bool = False, stats: bool = False):
+        """Direct light of the scene's own emissive triangles at each ray's
+        first hit (zrt_context_area_lights): `spp` next-event samples per ray
+        from the set `emitters` (an Emitters of this context), drawn from the
+        stream (seed, index_base + ray, sample), each shadowed through at most
+        `max_crossings` transparent hits (unshadowed=True: T = 1, nothing
+        traced).  Per ray the irradiance estimate and the Lambertian radiance
+        emissive + base_color * irradiance / pi; a miss is zero in both.
+
+        Inputs, outputs and "stats" are direct()'s: two (n, 3) float32 numpy
+        arrays or CUDA tensors on the context's device; "samples" counts the
+        traced (ray, sample) items."""
+        if not (irradiance or radiance):
+            raise ValueError("area_lights: irradiance or radiance must be asked for")
+        flags = int(flags) | (FLAG_COUNT_STATS if stats else 0) | (AREA_UNSHADOWED if unshadowed else 0)
+        torch, n, rays = self._rays("area_lights", origins, dirs)
+        if torch:
+            irr = torch.empty((n, 3), dtype=torch.float32, device=origins.device) if irradiance else None
+            rad = torch.empty((n, 3), dtype=torch.float32, device=origins.device) if radiance else None
+            rec = torch.empty((n, 4), dtype=torch.float32, device=origins.device) if hits else None
+            torch.cuda.current_stream(origins.device).synchronize()
+            ptr = lambda x: x.data_ptr() if x is not None and n else None
+        else:
+            irr = np.empty((n, 3), np.float32) if irradiance else None
+            rad = np.empty((n, 3), np.float32) if radiance else None
+            rec = np.empty(n, HIT_DTYPE) if hits else None
+            ptr = lambda x: x.ctypes.data if x is not None and n else None
+        st = self.area_lights_raw(n, ptr(rays), emitters, ptr(irr), ptr(rad), ptr(rec), bool(torch), spp,
+                                  max_crossings, seed, index_base, flags)
         res = {"stats": st}
         if irradiance:
             res["irradiance"] = irr
