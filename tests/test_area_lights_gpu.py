@@ -471,6 +471,61 @@ def test_a_ray_whose_samples_straddle_the_sub_chunk_cut(cornell):
         check_comp(call(rs, rs.emitters(), o, d, S, 9, flags=flags), comp, f"4099 x 257, {path}")
 
 
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+def test_a_batch_across_the_ray_chunk_cut(device, cornell):
+    """2^20 + 77 rays x 1 sample: two chunks; a host batch's contribution row
+    lies 16-byte aligned behind a whole chunk's rays.  The rays around the cut
+    against a call on those 205 alone with index_base advanced to them, bit for
+    bit; the totals from the composition."""
+    if device and (torch is None or not torch.cuda.is_available()):
+        pytest.skip("torch sees no device")
+    soup, rs, es = cornell
+    n = (1 << 20) + 77
+    idx = np.arange(n) % 128
+    o, d = (np.ascontiguousarray(x[idx]) for x in box_rays(soup, 128, 6))
+    comp = composition(rs, es, o, d, 1, seed=4, index_base=1000)
+    lo = (1 << 20) - 128
+    assert comp["traced"][lo:1 << 20].any() and comp["traced"][1 << 20:].any()
+    for path, flags in PATHS.items():
+        E, R, hits, st = call(rs, rs.emitters(), o, d, 1, 4, 1000, flags=flags, device=device)
+        near = call(rs, rs.emitters(), o[lo:], d[lo:], 1, 4, 1000 + lo, flags=flags, device=device)
+        check((E[lo:], R[lo:], hits[lo:], near[3]), near[0], near[1], near[2], near[3]["segments"] - 205,
+              near[3]["samples"], near[3]["hits"], f"around the cut, {path}")
+        print("area lights segments", path, st["segments"], n + comp["segments"])
+        assert (st["segments"], st["samples"], st["hits"]) == (n + comp["segments"], comp["samples"], comp["crossings"]), path
+
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+def test_the_launches_of_one_small_chunk(device, cornell):
+    """128 rays x 2 samples in the Cornell box, one chunk and one sub-chunk:
+    zrt_stats.trace_launches per mode, as the sequence in light_items' comment
+    gives them (recorded on the GPU at the commit before the query calls came
+    to share their host code)."""
+    if device and (torch is None or not torch.cuda.is_available()):
+        pytest.skip("torch sees no device")
+    soup, rs, es = cornell
+    o, d = box_rays(soup, 128, 6)
+    comp = composition(rs, es, o, d, 2, seed=4)
+    assert comp["samples"] > 0
+    em = rs.emitters()
+    want = {"lane": 2 + 1 + 2 + 1,                  # first hits: the fast walk + the rest; gen; chains: the fast walk +
+                                                    # the rest; reduce
+            "park": 4 + 1 + 2 + 1,                  # first hits: pack + park + out + the rest; gen; chains; reduce
+            "counting": 1 + 1 + 1 + 1,              # first hits: the counting walk; gen; the counting chain walk; reduce
+            "lane unshadowed": 2 + 1 + 1,           # first hits; gen; reduce: no chain is walked
+            "park unshadowed": 4 + 1 + 1,
+            "counting unshadowed": 1 + 1 + 1}
+    got = {}
+    for mode, kw in (("lane", {"flags": native.FLAG_LANE_WALK}), ("park", {"flags": native.TRACE_PARK}),
+                     ("counting", {"stats": True})):
+        res = call(rs, em, o, d, 2, 4, device=device, **kw)
+        check_comp(res, comp, f"128 rays, {mode}")
+        got[mode] = res[3]["trace_launches"]
+        got[mode + " unshadowed"] = call(rs, em, o, d, 2, 4, device=device, unshadowed=True, **kw)[3]["trace_launches"]
+    print("area lights launches", "device" if device else "host", got)
+    assert got == want
+
+
 def test_output_subsets_leave_the_other_arrays_alone(cornell):
     soup, rs, es = cornell
     o, d = box_rays(soup, 300, 8)

@@ -333,6 +333,59 @@ def test_torch_tensors_in_place_across_the_ray_chunk_cut(cornell):
     assert comp["irradiance"][1 << 20:].any() and comp["irradiance"][:1 << 20].any()
 
 
+def test_a_host_batch_across_the_ray_chunk_cut(cornell):
+    """2^20 + 77 host rays x 1 light: two chunks, the light staged behind a
+    whole chunk's rays.  The rays around the cut against a call on those 205
+    alone, bit for bit; the totals from the 128 rays the batch tiles."""
+    soup, rs = cornell
+    n = (1 << 20) + 77
+    o128, d128 = box_rays(soup, 128, 6)
+    idx = np.arange(n) % 128
+    o, d = np.ascontiguousarray(o128[idx]), np.ascontiguousarray(d128[idx])
+    lights = box_lights(soup, 1, 3)
+    tile, rest = composition(rs, o128, d128, lights), composition(rs, o128[:77], d128[:77], lights)
+    want = {k: (n // 128) * tile[k] + rest[k] for k in ("segments", "samples", "crossings")}
+    assert rest["samples"] > 0 and tile["irradiance"][64:].any()
+    lo = (1 << 20) - 128
+    for path, flags in PATHS.items():
+        E, R, hits, st = call(rs, o, d, lights, flags=flags)
+        near = call(rs, o[lo:], d[lo:], lights, flags=flags)
+        check((E[lo:], R[lo:], hits[lo:], near[3]), near[0], near[1], near[2], near[3]["segments"] - 205,
+              near[3]["samples"], near[3]["hits"], f"around the cut, {path}")
+        print("direct segments", path, st["segments"], n + want["segments"])
+        assert (st["segments"], st["samples"], st["hits"]) == (n + want["segments"], want["samples"], want["crossings"]), path
+
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+def test_the_launches_of_one_small_chunk(device, case, context):
+    """A seed's 128 rays x its 4 lights, one chunk and one sub-chunk:
+    zrt_stats.trace_launches per mode, as the sequence in zrt_context_direct's
+    comment gives them (recorded on the GPU at the commit before the query
+    calls came to share their host code)."""
+    if device and (torch is None or not torch.cuda.is_available()):
+        pytest.skip("torch sees no device")
+    cs, rs = case(18), context(18)
+    lights, rays = direct_ref.cached_rays(cs)
+    E, R, tot = direct_ref.direct_batch(cs.ref, cs.soup, rays, lights)
+    assert len(lights) == 4 and tot["samples"] > 0
+    want = {"lane": 2 + 1 + 2 + 1,                  # first hits: the fast walk + the rest; gen; chains: the fast walk +
+                                                    # the rest; reduce
+            "park": 4 + 1 + 2 + 1,                  # first hits: pack + park + out + the rest; gen; chains; reduce
+            "counting": 1 + 1 + 1 + 1,              # first hits: the counting walk; gen; the counting chain walk; reduce
+            "lane unshadowed": 2 + 1 + 1,           # first hits; gen; reduce: no chain is walked
+            "park unshadowed": 4 + 1 + 1,
+            "counting unshadowed": 1 + 1 + 1}
+    got = {}
+    for mode, kw in (("lane", {"flags": native.FLAG_LANE_WALK}), ("park", {"flags": native.TRACE_PARK}),
+                     ("counting", {"stats": True})):
+        res = call(rs, cs.o, cs.d, lights, device=device, **kw)
+        check(res, E, R, cs.bits, tot["segments"], tot["samples"], tot["hits"], f"128 rays, {mode}")
+        got[mode] = res[3]["trace_launches"]
+        got[mode + " unshadowed"] = call(rs, cs.o, cs.d, lights, device=device, unshadowed=True, **kw)[3]["trace_launches"]
+    print("direct launches", "device" if device else "host", got)
+    assert got == want
+
+
 def test_output_subsets_leave_the_other_arrays_alone(cornell):
     soup, rs = cornell
     o, d = box_rays(soup, 300, 8)

@@ -331,6 +331,56 @@ def test_torch_tensors_in_place_across_the_ray_chunk_cut(cornell, oracle_mod):
     assert comp["occluded"][1 << 20:].any() and comp["occluded"][:1 << 20].any()
 
 
+def test_a_host_batch_across_the_ray_chunk_cut(cornell, oracle_mod):
+    """2^20 + 77 host rays at S = 1 with a radius per ray: two chunks, the radii
+    staged behind a whole chunk's rays.  The rays around the cut against a call
+    on those 205 alone with index_base advanced to them, bit for bit."""
+    soup, rs = cornell
+    n = (1 << 20) + 77
+    idx = np.arange(n) % 128
+    o, d = (np.ascontiguousarray(x[idx]) for x in box_rays(soup, 128, 6))
+    radius = np.array([0.25, 1.0, np.inf, 0.0, np.nan, 0.5], F)[np.arange(n) % 6]
+    traced = composition(oracle_mod, rs, o, d, 1, radius, seed=2)["traced"]
+    lo = (1 << 20) - 128
+    for path, flags in PATHS.items():
+        occ, vis, hits, st = call(rs, o, d, 1, radius, seed=2, flags=flags)
+        near = call(rs, o[lo:], d[lo:], 1, radius[lo:], seed=2, key0=lo, flags=flags)
+        assert near[0][:128].any() and near[0][128:].any() and (near[0] == 0).any()
+        check((occ[lo:], vis[lo:], hits[lo:], near[3]), near[0], near[1], near[2],
+              near[3]["segments"] - 205, f"around the cut, {path}")
+        print("occlusion segments", path, st["segments"], n + traced)
+        assert (st["segments"], st["hits"]) == (n + traced, int(occ.astype(np.int64).sum())), path
+
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+def test_the_launches_of_one_small_chunk(device, case, context, oracle_mod):
+    """A seed's 128 rays at S = 3, one chunk and one sub-chunk:
+    zrt_stats.trace_launches per mode, as the sequence in
+    zrt_context_occlusion's comment gives them (recorded on the GPU at the
+    commit before the query calls came to share their host code)."""
+    if device and (torch is None or not torch.cuda.is_available()):
+        pytest.skip("torch sees no device")
+    seed = RADIUS_SEEDS[2]
+    cs, rs = case(seed), context(seed)
+    radius = occlusion_ref.fuzz_radius(cs.soup)
+    occ, vis, traced, _ = occlusion_ref.occlusion_batch(cs.ref, occlusion_ref.cached_samples(cs), radius, 3)
+    assert traced > 0
+    want = {"lane": 2 + 1 + 2 + 1 + 1,      # first hits: the fast walk + the rest; gen; the list: the fast walk + the
+                                            # rest; reduce (list); finish
+            "park": 4 + 1 + 2 + 1,          # first hits: pack + park + out + the rest; gen; park + reduce (queue): every
+                                            # sample is in the fast domain, the list is empty; finish
+            "counting": 1 + 1 + 1 + 1 + 1}  # first hits: the counting walk; gen; the counting any-hit walk; reduce
+                                            # (list); finish
+    got = {}
+    for mode, kw in (("lane", {"flags": native.FLAG_LANE_WALK}), ("park", {"flags": native.TRACE_PARK}),
+                     ("counting", {"stats": True})):
+        res = call(rs, cs.o, cs.d, 3, radius, seed=cs.rseed, device=device, **kw)
+        check(res, occ, vis, cs.bits, traced, f"128 rays, {mode}")
+        got[mode] = res[3]["trace_launches"]
+    print("occlusion launches", "device" if device else "host", got)
+    assert got == want
+
+
 def test_output_subsets_leave_the_other_arrays_alone(cornell, oracle_mod):
     soup, rs = cornell
     o, d = box_rays(soup, 300, 8)

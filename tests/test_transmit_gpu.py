@@ -275,6 +275,56 @@ def test_torch_tensors_in_place_across_the_chunk_cut(case, context):
     _check({k: res[k].cpu().numpy() for k in ("transmittance", "crossings")}, sT, sn.astype(np.int32), "torch scalar")
 
 
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+def test_the_launches_of_one_small_chunk(device, case, context):
+    """The seed's 128 rays, one chunk: zrt_stats.trace_launches per mode, as the
+    sequence in zrt_context_transmittance's comment gives them (recorded on the
+    GPU at the commit before the query calls came to share their host code)."""
+    if device and (torch is None or not torch.cuda.is_available()):
+        pytest.skip("torch sees no device")
+    cs, rs = case(BIG), context(BIG)
+    T, cr, _ = free_ref(cs)
+    o, d = cs.o, cs.d
+    if device:
+        o, d = torch.from_numpy(cs.o).to("cuda:0"), torch.from_numpy(cs.d).to("cuda:0")
+    want = {"lane": 1 + 1,              # the fast walk + the rest
+            "park": 1 + 2 + 1 + 1,      # pack + one (park, step) round + the tail (some chains go on, few) + the rest
+            "counting": 1}              # the counting IEEE-division walk alone
+    got = {}
+    for mode, kw in (("lane", {"flags": native.FLAG_LANE_WALK}), ("park", {"flags": native.TRACE_PARK}),
+                     ("counting", {"stats": True})):
+        res = rs.transmittance(o, d, crossings=True, **kw)
+        if device:
+            res = {k: (v.cpu().numpy() if k != "stats" else v) for k, v in res.items()}
+        _check(res, T, cr.astype(res["crossings"].dtype), f"128 rays, {mode}")
+        got[mode] = res["stats"]["trace_launches"]
+    print("transmittance launches", "device" if device else "host", got)
+    assert got == want
+
+
+def test_a_host_batch_across_the_chunk_cut(case, context):
+    """2^20 + 77 host rays with a bound and `crossings` per ray: two chunks,
+    the bounds staged behind a whole chunk's rays.  The rays around the cut
+    against a call on those 205 alone, bit for bit."""
+    cs, rs = case(BIG), context(BIG)
+    tm, _, _, tot = bounded_ref(cs)[:4]
+    n = (1 << 20) + 77
+    idx = np.arange(n) % qf.N_RAYS
+    o, d, bound = cs.o[idx], cs.d[idx], tm[idx]
+    rest = n % qf.N_RAYS
+    segments = (n // qf.N_RAYS) * tot[0] + transmit_ref.transmit_batch(cs.ref, cs.soup, cs.o[:rest], cs.d[:rest], tm[:rest],
+                                                                        CAP)[2][0]
+    lo = (1 << 20) - 128
+    for mode, flags in (("lane", native.FLAG_LANE_WALK), ("park", native.TRACE_PARK)):
+        res = rs.transmittance(o, d, bound, flags=flags, crossings=True)
+        near = rs.transmittance(o[lo:], d[lo:], bound[lo:], flags=flags, crossings=True)
+        assert near["crossings"].any() and (near["crossings"] == 0).any()
+        _check({k: res[k][lo:] for k in ("transmittance", "crossings")}, near["transmittance"].view(np.uint32),
+               near["crossings"], f"around the cut, {mode}")
+        print("transmittance segments", mode, res["stats"]["segments"], segments)
+        assert res["stats"]["segments"] == segments, mode
+
+
 # ------------------------------------------------------------------------ other
 def test_transmittance_renders_and_segments_share_a_context_cleanly(case, context):
     cs = case(BIG)

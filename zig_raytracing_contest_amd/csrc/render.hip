@@ -3208,7 +3208,7 @@ constexpr uint64_t kOccParkMin = kSegParkMin;
 // transmittance chain of the segment towards it, and the Lambertian radiance
 // that irradiance gives.  An item is a (ray, light) pair; a chunk's items run
 // in sub-chunks of at most kDirItems, item j of a sub-chunk being
-// (ray0 + (l0 + j) / L, (l0 + j) % L).  direct_gen_kernel computes the item's
+// (ray0 + (s0 + j) / L, (s0 + j) % L).  direct_gen_kernel computes the item's
 // direction w, bound b and factor f (include/zrt.h) and appends the traced
 // items -- the ray hit and is shaded, the light is in front of the surface and,
 // a spot, inside its cone -- to a list of plain rays and bounds that the
@@ -3232,7 +3232,7 @@ struct DirectParams {
     const zrt_light* lights;  // L lights, on the device
     uint32_t L;               // lights per ray, 1..65535
     uint32_t n;               // rays of this chunk
-    uint32_t ray0, l0;        // the sub-chunk's first item: light l0 of ray ray0
+    uint32_t ray0, s0;        // the sub-chunk's first item: light s0 of ray ray0
     uint32_t m;               // items of this sub-chunk (<= kDirItems)
     uint32_t unshadowed;      // ZRT_DIRECT_UNSHADOWED: no list is written, T = 1
     uint32_t fold;            // direct_reduce_kernel: the walk launches ran; move their counts
@@ -3265,7 +3265,7 @@ __global__ __launch_bounds__(kBlock) void direct_gen_kernel(const DirectParams r
         v3 o = mk(0, 0, 0), w = mk(0, 0, 0);
         float bound = 0.0f, f = 0.0f;
         if (j < r.m) {
-            const uint32_t I = j + r.l0, qr = I / r.L;
+            const uint32_t I = j + r.s0, qr = I / r.L;
             const uint32_t ray = r.ray0 + qr, l = I - qr * r.L;
             uint4 h = make_uint4(0x7F800000u, 0u, 0u, 0xFFFFFFFFu);
             if (ray < r.n) h = hit_load(r.hits, aligned, ray);                  // (always: m items of n rays)
@@ -3339,11 +3339,11 @@ __global__ __launch_bounds__(kBlock) void direct_reduce_kernel(const DirectParam
         r.stats[0] = 0ull;
         r.stats[3] = 0ull;
     }
-    const uint32_t end = r.l0 + r.m;                                            // (< 2^21: l0 < L < 2^16)
+    const uint32_t end = r.s0 + r.m;                                            // (< 2^21: s0 < L < 2^16)
     const uint32_t ray = r.ray0 + i;
     if ((uint64_t)i * r.L >= end || ray >= r.n) return;                         // (ray < n: always)
     const uint32_t first = i * r.L;
-    const uint32_t a = max(first, r.l0), e = min(first + r.L, end);
+    const uint32_t a = max(first, r.s0), e = min(first + r.L, end);
     const bool aligned = (reinterpret_cast<uintptr_t>(r.hits) & 15u) == 0u;
     const uint4 h = hit_load(r.hits, aligned, ray);
     const float t = __uint_as_float(h.x);
@@ -3352,7 +3352,7 @@ __global__ __launch_bounds__(kBlock) void direct_reduce_kernel(const DirectParam
     if (t != kInf) {
         if (a != first) E = ld3(Ep);
         for (uint32_t x = a; x < e; ++x) {
-            const uint32_t j = x - r.l0, s = r.slot[j];
+            const uint32_t j = x - r.s0, s = r.slot[j];
             if (s == 0xFFFFFFFFu) continue;
             const float T = r.unshadowed != 0u ? 1.0f : r.T[s];
             const float g = r.f[j] * T;
@@ -4127,14 +4127,17 @@ static int ray_launch(const zrt_context* c, const LaunchPlan& pl, bool counting,
 // alone.  `pack_out`: Q.rays are the caller's rays as given, so
 // query_pack_kernel fills the queue before the park kernel and
 // query_out_kernel writes its hit records to Q.hits / Q.occ after it.
-static int trace_first_segments(const zrt_context* c, const LaunchPlan& pl, const RayLaunch& rl, QueryParams& Q, uint32_t n,
-                                bool pack_out, uint32_t* launches) {
-    const uint32_t nblk = (n + kBlock - 1) / kBlock;             // one thread per ray; also all a walk launch needs
+static void identity_queue(QueryParams& Q, uint32_t n) {
     Q.n = n;
     Q.w.t.P = n;
     Q.w.t.S = 1;
     Q.w.t.total = n;
     Q.w.t.sdiv = div_magic(1);
+}
+static int trace_first_segments(const zrt_context* c, const LaunchPlan& pl, const RayLaunch& rl, QueryParams& Q, uint32_t n,
+                                bool pack_out, uint32_t* launches) {
+    const uint32_t nblk = (n + kBlock - 1) / kBlock;             // one thread per ray; also all a walk launch needs
+    identity_queue(Q, n);
     auto walk = [&](QueryFn f, uint32_t grid) {
         hipLaunchKernelGGL(f, dim3(std::min(grid, nblk)), dim3(kTraceThreads), pl.lds_wf, c->stream, Q);
     };
@@ -4157,6 +4160,125 @@ static int trace_first_segments(const zrt_context* c, const LaunchPlan& pl, cons
     return ZRT_OK;
 }
 
+// The lane kernels that walk whole transmittance chains (transmit_walk_kernel),
+// chosen as ray_launch chooses a query's, and their occupancy-sized persistent
+// grids; `grids` false: a call that launches none of them and so asks for none.
+struct TransmitLaunch {
+    TransmitFn f_fast;        // null (mtx, a counting call): every ray takes f_exact
+    TransmitFn f_exact;
+    uint32_t grid_fast, grid_exact;
+};
+static int transmit_launch(const zrt_context* c, const LaunchPlan& pl, bool counting, bool grids, TransmitLaunch& tl) {
+    int rc;
+    tl = TransmitLaunch{};
+    tl.f_fast = counting || pl.mtx ? nullptr : kTransmitWalk[pl.packed ? (pl.pbm ? 0 : 1) : 2];
+    tl.f_exact = kTransmitWalk[counting ? 4 : 3];
+    if (!grids) return ZRT_OK;
+    if (tl.f_fast && (rc = resident_blocks(c, (const void*)tl.f_fast, kTraceThreads, pl.lds_wf, &tl.grid_fast)) != ZRT_OK)
+        return rc;
+    return resident_blocks(c, (const void*)tl.f_exact, kTraceThreads, pl.lds_wf, &tl.grid_exact);
+}
+
+// One launch of a chain kernel over the rays `which` names, no more blocks than `nblk`.
+static void transmit_walk(const zrt_context* c, const LaunchPlan& pl, TransmitFn f, uint32_t grid, uint32_t nblk,
+                          TransmitParams& R, uint32_t which, uint32_t* launches) {
+    R.q.which = which;
+    hipLaunchKernelGGL(f, dim3(std::min(grid, nblk)), dim3(kTraceThreads), pl.lds_wf, c->stream, R);
+    ++*launches;
+}
+
+// The whole chains of R's first `live` rays, over the identity queue: the fast
+// kernel (kRaysFast), then the IEEE-division kernel over the rays it left
+// (kRaysRest); without a fast kernel that one over every ray (kRaysAll).
+static void transmit_chains(const zrt_context* c, const LaunchPlan& pl, const TransmitLaunch& tl, TransmitParams& R,
+                            uint32_t live, uint32_t* launches) {
+    const uint32_t lblk = (live + kBlock - 1) / kBlock;
+    identity_queue(R.q, live);
+    if (tl.f_fast) transmit_walk(c, pl, tl.f_fast, tl.grid_fast, lblk, R, kRaysFast, launches);
+    transmit_walk(c, pl, tl.f_exact, tl.grid_exact, lblk, R, tl.f_fast ? kRaysRest : kRaysAll, launches);
+}
+
+// ---------------------------------------------------------------------------
+// What the first-hit query calls (query_rays, zrt_context_transmittance,
+// zrt_context_occlusion, light_items) do alike on the host.  Each reads top to
+// bottom as: validate -> plan and buffers -> parameters -> chunk loop -> stats.
+
+// The bytes of the grow-only buffers every such call reuses: the staging
+// buffers, and of pass set 0 the queue and the hit records only.
+static size_t query_held(const zrt_context* c) {
+    const zrt_context::PassSet& ps = c->set[0];
+    return 4ull * (c->rays_cap + c->hits_cap) + 16ull * (ps.q0_cap + ps.hit_cap) + c->bfc_bytes + c->esc_extra;
+}
+
+// Rays per chunk: at most kTraceChunk, fewer (but 64) if the device is short of
+// memory for `per_ray` bytes of work buffers per ray (0: the call grows none).
+// The budget is read before any buffer grows (device_budget), so call this
+// first; `held`: query_held and whatever else of the context the call reuses.
+static uint64_t query_chunk(const zrt_context* c, uint64_t num_rays, uint64_t per_ray, size_t held) {
+    const size_t budget = device_budget(c, held);
+    uint64_t chunk = std::min<uint64_t>(kTraceChunk, num_rays);
+    if (per_ray) chunk = std::max<uint64_t>(64, std::min<uint64_t>(chunk, budget / per_ray));
+    return chunk;
+}
+
+// A buffer grown to `need` elements, then the capacity guard (shortfall) over
+// the same count: what a launch writes is what was asked for.
+template <class T>
+static int grow_checked(const char* what, T** p, size_t* cap, uint64_t need) {
+    const int rc = grow(p, cap, need);
+    if (rc != ZRT_OK) return rc;
+    return shortfall(what, *p, *cap, need) ? ZRT_ERR_INVALID_ARG : ZRT_OK;
+}
+
+// Pass set 0's buffers for a query's park path: queues of `q0` / `q1` slots (3
+// float4 each; 0: not used), `hits` hit records and `ctr_words` counter words.
+static int grow_park_buffers(zrt_context::PassSet& ps, uint64_t q0, uint64_t q1, uint64_t hits, size_t ctr_words) {
+    int rc;
+    if (q0 && (rc = grow_checked("q0", &ps.q0, &ps.q0_cap, 3 * q0)) != ZRT_OK) return rc;
+    if (q1 && (rc = grow_checked("q1", &ps.q1, &ps.q1_cap, 3 * q1)) != ZRT_OK) return rc;
+    if ((rc = grow_checked("hit records", &ps.hit, &ps.hit_cap, hits)) != ZRT_OK) return rc;
+    return grow_checked("counters", &ps.wfc, &ps.wfc_cap, ctr_words);
+}
+
+// A zeroed QueryParams' scene, counters and statistics: one segment per ray.
+static void query_params(const zrt_context* c, QueryParams& Q) {
+    scene_params(c, Q.w.t);
+    Q.w.t.max_bounce = 1;
+    Q.w.t.counter = c->d_counter;
+    Q.w.t.stats = c->d_stats;
+    Q.ctr = c->d_counter;
+}
+
+// ... and, for a call whose first hits or items take the park path, pass set
+// 0's queue, hit records and counters (launch 0's, bounce_params' layout).
+static void query_park_params(const zrt_context* c, const LaunchPlan& pl, const zrt_context::PassSet& ps, QueryParams& Q) {
+    Q.w.q_in = ps.q0;
+    Q.w.hit = ps.hit;
+    Q.w.fetch8 = ps.wfc;
+    Q.w.n_in8 = region_counts(ps, 0);
+    park_params(c, pl, Q.w);
+    Q.q = ps.q0;
+    Q.n_in8 = region_counts(ps, 0);
+}
+
+// A host batch's chunk on its way in: its n rays at the head of d_rays and, if
+// the call has one, its per-ray row (bounds, radii) behind a whole chunk's rays,
+// at d_rays + 6 * chunk; then the mark the chunk's kernel time counts from.
+static int stage_chunk(zrt_context* c, const float* rays, const float* row, uint64_t chunk, uint32_t n) {
+    HIP_TRY(hipMemcpyAsync(c->d_rays, rays, 24ull * n, hipMemcpyHostToDevice, c->stream));
+    if (row) HIP_TRY(hipMemcpyAsync(c->d_rays + 6 * chunk, row, 4ull * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipEventRecord(c->ev_trace[0], c->stream));
+    return ZRT_OK;
+}
+// ... and after its copies back: the time from that mark to the one the caller
+// recorded (ev_trace[1]) before them.
+static int chunk_kernel_time(zrt_context* c, zrt_stats& st) {
+    float t = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&t, c->ev_trace[0], c->ev_trace[1]));
+    st.trace_kernel_ms += t;
+    return ZRT_OK;
+}
+
 // The end of a query call: the call's time, and the kernel time of a batch
 // that stayed on the device (a host batch sums its chunks' between the copies).
 static int finish_query(zrt_context* c, bool on_device, uint32_t launches, zrt_stats& st) {
@@ -4167,6 +4289,21 @@ static int finish_query(zrt_context* c, bool on_device, uint32_t launches, zrt_s
     st.render_ms = ms;
     if (on_device) st.trace_kernel_ms = ms;
     st.trace_launches = launches;
+    return ZRT_OK;
+}
+// ... with the first `words` of the call's statistics read to `hs` (0: none);
+// a counting call's cells and tests are words 1 and 2.  The caller sets
+// segments, samples and hits, which differ per call.
+static int query_stats(zrt_context* c, bool on_device, uint32_t launches, bool counting, unsigned long long* hs,
+                       size_t words, zrt_stats& st) {
+    int rc;
+    if ((rc = finish_query(c, on_device, launches, st)) != ZRT_OK) return rc;
+    if (!words) return ZRT_OK;
+    HIP_TRY(copy_sync(hs, c->d_stats, 8 * words, hipMemcpyDeviceToHost, c->stream));
+    if (counting) {
+        st.cells_visited = hs[1];
+        st.triangle_tests = hs[2];
+    }
     return ZRT_OK;
 }
 
@@ -5189,41 +5326,22 @@ static int query_rays(zrt_context* c, const RayQuery* b, zrt_stats* stats) {
         return rc;
     const bool park = pl.park;
 
-    // chunk size: at most kTraceChunk rays, fewer if the device is short of
-    // memory (device_budget; of pass set 0 this call reuses the queue and the
-    // hit records only, so only those count as held)
+    // chunk size (query_chunk; this call also reuses the surface records), then
+    // the buffers a launch below writes, each grown to a chunk and guarded
     zrt_context::PassSet& ps = c->set[0];
+    const bool host = !b->on_device;
     const bool own_hits = b->surf && b->on_device && !b->hits;    // the gather reads records the caller did not ask for
-    const uint64_t per_ray = (b->on_device ? (own_hits ? 16ull : 0ull)
-                                           : 40ull + (seg ? kSegStageBytes : 0ull) + (b->surf ? 64ull : 0ull)) +
+    const uint64_t per_ray = (host ? 40ull + (seg ? kSegStageBytes : 0ull) + (b->surf ? 64ull : 0ull)
+                                   : own_hits ? 16ull : 0ull) +
                              (park ? 64ull : 0ull);
-    const size_t held = 4ull * (c->rays_cap + c->hits_cap) + 16ull * (ps.q0_cap + ps.hit_cap + c->surf_cap) + c->bfc_bytes + c->esc_extra;
-    const size_t budget = device_budget(c, held);
-    uint64_t chunk = std::min<uint64_t>(kTraceChunk, b->num_rays);
-    if (per_ray) chunk = std::max<uint64_t>(64, std::min<uint64_t>(chunk, budget / per_ray));
+    const uint64_t chunk = query_chunk(c, b->num_rays, per_ray, query_held(c) + 16ull * c->surf_cap);
     // staging words of a host batch's chunk: rays (+ bounds), hit records (+ bytes)
     const uint64_t rays_words = 6 * chunk + (seg ? chunk : 0), hits_words = 4 * chunk + (seg ? (chunk + 3) / 4 : 0);
-    if (!b->on_device) {
-        if ((rc = grow(&c->d_rays, &c->rays_cap, rays_words)) != ZRT_OK) return rc;
-        if ((rc = grow(&c->d_hits, &c->hits_cap, hits_words)) != ZRT_OK) return rc;
-        if (b->surf && (rc = grow(&c->d_surf, &c->surf_cap, 4 * chunk)) != ZRT_OK) return rc;
-    } else if (own_hits) {
-        if ((rc = grow(&c->d_hits, &c->hits_cap, hits_words)) != ZRT_OK) return rc;
-    }
-    const size_t ctr_words = wfc_words(0);         // (a render's smallest; this call uses 16 counters)
-    if (park) {
-        if ((rc = grow(&ps.q0, &ps.q0_cap, 3 * chunk)) != ZRT_OK) return rc;
-        if ((rc = grow(&ps.hit, &ps.hit_cap, chunk)) != ZRT_OK) return rc;
-        if ((rc = grow(&ps.wfc, &ps.wfc_cap, ctr_words)) != ZRT_OK) return rc;
-    }
-    // capacity guard: every buffer a launch below writes holds a chunk
-    if ((!b->on_device && (shortfall("rays", c->d_rays, c->rays_cap, rays_words) ||
-                           shortfall("hits", c->d_hits, c->hits_cap, hits_words) ||
-                           (b->surf && shortfall("surfaces", c->d_surf, c->surf_cap, 4 * chunk)))) ||
-        (own_hits && shortfall("hits", c->d_hits, c->hits_cap, hits_words)) ||
-        (park && (shortfall("q0", ps.q0, ps.q0_cap, 3 * chunk) || shortfall("hit records", ps.hit, ps.hit_cap, chunk) ||
-                  shortfall("counters", ps.wfc, ps.wfc_cap, ctr_words))))
-        return ZRT_ERR_INVALID_ARG;
+    if (host && (rc = grow_checked("rays", &c->d_rays, &c->rays_cap, rays_words)) != ZRT_OK) return rc;
+    if ((host || own_hits) && (rc = grow_checked("hits", &c->d_hits, &c->hits_cap, hits_words)) != ZRT_OK) return rc;
+    if (host && b->surf && (rc = grow_checked("surfaces", &c->d_surf, &c->surf_cap, 4 * chunk)) != ZRT_OK) return rc;
+    // (the counters: a render's smallest; this call uses 16)
+    if (park && (rc = grow_park_buffers(ps, chunk, 0, chunk, wfc_words(0))) != ZRT_OK) return rc;
     if ((rc = event_pool(c->ev_trace, 2)) != ZRT_OK) return rc;
 
     // occupancy-sized persistent grids (no more blocks than a chunk has work for)
@@ -5234,20 +5352,8 @@ static int query_rays(zrt_context* c, const RayQuery* b, zrt_stats* stats) {
     memset(&R, 0, sizeof R);
     R.t_max_all = b->t_max_all;
     R.count = b->seg == 1 ? 1u : 0u;               // an any-hit call: its kernels count the rays not missed
-    scene_params(c, R.w.t);
-    R.w.t.max_bounce = 1;
-    R.w.t.counter = c->d_counter;
-    R.w.t.stats = c->d_stats;
-    R.ctr = c->d_counter;
-    if (park) {
-        R.w.q_in = ps.q0;
-        R.w.hit = ps.hit;
-        R.w.fetch8 = ps.wfc;
-        R.w.n_in8 = region_counts(ps, 0);
-        park_params(c, pl, R.w);
-        R.q = ps.q0;
-        R.n_in8 = region_counts(ps, 0);
-    }
+    query_params(c, R);
+    if (park) query_park_params(c, pl, ps, R);
 
     HIP_TRY(hipMemsetAsync(c->d_stats, 0, 512, c->stream));
     HIP_TRY(hipEventRecord(c->ev_begin, c->stream));
@@ -5266,16 +5372,12 @@ static int query_rays(zrt_context* c, const RayQuery* b, zrt_stats* stats) {
             R.t_max = b->t_max ? b->t_max + off : nullptr;
             R.occ = b->occ ? b->occ + off : nullptr;
         } else {
-            HIP_TRY(hipMemcpyAsync(c->d_rays, b->rays + 6 * off, 24ull * n, hipMemcpyHostToDevice, c->stream));
+            if ((rc = stage_chunk(c, b->rays + 6 * off, b->t_max ? b->t_max + off : nullptr, chunk, n)) != ZRT_OK) return rc;
             R.rays = c->d_rays;
             R.hits = b->hits || b->surf ? c->d_hits : nullptr;
             S.surf = c->d_surf;
-            if (b->t_max) {
-                HIP_TRY(hipMemcpyAsync(c->d_rays + 6 * chunk, b->t_max + off, 4ull * n, hipMemcpyHostToDevice, c->stream));
-                R.t_max = c->d_rays + 6 * chunk;
-            }
+            if (b->t_max) R.t_max = c->d_rays + 6 * chunk;
             if (b->occ) R.occ = reinterpret_cast<uint8_t*>(c->d_hits + 4 * chunk);
-            HIP_TRY(hipEventRecord(c->ev_trace[0], c->stream));
         }
         HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
         // the work counters; query_pack_kernel writes the region counts
@@ -5294,22 +5396,14 @@ static int query_rays(zrt_context* c, const RayQuery* b, zrt_stats* stats) {
             if (b->hits) HIP_TRY(copy_sync(b->hits + off, c->d_hits, 16ull * n, hipMemcpyDeviceToHost, c->stream));
             if (b->surf) HIP_TRY(copy_sync(b->surf + off, c->d_surf, 64ull * n, hipMemcpyDeviceToHost, c->stream));
             if (b->occ) HIP_TRY(copy_sync(b->occ + off, R.occ, n, hipMemcpyDeviceToHost, c->stream));
-            float t = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&t, c->ev_trace[0], c->ev_trace[1]));
-            st.trace_kernel_ms += t;
+            if ((rc = chunk_kernel_time(c, st)) != ZRT_OK) return rc;
         }
     }
-    if ((rc = finish_query(c, b->on_device != 0, launches, st)) != ZRT_OK) return rc;
+    unsigned long long hs[4];
+    const bool read = counting || b->seg == 1;     // (an any-hit call counts its bytes in every call)
+    if ((rc = query_stats(c, b->on_device != 0, launches, counting, hs, read ? 4 : 0, st)) != ZRT_OK) return rc;
     st.segments = b->num_rays;
-    if (counting || b->seg == 1) {                 // (an any-hit call counts its bytes in every call)
-        unsigned long long hs[4];
-        HIP_TRY(copy_sync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
-        if (counting) {
-            st.cells_visited = hs[1];
-            st.triangle_tests = hs[2];
-        }
-        st.hits = hs[3];
-    }
+    if (read) st.hits = hs[3];
     if (stats) *stats = st;
     return ZRT_OK;
 }
@@ -5350,10 +5444,11 @@ extern "C" int zrt_context_segments(zrt_context* c, const zrt_segment_batch* b, 
 }
 
 // Transmittance along bounded rays: see include/zrt.h, the kernels' comment
-// (TransmitParams) and DESIGN 5.15.  A sibling of query_rays -- the same plan,
-// chunk loop, staging and stats -- because its launches per chunk differ:
+// (TransmitParams) and DESIGN 5.15.  query_rays' plan, chunk loop, staging and
+// stats (the helpers above); its launches per chunk differ:
 //   lane path:  transmit_walk_kernel as query_rays launches query_walk_kernel
-//               (kRaysFast then kRaysRest, or kRaysAll), whole chains per lane;
+//               (transmit_chains: kRaysFast then kRaysRest, or kRaysAll), whole
+//               chains per lane;
 //   park path:  query_pack_kernel<SEG> -> per round k < max_crossings:
 //               wf_park_kernel (bounded closest mode, unchanged) over queue
 //               k & 1 -> transmit_step_kernel, which appends the surviving
@@ -5395,61 +5490,35 @@ extern "C" int zrt_context_transmittance(zrt_context* c, const zrt_transmittance
     uint64_t tail_max = kTransmitTailMax;
     if (const char* e = getenv("ZRT_TRANSMIT_TAIL")) tail_max = (uint64_t)std::max(0ll, atoll(e));
 
-    // chunk size, as query_rays: the staging words of a host batch, the park
-    // path's two queues and hit records (2 * 48 + 16 B per ray)
+    // chunk size (query_chunk; the park path's two queues and hit records are
+    // 2 * 48 + 16 B per ray, and the second queue is reused too), then the
+    // buffers a launch below writes, each grown to a chunk and guarded
     zrt_context::PassSet& ps = c->set[0];
+    const bool host = !b->on_device;
     const bool own_n = b->on_device && park && !b->crossings;
-    const uint64_t per_ray = (b->on_device ? (own_n ? 4ull : 0ull) : 36ull) + (park ? 112ull : 0ull);
-    const size_t held = 4ull * (c->rays_cap + c->hits_cap) + 16ull * (ps.q0_cap + ps.q1_cap + ps.hit_cap) + c->bfc_bytes +
-                        c->esc_extra;
-    const size_t budget = device_budget(c, held);
-    uint64_t chunk = std::min<uint64_t>(kTraceChunk, b->num_rays);
-    if (per_ray) chunk = std::max<uint64_t>(64, std::min<uint64_t>(chunk, budget / per_ray));
-    const uint64_t rays_words = 7 * chunk, tn_words = b->on_device ? chunk : 2 * chunk;
-    if (!b->on_device) {
-        if ((rc = grow(&c->d_rays, &c->rays_cap, rays_words)) != ZRT_OK) return rc;
-        if ((rc = grow(&c->d_hits, &c->hits_cap, tn_words)) != ZRT_OK) return rc;
-    } else if (own_n) {
-        if ((rc = grow(&c->d_hits, &c->hits_cap, tn_words)) != ZRT_OK) return rc;
-    }
+    const uint64_t per_ray = (host ? 36ull : own_n ? 4ull : 0ull) + (park ? 112ull : 0ull);
+    const uint64_t chunk = query_chunk(c, b->num_rays, per_ray, query_held(c) + 16ull * ps.q1_cap);
+    if (host && (rc = grow_checked("rays", &c->d_rays, &c->rays_cap, 7 * chunk)) != ZRT_OK) return rc;
+    if ((host || own_n) && (rc = grow_checked("T, n", &c->d_hits, &c->hits_cap, host ? 2 * chunk : chunk)) != ZRT_OK)
+        return rc;
     // counters of a chunk's rounds: 8 work counters and 8 region counts per round, one more round's region counts
     const size_t ctr_words = kCtr * 16ull * (cap + 1ull);
-    if (park) {
-        if ((rc = grow(&ps.q0, &ps.q0_cap, 3 * chunk)) != ZRT_OK) return rc;
-        if ((rc = grow(&ps.q1, &ps.q1_cap, 3 * chunk)) != ZRT_OK) return rc;
-        if ((rc = grow(&ps.hit, &ps.hit_cap, chunk)) != ZRT_OK) return rc;
-        if ((rc = grow(&ps.wfc, &ps.wfc_cap, ctr_words)) != ZRT_OK) return rc;
-    }
-    // capacity guard: every buffer a launch below writes holds a chunk
-    if ((!b->on_device && (shortfall("rays", c->d_rays, c->rays_cap, rays_words) ||
-                           shortfall("T, n", c->d_hits, c->hits_cap, tn_words))) ||
-        (own_n && shortfall("n", c->d_hits, c->hits_cap, tn_words)) ||
-        (park && (shortfall("q0", ps.q0, ps.q0_cap, 3 * chunk) || shortfall("q1", ps.q1, ps.q1_cap, 3 * chunk) ||
-                  shortfall("hit records", ps.hit, ps.hit_cap, chunk) ||
-                  shortfall("counters", ps.wfc, ps.wfc_cap, ctr_words))))
-        return ZRT_ERR_INVALID_ARG;
+    if (park && (rc = grow_park_buffers(ps, chunk, chunk, chunk, ctr_words)) != ZRT_OK) return rc;
     if ((rc = event_pool(c->ev_trace, 2)) != ZRT_OK) return rc;
 
-    // the kernels and their occupancy-sized persistent grids (ray_launch's choices)
-    const TransmitFn f_fast = counting || pl.mtx ? nullptr : kTransmitWalk[pl.packed ? (pl.pbm ? 0 : 1) : 2];
-    const TransmitFn f_exact = kTransmitWalk[counting ? 4 : 3];
+    // the kernels and their occupancy-sized persistent grids (the park path launches the fast one for its tail)
     const WfFn f_park = park_fn<kParkClosest>(pl.esc, pl.pbm);
-    uint32_t grid_fast = 0, grid_exact = 0, grid_park = 0;
+    uint32_t grid_park = 0;
     if (park && (rc = resident_blocks(c, (const void*)f_park, pl.park_block, pl.lds_park, &grid_park)) != ZRT_OK) return rc;
-    if (f_fast && (rc = resident_blocks(c, (const void*)f_fast, kTraceThreads, pl.lds_wf, &grid_fast)) != ZRT_OK)
-        return rc;                                     // (the park path: its tail launch)
-    if ((rc = resident_blocks(c, (const void*)f_exact, kTraceThreads, pl.lds_wf, &grid_exact)) != ZRT_OK) return rc;
+    TransmitLaunch tl;
+    if ((rc = transmit_launch(c, pl, counting, true, tl)) != ZRT_OK) return rc;
 
     TransmitParams R;
     memset(&R, 0, sizeof R);
     R.q.t_max_all = b->t_max_all;
     R.max_cross = cap;
-    scene_params(c, R.q.w.t);
-    R.q.w.t.max_bounce = 1;
-    R.q.w.t.counter = c->d_counter;
-    R.q.w.t.stats = c->d_stats;
-    R.q.ctr = c->d_counter;
-    if (park) {
+    query_params(c, R.q);
+    if (park) {                                        // (the rounds below wire the queues and counters)
         R.q.w.hit = ps.hit;
         park_params(c, pl, R.q.w);
     }
@@ -5466,28 +5535,15 @@ extern "C" int zrt_context_transmittance(zrt_context* c, const zrt_transmittance
             R.T = b->transmittance + off;
             R.cross = b->crossings ? b->crossings + off : own_n ? c->d_hits : nullptr;
         } else {
-            HIP_TRY(hipMemcpyAsync(c->d_rays, b->rays + 6 * off, 24ull * n, hipMemcpyHostToDevice, c->stream));
+            if ((rc = stage_chunk(c, b->rays + 6 * off, b->t_max ? b->t_max + off : nullptr, chunk, n)) != ZRT_OK) return rc;
             R.q.rays = c->d_rays;
-            if (b->t_max) {
-                HIP_TRY(hipMemcpyAsync(c->d_rays + 6 * chunk, b->t_max + off, 4ull * n, hipMemcpyHostToDevice, c->stream));
-                R.q.t_max = c->d_rays + 6 * chunk;
-            }
+            if (b->t_max) R.q.t_max = c->d_rays + 6 * chunk;
             R.T = reinterpret_cast<float*>(c->d_hits);
             R.cross = c->d_hits + chunk;
-            HIP_TRY(hipEventRecord(c->ev_trace[0], c->stream));
         }
         HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
-        R.q.n = n;
-        R.q.w.t.P = n;
-        R.q.w.t.S = 1;
-        R.q.w.t.total = n;
-        R.q.w.t.sdiv = div_magic(1);
-        auto walk = [&](TransmitFn f, uint32_t grid, uint32_t which) {
-            R.q.which = which;
-            hipLaunchKernelGGL(f, dim3(std::min(grid, nblk)), dim3(kTraceThreads), pl.lds_wf, c->stream, R);
-            ++launches;
-        };
         if (park) {
+            identity_queue(R.q, n);
             HIP_TRY(hipMemsetAsync(ps.wfc, 0, 4ull * ctr_words, c->stream));
             QueryParams Q = R.q;                       // the queue fill: query_pack_kernel<SEG>, (d, bound) records
             Q.which = kRaysAll;
@@ -5518,42 +5574,36 @@ extern "C" int zrt_context_transmittance(zrt_context* c, const zrt_transmittance
                     if (alive <= tail_max) {           // the tail: the survivors' whole chains in one lane launch
                         R.q_in = R.q_out;
                         R.q.w.n_in8 = R.n_out8;
-                        walk(f_fast, grid_fast, kRaysQueue);
+                        transmit_walk(c, pl, tl.f_fast, tl.grid_fast, nblk, R, kRaysQueue, &launches);
                         break;
                     }
                 }
             }
-        } else if (f_fast) {
-            walk(f_fast, grid_fast, kRaysFast);
+            transmit_walk(c, pl, tl.f_exact, tl.grid_exact, nblk, R, kRaysRest, &launches);
+        } else {
+            transmit_chains(c, pl, tl, R, n, &launches);
         }
-        walk(f_exact, grid_exact, park || f_fast ? kRaysRest : kRaysAll);
         HIP_TRY(hipGetLastError());
-        if (!b->on_device) {
+        if (host) {
             HIP_TRY(hipEventRecord(c->ev_trace[1], c->stream));
             HIP_TRY(copy_sync(b->transmittance + off, R.T, 4ull * n, hipMemcpyDeviceToHost, c->stream));
             if (b->crossings) HIP_TRY(copy_sync(b->crossings + off, R.cross, 4ull * n, hipMemcpyDeviceToHost, c->stream));
-            float t = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&t, c->ev_trace[0], c->ev_trace[1]));
-            st.trace_kernel_ms += t;
+            if ((rc = chunk_kernel_time(c, st)) != ZRT_OK) return rc;
         }
     }
-    if ((rc = finish_query(c, b->on_device != 0, launches, st)) != ZRT_OK) return rc;
     unsigned long long hs[4];
-    HIP_TRY(copy_sync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = query_stats(c, !host, launches, counting, hs, 4, st)) != ZRT_OK) return rc;
     st.segments = hs[0];
     st.hits = hs[3];
-    if (counting) {
-        st.cells_visited = hs[1];
-        st.triangle_tests = hs[2];
-    }
     if (stats) *stats = st;
     return ZRT_OK;
 }
 
 // Hemisphere occlusion at each ray's first hit: see include/zrt.h, the kernels'
-// comment (OcclusionParams) and DESIGN 5.17.  A sibling of query_rays -- the
-// same plan, chunk loop, staging and stats.  Per chunk of at most kTraceChunk
-// rays, all on the context's stream:
+// comment (OcclusionParams) and DESIGN 5.17.  query_rays' plan, chunk loop,
+// staging and stats (the helpers above) and its first hits; the items' loop --
+// two live counts, a park path of its own, a finish pass -- is this call's
+// alone.  Per chunk of at most kTraceChunk rays, all on the context's stream:
 //   the first hits as zrt_context_trace traces them (trace_first_segments, the
 //   park path from kTraceParkMin rays or as ZRT_TRACE_PARK asks), their records
 //   in `hits` or in the context's staging buffer; the counts zeroed;
@@ -5596,16 +5646,13 @@ extern "C" int zrt_context_occlusion(zrt_context* c, const zrt_occlusion_batch* 
         return rc;
     const bool park_first = pl.park_ok && want_first, park_items = pl.park_ok && want_items;
 
-    // chunk size, as query_rays; a sub-chunk's buffers are bounded by kOccItems
+    // chunk size (query_chunk); a sub-chunk's buffers are bounded by kOccItems
     zrt_context::PassSet& ps = c->set[0];
     const bool dev = b->on_device != 0;
     const bool own_hits = !dev || !b->hits, own_occ = !dev || !b->occluded, own_vis = !dev && b->visibility;
     const uint64_t per_ray = (dev ? 0ull : 28ull) + (own_hits ? 16ull : 0ull) + (own_occ ? 4ull : 0ull) +
                              (own_vis ? 4ull : 0ull) + (park_first ? 64ull : 0ull);
-    const size_t held = 4ull * (c->rays_cap + c->hits_cap) + 16ull * (ps.q0_cap + ps.hit_cap) + c->bfc_bytes + c->esc_extra;
-    const size_t budget = device_budget(c, held);
-    uint64_t chunk = std::min<uint64_t>(kTraceChunk, b->num_rays);
-    if (per_ray) chunk = std::max<uint64_t>(64, std::min<uint64_t>(chunk, budget / per_ray));
+    const uint64_t chunk = query_chunk(c, b->num_rays, per_ray, query_held(c));
     const uint64_t M = std::min<uint64_t>(kOccItems, chunk * S);          // items of a sub-chunk
     // words of d_rays: a host batch's rays and radii, then the list
     const uint64_t off_list = dev ? 0 : 7 * chunk, rays_words = off_list + 8 * M;
@@ -5613,20 +5660,10 @@ extern "C" int zrt_context_occlusion(zrt_context* c, const zrt_occlusion_batch* 
     const uint64_t off_occ = own_hits ? 4 * chunk : 0, off_vis = off_occ + (own_occ ? chunk : 0),
                    off_bytes = off_vis + (own_vis ? chunk : 0), hits_words = off_bytes + (M + 3) / 4;
     const uint64_t q_slots = std::max<uint64_t>(park_first ? chunk : 0, park_items ? M : 0);
-    const size_t ctr_words = wfc_words(0);
-    if ((rc = grow(&c->d_rays, &c->rays_cap, rays_words)) != ZRT_OK) return rc;
-    if ((rc = grow(&c->d_hits, &c->hits_cap, hits_words)) != ZRT_OK) return rc;
-    if (q_slots) {
-        if ((rc = grow(&ps.q0, &ps.q0_cap, 3 * q_slots)) != ZRT_OK) return rc;
-        if ((rc = grow(&ps.hit, &ps.hit_cap, q_slots)) != ZRT_OK) return rc;
-        if ((rc = grow(&ps.wfc, &ps.wfc_cap, ctr_words)) != ZRT_OK) return rc;
-    }
-    // capacity guard: every buffer a launch below writes holds a chunk / a sub-chunk
-    if (shortfall("rays, list", c->d_rays, c->rays_cap, rays_words) ||
-        shortfall("hits, counts", c->d_hits, c->hits_cap, hits_words) ||
-        (q_slots && (shortfall("q0", ps.q0, ps.q0_cap, 3 * q_slots) || shortfall("hit records", ps.hit, ps.hit_cap, q_slots) ||
-                     shortfall("counters", ps.wfc, ps.wfc_cap, ctr_words))))
-        return ZRT_ERR_INVALID_ARG;
+    // every buffer a launch below writes, grown to a chunk / a sub-chunk and guarded
+    if ((rc = grow_checked("rays, list", &c->d_rays, &c->rays_cap, rays_words)) != ZRT_OK) return rc;
+    if ((rc = grow_checked("hits, counts", &c->d_hits, &c->hits_cap, hits_words)) != ZRT_OK) return rc;
+    if (q_slots && (rc = grow_park_buffers(ps, q_slots, 0, q_slots, wfc_words(0))) != ZRT_OK) return rc;
     if ((rc = event_pool(c->ev_trace, 2)) != ZRT_OK) return rc;
 
     RayLaunch rl, ri;                              // the first hits: a trace call's; the items: a segment call's
@@ -5637,20 +5674,8 @@ extern "C" int zrt_context_occlusion(zrt_context* c, const zrt_occlusion_batch* 
 
     QueryParams R;
     memset(&R, 0, sizeof R);
-    scene_params(c, R.w.t);
-    R.w.t.max_bounce = 1;
-    R.w.t.counter = c->d_counter;
-    R.w.t.stats = c->d_stats;
-    R.ctr = c->d_counter;
-    if (q_slots) {
-        R.w.q_in = ps.q0;
-        R.w.hit = ps.hit;
-        R.w.fetch8 = ps.wfc;
-        R.w.n_in8 = region_counts(ps, 0);
-        park_params(c, pl, R.w);
-        R.q = ps.q0;
-        R.n_in8 = region_counts(ps, 0);
-    }
+    query_params(c, R);
+    if (q_slots) query_park_params(c, pl, ps, R);
     OcclusionParams O;
     memset(&O, 0, sizeof O);
     O.radius_all = b->radius_all;
@@ -5687,13 +5712,9 @@ extern "C" int zrt_context_occlusion(zrt_context* c, const zrt_occlusion_batch* 
             R.rays = b->rays + 6 * off;
             O.radius = b->radius ? b->radius + off : nullptr;
         } else {
-            HIP_TRY(hipMemcpyAsync(c->d_rays, b->rays + 6 * off, 24ull * n, hipMemcpyHostToDevice, c->stream));
+            if ((rc = stage_chunk(c, b->rays + 6 * off, b->radius ? b->radius + off : nullptr, chunk, n)) != ZRT_OK) return rc;
             R.rays = c->d_rays;
-            if (b->radius) {
-                HIP_TRY(hipMemcpyAsync(c->d_rays + 6 * chunk, b->radius + off, 4ull * n, hipMemcpyHostToDevice, c->stream));
-                O.radius = c->d_rays + 6 * chunk;
-            }
-            HIP_TRY(hipEventRecord(c->ev_trace[0], c->stream));
+            if (b->radius) O.radius = c->d_rays + 6 * chunk;
         }
         R.hits = own_hits ? c->d_hits : reinterpret_cast<uint32_t*>(b->hits + off);
         O.occluded = own_occ ? c->d_hits + off_occ : b->occluded + off;
@@ -5726,10 +5747,7 @@ extern "C" int zrt_context_occlusion(zrt_context* c, const zrt_occlusion_batch* 
             if (live[0] > m || live[1] > m || live[0] > live[1]) return ZRT_ERR_HIP;   // (never: the kernel's own bounds)
             traced += live[1];
             if (park_items && live[1] > live[0]) {
-                I.w.t.P = m;
-                I.w.t.S = 1;
-                I.w.t.total = m;
-                I.w.t.sdiv = div_magic(1);
+                identity_queue(I, m);                  // (I.n: the list walks below set their own)
                 hipLaunchKernelGGL(ri.f_park, dim3(ri.grid_park), dim3(pl.park_block), pl.lds_park, c->stream, I.w);
                 O.mode = kOccQueue;
                 hipLaunchKernelGGL(occlusion_reduce_kernel, dim3(mblk), dim3(kBlock), 0, c->stream, O);
@@ -5768,166 +5786,148 @@ extern "C" int zrt_context_occlusion(zrt_context* c, const zrt_occlusion_batch* 
             if (b->occluded) HIP_TRY(copy_sync(b->occluded + off, O.occluded, 4ull * n, hipMemcpyDeviceToHost, c->stream));
             if (b->visibility)
                 HIP_TRY(copy_sync(b->visibility + off, O.visibility, 4ull * n, hipMemcpyDeviceToHost, c->stream));
-            float t = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&t, c->ev_trace[0], c->ev_trace[1]));
-            st.trace_kernel_ms += t;
+            if ((rc = chunk_kernel_time(c, st)) != ZRT_OK) return rc;
         }
     }
-    if ((rc = finish_query(c, dev, launches, st)) != ZRT_OK) return rc;
     unsigned long long hs[kOccStat + 1];
-    HIP_TRY(copy_sync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = query_stats(c, dev, launches, counting, hs, kOccStat + 1, st)) != ZRT_OK) return rc;
     st.segments = b->num_rays + traced;
     st.hits = hs[kOccStat];
-    if (counting) {
-        st.cells_visited = hs[1];
-        st.triangle_tests = hs[2];
-    }
     if (stats) *stats = st;
     return ZRT_OK;
 }
 
-// Direct light of punctual lights at each ray's first hit: see include/zrt.h,
-// the kernels' comment (DirectParams) and DESIGN 5.18.  A sibling of
-// zrt_context_occlusion -- the same plan, chunk loop, staging and stats.  Per
-// chunk of at most kTraceChunk rays, all on the context's stream:
+// The fields of their own that the two item-parameter structs of light_items
+// get there: the call's own rows in d_rays (`rows`: behind a host batch's rays;
+// `extra`: the row between T and the slots), and the stream key of a chunk's
+// ray 0.  Direct: the lights and the items' factors; area lights: the items'
+// contributions, a float4 each.
+static void light_rows(DirectParams& D, float* rows, float* extra) {
+    D.lights = reinterpret_cast<const zrt_light*>(rows);
+    D.f = extra;
+}
+static void light_key(DirectParams&, uint64_t) {}          // (its items draw nothing)
+static void light_rows(AreaParams& D, float* rows, float*) { D.contrib = reinterpret_cast<float4*>(rows); }
+static void light_key(AreaParams& D, uint64_t key) { D.key0 = (uint32_t)key; }
+static_assert(kAreaItems == kDirItems && kAreaStat == kDirStat, "light_items: one sub-chunk size, one pair of statistics");
+
+// What zrt_context_direct and zrt_context_area_lights share (light_items): per
+// ray the irradiance of `per` light items at its first hit, each shadowed by a
+// transmittance chain, and the radiance it gives.  The plan, chunk loop,
+// staging and stats are zrt_context_occlusion's.  Per chunk of at most
+// kTraceChunk rays, all on the context's stream:
 //   the first hits as zrt_context_trace traces them (trace_first_segments, the
 //   park path from kTraceParkMin rays or as ZRT_TRACE_PARK asks), their records
 //   in `hits` or in the context's staging buffer; the walk counters those
 //   launches added to (stats[0], stats[3]) cleared;
 //   per sub-chunk of at most kDirItems items:
-//     direct_gen_kernel, then the list's size read back;
-//     the transmittance call's lane launches over the list (kRaysFast then
-//     kRaysRest; an mt_exact context, a flag or a counting call: kRaysAll),
-//     unless the list is empty or ZRT_DIRECT_UNSHADOWED is set;
-//     direct_reduce_kernel.
+//     the call's gen kernel, then the list's size read back;
+//     the transmittance call's lane launches over the list (transmit_chains:
+//     kRaysFast then kRaysRest; an mt_exact context, a flag or a counting call:
+//     kRaysAll), unless the list is empty or the call is unshadowed;
+//     the call's reduce kernel.
 // The chains never take the park-and-step rounds (DESIGN 5.15 measured the lane
-// chain as fast or faster).  The lights, a host batch's rays, the list and the
-// item rows lie in d_rays; the hit records and a host batch's (or an unasked)
-// irradiance and radiance in d_hits.  Each use writes what it reads first.
-extern "C" int zrt_context_direct(zrt_context* c, const zrt_direct_batch* b, zrt_stats* stats) {
-    if (!c || !direct_batch_ok(b, kTraceFlags)) return ZRT_ERR_INVALID_ARG;
-    if (b->num_rays == 0) { if (stats) *stats = zrt_stats{}; return ZRT_OK; }
+// chain as fast or faster).  d_rays holds a host batch's rays, then the call's
+// own rows (light_rows: `head_words` words, and `item_words` per item from a
+// 16-byte boundary), then the list (rays, bounds), T, `extra_rows` rows of the
+// call's own and the slots; d_hits the hit records and a host batch's (or an
+// unasked) irradiance and radiance.  Each use writes what it reads first.
+struct LightCall {
+    uint64_t num_rays;
+    const float* rays;
+    zrt_hit* hits;            // may be null
+    float* irradiance;        // may be null (then `radiance` is not)
+    float* radiance;
+    bool dev;                 // the batch's pointers are the device's
+    uint32_t flags;           // the batch's, without the call's own bits
+    bool unshadowed;
+    bool any;                 // false: no item can be traced (an empty set)
+    uint32_t per;             // items per ray: lights, samples
+    uint32_t max_crossings;
+    uint64_t index_base;      // stream key of ray 0 (light_key)
+    const void* head;         // uploaded once to the head of the call's own rows, or null
+    uint64_t head_words;
+    uint32_t item_words, extra_rows;
+};
+template <class P>
+static int light_items(zrt_context* c, const LightCall& k, P& D, int (*gen)(const P&, hipStream_t),
+                       int (*reduce)(const P&, uint32_t, hipStream_t), zrt_stats* stats) {
     zrt_stats st{};
-    DeviceGuard g(c->device);
-    const bool counting = (b->flags & ZRT_FLAG_COUNT_STATS) != 0;
-    const bool unshadowed = (b->flags & ZRT_DIRECT_UNSHADOWED) != 0;
-    const uint32_t flags = b->flags & ~ZRT_DIRECT_UNSHADOWED;
-    const uint32_t L = b->num_lights;
-    const bool want_first = (flags & ZRT_TRACE_PARK) != 0 || b->num_rays >= kTraceParkMin;
+    const bool counting = (k.flags & ZRT_FLAG_COUNT_STATS) != 0;
+    const uint32_t per = k.per;
+    const bool want_first = (k.flags & ZRT_TRACE_PARK) != 0 || k.num_rays >= kTraceParkMin;
     LaunchPlan pl;
     int rc;
-    if ((rc = resolve_plan(c, flags, counting, want_first, b->num_rays >= kSetsMinSamples, pl)) != ZRT_OK) return rc;
+    if ((rc = resolve_plan(c, k.flags, counting, want_first, k.num_rays >= kSetsMinSamples, pl)) != ZRT_OK) return rc;
     const bool park_first = pl.park_ok && want_first;
 
-    // chunk size, as query_rays; a sub-chunk's buffers are bounded by kDirItems
+    // chunk size (query_chunk); a sub-chunk's buffers are bounded by kDirItems
     zrt_context::PassSet& ps = c->set[0];
-    const bool dev = b->on_device != 0;
-    const bool own_hits = !dev || !b->hits, own_E = !dev || !b->irradiance, own_rad = !dev && b->radiance;
+    const bool dev = k.dev;
+    const bool own_hits = !dev || !k.hits, own_E = !dev || !k.irradiance, own_rad = !dev && k.radiance;
     const uint64_t per_ray = (dev ? 0ull : 24ull) + (own_hits ? 16ull : 0ull) + (own_E ? 12ull : 0ull) +
                              (own_rad ? 12ull : 0ull) + (park_first ? 64ull : 0ull);
-    const size_t held = 4ull * (c->rays_cap + c->hits_cap) + 16ull * (ps.q0_cap + ps.hit_cap) + c->bfc_bytes + c->esc_extra;
-    const size_t budget = device_budget(c, held);
-    uint64_t chunk = std::min<uint64_t>(kTraceChunk, b->num_rays);
-    if (per_ray) chunk = std::max<uint64_t>(64, std::min<uint64_t>(chunk, budget / per_ray));
-    const uint64_t M = std::min<uint64_t>(kDirItems, chunk * L);          // items of a sub-chunk
-    // words of d_rays: a host batch's rays, the lights, the list (rays, bounds), T, f, slots
-    const uint64_t off_lights = dev ? 0 : 6 * chunk, off_list = off_lights + 12ull * L, rays_words = off_list + 10 * M;
+    const uint64_t chunk = query_chunk(c, k.num_rays, per_ray, query_held(c));
+    const uint64_t M = std::min<uint64_t>(kDirItems, chunk * per);        // items of a sub-chunk
+    // words of d_rays: a host batch's rays, the call's own rows, the list (rays, bounds), T, its extra rows, slots
+    const uint64_t off_rows = k.item_words ? ((dev ? 0 : 6 * chunk) + 3) & ~3ull : dev ? 0 : 6 * chunk,
+                   off_list = off_rows + k.head_words + k.item_words * M, rays_words = off_list + (9 + k.extra_rows) * M;
     // words of d_hits: hit records, irradiance, radiance
     const uint64_t off_E = own_hits ? 4 * chunk : 0, off_rad = off_E + (own_E ? 3 * chunk : 0),
                    hits_words = off_rad + (own_rad ? 3 * chunk : 0);
-    const size_t ctr_words = wfc_words(0);
-    if ((rc = grow(&c->d_rays, &c->rays_cap, rays_words)) != ZRT_OK) return rc;
-    if (hits_words && (rc = grow(&c->d_hits, &c->hits_cap, hits_words)) != ZRT_OK) return rc;
-    if (park_first) {
-        if ((rc = grow(&ps.q0, &ps.q0_cap, 3 * chunk)) != ZRT_OK) return rc;
-        if ((rc = grow(&ps.hit, &ps.hit_cap, chunk)) != ZRT_OK) return rc;
-        if ((rc = grow(&ps.wfc, &ps.wfc_cap, ctr_words)) != ZRT_OK) return rc;
-    }
-    // capacity guard: every buffer a launch below writes holds a chunk / a sub-chunk
-    if (shortfall("rays, lights, list", c->d_rays, c->rays_cap, rays_words) ||
-        (hits_words && shortfall("hits, irradiance", c->d_hits, c->hits_cap, hits_words)) ||
-        (park_first && (shortfall("q0", ps.q0, ps.q0_cap, 3 * chunk) || shortfall("hit records", ps.hit, ps.hit_cap, chunk) ||
-                        shortfall("counters", ps.wfc, ps.wfc_cap, ctr_words))))
-        return ZRT_ERR_INVALID_ARG;
+    // every buffer a launch below writes, grown to a chunk / a sub-chunk and guarded
+    if ((rc = grow_checked("rays, rows, list", &c->d_rays, &c->rays_cap, rays_words)) != ZRT_OK) return rc;
+    if (hits_words && (rc = grow_checked("hits, irradiance", &c->d_hits, &c->hits_cap, hits_words)) != ZRT_OK) return rc;
+    if (park_first && (rc = grow_park_buffers(ps, chunk, 0, chunk, wfc_words(0))) != ZRT_OK) return rc;
     if ((rc = event_pool(c->ev_trace, 2)) != ZRT_OK) return rc;
 
     RayLaunch rl;                                  // the first hits: a trace call's
     if ((rc = ray_launch(c, pl, counting, park_first, rl, -1)) != ZRT_OK) return rc;
-    // the chains: a transmittance call's lane kernels and their occupancy-sized persistent grids
-    const TransmitFn f_fast = counting || pl.mtx ? nullptr : kTransmitWalk[pl.packed ? (pl.pbm ? 0 : 1) : 2];
-    const TransmitFn f_exact = kTransmitWalk[counting ? 4 : 3];
-    uint32_t grid_fast = 0, grid_exact = 0;
-    if (!unshadowed) {
-        if (f_fast && (rc = resident_blocks(c, (const void*)f_fast, kTraceThreads, pl.lds_wf, &grid_fast)) != ZRT_OK)
-            return rc;
-        if ((rc = resident_blocks(c, (const void*)f_exact, kTraceThreads, pl.lds_wf, &grid_exact)) != ZRT_OK) return rc;
-    }
+    TransmitLaunch tl;                             // the chains: a transmittance call's lane kernels
+    if ((rc = transmit_launch(c, pl, counting, !k.unshadowed && k.any, tl)) != ZRT_OK) return rc;
 
     QueryParams R;
     memset(&R, 0, sizeof R);
-    scene_params(c, R.w.t);
-    R.w.t.max_bounce = 1;
-    R.w.t.counter = c->d_counter;
-    R.w.t.stats = c->d_stats;
-    R.ctr = c->d_counter;
-    if (park_first) {
-        R.w.q_in = ps.q0;
-        R.w.hit = ps.hit;
-        R.w.fetch8 = ps.wfc;
-        R.w.n_in8 = region_counts(ps, 0);
-        park_params(c, pl, R.w);
-        R.q = ps.q0;
-        R.n_in8 = region_counts(ps, 0);
-    }
-    DirectParams D;
-    memset(&D, 0, sizeof D);
+    query_params(c, R);
+    if (park_first) query_park_params(c, pl, ps, R);
     D.tri_data = c->d_data;
     D.mats = c->d_mats;
     D.texels = c->d_texels;
-    D.lights = reinterpret_cast<const zrt_light*>(c->d_rays + off_lights);
-    D.L = L;
-    D.unshadowed = unshadowed ? 1u : 0u;
+    D.unshadowed = k.unshadowed ? 1u : 0u;
     D.irays = c->d_rays + off_list;
     D.ibound = D.irays + 6 * M;
     float* const dT = D.ibound + M;
     D.T = dT;
-    D.f = dT + M;
-    D.slot = reinterpret_cast<uint32_t*>(D.f + M);
+    D.slot = reinterpret_cast<uint32_t*>(dT + (1 + k.extra_rows) * M);
     D.ctr = c->d_counter;
     D.stats = c->d_stats;
+    light_rows(D, c->d_rays + off_rows, dT + M);
     // the chains' walks: the list as a transmittance call's rays and bounds
     TransmitParams I;
     memset(&I, 0, sizeof I);
-    scene_params(c, I.q.w.t);
-    I.q.w.t.max_bounce = 1;
-    I.q.w.t.counter = c->d_counter;
-    I.q.w.t.stats = c->d_stats;
-    I.q.ctr = c->d_counter;
+    query_params(c, I.q);
     I.q.rays = D.irays;
     I.q.t_max = D.ibound;
     I.T = dT;
-    I.max_cross = b->max_crossings;
-    I.q.w.t.S = 1;
-    I.q.w.t.sdiv = div_magic(1);
+    I.max_cross = k.max_crossings;
 
     HIP_TRY(hipMemsetAsync(c->d_stats, 0, 512, c->stream));
     HIP_TRY(hipEventRecord(c->ev_begin, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_rays + off_lights, b->lights, sizeof(zrt_light) * (size_t)L, hipMemcpyHostToDevice,
-                           c->stream));
+    if (k.head)
+        HIP_TRY(hipMemcpyAsync(c->d_rays + off_rows, k.head, 4 * k.head_words, hipMemcpyHostToDevice, c->stream));
     uint32_t launches = 0;
     uint64_t traced = 0;
-    for (uint64_t off = 0; off < b->num_rays; off += chunk) {
-        const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, b->num_rays - off);
+    for (uint64_t off = 0; off < k.num_rays; off += chunk) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, k.num_rays - off);
         if (dev) {
-            R.rays = b->rays + 6 * off;
+            R.rays = k.rays + 6 * off;
         } else {
-            HIP_TRY(hipMemcpyAsync(c->d_rays, b->rays + 6 * off, 24ull * n, hipMemcpyHostToDevice, c->stream));
+            if ((rc = stage_chunk(c, k.rays + 6 * off, nullptr, chunk, n)) != ZRT_OK) return rc;
             R.rays = c->d_rays;
-            HIP_TRY(hipEventRecord(c->ev_trace[0], c->stream));
         }
-        R.hits = own_hits ? c->d_hits : reinterpret_cast<uint32_t*>(b->hits + off);
-        D.E = own_E ? reinterpret_cast<float*>(c->d_hits + off_E) : b->irradiance + 3 * off;
-        D.radiance = own_rad ? reinterpret_cast<float*>(c->d_hits + off_rad) : dev && b->radiance ? b->radiance + 3 * off
+        R.hits = own_hits ? c->d_hits : reinterpret_cast<uint32_t*>(k.hits + off);
+        D.E = own_E ? reinterpret_cast<float*>(c->d_hits + off_E) : k.irradiance + 3 * off;
+        D.radiance = own_rad ? reinterpret_cast<float*>(c->d_hits + off_rad) : dev && k.radiance ? k.radiance + 3 * off
                                                                                                  : nullptr;
         HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
         if (park_first) HIP_TRY(hipMemsetAsync(ps.wfc, 0, 4ull * 16 * kCtr, c->stream));
@@ -5938,77 +5938,82 @@ extern "C" int zrt_context_direct(zrt_context* c, const zrt_direct_batch* b, zrt
         D.rays = R.rays;
         D.hits = R.hits;
         D.n = n;
-        const uint64_t items = (uint64_t)n * L;
+        light_key(D, k.index_base + off);
+        const uint64_t items = (uint64_t)n * per;
         for (uint64_t i0 = 0; i0 < items; i0 += kDirItems) {
             const uint32_t m = (uint32_t)std::min<uint64_t>(kDirItems, items - i0);
-            const uint32_t mblk = (m + kBlock - 1) / kBlock;
-            D.ray0 = (uint32_t)(i0 / L);
-            D.l0 = (uint32_t)(i0 % L);
+            D.ray0 = (uint32_t)(i0 / per);
+            D.s0 = (uint32_t)(i0 % per);
             D.m = m;
             HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
-            hipLaunchKernelGGL(direct_gen_kernel, dim3((mblk + kDirGenItems - 1) / kDirGenItems), dim3(kBlock), 0, c->stream,
-                               D);
+            if ((rc = gen(D, c->stream)) != ZRT_OK) return rc;
             ++launches;
-            HIP_TRY(hipGetLastError());
             uint32_t live = 0;                         // the list's entries: the traced items
             HIP_TRY(copy_sync(&live, c->d_counter + 4, sizeof live, hipMemcpyDeviceToHost, c->stream));
             if (live > m) return ZRT_ERR_HIP;          // (never: the kernel's own bounds)
             traced += live;
             D.fold = 0u;
-            if (live != 0u && !unshadowed) {
-                const uint32_t lblk = (live + kBlock - 1) / kBlock;
-                I.q.n = live;
-                I.q.w.t.P = live;
-                I.q.w.t.total = live;
-                auto walk = [&](TransmitFn f, uint32_t grid, uint32_t which) {
-                    I.q.which = which;
-                    hipLaunchKernelGGL(f, dim3(std::min(grid, lblk)), dim3(kTraceThreads), pl.lds_wf, c->stream, I);
-                    ++launches;
-                };
-                if (f_fast) walk(f_fast, grid_fast, kRaysFast);
-                walk(f_exact, grid_exact, f_fast ? kRaysRest : kRaysAll);
+            if (live != 0u && !k.unshadowed) {
+                transmit_chains(c, pl, tl, I, live, &launches);
                 D.fold = 1u;
             }
-            const uint32_t nr = (uint32_t)((D.l0 + (uint64_t)m + L - 1) / L);   // rays with an item in the sub-chunk
-            hipLaunchKernelGGL(direct_reduce_kernel, dim3((nr + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, D);
+            const uint32_t nr = (uint32_t)((D.s0 + (uint64_t)m + per - 1) / per);   // rays with an item in the sub-chunk
+            if ((rc = reduce(D, nr, c->stream)) != ZRT_OK) return rc;
             ++launches;
-            HIP_TRY(hipGetLastError());
         }
         if (!dev) {
             HIP_TRY(hipEventRecord(c->ev_trace[1], c->stream));
-            if (b->hits) HIP_TRY(copy_sync(b->hits + off, c->d_hits, 16ull * n, hipMemcpyDeviceToHost, c->stream));
-            if (b->irradiance) HIP_TRY(copy_sync(b->irradiance + 3 * off, D.E, 12ull * n, hipMemcpyDeviceToHost, c->stream));
-            if (b->radiance)
-                HIP_TRY(copy_sync(b->radiance + 3 * off, D.radiance, 12ull * n, hipMemcpyDeviceToHost, c->stream));
-            float t = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&t, c->ev_trace[0], c->ev_trace[1]));
-            st.trace_kernel_ms += t;
+            if (k.hits) HIP_TRY(copy_sync(k.hits + off, c->d_hits, 16ull * n, hipMemcpyDeviceToHost, c->stream));
+            if (k.irradiance) HIP_TRY(copy_sync(k.irradiance + 3 * off, D.E, 12ull * n, hipMemcpyDeviceToHost, c->stream));
+            if (k.radiance) HIP_TRY(copy_sync(k.radiance + 3 * off, D.radiance, 12ull * n, hipMemcpyDeviceToHost, c->stream));
+            if ((rc = chunk_kernel_time(c, st)) != ZRT_OK) return rc;
         }
     }
-    if ((rc = finish_query(c, dev, launches, st)) != ZRT_OK) return rc;
     unsigned long long hs[kDirStat + 2];
-    HIP_TRY(copy_sync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
-    st.segments = b->num_rays + hs[kDirStat];
+    if ((rc = query_stats(c, dev, launches, counting, hs, kDirStat + 2, st)) != ZRT_OK) return rc;
+    st.segments = k.num_rays + hs[kDirStat];
     st.samples = traced;
     st.hits = hs[kDirStat + 1];
-    if (counting) {
-        st.cells_visited = hs[1];
-        st.triangle_tests = hs[2];
-    }
     if (stats) *stats = st;
     return ZRT_OK;
 }
 
+// Direct light of punctual lights at each ray's first hit: see include/zrt.h,
+// the kernels' comment (DirectParams) and DESIGN 5.18.  light_items with a
+// (ray, light) item: the lights, uploaded once, lie behind a host batch's rays,
+// the items' factors in a row of their own between T and the slots; the gen
+// and reduce launches are direct_gen_kernel and direct_reduce_kernel.
+static int direct_gen_launch(const DirectParams& D, hipStream_t stream) {
+    const uint32_t mblk = (D.m + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(direct_gen_kernel, dim3((mblk + kDirGenItems - 1) / kDirGenItems), dim3(kBlock), 0, stream, D);
+    HIP_TRY(hipGetLastError());
+    return ZRT_OK;
+}
+static int direct_reduce_launch(const DirectParams& D, uint32_t rays, hipStream_t stream) {
+    hipLaunchKernelGGL(direct_reduce_kernel, dim3((rays + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, D);
+    HIP_TRY(hipGetLastError());
+    return ZRT_OK;
+}
+static_assert(sizeof(zrt_light) == 48, "light_items counts a light as 12 words");
+extern "C" int zrt_context_direct(zrt_context* c, const zrt_direct_batch* b, zrt_stats* stats) {
+    if (!c || !direct_batch_ok(b, kTraceFlags)) return ZRT_ERR_INVALID_ARG;
+    if (b->num_rays == 0) { if (stats) *stats = zrt_stats{}; return ZRT_OK; }
+    DeviceGuard g(c->device);
+    const bool unshadowed = (b->flags & ZRT_DIRECT_UNSHADOWED) != 0;
+    const LightCall k{b->num_rays, b->rays, b->hits, b->irradiance, b->radiance, b->on_device != 0,
+                      b->flags & ~ZRT_DIRECT_UNSHADOWED, unshadowed, true, b->num_lights, b->max_crossings, 0, b->lights,
+                      12ull * b->num_lights, 0, 1};
+    DirectParams D;
+    memset(&D, 0, sizeof D);
+    D.L = b->num_lights;
+    return light_items(c, k, D, direct_gen_launch, direct_reduce_launch, stats);
+}
+
 // zrt_context_area_lights (include/zrt.h): next-event estimation over an
 // emitter set; the (ray, sample) items, the set and the two item kernels are
-// emitters.hip's (emitters.h).  zrt_context_direct's plan, chunk
-// loop, staging, chains and stats with the lights' row replaced by the set,
-// which lives in memory of its own: per chunk the first hits, then per
-// sub-chunk of at most kAreaItems items area_gen_kernel, the list's size read
-// back, the transmittance call's lane launches over the list and
-// area_reduce_kernel.  A host batch's rays, the list and the item rows lie in
-// d_rays; the hit records and a host batch's (or an unasked) irradiance and
-// radiance in d_hits.  Each use writes what it reads first.
+// emitters.hip's (emitters.h).  light_items with the lights' row
+// replaced by the set, which lives in memory of its own, and the factors' row
+// by the items' contributions, a float4 each, behind a host batch's rays.
 static_assert((ZRT_AREA_UNSHADOWED & (kTraceFlags | ZRT_RADIANCE_PER_SAMPLE | ZRT_SEGMENT_ANY | ZRT_DIRECT_UNSHADOWED |
                                       ZRT_DENOISE_ROW_MAJOR | ZRT_REPROJECT_ROW_MAJOR | ZRT_SVGF_ROW_MAJOR | 0xFFFFu)) == 0u,
               "a bit of its own");
@@ -6016,84 +6021,14 @@ static_assert(sizeof(zrt_emitter) == 80 && sizeof(zrt_area_light_batch) == 80, "
 extern "C" int zrt_context_area_lights(zrt_context* c, const zrt_area_light_batch* b, zrt_stats* stats) {
     if (!c || !area_light_batch_ok(c, b, kTraceFlags)) return ZRT_ERR_INVALID_ARG;
     if (b->num_rays == 0) { if (stats) *stats = zrt_stats{}; return ZRT_OK; }
-    zrt_stats st{};
     DeviceGuard g(c->device);
     const zrt_emitters* const es = b->emitters;
-    const bool counting = (b->flags & ZRT_FLAG_COUNT_STATS) != 0;
     const bool unshadowed = (b->flags & ZRT_AREA_UNSHADOWED) != 0;
-    const uint32_t flags = b->flags & ~ZRT_AREA_UNSHADOWED;
-    const uint32_t S = b->num_samples;
-    const bool want_first = (flags & ZRT_TRACE_PARK) != 0 || b->num_rays >= kTraceParkMin;
-    LaunchPlan pl;
-    int rc;
-    if ((rc = resolve_plan(c, flags, counting, want_first, b->num_rays >= kSetsMinSamples, pl)) != ZRT_OK) return rc;
-    const bool park_first = pl.park_ok && want_first;
-
-    // chunk size, as query_rays; a sub-chunk's buffers are bounded by kAreaItems
-    zrt_context::PassSet& ps = c->set[0];
-    const bool dev = b->on_device != 0;
-    const bool own_hits = !dev || !b->hits, own_E = !dev || !b->irradiance, own_rad = !dev && b->radiance;
-    const uint64_t per_ray = (dev ? 0ull : 24ull) + (own_hits ? 16ull : 0ull) + (own_E ? 12ull : 0ull) +
-                             (own_rad ? 12ull : 0ull) + (park_first ? 64ull : 0ull);
-    const size_t held = 4ull * (c->rays_cap + c->hits_cap) + 16ull * (ps.q0_cap + ps.hit_cap) + c->bfc_bytes + c->esc_extra;
-    const size_t budget = device_budget(c, held);
-    uint64_t chunk = std::min<uint64_t>(kTraceChunk, b->num_rays);
-    if (per_ray) chunk = std::max<uint64_t>(64, std::min<uint64_t>(chunk, budget / per_ray));
-    const uint64_t M = std::min<uint64_t>(kAreaItems, chunk * S);         // items of a sub-chunk
-    // words of d_rays: a host batch's rays, (16-byte aligned) the contributions, the list (rays, bounds), T, slots
-    const uint64_t off_con = ((dev ? 0 : 6 * chunk) + 3) & ~3ull, off_list = off_con + 4 * M, rays_words = off_list + 9 * M;
-    // words of d_hits: hit records, irradiance, radiance
-    const uint64_t off_E = own_hits ? 4 * chunk : 0, off_rad = off_E + (own_E ? 3 * chunk : 0),
-                   hits_words = off_rad + (own_rad ? 3 * chunk : 0);
-    const size_t ctr_words = wfc_words(0);
-    if ((rc = grow(&c->d_rays, &c->rays_cap, rays_words)) != ZRT_OK) return rc;
-    if (hits_words && (rc = grow(&c->d_hits, &c->hits_cap, hits_words)) != ZRT_OK) return rc;
-    if (park_first) {
-        if ((rc = grow(&ps.q0, &ps.q0_cap, 3 * chunk)) != ZRT_OK) return rc;
-        if ((rc = grow(&ps.hit, &ps.hit_cap, chunk)) != ZRT_OK) return rc;
-        if ((rc = grow(&ps.wfc, &ps.wfc_cap, ctr_words)) != ZRT_OK) return rc;
-    }
-    // capacity guard: every buffer a launch below writes holds a chunk / a sub-chunk
-    if (shortfall("rays, items, list", c->d_rays, c->rays_cap, rays_words) ||
-        (hits_words && shortfall("hits, irradiance", c->d_hits, c->hits_cap, hits_words)) ||
-        (park_first && (shortfall("q0", ps.q0, ps.q0_cap, 3 * chunk) || shortfall("hit records", ps.hit, ps.hit_cap, chunk) ||
-                        shortfall("counters", ps.wfc, ps.wfc_cap, ctr_words))))
-        return ZRT_ERR_INVALID_ARG;
-    if ((rc = event_pool(c->ev_trace, 2)) != ZRT_OK) return rc;
-
-    RayLaunch rl;                                  // the first hits: a trace call's
-    if ((rc = ray_launch(c, pl, counting, park_first, rl, -1)) != ZRT_OK) return rc;
-    // the chains: a transmittance call's lane kernels and their occupancy-sized persistent grids
-    const TransmitFn f_fast = counting || pl.mtx ? nullptr : kTransmitWalk[pl.packed ? (pl.pbm ? 0 : 1) : 2];
-    const TransmitFn f_exact = kTransmitWalk[counting ? 4 : 3];
-    uint32_t grid_fast = 0, grid_exact = 0;
-    if (!unshadowed && es->count != 0u) {
-        if (f_fast && (rc = resident_blocks(c, (const void*)f_fast, kTraceThreads, pl.lds_wf, &grid_fast)) != ZRT_OK)
-            return rc;
-        if ((rc = resident_blocks(c, (const void*)f_exact, kTraceThreads, pl.lds_wf, &grid_exact)) != ZRT_OK) return rc;
-    }
-
-    QueryParams R;
-    memset(&R, 0, sizeof R);
-    scene_params(c, R.w.t);
-    R.w.t.max_bounce = 1;
-    R.w.t.counter = c->d_counter;
-    R.w.t.stats = c->d_stats;
-    R.ctr = c->d_counter;
-    if (park_first) {
-        R.w.q_in = ps.q0;
-        R.w.hit = ps.hit;
-        R.w.fetch8 = ps.wfc;
-        R.w.n_in8 = region_counts(ps, 0);
-        park_params(c, pl, R.w);
-        R.q = ps.q0;
-        R.n_in8 = region_counts(ps, 0);
-    }
+    const LightCall k{b->num_rays, b->rays, b->hits, b->irradiance, b->radiance, b->on_device != 0,
+                      b->flags & ~ZRT_AREA_UNSHADOWED, unshadowed, es->count != 0u, b->num_samples, b->max_crossings,
+                      b->index_base, nullptr, 0, 4, 0};
     AreaParams D;
     memset(&D, 0, sizeof D);
-    D.tri_data = c->d_data;
-    D.mats = c->d_mats;
-    D.texels = c->d_texels;
     D.rec = reinterpret_cast<const float4*>(es->d_rec);
     D.C = es->d_C;
     D.Q = es->Q;
@@ -6101,113 +6036,8 @@ extern "C" int zrt_context_area_lights(zrt_context* c, const zrt_area_light_batc
     D.count = es->count;
     while ((1ull << D.steps) <= es->count) ++D.steps;
     D.seed = b->seed;
-    D.S = S;
-    D.unshadowed = unshadowed ? 1u : 0u;
-    D.contrib = reinterpret_cast<float4*>(c->d_rays + off_con);
-    D.irays = c->d_rays + off_list;
-    D.ibound = D.irays + 6 * M;
-    float* const dT = D.ibound + M;
-    D.T = dT;
-    D.slot = reinterpret_cast<uint32_t*>(dT + M);
-    D.ctr = c->d_counter;
-    D.stats = c->d_stats;
-    // the chains' walks: the list as a transmittance call's rays and bounds
-    TransmitParams I;
-    memset(&I, 0, sizeof I);
-    scene_params(c, I.q.w.t);
-    I.q.w.t.max_bounce = 1;
-    I.q.w.t.counter = c->d_counter;
-    I.q.w.t.stats = c->d_stats;
-    I.q.ctr = c->d_counter;
-    I.q.rays = D.irays;
-    I.q.t_max = D.ibound;
-    I.T = dT;
-    I.max_cross = b->max_crossings;
-    I.q.w.t.S = 1;
-    I.q.w.t.sdiv = div_magic(1);
-
-    HIP_TRY(hipMemsetAsync(c->d_stats, 0, 512, c->stream));
-    HIP_TRY(hipEventRecord(c->ev_begin, c->stream));
-    uint32_t launches = 0;
-    uint64_t traced = 0;
-    for (uint64_t off = 0; off < b->num_rays; off += chunk) {
-        const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, b->num_rays - off);
-        if (dev) {
-            R.rays = b->rays + 6 * off;
-        } else {
-            HIP_TRY(hipMemcpyAsync(c->d_rays, b->rays + 6 * off, 24ull * n, hipMemcpyHostToDevice, c->stream));
-            R.rays = c->d_rays;
-            HIP_TRY(hipEventRecord(c->ev_trace[0], c->stream));
-        }
-        R.hits = own_hits ? c->d_hits : reinterpret_cast<uint32_t*>(b->hits + off);
-        D.E = own_E ? reinterpret_cast<float*>(c->d_hits + off_E) : b->irradiance + 3 * off;
-        D.radiance = own_rad ? reinterpret_cast<float*>(c->d_hits + off_rad) : dev && b->radiance ? b->radiance + 3 * off
-                                                                                                 : nullptr;
-        HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
-        if (park_first) HIP_TRY(hipMemsetAsync(ps.wfc, 0, 4ull * 16 * kCtr, c->stream));
-        if ((rc = trace_first_segments(c, pl, rl, R, n, true, &launches)) != ZRT_OK) return rc;
-        // the first hits' segments and hits are not the chains'
-        HIP_TRY(hipMemsetAsync(c->d_stats, 0, 8, c->stream));
-        HIP_TRY(hipMemsetAsync(c->d_stats + 3, 0, 8, c->stream));
-        D.rays = R.rays;
-        D.hits = R.hits;
-        D.n = n;
-        D.key0 = (uint32_t)(b->index_base + off);
-        const uint64_t items = (uint64_t)n * S;
-        for (uint64_t i0 = 0; i0 < items; i0 += kAreaItems) {
-            const uint32_t m = (uint32_t)std::min<uint64_t>(kAreaItems, items - i0);
-            D.ray0 = (uint32_t)(i0 / S);
-            D.s0 = (uint32_t)(i0 % S);
-            D.m = m;
-            HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
-            if ((rc = area_gen_launch(D, c->stream)) != ZRT_OK) return rc;
-            ++launches;
-            uint32_t live = 0;                         // the list's entries: the traced items
-            HIP_TRY(copy_sync(&live, c->d_counter + 4, sizeof live, hipMemcpyDeviceToHost, c->stream));
-            if (live > m) return ZRT_ERR_HIP;          // (never: the kernel's own bounds)
-            traced += live;
-            D.fold = 0u;
-            if (live != 0u && !unshadowed) {
-                const uint32_t lblk = (live + kBlock - 1) / kBlock;
-                I.q.n = live;
-                I.q.w.t.P = live;
-                I.q.w.t.total = live;
-                auto walk = [&](TransmitFn f, uint32_t grid, uint32_t which) {
-                    I.q.which = which;
-                    hipLaunchKernelGGL(f, dim3(std::min(grid, lblk)), dim3(kTraceThreads), pl.lds_wf, c->stream, I);
-                    ++launches;
-                };
-                if (f_fast) walk(f_fast, grid_fast, kRaysFast);
-                walk(f_exact, grid_exact, f_fast ? kRaysRest : kRaysAll);
-                D.fold = 1u;
-            }
-            const uint32_t nr = (uint32_t)((D.s0 + (uint64_t)m + S - 1) / S);   // rays with an item in the sub-chunk
-            if ((rc = area_reduce_launch(D, nr, c->stream)) != ZRT_OK) return rc;
-            ++launches;
-        }
-        if (!dev) {
-            HIP_TRY(hipEventRecord(c->ev_trace[1], c->stream));
-            if (b->hits) HIP_TRY(copy_sync(b->hits + off, c->d_hits, 16ull * n, hipMemcpyDeviceToHost, c->stream));
-            if (b->irradiance) HIP_TRY(copy_sync(b->irradiance + 3 * off, D.E, 12ull * n, hipMemcpyDeviceToHost, c->stream));
-            if (b->radiance)
-                HIP_TRY(copy_sync(b->radiance + 3 * off, D.radiance, 12ull * n, hipMemcpyDeviceToHost, c->stream));
-            float t = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&t, c->ev_trace[0], c->ev_trace[1]));
-            st.trace_kernel_ms += t;
-        }
-    }
-    if ((rc = finish_query(c, dev, launches, st)) != ZRT_OK) return rc;
-    unsigned long long hs[kAreaStat + 2];
-    HIP_TRY(copy_sync(hs, c->d_stats, sizeof hs, hipMemcpyDeviceToHost, c->stream));
-    st.segments = b->num_rays + hs[kAreaStat];
-    st.samples = traced;
-    st.hits = hs[kAreaStat + 1];
-    if (counting) {
-        st.cells_visited = hs[1];
-        st.triangle_tests = hs[2];
-    }
-    if (stats) *stats = st;
-    return ZRT_OK;
+    D.S = b->num_samples;
+    return light_items(c, k, D, area_gen_launch, area_reduce_launch, stats);
 }
 
 // What zrt_context_radiance and zrt_context_light_probes settle alike before
