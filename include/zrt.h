@@ -911,6 +911,85 @@ typedef struct zrt_area_light_batch {
  * zrt_context_transmittance call over exactly the traced items. */
 int zrt_context_area_lights(zrt_context* ctx, const zrt_area_light_batch* batch, zrt_stats* stats_or_null);
 
+/* ---- sky-light queries (ABI 2, added) ------------------------------------ */
+
+/* Direct light from the sky: the environment every path that leaves the grid
+ * returns (getEnvColor, stage3.zig:144-150), sampled over the cosine-weighted
+ * hemisphere at each ray's first hit and shadowed through transparent hits as
+ * the path tracer sees them.  zrt_context_area_lights' sibling: with it,
+ * emissive + area lights + sky is, in expectation, the path tracer at
+ * max_bounce = 2 on opaque scenes.  Nothing per (ray, sample) item crosses the
+ * bus.  dot, length and normalize_rn as in zrt_context_direct; all arithmetic
+ * f32, nothing contracted, left to right.  For ray i:
+ *   h = the zrt_context_trace record of ray i (stored to hits[i] if asked)
+ *   r = the zrt_surface of (ray i, h)
+ *   a miss: irradiance[i], radiance[i] and visibility[i] are all +0.  This
+ *     visibility is not zrt_context_occlusion's: it is the estimator's weight
+ *     sum, and a miss has no estimator
+ *   a hit: N = normalize_rn(r.normal); the ray is shaded iff every component of
+ *     r.position and of N is finite, as in zrt_context_direct; a ray that is
+ *     not shaded has no traced item, irradiance = visibility = +0 and
+ *     radiance = r.emissive.  N is normalised here, unlike in
+ *     zrt_context_occlusion, on purpose: N + a uniform unit vector, normalised,
+ *     is cosine-distributed about N only for a unit N, and the estimator
+ *     divides by that density
+ *   A = (+0, +0, +0), V = +0; for s = 0 .. num_samples - 1, in this order:
+ *     (a, b, c) = the first three floatNorm draws of the stream (seed,
+ *       (uint32_t)(index_base + i), s) from its start -- zrt_context_occlusion's
+ *       draws
+ *     d_s = normalize_rn(N + normalize_rn((a, b, c)))
+ *     the item is traced iff every component of d_s is finite and d_s is not
+ *       all zero; an item that is not traced adds nothing
+ *     L_s = getEnvColor(d_s):  t = 0.5f * (d_s.y + 1.0f);
+ *       L_s.k = (1.0f - t) + c_k * t  with c = (0.5f, 0.7f, 1.0f)
+ *     T_s = the zrt_context_transmittance result of (r.position, d_s, +inf,
+ *       max_crossings), its rules as they stand.  With ZRT_SKY_UNSHADOWED
+ *       T_s = 1 and no segment is traced
+ *     A.k = A.k + L_s.k * T_s  for k = 0, 1, 2;  V = V + T_s
+ *   mean.k = A.k / (float)num_samples;  visibility[i] = V / (float)num_samples
+ *     -- the IEEE division
+ *   irradiance[i].k = mean.k * 0x1.921fb6p+1f -- pi rounded to f32, bits
+ *     0x40490FDB: the density is cos / pi, so E = pi * mean
+ *   radiance[i].k = r.emissive[k] + r.base_color[k] * mean.k -- the Lambertian
+ *     radiance base_color * E / pi without the round trip through pi
+ * A NaN or inf the arithmetic produces is stored as it is. */
+#define ZRT_SKY_UNSHADOWED 0x1000000u   /* zrt_sky_light_batch.flags only: T = 1 for every traced item, nothing
+                                           traced */
+
+typedef struct zrt_sky_light_batch {
+    uint64_t num_rays;
+    const float* rays;        /* num_rays * 6, as zrt_ray_batch */
+    float* irradiance;        /* num_rays * 3, or null */
+    float* radiance;          /* num_rays * 3, or null */
+    float* visibility;        /* num_rays, or null (the three not all null) */
+    zrt_hit* hits;            /* num_rays, or null: the first hits, as zrt_context_trace */
+    uint32_t on_device;       /* as zrt_ray_batch; applies to all six pointers */
+    uint32_t flags;           /* zrt_ray_batch's flags | ZRT_SKY_UNSHADOWED */
+    uint32_t num_samples;     /* S, 1..65535 */
+    uint32_t max_crossings;   /* 1..256, as zrt_transmittance_batch */
+    uint64_t seed;
+    uint64_t index_base;      /* stream key of ray 0; keys wrap at 2^32 */
+} zrt_sky_light_batch;        /* 80 B */
+
+/* Synchronous, one thread at a time per context; alternates freely with
+ * renders and the other queries and leaves zrt_context_profile's record
+ * untouched.  First hits, chunks of at most 2^20 rays, sub-chunks of at most
+ * 2^20 (ray, sample) items made on the device and the chains' lane walk are
+ * zrt_context_direct's.  A ray whose samples straddle a cut still adds in
+ * sample order, A and V alike, whichever outputs are asked for.
+ * num_rays == 0 returns ZRT_OK and touches nothing.  ZRT_ERR_INVALID_ARG before
+ * any device work, the outputs untouched: a null context, batch or rays,
+ * irradiance, radiance and visibility all null, num_samples 0 or above 65535,
+ * max_crossings 0 or above 256, on_device > 1, a flag zrt_context_trace would
+ * refuse.
+ * stats (may be null), in every call: segments = num_rays + the Scene.traceRay
+ * calls of all chains, samples = the traced items, hits = the sum of the
+ * chains' crossings, render_ms, trace_kernel_ms and trace_launches as in
+ * zrt_context_trace.  With ZRT_FLAG_COUNT_STATS cells_visited and
+ * triangle_tests: the sum of a counting zrt_context_trace call over the rays
+ * and a counting zrt_context_transmittance call over exactly the traced items. */
+int zrt_context_sky_light(zrt_context* ctx, const zrt_sky_light_batch* batch, zrt_stats* stats_or_null);
+
 /* ---- light-probe queries (ABI 2, added) --------------------------------- */
 
 /* The light arriving at a point from all directions: per probe position the

@@ -196,6 +196,12 @@ class RenderScene:
         by default this scene's own): see native.Context.area_lights."""
         return self.context.area_lights(origins, dirs, self.emitters() if emitters is None else emitters, spp, **kw)
 
+    def sky_light(self, origins, dirs, spp: int, **kw):
+        """The sky's direct light at each ray's first hit, `spp` cosine-weighted
+        hemisphere samples per ray shadowed through transparent hits: see
+        native.Context.sky_light."""
+        return self.context.sky_light(origins, dirs, spp, **kw)
+
     def light_probes(self, positions, num_directions: int, spp: int, max_bounce: int, seed: int = 0,
                      index_base: int = 0, flags: int = 0, sh: bool = True, distance: bool = False, hits: bool = False,
                      directions: bool = False, radiance: bool = False):

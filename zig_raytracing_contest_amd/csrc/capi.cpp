@@ -68,6 +68,15 @@ bool area_light_batch_ok(const zrt_context* c, const zrt_area_light_batch* b, ui
     return b->emitters->ctx == c;
 }
 
+bool sky_light_batch_ok(const zrt_sky_light_batch* b, uint32_t trace_flags) {
+    if (!b) return false;
+    if ((b->flags & ~(trace_flags | ZRT_SKY_UNSHADOWED)) != 0u || b->on_device > 1u || b->num_samples == 0u ||
+        b->num_samples > 65535u || b->max_crossings == 0u || b->max_crossings > 256u)
+        return false;
+    if (b->num_rays == 0) return true;
+    return b->rays && (b->irradiance || b->radiance || b->visibility);
+}
+
 bool light_probe_batch_ok(const zrt_light_probe_batch* b, uint32_t probe_flags) {
     if (!b) return false;
     if ((b->flags & ~probe_flags) != 0u || b->on_device > 1u || b->_reserved != 0u || b->num_directions == 0u ||

@@ -112,3 +112,45 @@ constexpr uint32_t kAreaStat = 16;             // (stats[0..3] are the walk kern
 int area_gen_launch(const AreaParams& p, hipStream_t stream);
 int area_reduce_launch(const AreaParams& p, uint32_t rays, hipStream_t stream);
 #pragma GCC visibility pop
+
+// Sky-light queries (zrt_context_sky_light): the area-light call
+// with the emitter drawn replaced by the direction the path tracer scatters
+// along, zrt_context_occlusion's draw about the normalised normal, and the
+// bound by +inf.  sky_gen_kernel appends the traced items to the list and
+// keeps every item's list slot (0xFFFFFFFF: not traced); the sky's colour
+// depends on the direction's y alone, which is in the list entry, so no
+// contribution row is kept: sky_reduce_kernel reads y back and computes
+// env_color.  An unshadowed call therefore still writes the entries'
+// directions (not their origins and bounds).  The running sums A and V of a
+// ray wait in the chunk's irradiance and visibility rows between sub-chunks.
+struct SkyParams {
+    const float* rays;        // this chunk: 6 floats per ray (origin, direction as given)
+    const uint32_t* hits;     // this chunk: the zrt_hit of every ray as 4 u32 (4-byte aligned)
+    const float4* tri_data;   // TraceParams::tri_data
+    const zrt::DevMat* mats;
+    const float* texels;
+    const double* zig;        // the ziggurat's tables (TraceParams::zig)
+    unsigned long long seed;
+    uint32_t key0;            // stream key of the chunk's ray 0, (uint32_t)(index_base + offset)
+    uint32_t S;               // samples per ray, 1..65535
+    uint32_t n;               // rays of this chunk
+    uint32_t ray0, s0;        // the sub-chunk's first item: sample s0 of ray ray0
+    uint32_t m;               // items of this sub-chunk (<= kAreaItems)
+    uint32_t unshadowed;      // ZRT_SKY_UNSHADOWED: T = 1, the list holds directions only
+    uint32_t fold;            // sky_reduce_kernel: the walk launches ran; move their counts
+    float* irays;             // the list: 6 floats and a bound per entry
+    float* ibound;
+    const float* T;           // the walk's transmittance per list entry
+    uint32_t* slot;           // the list entry of every item of the sub-chunk, or 0xFFFFFFFF
+    uint32_t* ctr;            // [4]: entries of the list
+    float* E;                 // this chunk: A, then the irradiance of every ray, 3 floats
+    float* V;                 // this chunk: V, then the visibility of every ray
+    float* radiance;          // this chunk: 3 floats per ray, or null
+    unsigned long long* stats;   // [kAreaStat]: the chains' segments, [kAreaStat + 1]: their crossings
+};
+
+// sky.hip's, for zrt_context_sky_light (hidden, as above)
+#pragma GCC visibility push(hidden)
+int sky_gen_launch(const SkyParams& p, hipStream_t stream);
+int sky_reduce_launch(const SkyParams& p, uint32_t rays, hipStream_t stream);
+#pragma GCC visibility pop

@@ -5809,11 +5809,18 @@ static void light_rows(DirectParams& D, float* rows, float* extra) {
 static void light_key(DirectParams&, uint64_t) {}          // (its items draw nothing)
 static void light_rows(AreaParams& D, float* rows, float*) { D.contrib = reinterpret_cast<float4*>(rows); }
 static void light_key(AreaParams& D, uint64_t key) { D.key0 = (uint32_t)key; }
+static void light_rows(SkyParams&, float*, float*) {}      // (the sky's colour is read off the list)
+static void light_key(SkyParams& D, uint64_t key) { D.key0 = (uint32_t)key; }
+// ... and the per-ray visibility row, which the sky-light call alone has
+static void light_vis(DirectParams&, float*) {}
+static void light_vis(AreaParams&, float*) {}
+static void light_vis(SkyParams& D, float* v) { D.V = v; }
 static_assert(kAreaItems == kDirItems && kAreaStat == kDirStat, "light_items: one sub-chunk size, one pair of statistics");
 
-// What zrt_context_direct and zrt_context_area_lights share (light_items): per
-// ray the irradiance of `per` light items at its first hit, each shadowed by a
-// transmittance chain, and the radiance it gives.  The plan, chunk loop,
+// What zrt_context_direct, zrt_context_area_lights and zrt_context_sky_light
+// share (light_items): per ray the irradiance of `per` light items at its first
+// hit, each shadowed by a transmittance chain, and the radiance it gives (the
+// sky-light call: the visibility too).  The plan, chunk loop,
 // staging and stats are zrt_context_occlusion's.  Per chunk of at most
 // kTraceChunk rays, all on the context's stream:
 //   the first hits as zrt_context_trace traces them (trace_first_segments, the
@@ -5831,13 +5838,16 @@ static_assert(kAreaItems == kDirItems && kAreaStat == kDirStat, "light_items: on
 // own rows (light_rows: `head_words` words, and `item_words` per item from a
 // 16-byte boundary), then the list (rays, bounds), T, `extra_rows` rows of the
 // call's own and the slots; d_hits the hit records and a host batch's (or an
-// unasked) irradiance and radiance.  Each use writes what it reads first.
+// unasked) irradiance and radiance and, for a call with a per-ray visibility
+// (`has_vis`: the sky-light call), that row on the same terms: a ray's sum
+// waits in it across a sub-chunk cut whether it was asked for or not.  Each use
+// writes what it reads first.
 struct LightCall {
     uint64_t num_rays;
     const float* rays;
     zrt_hit* hits;            // may be null
-    float* irradiance;        // may be null (then `radiance` is not)
-    float* radiance;
+    float* irradiance;        // may be null
+    float* radiance;          // may be null (one of irradiance, radiance and visibility is not)
     bool dev;                 // the batch's pointers are the device's
     uint32_t flags;           // the batch's, without the call's own bits
     bool unshadowed;
@@ -5848,6 +5858,8 @@ struct LightCall {
     const void* head;         // uploaded once to the head of the call's own rows, or null
     uint64_t head_words;
     uint32_t item_words, extra_rows;
+    bool has_vis;             // the call has a per-ray visibility (light_vis)
+    float* visibility;        // may be null
 };
 template <class P>
 static int light_items(zrt_context* c, const LightCall& k, P& D, int (*gen)(const P&, hipStream_t),
@@ -5865,16 +5877,17 @@ static int light_items(zrt_context* c, const LightCall& k, P& D, int (*gen)(cons
     zrt_context::PassSet& ps = c->set[0];
     const bool dev = k.dev;
     const bool own_hits = !dev || !k.hits, own_E = !dev || !k.irradiance, own_rad = !dev && k.radiance;
+    const bool own_V = k.has_vis && (!dev || !k.visibility);
     const uint64_t per_ray = (dev ? 0ull : 24ull) + (own_hits ? 16ull : 0ull) + (own_E ? 12ull : 0ull) +
-                             (own_rad ? 12ull : 0ull) + (park_first ? 64ull : 0ull);
+                             (own_rad ? 12ull : 0ull) + (own_V ? 4ull : 0ull) + (park_first ? 64ull : 0ull);
     const uint64_t chunk = query_chunk(c, k.num_rays, per_ray, query_held(c));
     const uint64_t M = std::min<uint64_t>(kDirItems, chunk * per);        // items of a sub-chunk
     // words of d_rays: a host batch's rays, the call's own rows, the list (rays, bounds), T, its extra rows, slots
     const uint64_t off_rows = k.item_words ? ((dev ? 0 : 6 * chunk) + 3) & ~3ull : dev ? 0 : 6 * chunk,
                    off_list = off_rows + k.head_words + k.item_words * M, rays_words = off_list + (9 + k.extra_rows) * M;
-    // words of d_hits: hit records, irradiance, radiance
+    // words of d_hits: hit records, irradiance, radiance, visibility
     const uint64_t off_E = own_hits ? 4 * chunk : 0, off_rad = off_E + (own_E ? 3 * chunk : 0),
-                   hits_words = off_rad + (own_rad ? 3 * chunk : 0);
+                   off_V = off_rad + (own_rad ? 3 * chunk : 0), hits_words = off_V + (own_V ? chunk : 0);
     // every buffer a launch below writes, grown to a chunk / a sub-chunk and guarded
     if ((rc = grow_checked("rays, rows, list", &c->d_rays, &c->rays_cap, rays_words)) != ZRT_OK) return rc;
     if (hits_words && (rc = grow_checked("hits, irradiance", &c->d_hits, &c->hits_cap, hits_words)) != ZRT_OK) return rc;
@@ -5929,6 +5942,8 @@ static int light_items(zrt_context* c, const LightCall& k, P& D, int (*gen)(cons
         D.E = own_E ? reinterpret_cast<float*>(c->d_hits + off_E) : k.irradiance + 3 * off;
         D.radiance = own_rad ? reinterpret_cast<float*>(c->d_hits + off_rad) : dev && k.radiance ? k.radiance + 3 * off
                                                                                                  : nullptr;
+        float* const dV = own_V ? reinterpret_cast<float*>(c->d_hits + off_V) : k.visibility ? k.visibility + off : nullptr;
+        light_vis(D, dV);
         HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, c->stream));
         if (park_first) HIP_TRY(hipMemsetAsync(ps.wfc, 0, 4ull * 16 * kCtr, c->stream));
         if ((rc = trace_first_segments(c, pl, rl, R, n, true, &launches)) != ZRT_OK) return rc;
@@ -5966,6 +5981,7 @@ static int light_items(zrt_context* c, const LightCall& k, P& D, int (*gen)(cons
             if (k.hits) HIP_TRY(copy_sync(k.hits + off, c->d_hits, 16ull * n, hipMemcpyDeviceToHost, c->stream));
             if (k.irradiance) HIP_TRY(copy_sync(k.irradiance + 3 * off, D.E, 12ull * n, hipMemcpyDeviceToHost, c->stream));
             if (k.radiance) HIP_TRY(copy_sync(k.radiance + 3 * off, D.radiance, 12ull * n, hipMemcpyDeviceToHost, c->stream));
+            if (k.visibility) HIP_TRY(copy_sync(k.visibility + off, dV, 4ull * n, hipMemcpyDeviceToHost, c->stream));
             if ((rc = chunk_kernel_time(c, st)) != ZRT_OK) return rc;
         }
     }
@@ -6002,7 +6018,7 @@ extern "C" int zrt_context_direct(zrt_context* c, const zrt_direct_batch* b, zrt
     const bool unshadowed = (b->flags & ZRT_DIRECT_UNSHADOWED) != 0;
     const LightCall k{b->num_rays, b->rays, b->hits, b->irradiance, b->radiance, b->on_device != 0,
                       b->flags & ~ZRT_DIRECT_UNSHADOWED, unshadowed, true, b->num_lights, b->max_crossings, 0, b->lights,
-                      12ull * b->num_lights, 0, 1};
+                      12ull * b->num_lights, 0, 1, false, nullptr};
     DirectParams D;
     memset(&D, 0, sizeof D);
     D.L = b->num_lights;
@@ -6026,7 +6042,7 @@ extern "C" int zrt_context_area_lights(zrt_context* c, const zrt_area_light_batc
     const bool unshadowed = (b->flags & ZRT_AREA_UNSHADOWED) != 0;
     const LightCall k{b->num_rays, b->rays, b->hits, b->irradiance, b->radiance, b->on_device != 0,
                       b->flags & ~ZRT_AREA_UNSHADOWED, unshadowed, es->count != 0u, b->num_samples, b->max_crossings,
-                      b->index_base, nullptr, 0, 4, 0};
+                      b->index_base, nullptr, 0, 4, 0, false, nullptr};
     AreaParams D;
     memset(&D, 0, sizeof D);
     D.rec = reinterpret_cast<const float4*>(es->d_rec);
@@ -6038,6 +6054,32 @@ extern "C" int zrt_context_area_lights(zrt_context* c, const zrt_area_light_batc
     D.seed = b->seed;
     D.S = b->num_samples;
     return light_items(c, k, D, area_gen_launch, area_reduce_launch, stats);
+}
+
+// zrt_context_sky_light (include/zrt.h): the sky's light over the cosine-
+// weighted hemisphere at each first hit; the (ray, sample) items and the two
+// item kernels are sky.hip's (emitters.h).  light_items with no
+// row of the call's own -- the reduce reads the direction's y off the list --
+// and the per-ray visibility beside the irradiance.
+static_assert((ZRT_SKY_UNSHADOWED & (kTraceFlags | ZRT_RADIANCE_PER_SAMPLE | ZRT_SEGMENT_ANY | ZRT_DIRECT_UNSHADOWED |
+                                     ZRT_AREA_UNSHADOWED | ZRT_DENOISE_ROW_MAJOR | ZRT_REPROJECT_ROW_MAJOR |
+                                     ZRT_SVGF_ROW_MAJOR | 0xFFFFu)) == 0u,
+              "a bit of its own");
+static_assert(sizeof(zrt_sky_light_batch) == 80, "include/zrt.h");
+extern "C" int zrt_context_sky_light(zrt_context* c, const zrt_sky_light_batch* b, zrt_stats* stats) {
+    if (!c || !sky_light_batch_ok(b, kTraceFlags)) return ZRT_ERR_INVALID_ARG;
+    if (b->num_rays == 0) { if (stats) *stats = zrt_stats{}; return ZRT_OK; }
+    DeviceGuard g(c->device);
+    const bool unshadowed = (b->flags & ZRT_SKY_UNSHADOWED) != 0;
+    const LightCall k{b->num_rays, b->rays, b->hits, b->irradiance, b->radiance, b->on_device != 0,
+                      b->flags & ~ZRT_SKY_UNSHADOWED, unshadowed, true, b->num_samples, b->max_crossings, b->index_base,
+                      nullptr, 0, 0, 0, true, b->visibility};
+    SkyParams D;
+    memset(&D, 0, sizeof D);
+    D.zig = c->d_zig;
+    D.seed = b->seed;
+    D.S = b->num_samples;
+    return light_items(c, k, D, sky_gen_launch, sky_reduce_launch, stats);
 }
 
 // What zrt_context_radiance and zrt_context_light_probes settle alike before

@@ -104,6 +104,10 @@ bool direct_batch_ok(const zrt_direct_batch* b, uint32_t trace_flags);
 // num_rays != 0 -- its pointers and whether the set was made on `c`.
 bool area_light_batch_ok(const zrt_context* c, const zrt_area_light_batch* b, uint32_t trace_flags);
 
+// zrt_context_sky_light's, likewise: the batch's scalar fields, then --
+// num_rays != 0 -- its pointers.
+bool sky_light_batch_ok(const zrt_sky_light_batch* b, uint32_t trace_flags);
+
 // zrt_context_light_probes' argument checks, which need no device (capi.cpp):
 // the batch's scalar fields, then -- num_probes != 0 -- its size (at most 2^47
 // probes) and its pointers.

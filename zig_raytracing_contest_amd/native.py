@@ -32,6 +32,7 @@ RADIANCE_PER_SAMPLE = 0x20000   # ZRT_RADIANCE_PER_SAMPLE (zrt_radiance_batch.fl
 SEGMENT_ANY = 0x40000      # ZRT_SEGMENT_ANY (zrt_segment_batch.flags only)
 DIRECT_UNSHADOWED = 0x80000   # ZRT_DIRECT_UNSHADOWED (zrt_direct_batch.flags only)
 AREA_UNSHADOWED = 0x800000    # ZRT_AREA_UNSHADOWED (zrt_area_light_batch.flags only)
+SKY_UNSHADOWED = 0x1000000    # ZRT_SKY_UNSHADOWED (zrt_sky_light_batch.flags only)
 DENOISE_ROW_MAJOR = 0x100000  # ZRT_DENOISE_ROW_MAJOR (zrt_denoise_batch.flags only)
 # Context.denoise's default sigmas (colour, normal, depth, albedo): the C interface has none.  Chosen on the
 # CPU reference over oracle frames: every finite sigma_color tried lowers the error of a
@@ -231,6 +232,13 @@ class AreaLightBatch(C.Structure):
                 ("index_base", C.c_uint64)]
 
 
+class SkyLightBatch(C.Structure):
+    _fields_ = [("num_rays", C.c_uint64), ("rays", C.c_void_p), ("irradiance", C.c_void_p), ("radiance", C.c_void_p),
+                ("visibility", C.c_void_p), ("hits", C.c_void_p), ("on_device", C.c_uint32), ("flags", C.c_uint32),
+                ("num_samples", C.c_uint32), ("max_crossings", C.c_uint32), ("seed", C.c_uint64),
+                ("index_base", C.c_uint64)]
+
+
 # zrt_emitter, 80 bytes
 EMITTER_DTYPE = np.dtype([("v0", np.float32, 3), ("a", np.float32), ("e1", np.float32, 3), ("q", np.uint32),
                           ("e2", np.float32, 3), ("material", np.uint32), ("texcoords", np.float32, 6),
@@ -301,6 +309,7 @@ EXPORTS = [
     "zrt_context_illumination", "zrt_context_svgf",
     "zrt_emitters_create", "zrt_emitters_info", "zrt_emitters_read", "zrt_emitters_destroy",
     "zrt_context_area_lights",
+    "zrt_context_sky_light",
 ]
 
 
@@ -381,6 +390,8 @@ def lib():
         L.zrt_emitters_destroy.argtypes = [C.c_void_p]
         L.zrt_emitters_destroy.restype = None
         L.zrt_context_area_lights.argtypes = [C.c_void_p, C.POINTER(AreaLightBatch), C.POINTER(Stats)]
+    if hasattr(L, "zrt_context_sky_light"):   # (likewise)
+        L.zrt_context_sky_light.argtypes = [C.c_void_p, C.POINTER(SkyLightBatch), C.POINTER(Stats)]
     if hasattr(L, "zrt_group_create"):     # ABI 2 (an ABI-1 build: tools/ A/B baselines only)
         L.zrt_group_create.argtypes = [C.POINTER(Scene), C.POINTER(C.c_int32), C.c_uint32, C.POINTER(C.c_void_p)]
         L.zrt_group_create_built.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -1616,6 +1627,66 @@ class Context:
             res["irradiance"] = irr
         if radiance:
             res["radiance"] = rad
+        if hits and torch:
+            res["hits"] = rec
+        elif hits:
+            res.update(t=rec["t"].copy(), u=rec["u"].copy(), v=rec["v"].copy(), triangle=rec["triangle"].copy())
+        return res
+
+    def sky_light_raw(self, num_rays: int, rays_ptr, irradiance_ptr, radiance_ptr, visibility_ptr, hits_ptr,
+                      on_device: bool, spp: int, max_crossings: int = 16, seed: int = 0, index_base: int = 0,
+                      flags: int = 0):
+        """zrt_context_sky_light on raw pointers.  Returns the stats dict."""
+        batch = SkyLightBatch(int(num_rays), rays_ptr, irradiance_ptr, radiance_ptr, visibility_ptr, hits_ptr,
+                              1 if on_device else 0, int(flags), int(spp), int(max_crossings),
+                              int(seed) & (2 ** 64 - 1), int(index_base) & (2 ** 64 - 1))
+        st = Stats()
+        check(lib().zrt_context_sky_light(self._h, C.byref(batch), C.byref(st)), "zrt_context_sky_light")
+        return st.as_dict()
+
+    def sky_light(self, origins, dirs, spp: int, max_crossings: int = 16, seed: int = 0, index_base: int = 0,
+                  flags: int = 0, unshadowed: bool = False, irradiance: bool = True, radiance: bool = True,
+                  visibility: bool = True, hits: bool = False, stats: bool = False):
+        """The sky's direct light at each ray's first hit
+        (zrt_context_sky_light): `spp` cosine-weighted hemisphere samples per
+        ray about the normalised shading normal, drawn from the stream (seed,
+        index_base + ray, sample) as occlusion() draws them, each weighted by
+        the reference's sky colour along it and shadowed through at most
+        `max_crossings` transparent hits (unshadowed=True: T = 1, nothing
+        traced).  Per ray the irradiance estimate pi * mean(L * T), the
+        Lambertian radiance emissive + base_color * mean(L * T) and the
+        visibility mean(T); a miss is zero in all three.
+
+        Inputs and "stats" are area_lights()': two (n, 3) float32 numpy arrays
+        or CUDA tensors on the context's device; "irradiance" and "radiance"
+        are (n, 3) float32, "visibility" (n,) float32, each only when asked;
+        "samples" counts the traced (ray, sample) items."""
+        if not (irradiance or radiance or visibility):
+            raise ValueError("sky_light: irradiance, radiance or visibility must be asked for")
+        flags = int(flags) | (FLAG_COUNT_STATS if stats else 0) | (SKY_UNSHADOWED if unshadowed else 0)
+        torch, n, rays = self._rays("sky_light", origins, dirs)
+        if torch:
+            irr = torch.empty((n, 3), dtype=torch.float32, device=origins.device) if irradiance else None
+            rad = torch.empty((n, 3), dtype=torch.float32, device=origins.device) if radiance else None
+            vis = torch.empty((n,), dtype=torch.float32, device=origins.device) if visibility else None
+            rec = torch.empty((n, 4), dtype=torch.float32, device=origins.device) if hits else None
+            torch.cuda.current_stream(origins.device).synchronize()
+            ptr = lambda x: x.data_ptr() if x is not None and n else None
+        else:
+            irr = np.empty((n, 3), np.float32) if irradiance else None
+            rad = np.empty((n, 3), np.float32) if radiance else None
+            vis = np.empty(n, np.float32) if visibility else None
+            rec = np.empty(n, HIT_DTYPE) if hits else None
+            ptr = lambda x: x.ctypes.data if x is not None and n else None
+        st = self.sky_light_raw(n, ptr(rays), ptr(irr), ptr(rad), ptr(vis), ptr(rec), bool(torch), spp, max_crossings,
+                                seed, index_base, flags)
+        res = {"stats": st}
+        if irradiance:
+            res["irradiance"] = irr
+        if radiance:
+            res["radiance"] = rad
+        if visibility:
+            res["visibility"] = vis
         if hits and torch:
             res["hits"] = rec
         elif hits:
